@@ -22,8 +22,17 @@ flatter the roofline).  `roofline.frac` is computed on the bytes a launch MUST m
 n[b] real rows of every query are read -- next to the padded-formula figure of SURVEY.md 8(d);
 `roofline.full_lists` is the n == list_len twin, where both figures coincide.
 
-Timing.  The timed region holds max(K, enough steps for >= 50 ms) steps, bracketed by barrier +
-synchronize; it is repeated 5 times and the MEDIAN repeat is reported (max over ranks per repeat).
+Timing.  W warm-up steps, then ONE timed region of exactly K steps, bracketed by barrier + synchronize
+(max over ranks); `ms_per_step` is that region's time / K.
+
+A plain run does only that: set up, warm up, time the K steps, write the outputs (--dump-outputs DIR)
+and print the line.  `--full` adds everything else the line used to carry -- `roofline` (per-kernel
+timings and probes), `cpu_baseline`, and in `extra` the other step forms, BASELINE configs and
+shapes, the MLP scorer, the all-reduce probe and, at N > 1, the alternative all-reduce steps.
+
+--dump-outputs DIR: after the timed region, what its last step computed -- the per-query losses, the
+updated weights and the bucket [dW | db | loss_sum] -- as DIR/<name>.npy (float32).  The inputs and
+initial weights are seeded, so the same arguments give the same outputs from run to run.
 
 N > 1: one process per GPU (the driver's `torch.distributed.run` launch; run BARE, `bench.py --gpus N` starts its N ranks
 itself; WORLD_SIZE must equal --gpus, and the line's n_gpus is the number of ranks that ran, config.devices where).  Queries are
@@ -36,7 +45,7 @@ its own and with an in-stream ncclAllReduce (RCCL) are timed next to it (extra.m
 extra.rccl_instream_step_us); a trial under a short time budget decides, on every rank alike, whether the headline falls back to
 them (config.allreduce says which ran).  `--accum K` (K > 1) is the gradient-accumulation variant, reported in `extra` at N > 1.
 
-Prints ONE JSON line on rank 0 (metric, value, ..., roofline, cpu_baseline, extra).
+Prints ONE JSON line on rank 0 (metric, value, ..., and with --full: roofline, cpu_baseline, extra).
 """
 import argparse
 import json
@@ -212,6 +221,14 @@ def time_region(fn, steps, barrier, repeats=5, reduce_max=None, finish=None):
 def median(xs):
     s = sorted(xs)
     return s[len(s) // 2]
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one float32 DIR/<name>.npy per device tensor (a few KB at every workload)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().to(torch.float32).cpu().numpy())
 
 
 # learning rate of the timed synchronous-SGD step: small enough that the weights stay where the synthetic
@@ -790,12 +807,19 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="only the headline step + roofline")
     ap.add_argument("--full-lists", action="store_true", help="n == list_len for every query in the timed step")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: roofline and per-kernel figures, the other step "
+                         "forms, configs and shapes, the MLP scorer, the CPU baseline, N > 1 alternatives")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed region's last step computed as DIR/<name>.npy (float32)")
     ap.add_argument("--allreduce-probe", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.allreduce_probe:
         return allreduce_probe()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return spawn_ranks(args.gpus)        # run bare: one rank per GPU, started here
     if int(os.environ.get("WORLD_SIZE", "1")) != args.gpus:
@@ -879,6 +903,7 @@ def main():
     red = None
     allreduce_impl = None
     finish = None
+    bucket_out = True        # the step leaves [dW | db | loss_sum] in fs.flat (not the all-reduce handles' own buckets)
     lazy_headline = dist is None and os.environ.get("LTR_BENCH_EAGER_STEP") != "1" and hasattr(_C.lib(), "ltr_linear_sgd_lazy_step_f32")
     if lazy_headline:
         # one C-ABI call and ONE launch per step: the update of step k rides in step k + 1's launch (bit-identical weights:
@@ -945,6 +970,7 @@ def main():
                 def finish():
                     fs.lazy_flush()
             else:
+                bucket_out = False
                 if mode == "mailbox":
                     allreduce_impl = ("ltr_linear_sgd_step_f32 + mailbox all-reduce: one kernel per rank stores the bucket's tagged "
                                       "granules into every peer's HIP-IPC-mapped mailbox, adds the arrivals in rank order and applies "
@@ -968,6 +994,7 @@ def main():
                 fell_back.append("raw RCCL communicator unavailable (%s)" % raw.why)
                 raw.close()
             mode = "c10d"
+            bucket_out = False
             red = OverlappedBucketAllReduce(F, count=B, device=dev, depth=1)
             allreduce_impl = "torch.distributed all_reduce per step (blocking)"
 
@@ -989,42 +1016,30 @@ def main():
                 dist.all_reduce(ar_view, op=dist.ReduceOp.SUM)
 
     note("warm-up")
-    for i in range(max(args.warmup, 2 * nbuf)):
+    for i in range(args.warmup):
         step(i)
     if finish is not None:
         finish()
     torch.cuda.synchronize()
-    note("estimating the step")
-    # enough steps for a >= 50 ms timed region (aim at 60), a multiple of the all-reduce period
-    est_steps = 25 * accum
-    ests = []
-    for _ in range(3):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for i in range(est_steps):
-            step(i)
-        if finish is not None:
-            finish()
-        torch.cuda.synchronize()
-        ests.append((time.perf_counter() - t0) / est_steps)
-    est = min(ests)
-    steps_timed = max(args.steps, int(math.ceil(0.06 / max(est, 1e-7))))
-    if dist is not None:
-        t = torch.tensor([steps_timed], dtype=torch.int64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        steps_timed = int(t.item())
-    steps_timed = ((steps_timed + accum - 1) // accum) * accum
-    note("timing %d steps x 5" % steps_timed)
-    regions = time_region(step, steps_timed, barrier, repeats=5, reduce_max=reduce_max, finish=finish)
+    steps_timed = args.steps
+    note("timing %d steps" % steps_timed)
+    regions = time_region(step, steps_timed, barrier, repeats=1, reduce_max=reduce_max, finish=finish)
     note("timed")
-    elapsed = median(regions)
+    elapsed = regions[0]
     value = n_gpus * B * steps_timed / elapsed
+
+    if args.dump_outputs and rank == 0:
+        outputs = {"loss": fs.lossv, "weight": fs.W, "bias": fs.bias}
+        if bucket_out:
+            gw, gb, lsum, _ = bucket_views(fs.flat, F)
+            outputs.update(grad_weight=gw, grad_bias=gb, loss_sum=lsum)
+        dump_outputs(args.dump_outputs, outputs)
 
     # N > 1: every rank must hold the same weights after the same steps (synchronous SGD), and the other ways of carrying the
     # step's all-reduce are timed next to the headline's -- the mailbox step as three launches and the in-stream ncclAllReduce
     # (RCCL over xGMI: north_star's wording) -- so that one hardware run yields them all
     dp_extra = None
-    if dist is not None and accum == 1:
+    if args.full and dist is not None and accum == 1:
         dp_extra = {"allreduce_mode": mode, "fell_back": fell_back}
         torch.cuda.synchronize()
         wb = [None] * n_gpus
@@ -1071,7 +1086,7 @@ def main():
 
     # N > 1, headline mode: the gradient-accumulation variant (one all-reduce per 8 steps) next to it
     accum8 = None
-    if dist is not None and accum == 1:
+    if args.full and dist is not None and accum == 1:
         ar_view = fs.flat[:F + 2]
         fs.flat[F + 2] = float(B * n_gpus)
 
@@ -1089,7 +1104,7 @@ def main():
 
     # the same step without the weight update (what rounds 1-3 reported as `value`)
     noupd = None
-    if dist is None:
+    if args.full and dist is None:
         for i in range(2 * nbuf):
             fs.step(batches[i % nbuf])
         r0 = time_region(lambda i: fs.step(batches[i % nbuf]), max(1, steps_timed // 2), barrier, repeats=3, reduce_max=reduce_max)
@@ -1099,7 +1114,7 @@ def main():
 
     # the step as rounds 4-5 timed it: two launches per step (ltr_linear_sgd_step_f32: kernel, then reduction + update)
     eager2 = None
-    if lazy_headline:
+    if args.full and lazy_headline:
         for i in range(2 * nbuf):
             fs.sgd_step(batches[i % nbuf])
         r1 = time_region(lambda i: fs.sgd_step(batches[i % nbuf]), max(1, steps_timed // 2), barrier, repeats=3, reduce_max=reduce_max)
@@ -1109,8 +1124,9 @@ def main():
                           "headline of rounds 4-5; same weights bit for bit"}
 
     out = None
-    if rank == 0:
-        extra = {"timed_regions_s": regions, "steps_per_region": steps_timed}
+    extra = {"timed_regions_s": regions, "steps_per_region": steps_timed}
+    roofline = cpu = None
+    if rank == 0 and args.full:
         if noupd is not None:
             extra["step_without_weight_update"] = noupd
         if eager2 is not None:
@@ -1243,10 +1259,10 @@ def main():
             extra["loss_kernel"] = loss_kernel_extra(args.workload, kind, B, L, dev, batches)
         if n_gpus == 1 and not args.no_extra:
             extra.update(n1_extras(args, kind, B, L, F, dev, batches, steps_timed))
-        cpu = None
         if n_gpus == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(kind, B, L, F)
 
+    if rank == 0:
         out = {
             "metric": "queries/sec loss fwd+bwd (B=%d, list_len=%d) + achieved HBM GB/s" % (Bg, L),
             "value": value, "unit": "queries/s", "n_gpus": n_gpus, "steps": args.steps,
@@ -1275,14 +1291,16 @@ def main():
                                     ", the step's gradient all-reduce" if dist is not None else
                                     " with the update riding in it", SGD_LR))) if accum == 1 else
                                "gradient accumulation (no weight update in the timed region)",
-                       "batches_in_rotation": nbuf, "steps_timed": steps_timed, "repeats": 5,
-                       "statistic": "median of 5 timed regions",
+                       "batches_in_rotation": nbuf, "steps_timed": steps_timed, "repeats": 1,
+                       "statistic": "one timed region of --steps steps after --warmup steps",
                        "allreduce_every": accum if dist is not None else None,
                        "allreduce": (None if dist is None else
                                      ("one per step: " + str(allreduce_impl) if accum == 1 else
                                       "blocking, once per %d accumulated steps" % accum))},
-            "roofline": roofline, "cpu_baseline": cpu, "extra": extra,
+            "extra": extra,
         }
+        if args.full:
+            out.update(roofline=roofline, cpu_baseline=cpu)
     barrier()
     if dist is not None:
         dist.destroy_process_group()

@@ -10,10 +10,10 @@ root="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 cd "$root"
 out="gpurun_out/$round/prof"
 mkdir -p "$out"
-# kernel trace + stats of the DEFAULT bench command (the line the driver records)
-scripts/pmc_pass.sh "$out/trace_c2" none -- python "$root/bench.py" --steps 20 --warmup 5 --no-cpu-baseline
+# kernel trace + stats of the bench command with its --full measurements
+scripts/pmc_pass.sh "$out/trace_c2" none -- python "$root/bench.py" --full --steps 20 --warmup 5 --no-cpu-baseline
 for w in $wls; do
-  cmd="python $root/bench.py --workload $w --no-extra --no-cpu-baseline --steps 50 --warmup 10"
+  cmd="python $root/bench.py --full --workload $w --no-extra --no-cpu-baseline --steps 50 --warmup 10"
   scripts/pmc_pass.sh "$out/${w}_fetch" "FETCH_SIZE" -- $cmd
   scripts/pmc_pass.sh "$out/${w}_write" "WRITE_SIZE" -- $cmd
   scripts/pmc_pass.sh "$out/${w}_sq" "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU" -- $cmd

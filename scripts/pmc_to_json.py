@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""profiles/pmc_<workload>.json from the separate rocprofv3 PMC passes of `python bench.py --workload
-<w> --no-extra --no-cpu-baseline` (scripts/pmc_pass.sh: FETCH_SIZE, WRITE_SIZE and SQ passes):
+"""profiles/pmc_<workload>.json from the separate rocprofv3 PMC passes of `python bench.py --full
+--workload <w> --no-extra --no-cpu-baseline` (scripts/pmc_pass.sh: FETCH_SIZE, WRITE_SIZE and SQ passes):
 
     python scripts/pmc_to_json.py <workload> <fetch summary.json> <write summary.json> <sq summary.json>
 
@@ -42,7 +42,7 @@ def pick(doc, needle):
 def main(workload, fetch, write, sq):
     docs = [json.load(open(p)) for p in (fetch, write, sq)]
     out = {"_source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE | SQ_* (separate passes) -- "
-                      "python bench.py --workload %s --no-extra --no-cpu-baseline; FETCH_SIZE doubled "
+                      "python bench.py --full --workload %s --no-extra --no-cpu-baseline; FETCH_SIZE doubled "
                       "(gfx950: wide coalesced reads are tallied at half their bytes, MI355X_MICROARCH.md)" % workload,
            "_csrc_sha256": csrc_sha256()}
     for key, needle in KEYS.items():

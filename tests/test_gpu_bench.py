@@ -26,25 +26,65 @@ def _run(extra_args, env_extra=None):
     return json.loads(lines[0])
 
 
-def test_single_gpu_line_has_the_contract_fields():
-    out = _run([])
+def _assert_contract_fields(out, steps, warmup):
     assert out["metric"].startswith("queries/sec loss fwd+bwd (B=1024, list_len=128)")
-    assert out["n_gpus"] == 1 and out["steps"] == 20 and out["warmup"] == 5
+    assert out["n_gpus"] == 1 and out["steps"] == steps and out["warmup"] == warmup
     assert out["unit"] == "queries/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
     assert out["config"]["mode"] == "eager" and out["config"]["batches_in_rotation"] >= 4
     assert out["value"] > 1e6
+    # the timed region is exactly --steps steps, and value and ms_per_step describe the same region
+    assert out["config"]["steps_timed"] == steps
+    assert abs(out["value"] * out["ms_per_step"] * 1e-3 - 1024) < 1e-6 * 1024
+
+
+def test_single_gpu_line_has_the_contract_fields():
+    out = _run(["--full"])
+    _assert_contract_fields(out, 20, 5)
     r = out["roofline"]
     assert r["bound"] == "hbm" and 0 < r["frac"] < 1 and r["peak"] == 8000.0
     assert r["moved_bytes_per_launch"] < r["padded_formula"]["bytes_per_launch"]
     assert abs(r["achieved"] - r["moved_bytes_per_launch"] / (r["kernel_us_avg"] * 1e-6) / 1e9) < 1.0
-    # the timed region is long enough not to depend on --steps
-    assert out["ms_per_step"] * out["config"]["steps_timed"] >= 45.0
+
+
+def test_plain_run_times_the_headline_only_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) carries the headline fields and none of the separate measurements; --dump-outputs writes
+    what the timed region's last step computed, the same from run to run, and that is the fp64 oracle's step on the
+    batch that step took, at the weights it started from (the dumped weights + lr * the dumped gradient)."""
+    import numpy as np
+    outs = []
+    for name in ("a", "b"):
+        out = _run(["--steps", "7", "--warmup", "3", "--dump-outputs", str(tmp_path / name)])
+        _assert_contract_fields(out, 7, 3)
+        assert "roofline" not in out and "cpu_baseline" not in out
+        assert set(out["extra"]) == {"timed_regions_s", "steps_per_region"}
+        outs.append({f[:-4]: np.load(str(tmp_path / name / f)) for f in os.listdir(str(tmp_path / name))})
+    a, b = outs
+    shapes = {"loss": (1024,), "weight": (136,), "bias": (1,), "grad_weight": (136,), "grad_bias": (1,), "loss_sum": (1,)}
+    assert {k: v.shape for k, v in a.items()} == shapes
+    for k in shapes:
+        assert a[k].dtype == np.float32 and np.isfinite(a[k]).all(), k
+        assert np.allclose(a[k], b[k], rtol=1e-6, atol=1e-7), k
+    sys.path.insert(0, ROOT)
+    import bench
+    from oracle import ltr_oracle as O
+    B, L, F, kind = bench.WORKLOADS["c2"]
+    last = (7 - 1) % bench.nbuf_for(B, L, F)                  # the timed region's step k takes batch k % nbuf
+    _, rel, n, X = bench.synth(B, L, F, last, "cpu")
+    W = a["weight"].astype(np.float64) + bench.SGD_LR * a["grad_weight"]
+    bias = float(a["bias"][0]) + bench.SGD_LR * float(a["grad_bias"][0])
+    want_l, _, want_dW, want_db = O.linear_pairwise(kind, X.numpy(), W, bias, rel.numpy(), n.numpy(), np.full(B, 1.0 / B))
+    # (the tolerances of tests/test_gpu_fused.py's _check at this shape)
+    assert np.allclose(a["loss"], want_l, rtol=2e-5, atol=1e-5)
+    tol = 2e-5 * max(1.0, float(np.max(np.abs(want_dW))))
+    assert np.max(np.abs(a["grad_weight"] - want_dW)) < tol
+    assert abs(float(a["grad_bias"][0]) - want_db) < tol
+    assert np.allclose(a["loss_sum"], want_l.sum(), rtol=1e-4)
 
 
 def test_forced_process_group_default_is_one_overlapped_allreduce_per_step():
     """The N > 1 headline: one all-reduce per step (north_star / SURVEY.md 8(e)), double-buffered and
     asynchronous; the gradient-accumulation variant rides in extra."""
-    out = _run([], {"LTR_BENCH_FORCE_DIST": "1", "RANK": "0", "WORLD_SIZE": "1", "LOCAL_RANK": "0"})
+    out = _run(["--full"], {"LTR_BENCH_FORCE_DIST": "1", "RANK": "0", "WORLD_SIZE": "1", "LOCAL_RANK": "0"})
     assert out["config"]["allreduce_every"] == 1
     assert "one per step" in out["config"]["allreduce"]
     assert out["extra"]["gradient_accumulation_8"]["allreduce_every"] == 8
@@ -117,7 +157,7 @@ def test_bare_gpus_2_starts_its_ranks_and_takes_the_one_launch_data_parallel_ste
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update({"LTR_BENCH_BACKEND": "gloo", "HSA_ENABLE_IPC_MODE_LEGACY": "0"})
     pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "c2s", "--shard", "--steps", "20",
-                         "--warmup", "5", "--no-cpu-baseline", "--no-extra"], env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                         "--warmup", "5", "--no-cpu-baseline", "--no-extra", "--full"], env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                         timeout=600)
     assert pr.returncode == 0, pr.stderr.decode()[-3000:]
     lines = [ln for ln in pr.stdout.decode().splitlines() if ln.startswith("{")]

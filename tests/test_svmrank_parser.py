@@ -5,13 +5,14 @@ Three checkers, strongest first:
   * committed outputs of the REAL reference (tests/golden/svmrank_vectors.npz, made by
     tests/golden/generate_svmrank_golden.py): its C parser on the reference's own test data
     file and on edge-case / malformed texts, and its SVMRankDataset(normalize, filter_queries);
-  * the reference's C parser itself, compiled from where it lies into oracle/_ref/ by
-    oracle/build_ref.py, on seeded random and mutated files (skipped where neither the
-    reference nor a prebuilt oracle/_ref is available);
+  * the reference's C parser on seeded random and mutated files and on a large file: its status and
+    the sha256 of its (xs, ys, qids) per file (tests/golden/svmrank_fuzz_digests.npz, made by
+    tests/golden/generate_svmrank_fuzz_golden.py with the parser oracle/build_ref.py compiles);
   * properties: thread-count independence, float32 = one rounding of float64.
 Everything is compared bit-exactly.
 """
 import ctypes
+import hashlib
 import os
 import random
 import re
@@ -25,6 +26,8 @@ from pytorchltr_amd.datasets import svmrank as S
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "svmrank_vectors.npz")
 DATA = os.path.join(HERE, "golden", "svmrank_dataset.txt")
+FUZZ_DIGESTS = os.path.join(HERE, "golden", "svmrank_fuzz_digests.npz")
+FUZZ_SEED, FUZZ_CASES = 20240928, 1500
 
 
 @pytest.fixture(scope="module")
@@ -170,13 +173,16 @@ def test_truncated_record_is_rejected(tmp_path, text):
         S.parse_svmrank_file(_write(tmp_path, "t.txt", text))
 
 
-# ---- against the compiled reference (oracle/_ref) ---------------------------------------------
+# ---- against the compiled reference's outputs (tests/golden/svmrank_fuzz_digests.npz) ---------
 
-def _ref():
-    from oracle import build_ref
-    if build_ref.build() is None:
-        pytest.skip("reference parser sources not present and oracle/_ref not prebuilt")
-    return build_ref
+def _digest(xs, ys, qids):
+    """sha256 of a parse result: shapes and bytes of xs (float64), ys (int32), qids (int64)."""
+    h = hashlib.sha256()
+    for a, dt in ((xs, np.float64), (ys, np.int32), (qids, np.int64)):
+        a = np.ascontiguousarray(a, dtype=dt)
+        h.update(np.asarray(a.shape, dtype=np.int64).tobytes())
+        h.update(a.tobytes())
+    return h.digest()
 
 
 def _value(r):
@@ -224,41 +230,62 @@ def _mutate(r, s):
 _QUIRK = re.compile(r"qid:\d+([\n#\r]|$)|^ *\d+$|qid:?$|:-*$|\.$|[eE]$|^ *\d+ +q?i?d?$| \d+$", re.M)
 
 
-def test_random_and_mutated_files_match_compiled_reference(tmp_path):
-    ref = _ref()
-    r = random.Random(20240928)
-    compared = rejected = 0
-    for it in range(1500):
+def fuzz_cases(status_of):
+    """The seeded random and mutated files, in order: yields (case, text, n_threads or None).  status_of(case, text)
+    is the reference parser's status on the text -- it decides whether the case draws a thread count (a file the
+    reference accepts with a quirk of its own is not compared and draws none)."""
+    r = random.Random(FUZZ_SEED)
+    for it in range(FUZZ_CASES):
         text = _file(r, r.randint(0, 25))
         if r.random() < 0.6:
             text = _mutate(r, text)
+        if status_of(it, text) == 0 and _QUIRK.search(text):
+            yield it, text, None
+        else:
+            yield it, text, r.choice([1, 2, 3])
+
+
+def test_random_and_mutated_files_match_compiled_reference(tmp_path):
+    golden = np.load(FUZZ_DIGESTS)
+    status = golden["status"]
+    compared = rejected = 0
+    for it, text, threads in fuzz_cases(lambda it, text: int(status[it])):
+        assert hashlib.sha256(text.encode()).digest() == golden["text_sha256"][it].tobytes(), \
+            "case %d: not the text the golden digests were made from (the seeded generator changed)" % it
+        if threads is None:
+            continue
         path = _write(tmp_path, "f.txt", text)
-        rc, X, Y, Q = ref.parse_svmrank_file(path)
-        if rc == 0:
-            if _QUIRK.search(text):
-                continue
-            _same(S.parse_svmrank_file(path, n_threads=r.choice([1, 2, 3])), (X, Y, Q))
+        if status[it] == 0:
+            xs, ys, qids = S.parse_svmrank_file(path, n_threads=threads)
+            assert xs.dtype == np.float64 and ys.dtype == np.int32 and qids.dtype == np.int64
+            assert _digest(xs, ys, qids) == golden["out_sha256"][it].tobytes(), "case %d: %r" % (it, text)
             compared += 1
         else:
-            assert rc == _io.FORMAT_ERROR
+            assert status[it] == _io.FORMAT_ERROR
             with pytest.raises(ValueError):
-                S.parse_svmrank_file(path, n_threads=r.choice([1, 2, 3]))
+                S.parse_svmrank_file(path, n_threads=threads)
             rejected += 1
     assert compared > 400 and rejected > 300
 
 
-def test_large_file_threads_and_float32(tmp_path):
-    """~6 MB file (so several parser threads really run): thread-count independence, the
-    compiled reference when available, and float32 = one rounding of the float64 result."""
+def write_large_file(path):
+    """~6 MB SVMrank file (so several parser threads really run); returns (rows, F, ys, qids)."""
     rng = np.random.default_rng(5)
     rows, F = 4000, 136
     vals = rng.random((rows, F))
     q = np.repeat(np.arange(rows // 40), 40)
     y = rng.integers(0, 5, rows)
-    path = os.path.join(str(tmp_path), "big.txt")
     with open(path, "w") as f:
         for i in range(rows):
             f.write("%d qid:%d " % (y[i], q[i]) + " ".join("%d:%.6f" % (j + 1, vals[i, j]) for j in range(F)) + "\n")
+    return rows, F, y, q
+
+
+def test_large_file_threads_and_float32(tmp_path):
+    """Thread-count independence on a large file, the compiled reference's result on it, and
+    float32 = one rounding of the float64 result."""
+    path = os.path.join(str(tmp_path), "big.txt")
+    rows, F, y, q = write_large_file(path)
     assert os.path.getsize(path) > 4 << 20
     one = S.parse_svmrank_file(path, n_threads=1)
     for threads in (2, 5, 0):
@@ -266,11 +293,9 @@ def test_large_file_threads_and_float32(tmp_path):
     assert one[0].shape == (rows, F) and np.array_equal(one[1], y) and np.array_equal(one[2], q)
     x32 = S.parse_svmrank_file(path, n_threads=3, dtype=np.float32)[0]
     assert x32.dtype == np.float32 and np.array_equal(x32, one[0].astype(np.float32))
-    from oracle import build_ref
-    if build_ref.build() is not None:
-        rc, X, Y, Q = build_ref.parse_svmrank_file(path)
-        assert rc == 0
-        _same(one, (X, Y, Q))
+    golden = np.load(FUZZ_DIGESTS)
+    assert hashlib.sha256(open(path, "rb").read()).digest() == golden["large_text_sha256"].tobytes()
+    assert _digest(*one) == golden["large_out_sha256"].tobytes()
 
 
 # ---- device: file -> RaggedQueries -> padded batch ---------------------------------------------
