@@ -241,6 +241,46 @@ int ltr_arp_seed_f32(const float *scores, const void *rel, int rel_dtype, const 
 uint32_t ltr_tie_hash_word(uint64_t seed, uint32_t position);     /* host helper: the word itself */
 
 /*
+ * The three ranking entry points above on LONG lists (up to ltr_max_sort_list_len() = 2^24 documents, where the
+ * others stop at ltr_max_list_len() = 4096): rank_by_score / tiebreak_argsort (utils/tensor_operations.py:29-64),
+ * dcg / ndcg (evaluation/dcg.py:8-99), arp (evaluation/arp.py:7-42) -- the reference bounds none of them (a row-wise
+ * argsort).  Same semantics as ltr_rank_by_score_f32 / ltr_dcg_f32 / ltr_arp_f32 (padded labels counted by dcg,
+ * maxDCG == 0 -> 1, padded tail in index order).
+ *   Tie modes, one signature:  use_seed != 0: hashed words from `seed` (`seed_dev`, device int64[1], overrides it
+ *   when not NULL), as the _seed_ forms;  else tie != NULL: explicit priorities (L) int32, a permutation of
+ *   0..L-1, as the _tie_ forms;  else document-index order.
+ *   L <= ltr_max_list_len(): the call IS the existing entry point of its mode (_seed_ words included; workspace
+ *   unused, may be NULL).  Longer lists: every document gets the key (rank_key's score-order word, capped at
+ *   0xFFFFFFFE) << 32 | tie word -- the index, tie[j], or ltr_tie_hash_word_long(seed, j) --, padded documents
+ *   0xFFFFFFFF << 32 | j; the keys are unique, a chunk sort in LDS plus merge passes orders them.
+ *   Workspace (caller's device memory, any contents), op = 0 rank, 1 dcg / ndcg, 2 arp:
+ *     ltr_sort_workspace_bytes(op, B, L) = A(16 B L) + A(4 L) + (op ? 8 B ceil(L / 4096) : 0),  A(x) = x rounded up
+ *     to a multiple of 256  (two key buffers, the inverse tie map, per-tile partial sums); 0 for invalid arguments.
+ *   Deterministic (fixed-order sums, no atomics), no host synchronisation, nothing allocated: capturable.
+ *   Errors: LTR_ERR_LIST_TOO_LONG above ltr_max_sort_list_len(), LTR_ERR_WORKSPACE for a missing or short workspace
+ *   on the long path.
+ */
+int ltr_max_sort_list_len(void);
+size_t ltr_sort_workspace_bytes(int op, int B, int L);
+int ltr_rank_by_score_long_f32(const float *scores, const int64_t *n, const int32_t *tie, int use_seed, uint64_t seed,
+                               const int64_t *seed_dev, int B, int L, int64_t *ranking, void *workspace,
+                               size_t workspace_bytes, void *stream);
+int ltr_dcg_long_f32(const float *scores, const void *rel, int rel_dtype, const int64_t *n, const int32_t *tie,
+                     int use_seed, uint64_t seed, const int64_t *seed_dev, int B, int L, int k, int use_exp,
+                     int normalize, float *out, void *workspace, size_t workspace_bytes, void *stream);
+int ltr_arp_long_f32(const float *scores, const void *rel, int rel_dtype, const int64_t *n, const int32_t *tie,
+                     int use_seed, uint64_t seed, const int64_t *seed_dev, int B, int L, float *out, void *workspace,
+                     size_t workspace_bytes, void *stream);
+/* The long path's tie word, a keyed bijection of the 32-bit positions (distinct for every position), in uint32
+ * arithmetic mod 2^32 with k1 = the low and k2 = the high 32 bits of the seed:
+ *   x = (position ^ k1) * 0x9E3779B1;  x ^= x >> 16;  x *= 0x85EBCA6B;  word = x ^ k2.
+ * Equal scores rank in ascending word order: one pseudo-random permutation of the tied positions per seed, shared
+ * by all rows (tiebreak_argsort's `p = randperm(L)`, utils/tensor_operations.py:43-45). */
+uint32_t ltr_tie_hash_word_long(uint64_t seed, uint32_t position);
+/* Tests only: != 0 makes the _long_ entry points take the long path at every L >= 1; returns the old value. */
+LTR_DEBUG_HOOK int ltr_debug_long_sort_all(int on);
+
+/*
  * Listwise softmax cross-entropy (ListNet top-one; named by the project brief, ABSENT from the
  * reference: pytorchltr/loss/__init__.py:1-7 exports no such class -- parity unpinned, the
  * specification is this header):

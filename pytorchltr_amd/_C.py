@@ -57,6 +57,14 @@ SIGNATURES = {
     "ltr_dcg_seed_f32": (_i, [_vp, _vp, _i, _vp, ctypes.c_uint64, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "ltr_arp_seed_f32": (_i, [_vp, _vp, _i, _vp, ctypes.c_uint64, _vp, _i, _i, _vp, _vp]),
     "ltr_tie_hash_word": (ctypes.c_uint32, [ctypes.c_uint64, ctypes.c_uint32]),
+    "ltr_max_sort_list_len": (_i, []),
+    "ltr_sort_workspace_bytes": (_sz, [_i, _i, _i]),
+    "ltr_rank_by_score_long_f32": (_i, [_vp, _vp, _vp, _i, ctypes.c_uint64, _vp, _i, _i, _vp, _vp, _sz, _vp]),
+    "ltr_dcg_long_f32": (_i, [_vp, _vp, _i, _vp, _vp, _i, ctypes.c_uint64, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz,
+                              _vp]),
+    "ltr_arp_long_f32": (_i, [_vp, _vp, _i, _vp, _vp, _i, ctypes.c_uint64, _vp, _i, _i, _vp, _vp, _sz, _vp]),
+    "ltr_tie_hash_word_long": (ctypes.c_uint32, [ctypes.c_uint64, ctypes.c_uint32]),
+    "ltr_debug_long_sort_all": (_i, [_i]),
     "ltr_listwise_softmax_f32": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp]),
     "ltr_mask_padded_values_f32": (_i, [_vp, _vp, _i, _i, _f, _vp, _vp]),
     "ltr_batch_pairs": (_i, [_vp, _i, _i, _i, _vp, _vp]),
@@ -198,6 +206,23 @@ def max_list_len():
     if _max_len is None:
         _max_len = int(lib().ltr_max_list_len())
     return _max_len
+
+
+_max_sort_len = None
+
+
+def max_sort_list_len():
+    """Longest list the rankings and metrics take (their long path; the losses stop at max_list_len())."""
+    global _max_sort_len
+    if _max_sort_len is None:
+        _max_sort_len = int(lib().ltr_max_sort_list_len())
+    return _max_sort_len
+
+
+def sort_workspace(op, B, L, device):
+    """Workspace of the ltr_*_long_f32 entry points (op 0 rank, 1 dcg / ndcg, 2 arp): (tensor, bytes)."""
+    nbytes = int(lib().ltr_sort_workspace_bytes(op, B, L))
+    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device), nbytes
 
 
 def max_list_len_f64():

@@ -15,6 +15,8 @@ mode "random" (default, the reference's behaviour): a fresh pseudo-random order 
     `torch.manual_seed` makes it reproducible) and the kernels hash (seed, position) into the tie word
     themselves (include/ltr_hip.h: ltr_*_seed_f32).  A generator living on a device is honoured too:
     its draw stays on the device and the kernel reads it there;
+Lists longer than 4096 documents take the sort path (include/ltr_hip.h: ltr_*_long_f32), which hashes the same
+    seed into a 32-bit word of its own (ltr_tie_hash_word_long, hash_words_long below);
 mode "index": deterministic document-index order, no draw (the round-1 behaviour; bit-reproducible
     metrics, biased on tied scores).
 Rows without ties give the same result in both modes.
@@ -77,6 +79,18 @@ def hash_words(seed, L):
     from . import _C
     lib = _C.lib()
     return np.array([lib.ltr_tie_hash_word(seed, j) for j in range(L)], dtype=np.int32)
+
+
+def hash_words_long(seed, L):
+    """The long path's tie words (include/ltr_hip.h: ltr_tie_hash_word_long) for positions 0..L-1, restated in
+    numpy (uint32; for tests / oracles): a keyed bijection of the 32-bit positions."""
+    import numpy as np
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    k1, k2 = np.uint32(seed & 0xFFFFFFFF), np.uint32(seed >> 32)
+    x = (np.arange(L, dtype=np.uint32) ^ k1) * np.uint32(0x9E3779B1)
+    x ^= x >> np.uint32(16)
+    x *= np.uint32(0x85EBCA6B)
+    return x ^ k2
 
 
 def draw_priorities(L, device, generator=None):

@@ -1490,3 +1490,4 @@ int ltr_collate_pad_csr_f32(const int64_t *indptr, const int32_t *indices, const
 }  // extern "C"
 
 #include "ltr_f64.inc"
+#include "ltr_longsort.inc"

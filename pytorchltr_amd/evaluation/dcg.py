@@ -2,7 +2,8 @@
 
 One kernel per call ranks each query by score (and, for NDCG, by label) with an in-LDS
 counting rank, applies gains and log2 discounts and either reduces to metric@k or prefix-sums
-the whole curve.  As in the reference, labels of padded documents are not masked, and equal
+the whole curve.  Lists longer than one workgroup's LDS (4096) take a sort path of several
+launches (chunk sort, merge passes, epilogues) instead.  As in the reference, labels of padded documents are not masked, and equal
 scores are ordered by a random permutation drawn per call (``pytorchltr_amd.utils.tie_breaking``
 selects the deterministic index order instead).
 """
@@ -27,10 +28,12 @@ def _cutoff(k, L):
 
 
 def _run(scores, relevance, n, k, exp, normalize):
-    s, r, nn = _prepare(scores, relevance, n)
+    s, r, nn = _prepare(scores, relevance, n, limit_len=False)
     B, L = s.shape
     kk = _cutoff(k, L)
     out = _torch.empty((B,) if kk > 0 else (B, L), dtype=_torch.float32, device=s.device)
+    if L > _C.max_list_len():
+        return _run_long(s, r, nn, kk, exp, normalize, out)
     if B > 0:
         # the reference ranks through rank_by_score with its global-RNG tie-break (dcg.py:85)
         # (round 3: a seed drawn on the host, hashed into tie words inside the kernel -- no randperm launches)
@@ -43,6 +46,22 @@ def _run(scores, relevance, n, k, exp, normalize):
                 _C.check(_C.lib().ltr_dcg_seed_f32(_C.ptr(s), _C.ptr(r), _C.label_dtype(r), _C.ptr(nn), sd[0],
                                                    _C.ptr(sd[1]), B, L, kk, int(bool(exp)), int(normalize),
                                                    _C.ptr(out), _C.stream_of(s)))
+    return out
+
+
+def _run_long(s, r, nn, kk, exp, normalize, out):
+    """Lists past one workgroup's LDS: the sort path (include/ltr_hip.h: ltr_dcg_long_f32)."""
+    B, L = s.shape
+    if L > _C.max_sort_list_len():
+        raise ValueError("list_size %d exceeds the supported maximum %d" % (L, _C.max_sort_list_len()))
+    if B > 0:
+        sd = _ties.draw_seed(L, s.device)
+        ws, nbytes = _C.sort_workspace(1, B, L, s.device)
+        with _C.device_ctx(s):
+            _C.check(_C.lib().ltr_dcg_long_f32(
+                _C.ptr(s), _C.ptr(r), _C.label_dtype(r), _C.ptr(nn), None, int(sd is not None),
+                sd[0] if sd is not None else 0, _C.ptr(sd[1]) if sd is not None else None, B, L, kk,
+                int(bool(exp)), int(normalize), _C.ptr(out), _C.ptr(ws), nbytes, _C.stream_of(s)))
     return out
 
 
