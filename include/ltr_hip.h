@@ -94,13 +94,12 @@ int ltr_max_list_len_f64(void);
 int ltr_device_status(int clear);
 /* Tests only: != 0 makes every in-launch wait of the multi-workgroup kernels give up at once. */
 LTR_DEBUG_HOOK void ltr_debug_force_timeout(int on);
-/* Tests only: switches of the cluster kernel (long lists on small batches; LTR_CLUSTER_MODE=<bits> in the environment
- * does the same for a whole process).  Bit 0: treat every query's workgroups as spread over several XCDs, i.e. take the
+/* Tests only: switches of the cluster kernel (long lists on small batches).  Bit 0: treat every query's workgroups as spread over several XCDs, i.e. take the
  * write-through protocol the kernel falls back to when the placement check of a launch fails.  Bit 1: the hinge kinds by
  * the pair pass even where the labels are integer grades 0 .. 4 (which the kernel resolves by ranks). */
 LTR_DEBUG_HOOK void ltr_debug_cluster_mode(int bits);
 /* Tests only: != 0 lets the parts kernel (below) take every shape it CAN take instead of the shapes where it was
- * measured to pay (LTR_PARTS_ALL=1 in the environment does the same for a whole process); returns the old value. */
+ * measured to pay; returns the old value. */
 LTR_DEBUG_HOOK int ltr_debug_parts_all(int on);
 /*
  * Exchange areas.  The fused-scorer kernels that spread a query over several workgroups (the parts kernel
@@ -131,8 +130,7 @@ LTR_DEBUG_HOOK int ltr_debug_kernel_events(void *start /* hipEvent_t */, void *s
 /* Tests / measurements only: which kernel layout ltr_mlp_pairwise_f32 takes where both apply.
  * 0 = automatic (the 4-wave tile kernel of csrc/ltr_mlp2.inc for batches of at least two queries per
  * CU-slot and for lists over 128 documents, else the 8-wave kernel of csrc/ltr_mlp.inc), 1 = the
- * 8-wave kernel wherever it applies, 2 = the tile kernel wherever it applies.
- * LTR_MLP_LAYOUT in the environment sets the initial value. */
+ * 8-wave kernel wherever it applies, 2 = the tile kernel wherever it applies. */
 LTR_DEBUG_HOOK void ltr_debug_mlp_layout(int layout);
 
 /*

@@ -4,7 +4,8 @@
 ``pytorchltr_amd.build`` -- the ``.hip_fatbin`` section holds one clang offload bundle per translation
 unit -- and returns the per-kernel metadata the assembler left in their ELF notes (``.vgpr_count``,
 ``.vgpr_spill_count``, ``.sgpr_count``, ``.private_segment_fixed_size``, ``.group_segment_fixed_size``).
-Used by tests/test_codeobj.py (no product kernel may spill) and scripts/dev.
+Used by tests/test_codeobj.py (no product kernel may spill); ``python -m pytorchltr_amd._codeobj [pattern]``
+prints the records.
 """
 import os
 import re

@@ -27,26 +27,14 @@
 namespace {
 
 constexpr int kClThreads = 1024;
-#ifndef LTR_CLUSTER_NI
-#define LTR_CLUSTER_NI 12
-#endif
-constexpr int kClNI = LTR_CLUSTER_NI;         // row sweeps held in registers (12 float4 per thread)
+constexpr int kClNI = 12;         // row sweeps held in registers (12 float4 per thread)
 constexpr int kClNISmall = 8;
 constexpr int kClMaxParts = 16;
 constexpr int kClSpinLimit = 1 << 20;
 constexpr int kClCntStride = 64;              // ints between the counters of two queries (256 B: own cache line / channel)
-#ifndef LTR_CLUSTER_CNT_SCOPE
-#define LTR_CLUSTER_CNT_SCOPE __HIP_MEMORY_SCOPE_SYSTEM
-#endif
-#ifndef LTR_CLUSTER_ALL_PAIR
-#define LTR_CLUSTER_ALL_PAIR 1        // (limiting the pair pass to fewer workgroups of the cluster lost: 0-20 %)
-#endif
-#ifndef LTR_CLUSTER_NI_WIDE
-#define LTR_CLUSTER_NI_WIDE 19          // (swept 12 / 19: 64 x 512 x 700 38 -> 27 us; 116 VGPRs of the 128 a 1024-thread workgroup may use)
-#endif
-#ifndef LTR_CLUSTER_SLEEP
-#define LTR_CLUSTER_SLEEP 8          // (swept 2 / 8 / 64: 64 costs 2-3 us per launch)
-#endif
+constexpr int kClCntScope = __HIP_MEMORY_SCOPE_SYSTEM;
+constexpr int kClNIWide = 19;          // (swept 12 / 19: 64 x 512 x 700 38 -> 27 us; 116 VGPRs of the 128 a 1024-thread workgroup may use)
+constexpr int kClSleep = 8;          // (swept 2 / 8 / 64: 64 costs 2-3 us per launch)
 
 // XCD-local clusters (round 5, verdict r4 item 2).  Block id i runs on XCD (i + k) mod 8 (k: where the
 // dispatcher's round-robin stood; profiles/r05_exchange_latency.txt), so a cluster laid out on block ids
@@ -139,21 +127,17 @@ __device__ __forceinline__ float sum_shared(const float *base, size_t stride, in
 
 __device__ __forceinline__ bool cluster_wait(int *counter, int want, int tid, int spin_limit)
 {
-#ifdef LTR_CLUSTER_DEBUG_NOWAIT
-    __syncthreads();
-    return true;
-#endif
     // every wave waits for its own stores to be acknowledged, the barrier collects the waves, then
     // tid 0 signals and spins (relaxed loads); the trailing barrier releases the workgroup
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     __shared__ int s_ok;
     if (tid == 0) {
-        __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, LTR_CLUSTER_CNT_SCOPE);
+        __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, kClCntScope);
         int ok = 0;
         for (int it = 0; it < spin_limit; ++it) {
-            if (__hip_atomic_load(counter, __ATOMIC_RELAXED, LTR_CLUSTER_CNT_SCOPE) >= want) { ok = 1; break; }
-            __builtin_amdgcn_s_sleep(LTR_CLUSTER_SLEEP);
+            if (__hip_atomic_load(counter, __ATOMIC_RELAXED, kClCntScope) >= want) { ok = 1; break; }
+            __builtin_amdgcn_s_sleep(kClSleep);
         }
         s_ok = ok;
     }
@@ -171,15 +155,15 @@ __device__ __forceinline__ unsigned cluster_wait_placed(int *counter, int want, 
     __shared__ int s_ok0;
     if (tid == 0) {
         const int x = (int)cluster_xcc_id();
-        __hip_atomic_fetch_add(counter, 1 | (x << 8) | ((x * x) << 16), __ATOMIC_RELAXED, LTR_CLUSTER_CNT_SCOPE);
+        __hip_atomic_fetch_add(counter, 1 | (x << 8) | ((x * x) << 16), __ATOMIC_RELAXED, kClCntScope);
         int ok = 0;
         for (int it = 0; it < spin_limit; ++it) {
-            const int v = __hip_atomic_load(counter, __ATOMIC_RELAXED, LTR_CLUSTER_CNT_SCOPE);
+            const int v = __hip_atomic_load(counter, __ATOMIC_RELAXED, kClCntScope);
             if ((v & 0xff) >= want) {
                 ok = 1 | ((((v >> 8) & 0xff) == want * x && ((unsigned)v >> 16) == (unsigned)(want * x * x)) ? 2 : 0);
                 break;
             }
-            __builtin_amdgcn_s_sleep(LTR_CLUSTER_SLEEP);
+            __builtin_amdgcn_s_sleep(kClSleep);
         }
         s_ok0 = ok;
     }
@@ -209,18 +193,8 @@ __device__ __forceinline__ unsigned cluster_wait_placed(int *counter, int want, 
 // int[2 rpw], after the exchange; behind gloc my rows' keys u64[rpw] | local ranks int[rpw], before it.
 constexpr int kClGrades = 5;
 constexpr int kClRunsLightMinL = 1000;       // (see choose_cluster_shape)
-#ifndef LTR_RUNS_MAX_NI
-#define LTR_RUNS_MAX_NI 8
-#endif
-#ifndef LTR_RUNS_WIDE
-#define LTR_RUNS_WIDE 1
-#endif
-#ifndef LTR_RUNS_NS_BIG
-#define LTR_RUNS_NS_BIG 2
-#endif
-#ifndef LTR_RUNS_PARK
-#define LTR_RUNS_PARK 2
-#endif
+constexpr int kRunsMaxNI = 8;
+constexpr int kRunsPark = 2;
 // bytes of the scratch region the sorted runs use (scores, table, counts); tile vectors are parked behind them
 __host__ __device__ inline size_t runs_park_offset(size_t L4, size_t rpw)
 {
@@ -464,20 +438,14 @@ __device__ __forceinline__ float cluster_hinge_from_runs(const QueryLds &q, cons
 // caller's workspace behind a magic word, which a recycled allocation could leave intact over dirty counters
 // (ADVICE r3).  A launch that gave up leaves them dirty: the host zeroes the area once the status has been cleared.
 
-#ifndef LTR_CLUSTER_MINW512
-#define LTR_CLUSTER_MINW512 6          // <= 80 VGPRs: three 512-thread workgroups per CU (logistic C4 shape 99 -> 84 us)
-#endif
+constexpr int kClMinW512 = 6;          // <= 80 VGPRs: three 512-thread workgroups per CU (logistic C4 shape 99 -> 84 us)
 // (LambdaNDCG2 at list lengths near 1000 needs 57 KB of LDS: two workgroups per CU whatever the registers -- its
 // kernels may use 128 VGPRs instead of spilling 20 under the 80 of the others: 256 x 1000 x 220 148 -> 125 us; LambdaNDCG1
 // is FASTER spilling 12 registers at three workgroups per CU than clean at two: 113 vs 125)
-#ifndef LTR_CLUSTER_MINW512_N1
-#define LTR_CLUSTER_MINW512_N1 6
-#endif
-#ifndef LTR_CLUSTER_MINW512_N2
-#define LTR_CLUSTER_MINW512_N2 4
-#endif
+constexpr int kClMinW512N1 = 6;
+constexpr int kClMinW512N2 = 4;
 template <int KIND, int T, int NI>
-__global__ void __launch_bounds__(T, (T == 512 ? (KIND == LTR_NDCG2 ? LTR_CLUSTER_MINW512_N2 : (KIND == LTR_NDCG1 ? LTR_CLUSTER_MINW512_N1 : LTR_CLUSTER_MINW512)) : 4))
+__global__ void __launch_bounds__(T, (T == 512 ? (KIND == LTR_NDCG2 ? kClMinW512N2 : (KIND == LTR_NDCG1 ? kClMinW512N1 : kClMinW512)) : 4))
 linear_cluster_kernel(ClusterParams cp)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -584,7 +552,7 @@ linear_cluster_kernel(ClusterParams cp)
     // members for wide rows; the 12-sweep tile sits at its register bound: with this path compiled in it spills two tile
     // vectors INSIDE the load burst, C4 59.9 -> 62.0 us -- as the 19-sweep tile did (the C5 shard 29.0 -> 33.2) until the
     // searches kept three registers per search)
-    constexpr bool kRuns = (KIND == LTR_HINGE || KIND == LTR_DCG_HINGE) && ((T == 512 && NI <= LTR_RUNS_MAX_NI) || (T == 1024 && LTR_RUNS_WIDE));
+    constexpr bool kRuns = (KIND == LTR_HINGE || KIND == LTR_DCG_HINGE) && ((T == 512 && NI <= kRunsMaxNI) || T == 1024);
     if constexpr (kRuns) {
         // (the 1024-thread members for wide rows: only while a member's rows fit the registers of the local ranking -- 64 x 512 x
         // 700, 95 rows: 28.7 -> 28.2 us, 64 x 1000 x 700 45.6 -> 41.2; with 133 rows on the LDS path 64 x 512 x 520 21.4 -> 23.8)
@@ -630,9 +598,6 @@ linear_cluster_kernel(ClusterParams cp)
         __syncthreads();
         cluster_local_ranks<T>(runs, gloc, cp.sbuf + row + r0, cp.rbuf() + row + r0, max(0, r1 - r0), tid);
     }
-#ifdef LTR_CLUSTER_DEBUG_STOP1
-    return;
-#endif
     int *cnt = cp.cnt + (size_t)kClCntStride * b;
     CL_STAMP(2);
     // the step's state in ONE scalar register (the 12-sweep members sit at their 80 VGPRs and 106 SGPRs): bit 0 = no
@@ -719,7 +684,7 @@ linear_cluster_kernel(ClusterParams cp)
         // The 12-sweep tile sits at the 80 VGPRs of three workgroups per CU: with this path compiled in, the allocator spilled
         // two tile vectors for their WHOLE life -- stored to scratch inside the load burst, behind a wait for them.  The live
         // range is split by hand instead: kPark vectors wait in the part of the LDS scratch the runs leave free.
-        constexpr int kPark = (NI > kClNISmall) ? LTR_RUNS_PARK : 0;
+        constexpr int kPark = (NI > kClNISmall) ? kRunsPark : 0;
         float4 *park = reinterpret_cast<float4 *>(reinterpret_cast<unsigned char *>(q.gpart) + runs_park_offset(L4, rpw));
 #pragma unroll
         for (int e = 0; e < kPark; ++e) park[e * T + tid] = x[NI - 1 - e];
@@ -740,15 +705,13 @@ linear_cluster_kernel(ClusterParams cp)
         // (gloc = the UNSCALED integer gradients of my rows; the DCG modifier's scale needs the whole query's pair sum:
         // the last workgroup of the cluster applies it to the summed shares)
     } else {
-    // Only the first PP workgroups of the cluster take pair units: a share needs enough steps per
-    // wave to be worth its fixed cost (the rule of the split-query launch), the others go straight
-    // to the second wait.
-    const int PP = LTR_CLUSTER_ALL_PAIR ? P : split_parts_for(nb, P, msplit);
-    if (part < PP) {
+    // Every workgroup of the cluster takes pair units (limiting the pair pass to fewer of them, by the
+    // rule of the split-query launch, lost 0-20 %).
+    if (part < P) {
         float unused = 1.0f;
         const bool intlab = (KIND == LTR_HINGE || KIND == LTR_DCG_HINGE) && p.rel_dtype != LTR_LABEL_F32;
-        const float raw = intlab ? pairwise_core_sym<KIND, 0, false, true>(q, nb, L4, p.sigma, unused, part, PP, true)
-                                 : pairwise_core_sym<KIND>(q, nb, L4, p.sigma, unused, part, PP, true);
+        const float raw = intlab ? pairwise_core_sym<KIND, 0, false, true>(q, nb, L4, p.sigma, unused, part, P, true)
+                                 : pairwise_core_sym<KIND>(q, nb, L4, p.sigma, unused, part, P, true);
         float *wg = cp.slices() + slot * L;
         for (int k = tid; k < nb; k += T) {
             float g = 0.f;
@@ -763,7 +726,7 @@ linear_cluster_kernel(ClusterParams cp)
     CL_STAMP(8);
 
     // ---- loss of the query; d loss / d s of my rows ----
-    float total = sum_shared(cp.wl() + (size_t)b * cp.Pmax, 1, PP);     // every thread, same order
+    float total = sum_shared(cp.wl() + (size_t)b * cp.Pmax, 1, P);     // every thread, same order
     float gscale = 1.0f;
     if (KIND == LTR_DCG_HINGE) {
         const float lg = logf(2.0f + total);
@@ -782,7 +745,7 @@ linear_cluster_kernel(ClusterParams cp)
         p.loss[b] = __builtin_nanf("");
     }
     for (int lr = tid; lr < r1 - r0; lr += T) {
-        const float g = sum_shared<(NI <= kClNISmall ? 8 : 4)>(cp.slices() + (size_t)b * cp.Pmax * L + r0 + lr, (size_t)L, PP);
+        const float g = sum_shared<(NI <= kClNISmall ? 8 : 4)>(cp.slices() + (size_t)b * cp.Pmax * L + r0 + lr, (size_t)L, P);
         gloc[lr] = g * gscale;
     }
     __syncthreads();
@@ -828,7 +791,7 @@ linear_cluster_kernel(ClusterParams cp)
     __syncthreads();
     __shared__ int s_last;
     if (tid == 0)
-        s_last = (__hip_atomic_fetch_add(cnt + kClCntFinal, 1, __ATOMIC_RELAXED, LTR_CLUSTER_CNT_SCOPE) == P - 1) ? 1 : 0;
+        s_last = (__hip_atomic_fetch_add(cnt + kClCntFinal, 1, __ATOMIC_RELAXED, kClCntScope) == P - 1) ? 1 : 0;
     __syncthreads();
     if (s_last) {
         float fs = 1.0f;
@@ -859,50 +822,31 @@ linear_cluster_kernel(ClusterParams cp)
 
 struct ClusterShape { int Pmax, rpw, pitch, threads, ni; unsigned lds_scratch; size_t lds; size_t scratch_floats; };
 
-#ifndef LTR_CLUSTER_MIN_L
-#define LTR_CLUSTER_MIN_L 256
-#endif
-#ifndef LTR_CLUSTER_MAX_PER_CU
-#define LTR_CLUSTER_MAX_PER_CU 4
-#endif
+constexpr int kClMinL = 256;
 
 // Shapes the cluster kernel takes: lists the symmetric pair pass covers, rows of whole float4 that fit the
 // 1024-thread tile, and a batch that is small enough for the plain path to be out of balance.
 // labels: 1 = an integer label dtype (the hinge kinds can run by sorted runs), 0 = float labels, -1 = not known (plan queries)
 bool choose_cluster_shape(int kind, int B, int L, int F, ClusterShape &s, int labels = -1)
 {
-#ifdef LTR_NO_CLUSTER
-    return false;
-#endif
-    // runtime switch (read once): LTR_DISABLE_CLUSTER=1 keeps every shape on the one-workgroup-per-query kernels
-    static const bool disabled = [] { const char *e = getenv("LTR_DISABLE_CLUSTER"); return e && e[0] == '1'; }();
-    if (disabled) return false;
-#ifdef LTR_CLUSTER_NO_NDCG
-    if (kind == LTR_NDCG1 || kind == LTR_NDCG2) return false;
-#endif
-    if (L <= LTR_CLUSTER_MIN_L || L > kSymMaxLen) return false;
+    if (L <= kClMinL || L > kSymMaxLen) return false;
     if (F % 4 != 0 || F / 4 > kClThreads) return false;
     const int C = F / 4;
     // 512-thread workgroups where a sweep of them still covers whole rows well: two fit a CU (the
     // kernel needs ~85 VGPRs) and overlap one's loads with the other's pair pass; wide rows keep 1024
-#ifdef LTR_CLUSTER_THREADS
-    s.threads = LTR_CLUSTER_THREADS;
-#else
     s.threads = (C <= 128) ? 512 : kClThreads;
-#endif
     if (C > s.threads) return false;
     const int R = s.threads / C;
     // sweeps in registers: 19 for wide rows (fewer parts); 12 for long lists on mid-size batches, 8
     // otherwise (more, lighter workgroups: 32 x 1000 x 220 logistic 32 -> 28 us, 192 x 600 x 136 45 -> 37;
     // but C4 hinge 64 -> 73 with 8)
-    if (s.threads == 1024) s.ni = LTR_CLUSTER_NI_WIDE;
+    if (s.threads == 1024) s.ni = kClNIWide;
     else s.ni = kClNISmall;
     s.rpw = s.ni * R;
     s.Pmax = (L + s.rpw - 1) / s.rpw;
     // the light workgroups while a query needs at most 6 of them, or on the smallest batches (many
     // workgroups fill the chip); otherwise 12 sweeps: fewer parts, less exchanged per query
-    static const int light_max_b = [] { const char *e = getenv("LTR_CLUSTER_LIGHT_MAXB"); return e ? atoi(e) : 0; }();   // (tuning)
-    const int light_b = light_max_b > 0 ? light_max_b : device_cu_count() / 4;
+    const int light_b = device_cu_count() / 4;
     // Round 5: the hinge kinds on integer labels run the light members by sorted runs, not by the pair pass -- on the longest
     // lists they then beat the 12-sweep members at every batch size (cold sweep of 36 cells, B = 160 .. 384, us, 12 sweeps ->
     // light: 256 x 1000 x 220 59.0 -> 56.0 (C4), 160 x 1000 x 220 41.7 -> 38.4, 256 x 1000 x 136 46.9 -> 38.5, 384 x 1000 x 136
@@ -946,7 +890,6 @@ bool choose_cluster_shape(int kind, int B, int L, int F, ClusterShape &s, int la
         }
         // NDCG kinds: until round 3 every member repeated the two rankings (~12 us) and the kernel only paid for
         // B <= #CUs / 4; with the rank exchange (a member ranks its rows, round 4) they follow the heavy kinds
-        // (LTR_CLUSTER_NDCG_LIMIT in the environment: a batch limit for sweeps)
         // Measured cold against what the dispatcher took before (general / parts kernel; NDCG1 / NDCG2, us):
         //   32 x 1000 x 220 60.6 / 63.7 (the old cluster kernel) -> 35.9 / 37.2    128 x 1000 x 220 92 / 108 -> 62 / 80
         //   256 x 1000 x 220 164 / 158 -> 113 / 148     384 x 1000 x 220 169 / 162 -> 145 / 192 (!)
@@ -960,12 +903,7 @@ bool choose_cluster_shape(int kind, int B, int L, int F, ClusterShape &s, int la
             if (s.threads != 512) limit = cus / 8;
             else if (C > 96) limit = 0;              // (200 x 768 x 512: 147 / 166 against 96 / 120 on the parts kernel)
             else if (kind == LTR_NDCG2 && L >= 768) limit = cus;
-            static const int forced = [] { const char *e = getenv("LTR_CLUSTER_NDCG_LIMIT"); return e ? atoi(e) : 0; }();
-            if (forced > 0) limit = forced;
         }
-#ifdef LTR_CLUSTER_MAX_B
-        limit = LTR_CLUSTER_MAX_B;
-#endif
         if (B > limit) return false;
     }
     s.pitch = (F + 1 + 3) & ~3;
@@ -979,7 +917,7 @@ bool choose_cluster_shape(int kind, int B, int L, int F, ClusterShape &s, int la
     if (ndcg && scratch < 24 * L4) scratch = 24 * L4;               // rank arrays + packed keys / sort buffer
     if ((kind == LTR_HINGE || kind == LTR_DCG_HINGE) && s.threads == 512) {
         // the sorted runs, and behind them the tile vectors the 12-sweep members park while they search
-        const size_t need = runs_park_offset(L4, (size_t)s.rpw) + (s.ni > kClNISmall ? (size_t)LTR_RUNS_PARK * 16 * s.threads : 0);
+        const size_t need = runs_park_offset(L4, (size_t)s.rpw) + (s.ni > kClNISmall ? (size_t)kRunsPark * 16 * s.threads : 0);
         if (scratch < need) scratch = need;
     }
     scratch = (scratch + 15) & ~(size_t)15;
@@ -1005,8 +943,8 @@ int launch_cluster_kind(const ClusterParams &cp, const ClusterShape &s, hipStrea
         LTR_ENSURE_LDS((linear_cluster_kernel<KIND, 512, kClNI>), s.lds);
         hipLaunchKernelGGL((linear_cluster_kernel<KIND, 512, kClNI>), grid, dim3(512), s.lds, stream, cp);
     } else {
-        LTR_ENSURE_LDS((linear_cluster_kernel<KIND, 1024, LTR_CLUSTER_NI_WIDE>), s.lds);
-        hipLaunchKernelGGL((linear_cluster_kernel<KIND, 1024, LTR_CLUSTER_NI_WIDE>), grid, dim3(1024), s.lds, stream, cp);
+        LTR_ENSURE_LDS((linear_cluster_kernel<KIND, 1024, kClNIWide>), s.lds);
+        hipLaunchKernelGGL((linear_cluster_kernel<KIND, 1024, kClNIWide>), grid, dim3(1024), s.lds, stream, cp);
     }
     return (int)hipGetLastError();
 }
@@ -1020,8 +958,7 @@ int launch_cluster(int kind, const LinearParams &p, const ClusterShape &s, float
     cp.lp = p;
     cp.status = status_device_ptr(stream);
     cp.spin_limit = cluster_force_timeout() ? -1 : kClSpinLimit;
-    static const int env_mode = [] { const char *e = getenv("LTR_CLUSTER_MODE"); return e ? atoi(e) : 0; }();
-    cp.mode = cluster_debug_mode() | env_mode;
+    cp.mode = cluster_debug_mode();
     cp.Pmax = s.Pmax; cp.rpw = s.rpw; cp.pitch = s.pitch; cp.scratch_bytes = s.lds_scratch;
     cp.sbuf = scratch;
     // the counters: in the exchange area of this (device, stream), behind the parts kernel's control block

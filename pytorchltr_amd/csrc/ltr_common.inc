@@ -122,15 +122,9 @@ __device__ __forceinline__ int clamp_n(int64_t n, int L)
 // with ballots (uniform control flow, ~100 instructions), ties by lane order.  A bijection inside
 // each group and a pure function of n[]; every output is indexed by the query, so results do not
 // depend on it.
-#ifndef LTR_SCHED_SNAKE
-#define LTR_SCHED_SNAKE 2       // 0: never; 1: every odd round dealt backwards; 2: straight, back, back, straight
-#endif
-#ifndef LTR_SCHED_MAX_PER_CU
-#define LTR_SCHED_MAX_PER_CU 4        // register-tile kernel (B = 8 x #CUs: 22.1 -> 23.9 us with it)
-#endif
-#ifndef LTR_LOSS_SCHED_MAX_PER_CU
-#define LTR_LOSS_SCHED_MAX_PER_CU 16   // loss kernel, general fused kernel
-#endif
+constexpr int kSchedMaxPerCu = 4;        // register-tile kernel (B = 8 x #CUs: 22.1 -> 23.9 us with it)
+constexpr int kLossSchedMaxPerCu = 16;   // loss kernel, general fused kernel
+constexpr int kSchedLowBits = 3;         // low bits of n the selection ignores
 __device__ __forceinline__ int sched_query_sampled(const int64_t *__restrict__ n, int B, int L, int G, int tid,
                                                    int &nb_out, int pos, int round_cus = 0)
 {
@@ -140,7 +134,6 @@ __device__ __forceinline__ int sched_query_sampled(const int64_t *__restrict__ n
         const int u = pos >> 3;
         int jp = u / G;
         const int gam = u - jp * G;
-#if LTR_SCHED_SNAKE
         // (round_cus > 0: snake over the rounds of one workgroup per CU.  8 G block ids take one eighth of every group -- `jp`,
         // the jp-th longest eighth --, a round of round_cus CUs is `per` of those steps, and a CU hosts ids i, i + #CUs, ...:
         // dealt straight, the CUs of the first half of every round get the longer half of EVERY round's lists (B = 1024,
@@ -149,27 +142,19 @@ __device__ __forceinline__ int sched_query_sampled(const int64_t *__restrict__ n
             const int per = round_cus / (8 * G);                 // steps per round (256 CUs, G = 16: 2)
             if (per >= 2) {
                 const int rd = jp / per, base = rd * per;
-#if LTR_SCHED_SNAKE == 2
                 const int back = (rd ^ (rd >> 1)) & 1;           // straight, back, back, straight: the last round ends on the shortest lists
-#else
-                const int back = rd & 1;
-#endif
                 if (back && base + per <= 8) jp = base + (per - 1 - (jp - base));
             }
         }
-#endif
         int rho = jp * 8 + (pos & 7);                            // this block's member number
         const int id = ((lane >> 3) * G + gam) * 8 + (lane & 7); // member `lane` of the group
         unsigned long long cand = __ballot(id < B);              // a prefix of the lanes (ids grow with lane)
         const int key = clamp_n(n[min(id, B - 1)], L);
         // (all lists equally long, e.g. full lists: cand stays the whole group and rho the lane)
         const bool flat = __ballot(key != __builtin_amdgcn_readfirstlane(key)) == 0ull;
-        // (LTR_SCHED_LOW_BITS low bits of n are ignored: an approximate order balances as well and
+        // (the kSchedLowBits low bits of n are ignored: an approximate order balances as well and
         // every bit is one more dependent ballot round in front of the first load)
-#ifndef LTR_SCHED_LOW_BITS
-#define LTR_SCHED_LOW_BITS 3
-#endif
-        for (int bt = flat ? -1 : 31 - __builtin_clz(L); bt >= LTR_SCHED_LOW_BITS; --bt) {   // descending n: set bits first
+        for (int bt = flat ? -1 : 31 - __builtin_clz(L); bt >= kSchedLowBits; --bt) {   // descending n: set bits first
             const unsigned long long m = __ballot(((key >> bt) & 1) != 0) & cand;
             const int c = __popcll(m);
             if (rho < c) cand = m;
@@ -369,10 +354,7 @@ __device__ __forceinline__ void pair_rowweight(float sk, float ak, float sm, flo
 }
 
 // lists longer than this take the sort path (DPT == 0 instantiation of metric_kernel)
-#ifndef LTR_SORT_RANK_MIN
-#define LTR_SORT_RANK_MIN 256
-#endif
-constexpr int kSortRankMinLen = LTR_SORT_RANK_MIN;
+constexpr int kSortRankMinLen = 256;
 __host__ __device__ inline int sort_pow2(int L)
 {
     int P = 64;
@@ -898,13 +880,11 @@ __device__ __forceinline__ float lds_at_absdiff(unsigned base, int a, int b)
 // launch); raw: return the plain pair sum (no loss modifier, gscale untouched).
 // TW > 0: the workgroup has TW waves (compile-time: no dispatch-packet read, shifts instead of
 // divisions) and, when it owns the whole query, only as many of them take pair units as the query
-// has work for (at least LTR_SYM_MIN_STEPS steps per wave, a power of two of waves).  Measured (C2,
+// has work for (at least kSymMinSteps steps per wave, a power of two of waves).  Measured (C2,
 // fused hinge step, us): 1 step per wave 11.3, 4: 11.6, 8: 11.9, 16: 12.3 -- the pass is latency-
 // bound, more waves with fewer steps each win, so the default is 1 (every wave that can get a step).
 // Idle waves still publish a zero gradient slice.
-#ifndef LTR_SYM_MIN_STEPS
-#define LTR_SYM_MIN_STEPS 1
-#endif
+constexpr int kSymMinSteps = 1;
 #ifdef LTR_TRACE
 #define LTR_SYM_STAMP(i) do { if (trace && threadIdx.x == 0) trace[i] = (long long)wall_clock64(); } while (0)
 #else
@@ -950,9 +930,9 @@ __device__ __forceinline__ float pairwise_core_sym(const QueryLds &q, int nb, in
     const int S = (nt > 0) ? (32 * nt * nt - (32 - dlast)) : 0;
     int u, u1;
     if (TW > 0 && parts == 1 && (TW & (TW - 1)) == 0) {
-        // waves that take units: the largest power of two <= S / LTR_SYM_MIN_STEPS, in [1, TW]
+        // waves that take units: the largest power of two <= S / kSymMinSteps, in [1, TW]
         int sh = 0;
-        while ((2 << sh) <= TW && (2 << sh) * LTR_SYM_MIN_STEPS <= S) ++sh;
+        while ((2 << sh) <= TW && (2 << sh) * kSymMinSteps <= S) ++sh;
         W = 1 << sh;
         u = (wl * S) >> sh;
         u1 = (wl < W) ? ((wl + 1) * S) >> sh : u;
@@ -1180,22 +1160,15 @@ __device__ __forceinline__ float pairwise_core_sym(const QueryLds &q, int nb, in
     return total;
 }
 
-#ifndef LTR_SPLIT_WAVES
-#define LTR_SPLIT_WAVES 4
-#endif
-#ifndef LTR_SPLIT_MAX
-#define LTR_SPLIT_MAX 8
-#endif
-#ifndef LTR_SPLIT_MIN_STEPS
-#define LTR_SPLIT_MIN_STEPS 16
-#endif
+constexpr int kSplitMax = 8;
+constexpr int kSplitMinSteps = 16;
 __host__ __device__ inline int split_parts_for(int nb, int nsplit, int waves)
 {
     // a part should have at least ~16 pair steps per wave to be worth a workgroup (swept 8..96 with the
     // list-length order in place: C4 hinge 34.7 us at 96, 31.7 at 48, 28.4 at 16)
     const int nt = (nb + 63) >> 6;
     const int units = 32 * nt * nt;
-    int e = units / (LTR_SPLIT_MIN_STEPS * waves);
+    int e = units / (kSplitMinSteps * waves);
     e = e < 1 ? 1 : e;
     return e < nsplit ? e : nsplit;
 }
@@ -1244,13 +1217,8 @@ inline int device_cu_count()
 // workgroup per CU and up to `max_per_cu` of them (beyond that the order stops mattering).
 inline int sched_groups(int B, int max_per_cu)
 {
-#ifdef LTR_NO_SCHED
-    (void)B; (void)max_per_cu;
-    return 0;
-#else
     const int cus = device_cu_count();
     return (B > cus + cus / 8 && (long long)B <= (long long)max_per_cu * cus) ? (B + 63) / 64 : 0;
-#endif
 }
 
 // The loss kernel and the general fused kernel: the pass costs ~0.3 us per launch, which short
@@ -1261,7 +1229,7 @@ inline int sched_groups_for_lists(int B, int L)
 {
     if (L <= 64) return 0;
     if (L < 256 && B < 4 * device_cu_count()) return 0;
-    return sched_groups(B, LTR_LOSS_SCHED_MAX_PER_CU);
+    return sched_groups(B, kLossSchedMaxPerCu);
 }
 
 

@@ -112,9 +112,6 @@ __device__ __forceinline__ void pairwise_loss_body(const LossParams &p)
     const int L4 = kSym ? ((L + 63) & ~63) : ((L + 3) & ~3);
     const int msplit = kSym ? (T >> 6) : p.msplit; // gradient slices: per wave / per m-slice
     const QueryLds q = carve_query_lds<KIND>(smem, L4, msplit);
-#if defined(LTR_DEBUG_STOP) && LTR_DEBUG_STOP == 0
-    if (p.B >= 0) return;                        // tuning: launch + dispatch floor
-#endif
 
     // ---- stage this query's (score, label) row: coalesced 4 B / 8 B per lane.  The loads do
     // not wait for n[b] (they are issued for the whole row and only the first n[b] entries
@@ -124,9 +121,6 @@ __device__ __forceinline__ void pairwise_loss_body(const LossParams &p)
     if (KIND == LTR_NDCG1 || KIND == LTR_NDCG2)
         for (int m = tid; m < 2 * L4; m += T) q.rank_s[m] = 0;
     __syncthreads();
-#if defined(LTR_DEBUG_STOP) && LTR_DEBUG_STOP == 1
-    if (p.B >= 0) { if (tid == 0) p.loss[b] = q.sy[0].x; return; }   // tuning: + staging
-#endif
 
     float gscale, gsum;
     float total;
@@ -149,9 +143,6 @@ __device__ __forceinline__ void pairwise_loss_body(const LossParams &p)
         total = pairwise_core<KIND, (DPT > 0 ? DPT : 1)>(q, nb, L4, msplit, p.sigma, gscale, gsum);
     }
     (void)gsum;
-#if defined(LTR_DEBUG_STOP) && LTR_DEBUG_STOP == 2
-    if (p.B >= 0) { if (tid == 0) p.loss[b] = total; return; }       // tuning: + pair pass
-#endif
 
     if (tid == 0) p.loss[b] = total;
     if (p.dscores != nullptr) {
@@ -886,7 +877,6 @@ LaunchShape choose_shape(int B, int L)
 // is why they want their ~8 k pairs per wave where the hinge kinds take 32 k.)
 LaunchShape choose_loss_shape(int kind, int B, int L)
 {
-#ifndef LTR_NO_SYM
     if (L <= kLossSymMaxLen) {
         LaunchShape s;
         s.dpt = 0;
@@ -911,7 +901,6 @@ LaunchShape choose_loss_shape(int kind, int B, int L)
         s.msplit = waves;
         return s;
     }
-#endif
     (void)kind;
     return choose_shape(B, L);
 }
@@ -973,7 +962,7 @@ int launch_loss(int kind, const LossParams &p, const LaunchShape &s, hipStream_t
 
 // How many workgroups share a query in the split launch (1 = use the one-kernel path): long lists
 // only, and only while the batch alone cannot give every CU several queries to balance with.
-constexpr int kSplitWaves = LTR_SPLIT_WAVES;   // waves per part: small workgroups, many per CU
+constexpr int kSplitWaves = 4;   // waves per part: small workgroups, many per CU
 static int choose_loss_splits(int kind, int B, int L)
 {
     if (L <= 256 || L > kLossSymMaxLen) return 1;
@@ -999,8 +988,8 @@ static int choose_loss_splits(int kind, int B, int L)
     if (2 * B > 3 * cus && !(!ndcg && B <= 2 * cus && L > 640)) return 1;
     // up to 8 parts per query; 16 on the smallest batches (64 x 1000: hinge 22.4 -> 16.5 us, logistic
     // 28.6 -> 20.7, LambdaNDCG2 55 -> 45; at 128 x 600 and above 8 is better)
-    const int cap = (4 * B <= cus) ? 2 * LTR_SPLIT_MAX : LTR_SPLIT_MAX;
-    int s = (LTR_SPLIT_MAX * cus) / (B > 0 ? B : 1);
+    const int cap = (4 * B <= cus) ? 2 * kSplitMax : kSplitMax;
+    int s = (kSplitMax * cus) / (B > 0 ? B : 1);
     if (s > cap) s = cap;
     return s < 2 ? 1 : s;
 }
@@ -1034,7 +1023,6 @@ template <int OP>
 int launch_metric(const MetricParams &p0, hipStream_t stream)
 {
     MetricParams p = p0;
-#ifndef LTR_NO_SORT_RANK
     if (p.L > kSortRankMinLen) {
         const int P = sort_pow2(p.L);
         int T = P < 1024 ? P : 1024;                    // E = P / T <= 4 keys per thread
@@ -1058,7 +1046,6 @@ int launch_metric(const MetricParams &p0, hipStream_t stream)
         }
         return (int)hipGetLastError();
     }
-#endif
     LaunchShape s = choose_shape(p.B, p.L);
     // (many rounds of queries per CU: ONE wave per query, two documents per thread -- what bounds the launch then is the number of
     // queries a CU has in flight, see choose_loss_shape.  Lists of 128, round 6: ndcg@10 65 536 queries 116 -> 99 us, 2^20: 1667 ->
@@ -1190,11 +1177,7 @@ int ltr_pairwise_loss_ws_f32(int kind, float sigma, const float *scores, const v
     LossParams p;
     p.scores = scores; p.rel = rel; p.n = n; p.loss = loss; p.dscores = dscores;
     p.B = B; p.L = L; p.sigma = sigma; p.rel_dtype = rel_dtype; p.msplit = kSplitWaves;
-#ifdef LTR_NO_SPLIT_SCHED
-    p.sched = 0;
-#else
     p.sched = (B >= 16) ? (B + 63) / 64 : 0;            // (ignored by the part-major order)
-#endif
     float *ws = (float *)workspace;
     hipStream_t st = (hipStream_t)stream;
     switch (kind) {

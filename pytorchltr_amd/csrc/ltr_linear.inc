@@ -23,16 +23,9 @@
 
 namespace {
 
-#ifndef LTR_LINEAR_THREADS
-#define LTR_LINEAR_THREADS 512
-#endif
-#ifndef LTR_P1_UNR
-#define LTR_P1_UNR 4
-#endif
-#ifndef LTR_P3_UNR
-#define LTR_P3_UNR 4
-#endif
-constexpr int kLinearThreads = LTR_LINEAR_THREADS;
+constexpr int kP1Unr = 4;
+constexpr int kP3Unr = 4;
+constexpr int kLinearThreads = 512;
 
 // Per-query partials: row b of a (B, PF) row-major matrix, PF = partial_pitch(F) floats:
 // [d loss[b]/dW_0 .. dW_{F-1} | d loss[b]/d bias | zero padding to a multiple of 4].  A query's row is
@@ -187,15 +180,12 @@ __device__ __forceinline__ void linear_pairwise_body(const LinearParams &p)
         for (int m = tid; m < 2 * L4; m += T) q.rank_s[m] = 0;
     const float bias = p.bias ? p.bias[0] : 0.f;
     __syncthreads();
-#if defined(LTR_DEBUG_STOP) && LTR_DEBUG_STOP == 0
-    if (p.B >= 0) return;
-#endif
 
     // ---- phase 1: scores = X.W + bias, one wave per row, 4 rows in flight per wave ----
     {
         const int nrows = p.scores_out ? L : nb;
         const V *wv = reinterpret_cast<const V *>(wl);
-        constexpr int UNR = LTR_P1_UNR;
+        constexpr int UNR = kP1Unr;
         for (int l0 = wave; l0 < nrows; l0 += nwaves * UNR) {
             float acc[UNR];
 #pragma unroll
@@ -223,9 +213,6 @@ __device__ __forceinline__ void linear_pairwise_body(const LinearParams &p)
         }
     }
     __syncthreads();
-#if defined(LTR_DEBUG_STOP) && LTR_DEBUG_STOP == 1
-    if (p.B >= 0) { if (tid == 0) p.loss[b] = q.sy[0].x; return; }   // tuning: phase 1 only
-#endif
 
     // ---- phase 2: pair pass ----
     float gscale, gsum = 0.f;
@@ -256,9 +243,6 @@ __device__ __forceinline__ void linear_pairwise_body(const LinearParams &p)
     }
     if (kSym) gsum = block_sum(gs, q.red);        // d/d bias; its barriers also publish gfin
     else __syncthreads();
-#if defined(LTR_DEBUG_STOP) && LTR_DEBUG_STOP == 2
-    if (p.B >= 0) { if (tid == 0) p.part[(size_t)b * partial_pitch(F)] = gsum; return; }        // tuning: phases 1+2
-#endif
 
     // ---- phase 3: dW_b[f] = sum_l gfin[l] * X[b,l,f] ----
     float *part = p.part + (size_t)b * partial_pitch(F);    // this query's row of the partials
@@ -272,7 +256,7 @@ __device__ __forceinline__ void linear_pairwise_body(const LinearParams &p)
             const int c = c0 + cl;
             if (r < R && c < C) {
                 V acc = vzero<V>();
-                constexpr int UNR = LTR_P3_UNR;
+                constexpr int UNR = kP3Unr;
                 for (int l0 = r; l0 < nb; l0 += R * UNR) {
                     V x[UNR];
                     float g[UNR];
@@ -280,13 +264,9 @@ __device__ __forceinline__ void linear_pairwise_body(const LinearParams &p)
                     for (int u = 0; u < UNR; ++u) {
                         const int lf = l0 + u * R;
                         const bool ok = lf < nb;
-#ifndef LTR_P3_FORWARD
                         // rows in REVERSE: the rows phase 1 streamed last are the likeliest to be
                         // still in L2 / Infinity Cache (C5 full lists 264 -> 249 us)
                         const int l = ok ? nb - 1 - lf : 0;
-#else
-                        const int l = lf;
-#endif
                         g[u] = ok ? gfin[l] : 0.f;
                         x[u] = ok ? reinterpret_cast<const V *>(Xq + (size_t)l * F)[c] : vzero<V>();
                     }
@@ -328,21 +308,12 @@ __device__ __forceinline__ void linear_pairwise_body(const LinearParams &p)
 // Features cross HBM exactly once and never touch LDS.  Four workgroups (32 waves) per CU:
 // some compute while the others' loads are in flight.
 // ---------------------------------------------------------------------------------
-#ifndef LTR_REGTILE_THREADS
-#define LTR_REGTILE_THREADS 512       // measured sweet spot on MI355X (256..1024 swept)
-#endif
-#ifndef LTR_REGTILE_MINW
-#define LTR_REGTILE_MINW 6       // waves/SIMD the register allocator must allow (<= 80 VGPRs)
-#endif
-constexpr int kRegtileThreads = LTR_REGTILE_THREADS;
+constexpr int kRegtileMinW = 6;       // waves/SIMD the register allocator must allow (<= 80 VGPRs)
+constexpr int kRegtileThreads = 512;       // measured sweet spot on MI355X (256..1024 swept)
 
 // LDS after the query block: gfin float[L4], then max(pd float[L*(C+1)], dred float4[R*C]).
 // (L <= 256: symmetric pair pass -- LDS rows padded to 64-wide tiles, one slice per wave)
-#ifdef LTR_FUSED_NO_SYM
-__host__ __device__ inline bool regtile_sym(int L) { (void)L; return false; }
-#else
 __host__ __device__ inline bool regtile_sym(int L) { return L <= 256; }
-#endif
 __host__ __device__ inline int regtile_stride(int L) { return regtile_sym(L) ? ((L + 63) & ~63) : ((L + 3) & ~3); }
 
 __host__ __device__ inline size_t regtile_lds_bytes(int kind, int L, int F, int msplit)
@@ -409,9 +380,7 @@ __host__ __device__ inline size_t lazy_area_words(int F)
 // NI = 19 at TT = 512 (round 4): the lists the 9- / 12-sweep tiles cannot hold, at <= 128 VGPRs (two workgroups per
 // CU) -- see choose_regtile_shape.  TT = 1024 (nine sweeps, two workgroups per CU at <= 64 VGPRs) was built for the
 // same lists first and is not instantiated any more (8-9 % slower than 19 sweeps; EXPERIMENTS.md).
-#ifndef LTR_REGTILE_MINW1024
-#define LTR_REGTILE_MINW1024 8
-#endif
+constexpr int kRegtileMinW1024 = 8;
 // a * b rounded to fp32 on its own: the product is opaque to the compiler, which may not contract it with the sum behind it
 // (__fmul_rn is a plain multiplication in HIP)
 __device__ __forceinline__ float mul_rounded(float a, float b)
@@ -626,7 +595,7 @@ linear_regtile2_kernel(LinearParams p)
 }
 
 template <int KIND, int NI, int CT, int TT>
-__global__ void __launch_bounds__(TT, (TT == 512 ? (NI >= 19 ? 4 : LTR_REGTILE_MINW) : (TT == 1024 ? (NI <= 9 ? LTR_REGTILE_MINW1024 : 4) : 4)))
+__global__ void __launch_bounds__(TT, (TT == 512 ? (NI >= 19 ? 4 : kRegtileMinW) : (TT == 1024 ? (NI <= 9 ? kRegtileMinW1024 : 4) : 4)))
 linear_regtile2w_kernel(LinearParams p)
 {
     linear_regtile2_body<KIND, NI, CT, TT>(p);
@@ -776,7 +745,6 @@ __device__ __forceinline__ void linear_regtile2_body(const LinearParams &p)
     }
     __syncthreads();
     LTR_STAMP2(1);
-    LTR_STOP_AFTER(1, pd[0]);
     {
         const int h = tid & 3;
         for (int l = tid >> 2; l < nb; l += T >> 2) {
@@ -810,7 +778,6 @@ __device__ __forceinline__ void linear_regtile2_body(const LinearParams &p)
         prepare_ndcg<KIND, 1, msplit, true>(q, nb, owners, tid % owners, m0, m1, ms > 1);
     }
     LTR_STAMP2(3);
-    LTR_STOP_AFTER(2, q.sy[0].x);
     // (integer label dtypes: the hinge kinds take the sign of a label difference from one v_med3)
     const bool intlab = (KIND == LTR_HINGE || KIND == LTR_DCG_HINGE) && p.rel_dtype != LTR_LABEL_F32;
     const float total = intlab ? pairwise_core_sym<KIND, msplit, true, true>(q, nb, L4, p.sigma, gscale LTR_SYM_TRACE_ARGS)
@@ -1121,12 +1088,8 @@ bool choose_linear_shape(int kind, int B, int L, int F, int vec, LinearShape &s)
     // threads, us: hinge 2048 x 300 x 64 51.6 -> 47.2, 4096 x 300 x 64 100.6 -> 88.1, 16 384 x 300 x 32 392 -> 316, 2048 x 128 x 45
     // 26.4 -> 20.2, 65 536 x 128 x 45 751 -> 496, LambdaNDCG2 16 384 x 128 x 45 259 -> 181; at 1024 queries 29.6 -> 41.9 and
     // 15.3 -> 16.0: not below eight per CU.  (128 threads: 65 536 x 128 x 45 439, but 4096 x 600 x 32 204 -> 259.)
-#ifdef LTR_LINEAR_T
-    const int T = LTR_LINEAR_T;
-#else
     const int cus = device_cu_count();
     const int T = (B <= 2 * cus) ? 1024 : (B >= 8 * cus ? 256 : kLinearThreads);
-#endif
     s.threads = T;
     const int C = F / vec;
     const int CT = C < T ? C : T;               // column vectors per phase-3 tile
@@ -1198,9 +1161,6 @@ struct RegtileShape { int ni, msplit; size_t lds; int v2, threads; };
 
 bool choose_regtile_shape(int kind, int L, int F, RegtileShape &s)
 {
-#if defined(LTR_NO_REGTILE)
-    return false;
-#endif
     if (F % 4 != 0 || L > kRegtileThreads) return false;
     const int C = F / 4;
     if (C > kRegtileThreads) return false;
@@ -1223,12 +1183,11 @@ bool choose_regtile_shape(int kind, int L, int F, RegtileShape &s)
         // 1024-thread tile of nine sweeps, two per CU, was built first this round and is 8-9 % slower than this one:
         // 24.4 us at 1024 x 256 x 136 -- and 45 % slower than the 512-thread tile on shapes that one holds, EXPERIMENTS.md;
         // the NDCG kinds on it are slower than the general kernel)
-        static const bool no19 = [] { const char *e = getenv("LTR_NO_REGTILE19"); return e && e[0] == '1'; }();
         // (24 sweeps: 216 documents at F = 220 -- Istella-S reaches 182 -- in 116-121 VGPRs for the rank-free kinds; the
         // NDCG kinds spill 4-12 registers under the 128 there and still beat the two-pass kernel: 1024 x 200 x 220
         // LambdaNDCG1 / 2 43.9 / 44.6 -> 37.5 / 39.5 us, 512 x 200 x 220 40.9 -> 24.9)
         const int nsw = (ni <= 19) ? 19 : ((ni <= 24) ? 24 : 0);
-        if (no19 || !regtile_sym(L) || nsw == 0) return false;
+        if (!regtile_sym(L) || nsw == 0) return false;
         const size_t lds19 = regtile2_lds_bytes(kind, L, F, nsw, kRegtileThreads);
         if (lds19 > 78 * 1024) return false;
         s.ni = nsw; s.msplit = kRegtileThreads / 64; s.lds = lds19; s.v2 = 1; s.threads = kRegtileThreads;
@@ -1499,11 +1458,10 @@ inline size_t linear_partials_bytes(int B, int F)
 
 namespace {
 // The cluster kernel takes the shapes it covers first (small batches of lists the symmetric pass takes: measured
-// faster than the parts kernel there, round 4); LTR_PARTS_FIRST=1 is the A/B switch of the development builds
+// faster than the parts kernel there, round 4)
 inline bool prefer_cluster()
 {
-    static const bool v = [] { const char *e = getenv("LTR_PARTS_FIRST"); return !(e && e[0] == '1'); }();
-    return v && !parts_debug_all();          // (tests of the parts kernel: ltr_debug_parts_all puts it first, too)
+    return !parts_debug_all();          // (tests of the parts kernel: ltr_debug_parts_all puts it first)
 }
 }  // namespace
 
@@ -1620,24 +1578,14 @@ int linear_partials_launch(int kind, float sigma, const float *X, const float *W
     p.sched = 0;
     RegtileShape rs;
     const bool allow_fast = LTR_TRACE_ALLOW_FAST(scores_out);
-#ifdef LTR_DEV_SUBSET
-    {   // development build: the parts kernel only (scripts/dev/spills.py)
-        PartsShape ps0;
-        if (!choose_parts_shape(kind, B, L, F, ps0)) return LTR_ERR_CONFIG;
-        p.msplit = 0; p.rows_r = 0; p.sched = 0;
-        return launch_parts(kind, p, ps0, (hipStream_t)stream);
-    }
-#endif
     if (vec == 4 && allow_fast && choose_regtile_shape(kind, L, F, rs)) {
         p.msplit = rs.msplit; p.rows_r = 0;
-#ifndef LTR_NO_SCHED
         // (lists of 64 and fewer do not win the pass back: 512 x 64 x 136 6.7 -> 7.0 us; 1024 x 96: 11.3 -> 10.4)
-        p.sched = (L > 64) ? sched_groups(B, LTR_SCHED_MAX_PER_CU) : 0;
+        p.sched = (L > 64) ? sched_groups(B, kSchedMaxPerCu) : 0;
         // (snake dealing of the rounds, sched_query_sampled: measured round 6 on 1024 x 128 x 136 with four workgroups per CU resident --
         // LambdaNDCG2 16.6 -> 16.1 us, logistic 14.0 -> 13.5, hinge 11.84 -> 11.82: the kinds with compute behind their loads are
         // bound by their most loaded CU.  EXPERIMENTS.md round 6)
         if (p.sched) p.sched |= device_cu_count() << 16;
-#endif
         if (lazy) {
             if (!rs.v2) return LTR_ERR_CONFIG;             // (the caller checked: lazy_layout_g)
             p.part_g = lazy->part_g;
@@ -1651,10 +1599,7 @@ int linear_partials_launch(int kind, float sigma, const float *X, const float *W
             // four columns per reducer + the losses' one
             p.pend_nred = (F + 1 + 3) / 4 + 1;
             p.pend_general = (p.pend_mb || p.pend_wptr || !p.pend_W) ? 1 : 0;
-            {
-                static const int forced = [] { const char *e = getenv("LTR_LAZY_SLEEP"); return e ? atoi(e) : -1; }();
-                p.pend_sleep = forced >= 0 ? forced : 2;           // (a reducer sums ~1024 rows at most, whatever the batch size)
-            }
+            p.pend_sleep = 2;           // (a reducer sums ~1024 rows at most, whatever the batch size)
             p.status = status_device_ptr((hipStream_t)stream);
             p.spin_limit = cluster_force_timeout() ? -1 : (lazy->mb ? 0x7fffffff : (1 << 22));
         }
@@ -1943,7 +1888,7 @@ int ltr_linear_step_f32(int kind, float sigma, const float *X, const float *W, c
 namespace {
 // how long one all-reduce waits for its peers before it gives up (a collective library's watchdog waits minutes: a
 // rank may be late by a checkpoint, an evaluation pass, a stalled data loader).  LTR_MAILBOX_TIMEOUT_MS in the
-// environment (read once) or ltr_debug_mailbox_timeout_ms() override the default of 120 s.
+// environment (read once) or ltr_mailbox_set_timeout_ms() override the default of 120 s.
 inline long long *mailbox_timeout_ms()
 {
     static long long v = [] { const char *e = getenv("LTR_MAILBOX_TIMEOUT_MS"); const long long x = e ? atoll(e) : 0; return x > 0 ? x : 120000ll; }();
@@ -2224,12 +2169,6 @@ int ltr_linear_sgd_step_f32(int kind, float sigma, const float *X, float *W, flo
 // does not take, the pending update is flushed first and the step runs as the plain launch.
 // ---------------------------------------------------------------------------------------------
 namespace {
-// tuning / tests: LTR_DISABLE_LAZY=1 -- every lazy step flushes first and runs the plain launch
-inline bool lazy_disabled()
-{
-    static const bool v = [] { const char *e = getenv("LTR_DISABLE_LAZY"); return e && e[0] == '1'; }();
-    return v;
-}
 struct LazyArea { int device; hipStream_t stream; unsigned tag; unsigned long long *gran; size_t cap; };
 struct LazyAreas { std::mutex m; std::deque<LazyArea> v; };
 inline LazyAreas *lazy_areas() { static LazyAreas *a = new LazyAreas(); return a; }     // (a pointer: this sits inside extern "C")
@@ -2295,7 +2234,7 @@ bool stream_is_capturing(hipStream_t stream)
 static bool lazy_one_round(int B) { return B <= 4 * device_cu_count(); }
 static bool lazy_layout_g(int kind, int B, int L, int F)
 {
-    if (B <= 0 || F % 4 != 0 || lazy_disabled() || !lazy_one_round(B)) return false;
+    if (B <= 0 || F % 4 != 0 || !lazy_one_round(B)) return false;
     RegtileShape rs;
     return choose_regtile_shape(kind, L, F, rs) && rs.v2;
 }

@@ -153,10 +153,7 @@ __device__ __forceinline__ int mlp_schedule(const int64_t *__restrict__ n, int B
         __syncthreads();
         return nq;
     }
-#ifndef LTR_MLP_SAMPLED_SCHED
-#define LTR_MLP_SAMPLED_SCHED 1
-#endif
-    if (LTR_MLP_SAMPLED_SCHED && (long long)B <= 4LL * G) {
+    if ((long long)B <= 4LL * G) {
         // A few queries per workgroup (the named batch: two): the order only has to balance the workgroups,
         // so the approximate, one-wave selection of the fused-linear kernels does (sched_query_sampled: 64
         // sampled lengths per position, ballots only, one barrier) -- ~1 k cycles per position against the
@@ -874,9 +871,7 @@ mlp_reduce_kernel(const float *__restrict__ part, int nPart, int P, int pitch, f
 // The same sum with 16-byte loads: a block takes COLS4 float4 columns x 1024 / COLS4 row slices (every
 // load instruction of a wave moves COLS4 * 16 contiguous bytes of 64 / COLS4 rows -- four times fewer, wider
 // requests than the 4-byte version for the same 15 MB), the slices meet in LDS in two levels.  Fixed order.
-#ifndef LTR_MLP_RED_COLS4
-#define LTR_MLP_RED_COLS4 16
-#endif
+constexpr int kMlpRedCols4 = 16;
 template <int COLS4>
 __global__ void __launch_bounds__(1024)
 mlp_reduce4_kernel(const float *__restrict__ part, int nPart, int P, int pitch, float *__restrict__ grads,
@@ -946,17 +941,9 @@ inline int mlp_grid(int B)
 
 #include "ltr_mlp2.inc"
 
-// LTR_MLP_LAYOUT=1 in the environment (or ltr_debug_mlp_layout(1)) keeps the training step on the
-// 8-wave kernel of this file (A/B measurements, tests of both kernels; the 4-wave tile kernel of
-// ltr_mlp2.inc is the default where it applies)
-inline int &mlp_layout_choice()
-{
-    static int choice = [] {
-        const char *e = getenv("LTR_MLP_LAYOUT");
-        return e ? atoi(e) : 0;
-    }();
-    return choice;
-}
+// ltr_debug_mlp_layout(1) keeps the training step on the 8-wave kernel of this file (A/B measurements,
+// tests of both kernels; the 4-wave tile kernel of ltr_mlp2.inc is the default where it applies)
+inline int &mlp_layout_choice() { static int choice = 0; return choice; }
 
 // auto (0): the tile kernel where the batch gives every CU its two workgroups (B >= 2 x CUs) or the
 // lists are longer than the 8-wave kernel takes; below that the 8-wave kernel is 1.5-2 us faster
@@ -1080,7 +1067,7 @@ int ltr_mlp_pairwise_f32(int kind, float sigma, const float *X, const float *W1,
     // (grads as float4 needs a 16-byte aligned output; otherwise the 4-byte version)
     if ((reinterpret_cast<uintptr_t>(grads) & 15) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0) {
         const int P4 = mlp_pitch(P) >> 2;
-        hipLaunchKernelGGL(mlp_reduce4_kernel<LTR_MLP_RED_COLS4>, dim3((unsigned)((P4 + LTR_MLP_RED_COLS4 - 1) / LTR_MLP_RED_COLS4)),
+        hipLaunchKernelGGL(mlp_reduce4_kernel<kMlpRedCols4>, dim3((unsigned)((P4 + kMlpRedCols4 - 1) / kMlpRedCols4)),
                            dim3(1024), 0, s, (const float *)workspace, grid, P, mlp_pitch(P), grads, loss, B, loss_sum);
         return (int)hipGetLastError();
     }

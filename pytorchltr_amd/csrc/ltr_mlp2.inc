@@ -45,9 +45,7 @@
 constexpr int kM2Threads = 256;
 constexpr int kM2Waves = 4;
 constexpr int kM2Docs = 32;          // rows per fill (two 16-document subtiles)
-#ifndef LTR_M2_WGS
-#define LTR_M2_WGS 2                  // workgroups per CU the launch bounds and the grid are sized for
-#endif
+constexpr int kM2Wgs = 2;                  // workgroups per CU the launch bounds and the grid are sized for
 constexpr int kM2MaxLen = 256;       // longest list: 8 fills (lists over 128: no parking, see below)
 constexpr int kM2ParkLen = 128;      // lists up to here park the tiles of their first fills in LDS
 constexpr int kM2PS = 20;            // row pitch (floats) of the partial / scratch / dH2 images
@@ -94,7 +92,7 @@ using m2_ns = std::integral_constant<int, NS>;
 // wave stores one dword.  What this takes is what the fills + MFMA chains of ONE workgroup per two SIMD-slots can do
 // at this batch size; the fused step is judged against it.  The numbers it computes mean nothing.
 template <int KIND, int NT, int CT, int LT, bool FWD = false, bool PROBE = false>
-__global__ void __launch_bounds__(kM2Threads, LTR_M2_WGS)
+__global__ void __launch_bounds__(kM2Threads, kM2Wgs)
 mlp_tile_kernel(MlpParams p)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -179,13 +177,6 @@ mlp_tile_kernel(MlpParams p)
     const int nq = mlp_schedule<T, LT>(p.n, p.B, L, qlist, reinterpret_cast<unsigned *>(img), FWD);
     const int nqueries = nq < 0 ? (p.B - (int)blockIdx.x + G - 1) / G : nq;
     M2_STAMP(9);                                   // scheduling
-#ifdef LTR_MLP_TRACE_SCHED2
-    {   // tuning: the same pass a second time (warm instruction cache, n[] in the L2): slot 12
-        const int nq2 = mlp_schedule<T, LT>(p.n, p.B, L, qlist, reinterpret_cast<unsigned *>(img), FWD);
-        if (nq2 != nq) __builtin_trap();
-        M2_STAMP(12);
-    }
-#endif
     auto query_at = [&](int qi) { return nq < 0 ? (int)blockIdx.x + qi * G : qlist[qi]; };
     // the feature columns F .. 16*NT+3 of the image are never written by a fill: zero them once
     // (layer 1 multiplies them by zero weights, the dW1 columns they produce are not stored)
@@ -560,7 +551,7 @@ mlp_tile_kernel(MlpParams p)
 // ---- host side ----
 inline int mlp2_grid(int B)
 {
-    const int wgs = LTR_M2_WGS * device_cu_count();
+    const int wgs = kM2Wgs * device_cu_count();
     return B < wgs ? B : wgs;
 }
 

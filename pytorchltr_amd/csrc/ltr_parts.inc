@@ -61,69 +61,24 @@ constexpr int kPtMaxCV = 3;                     // column vectors per thread and
 //   2 workgroups per CU, <= 256 VGPRs: 36 / 40 / 42
 //   3 per CU, <= 168 VGPRs:            21 / 22 / 21
 //   4 per CU, <= 128 VGPRs:            14 / 12 / 12
-#ifndef LTR_NI_RD
-#define LTR_NI_RD 24        // registers the ranked hinge formulation's call needs of the tile's
-#endif
-#ifndef LTR_NI_O2
-#define LTR_NI_O2 0
-#endif
-#ifndef LTR_NI_O3
-#define LTR_NI_O3 0
-#endif
-#ifndef LTR_NI_O4
-#define LTR_NI_O4 0
-#endif
-#ifndef LTR_NI_U2
-#define LTR_NI_U2 0
-#endif
-#ifndef LTR_NI_U3
-#define LTR_NI_U3 0
-#endif
-#ifndef LTR_NI_U4
-#define LTR_NI_U4 0
-#endif
-// (the symmetric split pass -- sym -- carries the visitor's gradient through the rotation: a few registers more)
-__host__ __device__ constexpr int parts_ni_base(int wpc, int cv, bool sym)
+constexpr int kPtNIRanked = 24;        // registers the ranked hinge formulation's call needs of the tile's
+__host__ __device__ constexpr int parts_ni_base(int wpc, int cv)
 {
-    return sym ? (wpc == 2 ? (cv == 1 ? 48 + LTR_NI_U2 : (cv == 2 ? 24 + LTR_NI_U2 / 2 : 15 + LTR_NI_U2 / 3))
-                : wpc == 3 ? (cv == 1 ? 26 + LTR_NI_U3 : (cv == 2 ? 13 + LTR_NI_U3 / 2 : 8 + LTR_NI_U3 / 3))
-                           : (cv == 1 ? 14 + LTR_NI_U4 : (cv == 2 ? 7 + LTR_NI_U4 / 2 : 4 + LTR_NI_U4 / 3)))
-               : (wpc == 2 ? (cv == 1 ? 46 + LTR_NI_O2 : (cv == 2 ? 23 + LTR_NI_O2 / 2 : 16 + LTR_NI_O2 / 3))
-                : wpc == 3 ? (cv == 1 ? 27 + LTR_NI_O3 : (cv == 2 ? 13 + LTR_NI_O3 / 2 : 9 + LTR_NI_O3 / 3))
-                           : (cv == 1 ? 17 + LTR_NI_O4 : (cv == 2 ? 8 + LTR_NI_O4 / 2 : 5 + LTR_NI_O4 / 3)));
+    return wpc == 2 ? (cv == 1 ? 46 : (cv == 2 ? 23 : 16))
+         : wpc == 3 ? (cv == 1 ? 27 : (cv == 2 ? 13 : 9))
+                    : (cv == 1 ? 17 : (cv == 2 ? 8 : 5));
 }
 // (ranked: the counting formulation of the hinge kinds is a real call under the register-resident tile -- the
 // callee's registers come out of the tile's, or the caller spills them around the call)
 // (kind: the NDCG kinds' rankings and pair step need a few registers more -- sweeps fewer in the tile)
-#ifndef LTR_NI_N1
-#define LTR_NI_N1 1
-#endif
-#ifndef LTR_NI_N2
-#define LTR_NI_N2 1
-#endif
-__host__ __device__ constexpr int parts_ni(int wpc, int cv, bool sym = false, bool ranked = false, int kind = -1)
+constexpr int kPtNINdcg1 = 1;
+constexpr int kPtNINdcg2 = 1;
+__host__ __device__ constexpr int parts_ni(int wpc, int cv, bool ranked = false, int kind = -1)
 {
-    return (ranked ? parts_ni_base(wpc, cv, false) - (LTR_NI_RD / 4 + cv - 1) / cv : parts_ni_base(wpc, cv, sym))
-           - (kind == LTR_NDCG1 ? LTR_NI_N1 : (kind == LTR_NDCG2 ? LTR_NI_N2 : 0))
+    return parts_ni_base(wpc, cv) - (ranked ? (kPtNIRanked / 4 + cv - 1) / cv : 0)
+           - (kind == LTR_NDCG1 ? kPtNINdcg1 : (kind == LTR_NDCG2 ? kPtNINdcg2 : 0))
            - (((kind == LTR_NDCG1 || kind == LTR_NDCG2) && cv == 1 && wpc == 3) ? 1 : 0);
 }
-
-// SYM: the last parts_lds_sweeps() row sweeps of the tile live in LDS, not in registers, from their dot products
-// to the dW fold (thread-private 16-byte slots: the vector is stored behind its dot product and read straight
-// into the fold's multiply-add): between the two -- the exchanges, the pair pass with its visitor chains -- a
-// register file of 256 / 168 per lane holds the other sweeps and the working set without a spill.  As many
-// sweeps as the LDS of a workgroup has room for next to the longest list.  parts_park() = their float4 per thread.
-#ifndef LTR_PARTS_LDS_SWEEPS2
-#define LTR_PARTS_LDS_SWEEPS2 8
-#endif
-#ifndef LTR_PARTS_LDS_SWEEPS3
-#define LTR_PARTS_LDS_SWEEPS3 2
-#endif
-__host__ __device__ constexpr int parts_lds_sweeps(int wpc, int cv)
-{
-    return wpc == 2 ? (LTR_PARTS_LDS_SWEEPS2 + cv - 1) / cv : (wpc == 3 ? (LTR_PARTS_LDS_SWEEPS3 + cv - 1) / cv : 0);
-}
-__host__ __device__ constexpr int parts_park(int wpc, int cv) { return parts_lds_sweeps(wpc, cv) * cv; }
 
 constexpr int kPtMaxParts = 32;                 // parts per query (classes of the counting sort)
 constexpr int kPtMaxB = 8192;
@@ -132,25 +87,14 @@ constexpr int kPtSpinLimit = 1 << 18;
 // [0] tag of the NEXT launch (0 = 1) | [4] tickets drawn | [5] workgroups gone | [8 + b] arrivals of query b
 constexpr int kPtCtrlHeader = 8;
 constexpr size_t kPtCtrlBytes = kExCtrlBytes;   // the control region of the exchange area (ltr_linear.inc), fixed: the shares start behind it
-#ifndef LTR_PARTS_SLEEP
-#define LTR_PARTS_SLEEP 4
-#endif
-#ifndef LTR_PARTS_NCH
-#define LTR_PARTS_NCH 4                  // visitor chains per wave in the symmetric split pass (2 or 4)
-#endif
-#ifndef LTR_PARTS_COMBINE_INFLIGHT
-#define LTR_PARTS_COMBINE_INFLIGHT 8      // shares per thread in flight when a query's shares are added up
-#endif
+constexpr int kPtSleep = 4;
+constexpr int kPtCombineInflight = 8;      // shares per thread in flight when a query's shares are added up
 
 // How a part gets d pair-sum / d s of its rows:
 //   ONESIDED  its rows against the whole query, every unordered pair met from both ends (by the part of
 //             either document): twice the symmetric pass's work, nothing to exchange but the scores;
-//   RANKED    the hinge kinds on long lists by counting (parts_hinge_ranked), else as ONESIDED;
-//   SYM       the query's symmetric pair units (pairwise_core_sym: every unordered pair ONCE) are dealt
-//             to its parts, every part publishes its gradient slice of the whole query as granules and
-//             sums, in part order, the slices' entries of its own rows -- half the pair work for a second
-//             exchange of P * n granules per query (lists up to kSymMaxLen).
-enum { PT_ONESIDED = 0, PT_RANKED = 1, PT_SYM = 2 };
+//   RANKED    the hinge kinds on long lists by counting (parts_hinge_ranked), else as ONESIDED.
+enum { PT_ONESIDED = 0, PT_RANKED = 1 };
 // LDS LANDING BUFFER (round 5, session 5; verdict r4 item 6).  A part's registers are taken from the request of its tile to its
 // dW fold, and nothing of the NEXT tile can be asked for in between: by Little's law the two tiles of a CU turn over at what
 // their life time allows (4.0 TB/s at C5).  The LDS the kernel leaves free (~50 KB per workgroup at two per CU) takes the first
@@ -161,21 +105,16 @@ enum { PT_ONESIDED = 0, PT_RANKED = 1, PT_SYM = 2 };
 // (logistic, LambdaARP1 / 2) draw it there already.  The hinge kinds poll INSIDE the pass and draw behind it; drawing in front
 // (safe once every ticket of the part's own query is out) was built and measured: the siblings of the early-drawn part start
 // up to a pair pass apart and wait for each other -- C5 102 -> 175 us (EXPERIMENTS.md) -- so they stay as they are.
-#ifndef LTR_PARTS_PF2
-#define LTR_PARTS_PF2 12                 // float4 per thread landing in LDS at two workgroups per CU (0: off)
-#endif
-#ifndef LTR_PARTS_PF3
-#define LTR_PARTS_PF3 0
-#endif
+constexpr int kPtPf2 = 12;                 // float4 per thread landing in LDS at two workgroups per CU (0: off)
 __host__ __device__ constexpr int parts_pf_sweeps(int wpc, int cv)
 {
-    return wpc == 2 ? LTR_PARTS_PF2 / cv : (wpc == 3 ? LTR_PARTS_PF3 / cv : 0);
+    return wpc == 2 ? kPtPf2 / cv : 0;
 }
 
 struct PartsParams {
     LinearParams lp;              // lp.part = the (B, PF) partials of the plain path
     unsigned long long *sbuf;     // (B, L) score granules: tag << 32 | score bits
-    unsigned long long *slices;   // SYM: (B * Pmax, L) gradient-slice granules: tag << 32 | d pair-sum / d s_k of the part's units
+    unsigned long long *slices;   // the NDCG kinds: (B, L) score-rank granules: tag << 32 | rank
     float *pvec;                  // (B * Pmax, pitch) shares: dW (F) | db | raw pair sum | padding
     int *ctrl;
     unsigned long long gran_words; // granules of the whole exchange area behind sbuf (sbuf and slices are one allocation): zeroed when the tag wraps
@@ -183,9 +122,9 @@ struct PartsParams {
     int rtarget;                  // rows per part aimed at (<= rpw): a query has ceil(n / rtarget) parts
     int RS, R;                    // threads per row (F/4 rounded up to 16), rows per sweep
     int rank_lds;                 // != 0: the LDS carries the tables of the ranked hinge formulation
-    int Lg;                       // SYM: floats per wave slice region (>= Ls; the sorted hinge formulation needs room for its tables)
-    unsigned park_off;            // SYM: byte offset of the parked tile vectors in the dynamic LDS
-    int sort_min;                 // SYM, hinge kinds: lists from this length on are sorted instead of paired (< 0: never)
+    int Lg;                       // (unused: the list rounded to 64)
+    unsigned park_off;            // byte offset in the dynamic LDS where W's slots end (the landing buffer, or the end of the LDS)
+    int sort_min;                 // (unused: -1)
     int direct;                   // != 0: one round -- workgroup t holds part t % Pmax of query t / Pmax (or nothing), no part table
     int *status;                  // process status word (pinned host page) or null
     int spin_limit;               // polls before a wait gives up; < 0: give up at once (tests)
@@ -201,11 +140,7 @@ __device__ __forceinline__ void pt_load_lds16(__amdgpu_buffer_rsrc_t rsrc, unsig
 }
 __device__ __forceinline__ bool direct_launch(const PartsParams &pp)
 {
-#ifdef LTR_PARTS_NO_DIRECT
-    return false;
-#else
     return pp.direct != 0;
-#endif
 }
 __device__ __forceinline__ unsigned long long pt_ld64(const void *ptr)
 {
@@ -431,7 +366,7 @@ __device__ __forceinline__ float parts_pair_pass(float2 *sy, int nb, int r0, int
         const bool need = (k < nb) && (k < r0 || k >= r0 + rows);
         while (__ballot(need && (unsigned)(gv >> 32) != tag) != 0ull) {
             if (++spins > spin_limit) { fine = false; break; }
-            __builtin_amdgcn_s_sleep(LTR_PARTS_SLEEP);
+            __builtin_amdgcn_s_sleep(kPtSleep);
             gv = fetch(v);
         }
         if (need) sy[k].x = __uint_as_float((unsigned)gv);
@@ -440,17 +375,6 @@ __device__ __forceinline__ float parts_pair_pass(float2 *sy, int nb, int r0, int
     if (!fine && ok) *ok = false;
     return lacc;
 }
-
-// (the symmetric split pair pass of the round-4 experiments -- parts_sym_pass, four visitor chains per wave -- lives in
-// experiments/ltr_parts_experiments.inc and is compiled under -DLTR_PARTS_SYM only; the PT_SYM instantiations that name it do not
-// exist in the product build, which sees this declaration and nothing else)
-#if defined(LTR_PARTS_SYM) || defined(LTR_PARTS_SORTED)
-#define LTR_PARTS_EXPERIMENTS_PART 1
-#include "experiments/ltr_parts_experiments.inc"
-#else
-template <int KIND, bool INTLAB, int NCH>
-__device__ float parts_sym_pass(const float2 *sy, int nb, float sigma, float *gw, int w, int W, int lane);
-#endif
 
 // ---------------------------------------------------------------------------------------------
 // The two hinge kinds on long lists WITHOUT the O(n^2) pair pass (VERDICT r2 item 3).  For a document k
@@ -471,10 +395,7 @@ __device__ float parts_sym_pass(const float2 *sy, int nb, float sigma, float *gw
 // by document index before anything is summed.
 // ---------------------------------------------------------------------------------------------
 constexpr int kPtRankMinN = 192;
-#ifndef LTR_PARTS_RANK_MIN_WORK
-#define LTR_PARTS_RANK_MIN_WORK 80000
-#endif
-constexpr long long kPtRankMinWork = LTR_PARTS_RANK_MIN_WORK;
+constexpr long long kPtRankMinWork = 80000;
 constexpr int kPtRankMaxN = 2048;
 __host__ __device__ inline int parts_rank_buckets(int n)
 {
@@ -529,10 +450,6 @@ __device__ __forceinline__ float pt_wave_minmax(float v)
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
 
-#if defined(LTR_PARTS_SYM) || defined(LTR_PARTS_SORTED)
-#define LTR_PARTS_EXPERIMENTS_PART 2          // (the hinge kinds by a bitonic sort of the whole query: compiled out of the product)
-#include "experiments/ltr_parts_experiments.inc"
-#endif
 
 // All 256 threads; contains barriers.  gloc[0 .. rpw) <- d pair-sum / d s of my rows (0 past `rows`);
 // raw_out <- twice my share of the pair sum (the caller halves the sum of an oriented kind).
@@ -548,11 +465,7 @@ __device__ __forceinline__ float pt_wave_minmax(float v)
 // (not inlined: its ~120 registers would otherwise be live next to the feature tile of every instantiation;
 // the LDS regions come as byte OFFSETS into the dynamic segment -- generic pointers through a real call make
 // every LDS access a flat_* instruction, 3x slower here)
-#ifdef LTR_PARTS_RANKED_INLINE
-__device__ __forceinline__ bool parts_hinge_ranked(
-#else
 __device__ __attribute__((noinline)) bool parts_hinge_ranked(
-#endif
 int nb, int r0, int rows, int rpw, unsigned rk_off,
                                    unsigned gloc_off, unsigned scr_off, float &raw_out, long long *trace = nullptr)
 {
@@ -756,11 +669,11 @@ int nb, int r0, int rows, int rpw, unsigned rk_off,
 
 // The query's loss and the factor on its unscaled gradient from the raw pair sum (the modifier of
 // loss/pairwise_additive.py:132-133 for the DCG hinge; sigma / ln 2 for the log2-sigmoid kinds).
-template <int KIND, bool SYM = false>
+template <int KIND>
 __device__ __forceinline__ float parts_finish(float raw, float sigma, float &gscale)
 {
-    // (the one-sided pass meets every unordered pair of an oriented kind from both ends; the symmetric one once)
-    float total = (KIND == LTR_ARP1 || KIND == LTR_NDCG1 || SYM) ? raw : 0.5f * raw;
+    // (the one-sided pass meets every unordered pair of an oriented kind from both ends)
+    float total = (KIND == LTR_ARP1 || KIND == LTR_NDCG1) ? raw : 0.5f * raw;
     gscale = 1.0f;
     if (KIND == LTR_DCG_HINGE) {
         const float lg = logf(2.0f + total);
@@ -772,18 +685,6 @@ __device__ __forceinline__ float parts_finish(float raw, float sigma, float &gsc
     return total;
 }
 
-// LDS of one workgroup (bytes); the layout is carved in the kernel in the same order.
-// SYM: floats of a wave's slice region -- the list in 64-wide tiles; the hinge kinds' sorted formulation keeps
-// sort_pow2(L) keys / table words / scores in the same regions
-__host__ __device__ inline size_t parts_slice_floats(int kind, int L)
-{
-    const size_t Ls = (size_t)((L + 63) & ~63);
-#ifndef LTR_PARTS_SORTED
-    return Ls;
-#endif
-    const size_t P2 = (size_t)sort_pow2(L);
-    return ((kind == LTR_HINGE || kind == LTR_DCG_HINGE) && P2 > Ls) ? P2 : Ls;
-}
 // The NDCG kinds: q4 (score, label, gain, rank) and the discount-difference table of LambdaNDCG2, then the score
 // ranks of the query [Ls], the label ranks of my rows [Ls] and the packed (score key, label key) pairs of the
 // keyed counting rank [Ls x 16 bytes] -- behind the ranked formulation's tables.
@@ -795,8 +696,9 @@ __host__ __device__ inline size_t parts_ndcg_lds_bytes(int kind, int L)
     if (kind == LTR_NDCG2) bytes += 16 * Ls + ((4 * ndcg2_delta_floats(Ls) + 15) & ~(size_t)15);
     return bytes;
 }
-__host__ __device__ inline size_t parts_lds_bytes(int B, int L, int RS, int R, int CV, int rpw, int Pmax, int kind = -1,
-                                                  bool sym = false, int park = 0, int sym_kind = -1)
+// LDS of one workgroup (bytes); the layout is carved in the kernel in the same order.  rank_kind: the kind when
+// the kernel carries the tables of the ranked hinge formulation, else -1.
+__host__ __device__ inline size_t parts_lds_bytes(int B, int L, int RS, int R, int CV, int rpw, int Pmax, int rank_kind, int kind)
 {
     const size_t Ls = (size_t)((L + 63) & ~63);
     const size_t rpwp = (size_t)((rpw + 63) & ~63);
@@ -805,20 +707,17 @@ __host__ __device__ inline size_t parts_lds_bytes(int B, int L, int RS, int R, i
     const size_t chunks = ((size_t)B + kPtThreads - 1) / kPtThreads;
     size_t bytes = 8 * Ls;                                           // sy
     bytes += 4 * (((size_t)rpw * SEGP + 3) & ~(size_t)3);            // pd
-    // gw: the waves' gradient slices -- of my rows, or (SYM) of the whole query, followed by the parts'
-    // entries for my rows [P][rows] (P * rows <= n + P); gloc
-    const size_t Lg = parts_slice_floats(sym_kind, L);
-    bytes += sym ? 4 * ((size_t)kPtWaves * Lg + Lg + 64) + 4 * rpwp : 4 * (size_t)kPtWaves * rpwp + 4 * rpwp;
+    bytes += 4 * (size_t)kPtWaves * rpwp + 4 * rpwp;                 // gw: the waves' gradient slices of my rows; gloc
     bytes += 16 * (size_t)R * RS * CV;                               // dred
     bytes += 4 * (32 + 16 + 2 * (kPtMaxParts + 2));                  // red, misc, tend, qstart
     bytes += 4 * 3 * Bp;                                             // nl, order, doneq
     bytes += 2 * 4 * chunks * kPtWaves * (size_t)Pmax;               // counting-sort counts, the waves' offsets
     bytes = (bytes + 15) & ~(size_t)15;
-    bytes += 4 * 64 + parts_rank_lds_bytes(kind, L);                 // scratch + tables of the ranked hinge formulation
+    bytes += 4 * 64 + parts_rank_lds_bytes(rank_kind, L);            // scratch + tables of the ranked hinge formulation
     bytes = (bytes + 15) & ~(size_t)15;
-    bytes += parts_ndcg_lds_bytes(sym_kind, L);                      // the NDCG kinds' rankings, gains and discount table
+    bytes += parts_ndcg_lds_bytes(kind, L);                          // the NDCG kinds' rankings, gains and discount table
     bytes += 16 * (size_t)RS * CV;                                   // W, one float4 per (lane of a row, column vector)
-    return bytes + 16 * (size_t)kPtThreads * (size_t)park;           // SYM: parked tile vectors
+    return bytes;
 }
 
 #ifdef LTR_TRACE
@@ -830,14 +729,12 @@ __host__ __device__ inline size_t parts_lds_bytes(int B, int L, int RS, int R, i
 // NI row sweeps x CV column vectors per thread in registers; MINW = workgroups per CU the register
 // allocation must allow (= waves per SIMD: a workgroup is one wave per SIMD).
 // MODE (PT_*): PT_RANKED compiles the ranked hinge formulation in (the hinge kinds on shapes where it can
-// pay: the call costs the other shapes registers -- C5 108 -> 124 us with it compiled in and never taken);
-// PT_SYM deals the query's symmetric pair units to its parts and exchanges gradient slices.
+// pay: the call costs the other shapes registers -- C5 108 -> 124 us with it compiled in and never taken).
 template <int KIND, int NI, int CV, int MINW, int MODE = PT_ONESIDED, bool PF = false>
 __global__ void __launch_bounds__(kPtThreads, MINW)
 linear_parts_kernel(PartsParams pp)
 {
     constexpr bool RK = (MODE == PT_RANKED);
-    constexpr bool SYM = (MODE == PT_SYM);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const LinearParams &p = pp.lp;
 #ifdef LTR_TRACE
@@ -859,10 +756,8 @@ linear_parts_kernel(PartsParams pp)
 
     float2 *sy = reinterpret_cast<float2 *>(smem);                    // [Ls] (score, label) of the query
     float *pd = reinterpret_cast<float *>(sy + Ls);                   // [rpw][SEGP] 16-lane partial dots
-    float *gw = pd + ((rpw * SEGP + 3) & ~3);                         // [NW][rpwp] gradient slices of the waves (SYM: [NW][Ls], of the whole query)
-    const int Lg = pp.Lg;                                             // (SYM: >= Ls)
-    float *gx = gw + NW * Lg;                                         // SYM: [P][rows] the parts' slice entries for my rows
-    float *gloc = SYM ? gx + Lg + 64 : gw + NW * rpwp;                // [rpwp] d pair-sum / d s of my rows
+    float *gw = pd + ((rpw * SEGP + 3) & ~3);                         // [NW][rpwp] gradient slices of the waves
+    float *gloc = gw + NW * rpwp;                                     // [rpwp] d pair-sum / d s of my rows
     float4 *dred = reinterpret_cast<float4 *>(gloc + rpwp);           // [R][CV * RS] dW partials of the row groups
     float *red = reinterpret_cast<float *>(dred + R * RSC);           // [32]
     int *misc = reinterpret_cast<int *>(red + 32);                    // [16]
@@ -899,8 +794,6 @@ linear_parts_kernel(PartsParams pp)
                   "landing buffer: the one-sided kernels of the kinds that draw their next ticket in front of the pair pass");
     static_assert(NPF < NI, "the landing buffer holds a part of the tile");
     const bool pf_on = NPF > 0 && !direct_launch(pp);
-    constexpr int NLS = SYM ? parts_lds_sweeps(MINW, CV) : 0;            // sweeps NI - NLS .. NI - 1 wait in LDS
-    float4 *xl = reinterpret_cast<float4 *>(smem + pp.park_off) + tid;    // [NLS * CV][T] thread-private slots
 
     // ---- control block: read now, looked at behind the table build ----
     // (plain loads: what an earlier launch left is visible at the kernel boundary, and hundreds of
@@ -908,11 +801,7 @@ linear_parts_kernel(PartsParams pp)
     // (a plain load: what an earlier launch left is visible at the kernel boundary; a fresh area holds 0: the first tag is 1)
     const unsigned tag_word = (unsigned)__builtin_amdgcn_readfirstlane(pp.ctrl[0]);
     const unsigned tag = tag_word ? tag_word : 1u;
-#ifdef LTR_PARTS_NO_DIRECT
-    const bool direct = false;
-#else
     const bool direct = pp.direct != 0;
-#endif
     // (DIRECT: the length of this workgroup's query, requested before anything else -- the tile cannot be asked
     // for without it)
     const int nb_direct = direct ? __builtin_amdgcn_readfirstlane(clamp_n(p.n[(int)blockIdx.x / pp.Pmax], p.L)) : 0;
@@ -1104,23 +993,20 @@ linear_parts_kernel(PartsParams pp)
     // eight coherent loads in flight (no tile is in the registers where this runs), the groups' sums meet in LDS
     // in a fixed order; the raw pair sum rides in lane y of the last column vector.  Contains barriers.
     auto combine = [&](int qb, int qP) {
-#ifdef LTR_PARTS_NO_COMBINE
-        return;
-#endif
         const int CG = C + 1;
         const int NG = T / CG;                                     // (>= 1: C + 1 <= 193)
         const int grp = tid / CG, col = tid - grp * CG;
         if (grp < NG) {
             float4 s4 = make_float4(0.f, 0.f, 0.f, 0.f);
-            for (int q0 = grp; q0 < qP; q0 += LTR_PARTS_COMBINE_INFLIGHT * NG) {
-                ltr_u32x4 v[LTR_PARTS_COMBINE_INFLIGHT];
+            for (int q0 = grp; q0 < qP; q0 += kPtCombineInflight * NG) {
+                ltr_u32x4 v[kPtCombineInflight];
 #pragma unroll
-                for (int u = 0; u < LTR_PARTS_COMBINE_INFLIGHT; ++u) {
+                for (int u = 0; u < kPtCombineInflight; ++u) {
                     const int qq = min(q0 + u * NG, qP - 1);
                     v[u] = __builtin_amdgcn_raw_buffer_load_b128(prsrc, ((qb * Pmax + qq) * pp.pitch) * 4 + 16 * col, 0, 16);
                 }
 #pragma unroll
-                for (int u = 0; u < LTR_PARTS_COMBINE_INFLIGHT; ++u)
+                for (int u = 0; u < kPtCombineInflight; ++u)
                     if (q0 + u * NG < qP)
                         vadd(s4, make_float4(__uint_as_float(v[u].x), __uint_as_float(v[u].y), __uint_as_float(v[u].z), __uint_as_float(v[u].w)));
             }
@@ -1135,7 +1021,7 @@ linear_parts_kernel(PartsParams pp)
         if (tid < CG) {
             float gscale;
             const float inv_mx = kNdcg ? 1.0f / (red[31] == 0.0f ? 1.0f : red[31]) : 1.0f;       // the parts' terms of maxDCG, in part order
-            const float total_l = parts_finish<KIND, SYM>(red[30] * inv_mx, p.sigma, gscale);
+            const float total_l = parts_finish<KIND>(red[30] * inv_mx, p.sigma, gscale);
             gscale *= inv_mx;
             float4 *dst4 = reinterpret_cast<float4 *>(p.part + (size_t)qb * partial_pitch(F));
             if (tid < C) dst4[tid] = f4_scale(tot, gscale);
@@ -1193,10 +1079,6 @@ linear_parts_kernel(PartsParams pp)
             d += dpp_move<0x141, 0xF>(d);
             d += dpp_move<0x140, 0xF>(d);
             if ((c & 15) == 0) pd[pdoff + i * (R * SEGP)] = d;
-            if (i >= NI - NLS) {
-#pragma unroll
-                for (int j = 0; j < CV; ++j) xl[((i - (NI - NLS)) * CV + j) * T] = x[i][j];
-            }
             // (the tile arrives in order: keep the folds in order too, a few at a time, instead of NI dot
             // products in flight -- registers)
             if ((i & 3) == 3) __builtin_amdgcn_sched_barrier(0);
@@ -1220,7 +1102,7 @@ linear_parts_kernel(PartsParams pp)
         // arrived.  The ranked formulation needs every score first: poll here, up to four per thread in flight ----
         // (the hinge kinds only: the log-sigmoid kinds' pass is several times longer and their kernels have no
         // registers to spare for it)
-        constexpr bool kPollInPass = !RK && !SYM && (KIND == LTR_HINGE || KIND == LTR_DCG_HINGE);
+        constexpr bool kPollInPass = !RK && (KIND == LTR_HINGE || KIND == LTR_DCG_HINGE);
         if (!kPollInPass && P > 1) {
             bool okw = true;
             for (int k0 = 0; k0 < nb; k0 += 4 * T) {
@@ -1245,7 +1127,7 @@ linear_parts_kernel(PartsParams pp)
                     }
                     if (__ballot(need != 0) == 0ull) break;
                     if (++spins > pp.spin_limit) { okw = false; break; }
-                    __builtin_amdgcn_s_sleep(LTR_PARTS_SLEEP);
+                    __builtin_amdgcn_s_sleep(kPtSleep);
                 }
             }
             if (!okw && lane == 0) misc[2] = 0;
@@ -1267,7 +1149,7 @@ linear_parts_kernel(PartsParams pp)
         int tnext = 0;
         if (!kPollInPass) {
             if (!misc[2]) ok_wg = false;
-            if (!SYM && !kNdcg && tid == 0) tnext = direct ? total : G + __hip_atomic_fetch_add(pp.ctrl + 4, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (!kNdcg && tid == 0) tnext = direct ? total : G + __hip_atomic_fetch_add(pp.ctrl + 4, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
 
         // ---- the NDCG kinds (round 4): a part ranks ITS rows against the whole query (keyed counting rank on the
@@ -1342,7 +1224,7 @@ linear_parts_kernel(PartsParams pp)
                         }
                         if (__ballot(need != 0) == 0ull) break;
                         if (++spins > pp.spin_limit) { okw = false; break; }
-                        __builtin_amdgcn_s_sleep(LTR_PARTS_SLEEP);
+                        __builtin_amdgcn_s_sleep(kPtSleep);
                     }
                 }
                 if (!okw && lane == 0) misc[2] = 0;
@@ -1367,140 +1249,6 @@ linear_parts_kernel(PartsParams pp)
         // kinds on long lists of integer grades, else the pair pass ----
         float raw = 0.f;
         bool ranked = false;
-        bool sorted = false;
-#ifdef LTR_PARTS_SORTED
-        // (compiled out by default: correct -- every row of C4 / C5 against the oracle, gradients bit for bit -- but
-        // the bitonic sort of a 1000-document query on four waves costs more than the pair units it replaces:
-        // C4 59.8 -> 72.3 us, 32 x 1000 x 220 27.0 -> 32.8; EXPERIMENTS.md)
-        if constexpr (SYM && (KIND == LTR_HINGE || KIND == LTR_DCG_HINGE)) {
-            // ---- the hinge kinds on integer grades: sort + binary searches instead of pair units (parts_hinge_sorted_e)
-            // -- every part of the query decides the same way: the test looks at the whole query ----
-            if (p.rel_dtype != LTR_LABEL_F32 && nb >= kPtSortMinN && pp.sort_min >= 0 && nb >= pp.sort_min) {
-                int bad = 0, gmax = 0;
-                for (int k = tid; k < nb; k += T) {
-                    const float2 v = sy[k];
-                    bad |= (int)!(fabsf(v.x) < __builtin_inff()) | (int)!(v.y == floorf(v.y) && v.y >= 0.0f && v.y <= 7.0f);
-                    gmax = max(gmax, (int)fminf(fmaxf(v.y, 0.0f), 7.0f));
-                }
-                const int hi4 = (__ballot(gmax > 4) != 0ull) ? 1 : 0;
-                bad = (__ballot(bad != 0) != 0ull) ? 1 : 0;
-                if (lane == 0) misc[8 + wl] = bad | (hi4 << 1);
-                __syncthreads();
-                const int fl = misc[8] | misc[9] | misc[10] | misc[11];
-                if (!(fl & 1)) {
-                    const int P2 = sort_pow2(nb);
-                    unsigned long long *tab = reinterpret_cast<unsigned long long *>(gw);
-                    unsigned long long *tots = reinterpret_cast<unsigned long long *>(rscr);
-                    const bool two = (fl & 2) != 0;
-                    if (P2 <= T) parts_hinge_sorted_e<1>(sy, nb, P2, r0, rows, rpw, tab, gx, gloc, red, tots, two, raw);
-                    else if (P2 <= 2 * T) parts_hinge_sorted_e<2>(sy, nb, P2, r0, rows, rpw, tab, gx, gloc, red, tots, two, raw);
-                    else parts_hinge_sorted_e<4>(sy, nb, P2, r0, rows, rpw, tab, gx, gloc, red, tots, two, raw);
-                    sorted = true;
-                    ranked = true;
-                    if (tid == 0) tnext = direct ? total : G + __hip_atomic_fetch_add(pp.ctrl + 4, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-        }
-#endif
-        if constexpr (SYM) if (!sorted) {
-            // ---- SYM: my share of the query's symmetric pair units (every unordered pair once, over all parts)
-            // -> this workgroup's gradient slice of the WHOLE query; its entries for the other parts' rows leave as
-            // granules, the other parts' entries for my rows are polled and added in part order ----
-            const bool intlab = (KIND == LTR_HINGE || KIND == LTR_DCG_HINGE) && p.rel_dtype != LTR_LABEL_F32;
-            constexpr int NCH = LTR_PARTS_NCH;
-#ifdef LTR_PARTS_EXP_NOPASS
-            float lacc = 0.f;
-#else
-            float lacc = intlab ? parts_sym_pass<KIND, true, NCH>(sy, nb, p.sigma, gw + wl * Ls, part * NW + wl, P * NW, lane)
-                                : parts_sym_pass<KIND, false, NCH>(sy, nb, p.sigma, gw + wl * Ls, part * NW + wl, P * NW, lane);
-#endif
-            if (KIND == LTR_ARP1 && part == 0)              // the i == j terms: a_i * log2(1 + e^0) = a_i
-                for (int k = tid; k < nb; k += T) lacc += sy[k].y;
-            {
-                const float ws = wave_sum(lacc);
-                if (lane == 0) red[16 + wl] = ws;
-            }
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < NW; ++i) raw += red[16 + i];
-            // (barrier passed: the waves' slices are complete, raw = this part's share of the pair sum)
-            PT_STAMP(12);
-            if (P == 1) {
-                for (int lr = tid; lr < rpw; lr += T) {
-                    float g = 0.f;
-                    if (lr < rows) {
-#pragma unroll
-                        for (int i = 0; i < NW; ++i) g += gw[i * Ls + lr];
-                    }
-                    gloc[lr] = g;
-                }
-                if (tid == 0) tnext = direct ? total : G + __hip_atomic_fetch_add(pp.ctrl + 4, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            } else {
-                unsigned long long *sl = pp.slices + ((size_t)b * Pmax + part) * (size_t)L;
-                for (int k = tid; k < nb; k += T) {
-                    float g = 0.f;
-#pragma unroll
-                    for (int i = 0; i < NW; ++i) g += gw[i * Ls + k];
-                    if (k >= r0 && k < r0 + rows) gx[part * rows + (k - r0)] = g;
-                    else pt_st64(sl + k, ((unsigned long long)tag << 32) | __float_as_uint(g));
-                }
-                PT_STAMP(13);
-                // the other parts' entries for my rows (part q's rows are [q * rp, q * rp + rp): the same rp everywhere)
-                const int rp = (nb + P - 1) / P;
-                const int items = P * rp;
-                bool okw = true;
-                for (int i0 = 0; i0 < items; i0 += 4 * T) {
-                    unsigned need = 0;
-                    const unsigned long long *src[4];
-                    int dst[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const int idx = i0 + u * T + tid;
-                        const int qq = idx / rp, lr = idx - qq * rp;
-                        src[u] = pp.slices + ((size_t)b * Pmax + qq) * (size_t)L + r0 + lr;
-                        dst[u] = qq * rows + lr;
-                        if (idx < items && lr < rows && qq != part) need |= 1u << u;
-                    }
-                    int spins = 0;
-                    while (__ballot(need != 0) != 0ull) {
-                        unsigned long long gv[4];
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) gv[u] = (need >> u & 1u) ? pt_ld64(src[u]) : 0ull;
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            if ((need >> u & 1u) && (unsigned)(gv[u] >> 32) == tag) {
-                                gx[dst[u]] = __uint_as_float((unsigned)gv[u]);
-                                need &= ~(1u << u);
-                            }
-                        }
-                        if (__ballot(need != 0) == 0ull) break;
-                        if (++spins > pp.spin_limit) { okw = false; break; }
-                        __builtin_amdgcn_s_sleep(LTR_PARTS_SLEEP);
-                    }
-                }
-                if (!okw && lane == 0) misc[2] = 0;
-                __syncthreads();
-                PT_STAMP(14);
-                // nobody is waited for any more: the next ticket (its return is looked at behind the dW fold)
-                if (!misc[2]) ok_wg = false;
-                if (tid == 0) tnext = direct ? total : G + __hip_atomic_fetch_add(pp.ctrl + 4, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                for (int lr = tid; lr < rpw; lr += T) {
-                    float g = 0.f;
-                    if (lr < rows) {
-                        // (part order; four reads at a time in flight: P dependent LDS round trips were 0.7 us at P = 16)
-                        int qq = 0;
-                        for (; qq + 4 <= P; qq += 4) {
-                            const float a0 = gx[qq * rows + lr], a1 = gx[(qq + 1) * rows + lr];
-                            const float a2 = gx[(qq + 2) * rows + lr], a3 = gx[(qq + 3) * rows + lr];
-                            g += a0; g += a1; g += a2; g += a3;
-                        }
-                        for (; qq < P; ++qq) g += gx[qq * rows + lr];
-                    }
-                    gloc[lr] = g;
-                }
-            }
-            ranked = true;                  // (gloc and raw are final: skip the wave folds below)
-        }
         if constexpr (RK && (KIND == LTR_HINGE || KIND == LTR_DCG_HINGE)) {
             // (measured, MI355X: the tables cost ~11-14 us per part whatever the list -- a dozen barriers of
             // latency-bound scans and scatters on four waves -- the pair pass rows * n / 64 steps over four waves:
@@ -1517,7 +1265,7 @@ linear_parts_kernel(PartsParams pp)
                                             (unsigned)(reinterpret_cast<unsigned char *>(rscr) - smem), raw);
 #endif
         }
-        if constexpr (!SYM) if (!ranked) {
+        if (!ranked) {
             float lacc;
             const bool intlab = (KIND == LTR_HINGE || KIND == LTR_DCG_HINGE) && p.rel_dtype != LTR_LABEL_F32;
             if constexpr (kNdcg) {
@@ -1537,7 +1285,7 @@ linear_parts_kernel(PartsParams pp)
             const float ws = wave_sum(lacc);
             if (lane == 0) red[wl] = ws;
         }
-        if (!kPollInPass && !SYM && tid == 0) misc[0] = tnext;
+        if (!kPollInPass && tid == 0) misc[0] = tnext;
         lds_barrier();
         PT_STAMP(5);
         if (kPollInPass) {
@@ -1556,7 +1304,7 @@ linear_parts_kernel(PartsParams pp)
                 }
             }
         }
-        if constexpr (!SYM) if (!ranked) {
+        if (!ranked) {
 #pragma unroll
             for (int i = 0; i < NW; ++i) raw += red[i];
             for (int lr = tid; lr < rpw; lr += T) {
@@ -1581,7 +1329,7 @@ linear_parts_kernel(PartsParams pp)
                 const float g = gloc[goff + i * R];
 #pragma unroll
                 for (int j = 0; j < CV; ++j) {
-                    const float4 xv = (i >= NI - NLS) ? xl[((i - (NI - NLS)) * CV + j) * T] : x[i][j];
+                    const float4 xv = x[i][j];
                     vfma(acc[j], g, xv);
                 }
                 gb += g;
@@ -1591,7 +1339,7 @@ linear_parts_kernel(PartsParams pp)
             for (int j = 0; j < CV; ++j) dred[r * RSC + j * RS + c] = acc[j];
             if (c == 0) pd[r] = gb;
         }
-        if ((kPollInPass || SYM) && tid == 0) misc[0] = tnext;         // (the ticket drawn behind the pair pass)
+        if (kPollInPass && tid == 0) misc[0] = tnext;         // (the ticket drawn behind the pair pass)
         __syncthreads();
         // column vector tid of the query's row (C <= kPtMaxCV * 64 < T); thread C carries (d/d bias, raw pair sum)
         float4 share = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1616,7 +1364,7 @@ linear_parts_kernel(PartsParams pp)
             issue(cur, landed);
             float gscale;
             const float inv_mx = kNdcg ? 1.0f / (mx_part == 0.0f ? 1.0f : mx_part) : 1.0f;      // loss/pairwise_lambda.py:227
-            const float total_l = parts_finish<KIND, SYM>(raw * inv_mx, p.sigma, gscale) * poison;
+            const float total_l = parts_finish<KIND>(raw * inv_mx, p.sigma, gscale) * poison;
             gscale *= poison * inv_mx;
             if (tid < C) part4[tid] = f4_scale(share, gscale);
             else if (tid == C) part4[C] = make_float4(share.x * gscale, 0.f, 0.f, 0.f);
@@ -1714,37 +1462,16 @@ linear_parts_kernel(PartsParams pp)
 
 struct PartsShape { int ni, cv, wpc, RS, R, rpw, rtarget, Pmax, pitch, grid, mode, direct; size_t lds; size_t gran_words, misc_bytes; unsigned pf_off; };
 
-#ifndef LTR_PARTS_MIN_L
-#define LTR_PARTS_MIN_L 256
-#endif
-constexpr size_t kPtMaxGranBytes = (size_t)1 << 30;      // granule buffers of one launch (else: no slice exchange)
-
-// tuning / tests: LTR_PARTS_PF=0 launches without the landing buffer
-inline bool parts_pf_enabled()
-{
-    static const bool v = [] { const char *e = getenv("LTR_PARTS_PF"); return !(e && e[0] == '0'); }();
-    return v;
-}
+constexpr int kPtMinL = 256;
 
 // tests (ltr_debug_parts_all): every shape the kernel can take, whatever the measured rule says
 inline int &parts_debug_all() { static int v = 0; return v; }
-
-inline int parts_env_int(const char *name)
-{
-    const char *e = getenv(name);
-    return e ? atoi(e) : 0;
-}
 
 // Shapes the parts kernel takes: rank-free kinds, rows of whole float4 up to kPtMaxCV * 64 vectors, lists
 // too long for the register tile.  A row's C = F/4 column vectors are dealt to RS lanes (a power of two,
 // 16 .. 64) with CV = ceil(C / RS) vectors per lane; RS is the choice that wastes the fewest registers.
 bool choose_parts_shape(int kind, int B, int L, int F, PartsShape &s)
 {
-#ifdef LTR_NO_PARTS
-    return false;
-#endif
-    static const bool disabled = [] { const char *e = getenv("LTR_DISABLE_PARTS"); return e && e[0] == '1'; }();
-    if (disabled) return false;
     const bool ndcg = (kind == LTR_NDCG1 || kind == LTR_NDCG2);
     // (lists of 64 .. 256 documents: only where measured -- below)
     if (L > kMaxListLen || L < 64) return false;
@@ -1755,25 +1482,10 @@ bool choose_parts_shape(int kind, int B, int L, int F, PartsShape &s)
     const int C = F / 4;
     if (C > kPtMaxCV * 64) return false;
     const int cus = device_cu_count();
-    static const bool force_all = [] { const char *e = getenv("LTR_PARTS_ALL"); return e && e[0] == '1'; }();
-    static const bool no_sym = [] { const char *e = getenv("LTR_PARTS_NOSYM"); return e && e[0] == '1'; }();
-    const bool heavy = !(kind == LTR_HINGE || kind == LTR_DCG_HINGE);
     // Where it pays against the one-workgroup-per-query kernels (measured, MI355X; profiles/README.md):
     //   * lists beyond the symmetric pass (L > 1024), where the general kernel visits both ends too and reads
     //     the features twice: 512 x 2000 x 64 678 -> 381 us, 256 x 4000 x 32 1030 -> 704;
-    //   * wide rows (>= 112 float4): 512 x 512 x 700 121 -> 108, 1024 x 512 x 700 250 -> 222;
-    //   * long lists on batches too small to balance one workgroup per query (the shapes of the former
-    //     cluster kernel), with the symmetric split pass.
-#ifdef LTR_PARTS_SYM
-    if (!force_all && L <= kSymMaxLen && C < 112) {
-        int limit;
-        if (L >= 768) limit = cus + cus / 2;
-        else if (L >= 512) limit = heavy ? cus + cus / 2 : cus;
-        else limit = heavy ? cus : cus - cus / 4;
-        if (B > limit) return false;
-    }
-#else
-    (void)heavy;
+    //   * wide rows (>= 112 float4): 512 x 512 x 700 121 -> 108, 1024 x 512 x 700 250 -> 222.
     // Lists the symmetric pass still takes (L <= 1024): against the general kernel (one workgroup per query, the
     // symmetric pair pass, features read twice) the one-sided parts win on WIDE rows only, and not on batches of
     // one workgroup per CU or fewer.  Measured cold (two batches in rotation, MI355X, round 4 session 3:
@@ -1790,14 +1502,14 @@ bool choose_parts_shape(int kind, int B, int L, int F, PartsShape &s)
     //   underfilled general kernel (B <= #CUs; F 700 unless noted): 256 x 300: 1.47 / 1.29 / 1.32, 192 x 400: 1.21 / 0.98 / 1.00,
     //                     256 x 400: 0.80 / 0.75 / 0.80, 192 x 512: 0.78 / 0.74 / 0.75, 256 x 512: 0.76 / 0.77 / 0.83,
     //                     256 x 768: 0.69 / 0.67 / 0.75, 256 x 1000: 0.64 / 0.63 / 0.69, 160 x 1000 x 512: 0.60 / 0.55 / 0.57
-    if (!(force_all || parts_debug_all()) && L <= LTR_PARTS_MIN_L) {
+    if (!parts_debug_all() && L <= kPtMinL) {
         // Short lists (the general kernel reads the features twice and is bandwidth-bound on that at wide rows: Yahoo-
         // shaped batches, 700 features, lists of ~100-250 documents), cold, parts / general, hinge / logistic:
         //   2048 x 128 x 700 0.81 / 0.81    1024 x 256 x 700 0.80 / 0.86    1024 x 200 x 700 0.86 / 0.92    512 x 256 x 640 0.88 / 0.93
         //   1024 x 128 x 700 0.98 / 0.92    1024 x 128 x 512 0.95 / 1.04    1024 x 200 x 448 1.03 / 1.17 (!)
         //   512 x 128 x 700 1.48 / 1.43 (!)  256 x 256 x 700 1.55 / 1.39 (!)   LambdaNDCG2: 0.92 ... 1.25 -- never
         if (ndcg || C < 160 || B < 512 || (long long)B * L < 130000) return false;
-    } else if (!(force_all || parts_debug_all()) && L <= kSymMaxLen) {
+    } else if (!parts_debug_all() && L <= kSymMaxLen) {
         if (ndcg) {
             // wide rows as above; or batches that leave the general kernel's one workgroup per query CUs empty, on
             // long lists (any row width; parts / general, NDCG1 / NDCG2: 128 x 1000 x 136 0.55 / 0.81, 192 x 1000 x 136
@@ -1819,7 +1531,6 @@ bool choose_parts_shape(int kind, int B, int L, int F, PartsShape &s)
             if (kind == LTR_ARP1 && B > cus && L < 400) return false;
         }
     }
-#endif
     s.RS = 0;
     for (int rs = 16; rs <= 64; rs *= 2) {
         const int cv = (C + rs - 1) / rs;
@@ -1828,62 +1539,38 @@ bool choose_parts_shape(int kind, int B, int L, int F, PartsShape &s)
     }
     if (s.RS == 0) return false;
     s.R = kPtThreads / s.RS;
-#ifdef LTR_PARTS_SYM
-    bool sym = (L <= kSymMaxLen) && !no_sym;
-#else
-    bool sym = false;       // (the symmetric split pass is a development build: measured, not faster -- EXPERIMENTS.md)
-    (void)no_sym;
-#endif
     // workgroups per CU (2 / 3 / 4, i.e. 256 / 168 / 128 VGPRs): the heaviest that still gives every CU-slot
     // a few parts
-    static const int forced = parts_env_int("LTR_PARTS_WPC");
-    static const int forced_rt = parts_env_int("LTR_PARTS_RT");
     s.wpc = 0;
     for (int wpc = 2; wpc <= 4 && s.wpc == 0; ++wpc) {
-        const int rpw = parts_ni(wpc, s.cv, sym, false, kind) * s.R;
+        const int rpw = parts_ni(wpc, s.cv, false, kind) * s.R;
         const long long parts = (long long)B * ((L / 2 + rpw - 1) / rpw);
         if (parts >= 2LL * wpc * cus || wpc == 4) s.wpc = wpc;
     }
-    // (light parts -- fewer rows than the tile holds -- only when even the lightest workgroups leave CU-slots empty)
-    const int light_wpc = (s.wpc == 4) ? 3 : 99;
-    if (forced >= 2 && forced <= 4) s.wpc = forced;
     if (ndcg && s.wpc > 3) s.wpc = 3;
     for (;; --s.wpc) {              // (too many parts per query, or too much LDS for that many workgroups: heavier ones)
         // the counting formulation of the hinge kinds (lists beyond the symmetric pass): its call takes registers
         // from the tile, so its kernels hold fewer sweeps -- taken when a part of THAT size can reach the threshold
         bool rank = false;
-        if (!sym && s.wpc == 2 && parts_rank_lds_bytes(kind, L) > 0) {          // (the heaviest workgroups only: six kernels)
-            const int rpw_r = parts_ni(s.wpc, s.cv, false, true) * s.R;
+        if (s.wpc == 2 && parts_rank_lds_bytes(kind, L) > 0) {          // (the heaviest workgroups only: six kernels)
+            const int rpw_r = parts_ni(s.wpc, s.cv, true) * s.R;
             rank = (long long)rpw_r * L >= kPtRankMinWork;
         }
         for (int attempt = 0; attempt < 2; ++attempt, rank = false) {
-            s.ni = parts_ni(s.wpc, s.cv, sym, rank, kind);
+            s.ni = parts_ni(s.wpc, s.cv, rank, kind);
             s.rpw = s.ni * s.R;
-            // rows per part aimed at: a full tile -- or, when even the lightest workgroups leave CU-slots empty,
-            // as few rows as fill them (a query then has up to kPtMaxParts parts; the symmetric split pass only:
-            // a one-sided part's work does not shrink with its rows)
+            // rows per part aimed at: a full tile (a one-sided part's work does not shrink with its rows)
             s.rtarget = s.rpw;
-            static const bool no_light = [] { const char *e = getenv("LTR_PARTS_NOLIGHT"); return e && e[0] == '1'; }();
-            if (sym && s.wpc >= light_wpc && !no_light) {
-                const long long slots = (long long)s.wpc * cus;
-                long long rt = ((long long)B * (L / 2) + slots - 1) / slots;
-                const long long lo = (L + kPtMaxParts - 1) / kPtMaxParts;
-                rt = rt < lo ? lo : rt;
-                rt = rt < 32 ? 32 : rt;
-                rt = (rt + 7) & ~7LL;
-                if (rt < s.rpw) s.rtarget = (int)rt;
-            }
-            if (forced_rt > 0 && forced_rt <= s.rpw) s.rtarget = forced_rt;
             s.Pmax = (L + s.rtarget - 1) / s.rtarget;
             s.pitch = (F + 2 + 3) & ~3;
-            s.gran_words = (size_t)B * L + (sym ? (size_t)B * s.Pmax * L : 0) + (ndcg ? (size_t)B * L : 0);     // (NDCG kinds: rank granules)
-            s.mode = sym ? PT_SYM : (rank ? PT_RANKED : PT_ONESIDED);
-            s.lds = parts_lds_bytes(B, L, s.RS, s.R, s.cv, s.rpw, s.Pmax, rank ? kind : -1, sym, sym ? parts_park(s.wpc, s.cv) : 0, kind);
+            s.gran_words = (size_t)B * L + (ndcg ? (size_t)B * L : 0);     // (NDCG kinds: rank granules)
+            s.mode = rank ? PT_RANKED : PT_ONESIDED;
+            s.lds = parts_lds_bytes(B, L, s.RS, s.R, s.cv, s.rpw, s.Pmax, rank ? kind : -1, kind);
             // the landing buffer for the next part's first sweeps, where the LDS of a workgroup has room for it
             s.pf_off = 0;
             {
                 const size_t pf_bytes = 16 * (size_t)kPtThreads * (size_t)(parts_pf_sweeps(s.wpc, s.cv) * s.cv);
-                if (s.mode == PT_ONESIDED && (kind == LTR_LOGISTIC || kind == LTR_ARP1 || kind == LTR_ARP2) && pf_bytes > 0 && parts_pf_enabled() && s.lds + pf_bytes <= kLdsBudget / s.wpc) {
+                if (s.mode == PT_ONESIDED && (kind == LTR_LOGISTIC || kind == LTR_ARP1 || kind == LTR_ARP2) && pf_bytes > 0 && s.lds + pf_bytes <= kLdsBudget / s.wpc) {
                     s.pf_off = (unsigned)s.lds;
                     s.lds += pf_bytes;
                 }
@@ -1891,7 +1578,6 @@ bool choose_parts_shape(int kind, int B, int L, int F, PartsShape &s)
             if (s.Pmax <= kPtMaxParts && s.lds <= kLdsBudget / s.wpc) break;
             if (!rank) break;                    // (second attempt: without the tables of the ranked formulation)
         }
-        if (sym && s.gran_words * 8 > kPtMaxGranBytes) { sym = false; ++s.wpc; continue; }
         if (s.Pmax <= kPtMaxParts && s.lds <= kLdsBudget / s.wpc) break;
         if (s.wpc == 2) return false;
     }
@@ -1899,8 +1585,7 @@ bool choose_parts_shape(int kind, int B, int L, int F, PartsShape &s)
     const long long items = (long long)B * s.Pmax;
     const long long slots = (long long)s.wpc * cus;
     // one round: every part gets a workgroup of its own and no table is built (DIRECT)
-    static const bool no_direct = [] { const char *e = getenv("LTR_PARTS_NODIRECT"); return e && e[0] == '1'; }();
-    s.direct = (items <= slots && !no_direct) ? 1 : 0;
+    s.direct = (items <= slots) ? 1 : 0;
     s.grid = (int)(items < slots ? items : slots);
     if (s.grid < s.Pmax) s.grid = s.Pmax;           // (forward progress: more running workgroups than parts per query)
     const size_t pv = (size_t)B * s.Pmax * s.pitch;
@@ -1913,29 +1598,14 @@ template <int KIND, int CV, int WPC, int MODE, bool PF = false>
 int launch_parts_mode(const PartsParams &pp, const PartsShape &s, hipStream_t stream)
 {
     const dim3 grid((unsigned)s.grid), block((unsigned)kPtThreads);
-    static const bool debug = [] { const char *e = getenv("LTR_PARTS_DEBUG"); return e && e[0] == '1'; }();
-    if (debug) {
-        int api = -1;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&api, linear_parts_kernel<KIND, parts_ni(WPC, CV, MODE == PT_SYM, MODE == PT_RANKED, KIND), CV, WPC, MODE, PF>, kPtThreads, s.lds);
-        static int shown = 0;
-        if (shown++ < 4)
-            fprintf(stderr, "parts: wpc %d ni %d cv %d RS %d rpw %d rtarget %d Pmax %d grid %d lds %zu mode %d direct %d occupancy api %d\n",
-                    s.wpc, s.ni, s.cv, s.RS, s.rpw, s.rtarget, s.Pmax, s.grid, s.lds, MODE, s.direct, api);
-    }
-    LTR_ENSURE_LDS((linear_parts_kernel<KIND, parts_ni(WPC, CV, MODE == PT_SYM, MODE == PT_RANKED, KIND), CV, WPC, MODE, PF>), s.lds);
-    hipLaunchKernelGGL((linear_parts_kernel<KIND, parts_ni(WPC, CV, MODE == PT_SYM, MODE == PT_RANKED, KIND), CV, WPC, MODE, PF>), grid, block, s.lds, stream, pp);
+    LTR_ENSURE_LDS((linear_parts_kernel<KIND, parts_ni(WPC, CV, MODE == PT_RANKED, KIND), CV, WPC, MODE, PF>), s.lds);
+    hipLaunchKernelGGL((linear_parts_kernel<KIND, parts_ni(WPC, CV, MODE == PT_RANKED, KIND), CV, WPC, MODE, PF>), grid, block, s.lds, stream, pp);
     return (int)hipGetLastError();
 }
 
 template <int KIND, int CV, int WPC>
 int launch_parts_wpc(const PartsParams &pp, const PartsShape &s, hipStream_t stream)
 {
-#ifdef LTR_PARTS_SYM
-    if (s.mode == PT_SYM) return launch_parts_mode<KIND, CV, WPC, PT_SYM>(pp, s, stream);
-#endif
-#ifdef LTR_DEV_SUBSET
-    return LTR_ERR_CONFIG;
-#else
     if constexpr ((KIND == LTR_HINGE || KIND == LTR_DCG_HINGE) && WPC == 2) {
         if (s.mode == PT_RANKED) return launch_parts_mode<KIND, CV, WPC, PT_RANKED>(pp, s, stream);
     }
@@ -1944,7 +1614,6 @@ int launch_parts_wpc(const PartsParams &pp, const PartsShape &s, hipStream_t str
         if (pp.pf_off) return launch_parts_mode<KIND, CV, WPC, PT_ONESIDED, true>(pp, s, stream);
     }
     return launch_parts_mode<KIND, CV, WPC, PT_ONESIDED>(pp, s, stream);
-#endif
 }
 
 template <int KIND, int CV>
@@ -1985,9 +1654,9 @@ int launch_parts(int kind, const LinearParams &p, const PartsShape &s, hipStream
     pp.Pmax = s.Pmax; pp.rpw = s.rpw; pp.rtarget = s.rtarget; pp.pitch = s.pitch; pp.RS = s.RS; pp.R = s.R;
     pp.rank_lds = (s.mode == PT_RANKED) ? 1 : 0;
     pp.direct = s.direct;
-    pp.Lg = (int)parts_slice_floats(kind, p.L);
-    pp.sort_min = getenv("LTR_PARTS_SORT_MIN") ? parts_env_int("LTR_PARTS_SORT_MIN") : -1;
-    pp.park_off = s.pf_off ? s.pf_off : (unsigned)(s.lds - 16 * (size_t)kPtThreads * (size_t)(s.mode == PT_SYM ? parts_park(s.wpc, s.cv) : 0));
+    pp.Lg = (p.L + 63) & ~63;
+    pp.sort_min = -1;
+    pp.park_off = s.pf_off ? s.pf_off : (unsigned)s.lds;
     // the exchange area of this (device, stream): granule buffers | control block + shares
     unsigned char *gran = nullptr, *misc = nullptr;
     size_t gran_have = 0;
@@ -2003,13 +1672,11 @@ int launch_parts(int kind, const LinearParams &p, const PartsShape &s, hipStream
     switch (kind) {
     case LTR_HINGE: return launch_parts_kind<LTR_HINGE>(pp, s, stream);
     case LTR_LOGISTIC: return launch_parts_kind<LTR_LOGISTIC>(pp, s, stream);
-#ifndef LTR_DEV_SUBSET
     case LTR_DCG_HINGE: return launch_parts_kind<LTR_DCG_HINGE>(pp, s, stream);
     case LTR_ARP1: return launch_parts_kind<LTR_ARP1>(pp, s, stream);
     case LTR_ARP2: return launch_parts_kind<LTR_ARP2>(pp, s, stream);
     case LTR_NDCG1: return launch_parts_kind<LTR_NDCG1>(pp, s, stream);
     case LTR_NDCG2: return launch_parts_kind<LTR_NDCG2>(pp, s, stream);
-#endif
     default: return LTR_ERR_KIND;
     }
 }

@@ -8,27 +8,17 @@
 // `model = pytorchltr_amd.fused.LinearScorer(F)` -- and for composing long-list steps out of
 // balanced pieces.  Both skip padded documents when `n` is given (score 0, no gradient).
 //
-//   scores: one wave per row, LTR_SC_UNR rows in flight, W in registers; grid-stride over rows.
+//   scores: one wave per row, kScUnr rows in flight, W in registers; grid-stride over rows.
 //   grad:   dW = sum_r g[r] X[r,:], db = sum_r g[r]: a workgroup takes kScRows consecutive rows,
 //           thread (column vector, row group) accumulates, row groups fold in LDS, one partial
 //           vector [dW | db] per workgroup; mlp_reduce_kernel adds the partials in a fixed order.
 #pragma once
 
-#ifndef LTR_SC_UNR
-#define LTR_SC_UNR 4                  // rows in flight per wave, scores kernel (swept 2..16 with branch-free loads: 4)
-#endif
-#ifndef LTR_SG_UNR
-#define LTR_SG_UNR 4                  // rows in flight per thread, gradient kernel
-#endif
-#ifndef LTR_SG_ROWS
-#define LTR_SG_ROWS 256                // (swept: 256)
-#endif
+constexpr int kScUnr = 4;                  // rows in flight per wave, scores kernel (swept 2..16 with branch-free loads: 4)
+constexpr int kSgUnr = 4;                  // rows in flight per thread, gradient kernel
 constexpr int kScThreads = 256;
-#ifndef LTR_SC_ROWS
-#define LTR_SC_ROWS 128
-#endif
-constexpr int kScRows = LTR_SC_ROWS;  // documents per job (query, chunk), scores kernel
-constexpr int kSgRows = LTR_SG_ROWS;  // same, gradient kernel
+constexpr int kScRows = 128;  // documents per job (query, chunk), scores kernel
+constexpr int kSgRows = 256;  // same, gradient kernel (swept: 256)
 constexpr int kScMaxVec = 16;         // column vectors per lane: F <= 64 * 16 * VEC
 
 struct ScorerParams {
@@ -66,7 +56,7 @@ linear_scores_kernel(ScorerParams p)
     }
     const float bias = p.bias ? p.bias[0] : 0.f;
     const float *Xq = p.X + row0 * (size_t)p.F;
-    constexpr int UNR = LTR_SC_UNR;
+    constexpr int UNR = kScUnr;
     for (int la = l0 + wave; la < lv; la += NW * UNR) {
         float acc[UNR];
 #pragma unroll
@@ -135,7 +125,7 @@ linear_grad_kernel(ScorerParams p)
         const int c = c0 + cl;
         V acc = vzero<V>();
         if (rg < RG && c < C) {
-            constexpr int UNR = LTR_SG_UNR;
+            constexpr int UNR = kSgUnr;
             for (int la = l0 + rg; la < lv; la += RG * UNR) {
                 V x[UNR];
                 float g[UNR];

@@ -1,8 +1,7 @@
-// ltr_trace.inc -- the tuning hooks of the fused Linear scorer + loss kernels, in ONE place.  In the product build (neither
-// -DLTR_TRACE nor -DLTR_V2_STOP) every macro below expands to nothing: the kernels carry no stamp, no cut-off and no extra
-// argument.  Tuning builds (scripts/build_variants.sh name:"-DLTR_TRACE -DLTR_TRACE_WALL", scripts/trace_regtile.py,
-// scripts/cu_bytes.py) write per-workgroup time stamps and the placement (HW_ID / XCC_ID) into the buffer passed as
-// `scores_out`; -DLTR_V2_STOP=1|2 cuts the register-tile kernel off behind its loads + dots / behind its scores.
+// ltr_trace.inc -- the trace stamps of the fused Linear scorer + loss kernels, in ONE place.  In the product build (no
+// -DLTR_TRACE) every macro below expands to nothing: the kernels carry no stamp and no extra argument.  Trace builds
+// (scripts/build_variants.sh name:"-DLTR_TRACE -DLTR_TRACE_WALL", scripts/trace_regtile.py, scripts/cu_bytes.py) write
+// per-workgroup time stamps and the placement (HW_ID / XCC_ID) into the buffer passed as `scores_out`.
 #ifdef LTR_TRACE
 // -DLTR_TRACE_WALL: stamps from the 100 MHz constant clock (comparable across CUs / XCDs)
 #ifdef LTR_TRACE_WALL
@@ -35,12 +34,4 @@
 #define LTR_TRACE_PLACEMENT() do { } while (0)
 #define LTR_SYM_TRACE_ARGS
 #define LTR_TRACE_ALLOW_FAST(scores_out) ((scores_out) == nullptr)
-#endif
-
-// -DLTR_V2_STOP=N: the register-tile kernel returns behind phase N (1: loads + dots, 2: + scores), storing VALUE so that the
-// phase is not dead code
-#ifdef LTR_V2_STOP
-#define LTR_STOP_AFTER(N, VALUE) do { if (LTR_V2_STOP == (N) && p.B >= 0) { if (tid == 0) p.loss[b] = (VALUE); return; } } while (0)
-#else
-#define LTR_STOP_AFTER(N, VALUE) do { } while (0)
 #endif

@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Per-phase cycle breakdown of the fused MLP kernel (needs a -DLTR_MLP_TRACE build):
-    hipcc ... -DLTR_MLP_TRACE -o build/variants/libltr_mlptrace.so pytorchltr_amd/csrc/ltr_kernels.hip
-    python scripts/trace_mlp.py [--full-lists] [--kind hinge]"""
+    python -c "from pytorchltr_amd import build; build.build_extension(force=True, extra_flags=['-DLTR_MLP_TRACE'],
+               lib_path='build/variants/libltr_mlptrace.so')"
+    python scripts/trace_mlp.py [--full-lists] [--kind hinge] [--layout wide]"""
 import argparse
 import ctypes
 import os
@@ -28,19 +29,19 @@ PHASES_TILE = ["rest of prologue", "(fwd) next fill issue + barrier", "layer-1 t
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--layout", default="tile", choices=["tile", "wide"],
-                    help="tile = 4-wave kernel of ltr_mlp2.inc (default dispatch), wide = LTR_MLP_LAYOUT=1")
+                    help="tile = 4-wave kernel of ltr_mlp2.inc (default dispatch), wide = ltr_debug_mlp_layout(1)")
     ap.add_argument("--lib", default=os.path.join(ROOT, "build", "variants", "libltr_mlptrace.so"))
     ap.add_argument("--kind", default="hinge")
     ap.add_argument("--full-lists", action="store_true")
     ap.add_argument("--B", type=int, default=1024)
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
-    if args.layout == "wide":
-        os.environ["LTR_MLP_LAYOUT"] = "1"
     lib = ctypes.CDLL(args.lib)
     for name, (res, argt) in _C.SIGNATURES.items():
         getattr(lib, name).restype = res
         getattr(lib, name).argtypes = argt
+    if args.layout == "wide":
+        lib.ltr_debug_mlp_layout(1)
     B, L, F, H1, H2 = args.B, 128, 136, 50, 10
     _, rel, n, X = bench.synth(B, L, F, 0, dev)
     if args.full_lists:

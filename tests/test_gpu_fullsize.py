@@ -110,8 +110,8 @@ def test_c5_full_size_parts_kernel_all_rows():
 
 
 def test_c5_full_size_general_kernel_all_rows():
-    """The same step on the general kernel (features read twice): LTR_DISABLE_PARTS is read once per
-    process, so the general kernel is reached through the shape rule instead -- rows of 220 features."""
+    """The same step on the general kernel (features read twice), reached through the shape rule:
+    rows of 220 features."""
     from pytorchltr_amd import _C
     _run("hinge", 512, 512, 220, 0, _C.PLAN_GENERAL)
 
