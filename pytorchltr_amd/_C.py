@@ -220,7 +220,10 @@ def max_sort_list_len():
 
 
 def sort_workspace(op, B, L, device):
-    """Workspace of the ltr_*_long_f32 entry points (op 0 rank, 1 dcg / ndcg, 2 arp): (tensor, bytes)."""
+    """Workspace of the ltr_*_long_f32 entry points (op 0 rank, 1 dcg / ndcg, 2 arp): (tensor, bytes).
+    (None, 0) for lists of at most max_list_len(): the entry points do not read it there."""
+    if L <= max_list_len():
+        return None, 0
     nbytes = int(lib().ltr_sort_workspace_bytes(op, B, L))
     return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device), nbytes
 

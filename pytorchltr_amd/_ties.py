@@ -6,7 +6,9 @@ torch's global RNG, :48-64, evaluation/dcg.py:85, evaluation/arp.py:32), so that
 outputs tie -- constant, zero-initialised, ReLU-dead -- gets an unbiased expected metric instead of
 whatever the storage order of the documents happens to reward.  The kernels take that permutation
 as an int32 priority per list position (include/ltr_hip.h: ltr_*_tie_f32): of two documents with
-equal score the one with the smaller priority ranks first.
+equal score the one with the smaller priority ranks first.  rank_by_score, dcg / ndcg and arp always
+call the ltr_*_long_f32 entry point with one of the two modes below; on lists of at most 4096 documents
+that call is the _seed_ (random) or plain (index) entry point.
 
 mode "random" (default, the reference's behaviour): a fresh pseudo-random order of the tied positions
     per call.  Round 3: no permutation is drawn on the device any more (torch.randperm cost five kernels

@@ -965,16 +965,7 @@ int launch_cluster(int kind, const LinearParams &p, const ClusterShape &s, float
     unsigned char *gran = nullptr, *misc = nullptr;
     if (const int rc = exchange_area_get(stream, 16, kExCtrlBytes, &gran, &misc)) return rc;
     cp.cnt = reinterpret_cast<int *>(misc + kExPartsCtrlBytes);
-    switch (kind) {
-    case LTR_HINGE: return launch_cluster_kind<LTR_HINGE>(cp, s, stream);
-    case LTR_DCG_HINGE: return launch_cluster_kind<LTR_DCG_HINGE>(cp, s, stream);
-    case LTR_LOGISTIC: return launch_cluster_kind<LTR_LOGISTIC>(cp, s, stream);
-    case LTR_ARP1: return launch_cluster_kind<LTR_ARP1>(cp, s, stream);
-    case LTR_ARP2: return launch_cluster_kind<LTR_ARP2>(cp, s, stream);
-    case LTR_NDCG1: return launch_cluster_kind<LTR_NDCG1>(cp, s, stream);
-    case LTR_NDCG2: return launch_cluster_kind<LTR_NDCG2>(cp, s, stream);
-    default: return LTR_ERR_KIND;
-    }
+    return with_kind(kind, [&](auto K) { return launch_cluster_kind<K>(cp, s, stream); });
 }
 
 }  // namespace

@@ -9,6 +9,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <type_traits>
 
 #include "ltr_hip.h"
 
@@ -1234,6 +1235,36 @@ inline int sched_groups_for_lists(int B, int L)
 
 
 inline bool bad_label_dtype(int d) { return d != LTR_LABEL_I64 && d != LTR_LABEL_F32 && d != LTR_LABEL_I32; }
+
+// The run-time loss kind as a template argument: f(std::integral_constant<int, KIND>{}) for each of the
+// seven kinds, LTR_ERR_KIND for anything else.
+template <class Fn>
+int with_kind(int kind, Fn &&f)
+{
+    switch (kind) {
+    case LTR_HINGE: return f(std::integral_constant<int, LTR_HINGE>{});
+    case LTR_DCG_HINGE: return f(std::integral_constant<int, LTR_DCG_HINGE>{});
+    case LTR_LOGISTIC: return f(std::integral_constant<int, LTR_LOGISTIC>{});
+    case LTR_ARP1: return f(std::integral_constant<int, LTR_ARP1>{});
+    case LTR_ARP2: return f(std::integral_constant<int, LTR_ARP2>{});
+    case LTR_NDCG1: return f(std::integral_constant<int, LTR_NDCG1>{});
+    case LTR_NDCG2: return f(std::integral_constant<int, LTR_NDCG2>{});
+    default: return LTR_ERR_KIND;
+    }
+}
+
+// Argument guards shared by the entry points; each returns the first failing code, or LTR_OK.
+// A loss kind and a label dtype:
+inline int check_kind(int kind, int rel_dtype)
+{
+    return (kind < LTR_HINGE || kind > LTR_NDCG2 || bad_label_dtype(rel_dtype)) ? LTR_ERR_KIND : LTR_OK;
+}
+// A (B, L) batch of lists of at most max_len documents:
+inline int check_lists(int B, int L, int max_len)
+{
+    if (B < 0 || L <= 0) return LTR_ERR_SHAPE;
+    return L > max_len ? LTR_ERR_LIST_TOO_LONG : LTR_OK;
+}
 
 inline unsigned grid_for(size_t items, int block)
 {

@@ -176,7 +176,7 @@ int ltr_pairwise_loss_f64(int kind, double sigma, const double *scores, const vo
                           double *dscores, void *stream)
 {
     LTR_CLEAR_STALE_ERROR();
-    if (kind < LTR_HINGE || kind > LTR_NDCG2 || bad_label_dtype(rel_dtype)) return LTR_ERR_KIND;
+    if (const int rc = check_kind(kind, rel_dtype)) return rc;
     if (B < 0 || L <= 0) return LTR_ERR_SHAPE;
     if (L > kMaxListLen || loss64_lds_bytes(L) > kLdsBudget) return LTR_ERR_LIST_TOO_LONG;
     if (B == 0) return LTR_OK;
@@ -184,16 +184,7 @@ int ltr_pairwise_loss_f64(int kind, double sigma, const double *scores, const vo
     LossParams64 p;
     p.scores = scores; p.rel = rel; p.n = n; p.loss = loss; p.dscores = dscores;
     p.B = B; p.L = L; p.sigma = sigma; p.rel_dtype = rel_dtype;
-    hipStream_t st = (hipStream_t)stream;
-    switch (kind) {
-    case LTR_HINGE: return launch_loss64<LTR_HINGE>(p, st);
-    case LTR_DCG_HINGE: return launch_loss64<LTR_DCG_HINGE>(p, st);
-    case LTR_LOGISTIC: return launch_loss64<LTR_LOGISTIC>(p, st);
-    case LTR_ARP1: return launch_loss64<LTR_ARP1>(p, st);
-    case LTR_ARP2: return launch_loss64<LTR_ARP2>(p, st);
-    case LTR_NDCG1: return launch_loss64<LTR_NDCG1>(p, st);
-    default: return launch_loss64<LTR_NDCG2>(p, st);
-    }
+    return with_kind(kind, [&](auto K) { return launch_loss64<K>(p, (hipStream_t)stream); });
 }
 
 int ltr_scale_rows_f64(const double *dscores, const double *grad_out, int B, int L, double *out,

@@ -948,16 +948,7 @@ int launch_loss_kind(const LossParams &p, const LaunchShape &s, hipStream_t stre
 
 int launch_loss(int kind, const LossParams &p, const LaunchShape &s, hipStream_t stream)
 {
-    switch (kind) {
-    case LTR_HINGE: return launch_loss_kind<LTR_HINGE>(p, s, stream);
-    case LTR_DCG_HINGE: return launch_loss_kind<LTR_DCG_HINGE>(p, s, stream);
-    case LTR_LOGISTIC: return launch_loss_kind<LTR_LOGISTIC>(p, s, stream);
-    case LTR_ARP1: return launch_loss_kind<LTR_ARP1>(p, s, stream);
-    case LTR_ARP2: return launch_loss_kind<LTR_ARP2>(p, s, stream);
-    case LTR_NDCG1: return launch_loss_kind<LTR_NDCG1>(p, s, stream);
-    case LTR_NDCG2: return launch_loss_kind<LTR_NDCG2>(p, s, stream);
-    default: return LTR_ERR_KIND;
-    }
+    return with_kind(kind, [&](auto K) { return launch_loss_kind<K>(p, s, stream); });
 }
 
 // How many workgroups share a query in the split launch (1 = use the one-kernel path): long lists
@@ -1068,6 +1059,45 @@ int launch_metric(const MetricParams &p0, hipStream_t stream)
     return (int)hipGetLastError();
 }
 
+int g_long_sort_all = 0;                 // ltr_debug_long_sort_all
+inline bool long_path(int L) { return L > kMaxListLen || __atomic_load_n(&g_long_sort_all, __ATOMIC_RELAXED) != 0; }
+
+// The seed forms' bound (the hashed tie words are distinct below kTieHashMaxLen) is implied by kMaxListLen.
+static_assert(kTieHashMaxLen >= kMaxListLen, "hashed tie words must cover every one-workgroup list");
+
+int long_metric(int op, const float *scores, const void *rel, int rel_dtype, const int64_t *n, const int32_t *tie,
+                int use_seed, uint64_t seed, const int64_t *seed_dev, int B, int L, int k, int use_exp, int normalize,
+                void *out, void *workspace, size_t workspace_bytes, hipStream_t s);     // ltr_longsort.inc
+
+// The one body of the twelve rank / dcg / arp entry points (OP = METRIC_*): the checks, then one
+// workgroup per query (launch_metric) or, for a _long_ form (max_len = kMaxSortListLen) past
+// kMaxListLen, the sort path (long_metric).  rank passes rel = null and rel_dtype = k = use_exp = normalize = 0,
+// arp the last three 0.
+// Tie mode: use_seed != 0 hashed words from seed / seed_dev, else tie (null: document index order).
+template <int OP>
+int metric_entry(const float *scores, const void *rel, int rel_dtype, const int64_t *n, const int32_t *tie, int use_seed,
+                 uint64_t seed, const int64_t *seed_dev, int B, int L, int k, int use_exp, int normalize, void *out,
+                 int max_len, void *workspace, size_t workspace_bytes, void *stream)
+{
+    LTR_CLEAR_STALE_ERROR();
+    if (bad_label_dtype(rel_dtype)) return LTR_ERR_KIND;
+    if (k < 0) return LTR_ERR_SHAPE;
+    if (const int rc = check_lists(B, L, max_len)) return rc;
+    if (B == 0) return LTR_OK;
+    if (!scores || (OP != METRIC_RANK && !rel) || !n || !out) return LTR_ERR_NULL;
+    const hipStream_t s = (hipStream_t)stream;
+    if (max_len <= kMaxListLen || !long_path(L)) {
+        MetricParams p{};
+        p.scores = scores; p.rel = rel; p.n = n; p.out = out; p.B = B; p.L = L;
+        p.rel_dtype = rel_dtype; p.k = k; p.use_exp = use_exp; p.normalize = normalize;
+        if (use_seed) { p.use_seed = 1; p.tie_seed = seed; p.tie_seed_dev = seed_dev; }
+        else p.tie = tie;
+        return launch_metric<OP>(p, s);
+    }
+    return long_metric(OP, scores, rel, rel_dtype, n, tie, use_seed, seed, seed_dev, B, L, k, use_exp, normalize, out,
+                       workspace, workspace_bytes, s);
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------
@@ -1116,9 +1146,8 @@ int ltr_pairwise_loss_f32_cfg(int kind, float sigma, const float *scores, const 
                               float *dscores, int owners, int dpt, int msplit, void *stream)
 {
     LTR_CLEAR_STALE_ERROR();
-    if (kind < LTR_HINGE || kind > LTR_NDCG2 || bad_label_dtype(rel_dtype)) return LTR_ERR_KIND;
-    if (B < 0 || L <= 0) return LTR_ERR_SHAPE;
-    if (L > kMaxListLen) return LTR_ERR_LIST_TOO_LONG;
+    if (const int rc = check_kind(kind, rel_dtype)) return rc;
+    if (const int rc = check_lists(B, L, kMaxListLen)) return rc;
     if (B == 0) return LTR_OK;
     if (!scores || !rel || !n || !loss) return LTR_ERR_NULL;
     if (owners <= 0 || owners % 64 != 0 || msplit <= 0 || owners * msplit > 1024 ||
@@ -1165,9 +1194,8 @@ int ltr_pairwise_loss_ws_f32(int kind, float sigma, const float *scores, const v
                              float *dscores, void *workspace, size_t workspace_bytes, void *stream)
 {
     LTR_CLEAR_STALE_ERROR();
-    if (kind < LTR_HINGE || kind > LTR_NDCG2 || bad_label_dtype(rel_dtype)) return LTR_ERR_KIND;
-    if (B < 0 || L <= 0) return LTR_ERR_SHAPE;
-    if (L > kMaxListLen) return LTR_ERR_LIST_TOO_LONG;
+    if (const int rc = check_kind(kind, rel_dtype)) return rc;
+    if (const int rc = check_lists(B, L, kMaxListLen)) return rc;
     if (B == 0) return LTR_OK;
     if (!scores || !rel || !n || !loss) return LTR_ERR_NULL;
     const int nsplit = choose_loss_splits(kind, B, L);
@@ -1178,17 +1206,7 @@ int ltr_pairwise_loss_ws_f32(int kind, float sigma, const float *scores, const v
     p.scores = scores; p.rel = rel; p.n = n; p.loss = loss; p.dscores = dscores;
     p.B = B; p.L = L; p.sigma = sigma; p.rel_dtype = rel_dtype; p.msplit = kSplitWaves;
     p.sched = (B >= 16) ? (B + 63) / 64 : 0;            // (ignored by the part-major order)
-    float *ws = (float *)workspace;
-    hipStream_t st = (hipStream_t)stream;
-    switch (kind) {
-    case LTR_HINGE: return launch_loss_split<LTR_HINGE>(p, nsplit, ws, st);
-    case LTR_DCG_HINGE: return launch_loss_split<LTR_DCG_HINGE>(p, nsplit, ws, st);
-    case LTR_LOGISTIC: return launch_loss_split<LTR_LOGISTIC>(p, nsplit, ws, st);
-    case LTR_ARP1: return launch_loss_split<LTR_ARP1>(p, nsplit, ws, st);
-    case LTR_ARP2: return launch_loss_split<LTR_ARP2>(p, nsplit, ws, st);
-    case LTR_NDCG1: return launch_loss_split<LTR_NDCG1>(p, nsplit, ws, st);
-    default: return launch_loss_split<LTR_NDCG2>(p, nsplit, ws, st);
-    }
+    return with_kind(kind, [&](auto K) { return launch_loss_split<K>(p, nsplit, (float *)workspace, (hipStream_t)stream); });
 }
 
 
@@ -1230,117 +1248,69 @@ int ltr_scale_rows_uniform_f32(const float *dscores, const float *grad_scalar, i
     return (int)hipGetLastError();
 }
 
+// ---- rank_by_score / dcg / arp: index-order, explicit (_tie_) and hashed (_seed_) tie words ----
+int ltr_rank_by_score_f32(const float *scores, const int64_t *n, int B, int L, int64_t *ranking, void *stream)
+{
+    return metric_entry<METRIC_RANK>(scores, nullptr, 0, n, nullptr, 0, 0, nullptr, B, L, 0, 0, 0, ranking, kMaxListLen,
+                                     nullptr, 0, stream);
+}
+
 int ltr_rank_by_score_tie_f32(const float *scores, const int64_t *n, const int32_t *tie, int B, int L,
                               int64_t *ranking, void *stream)
 {
-    LTR_CLEAR_STALE_ERROR();
-    if (B < 0 || L <= 0) return LTR_ERR_SHAPE;
-    if (L > kMaxListLen) return LTR_ERR_LIST_TOO_LONG;
-    if (B == 0) return LTR_OK;
-    if (!scores || !n || !ranking) return LTR_ERR_NULL;
-    MetricParams p{};
-    p.scores = scores; p.rel = nullptr; p.n = n; p.tie = tie; p.out = ranking; p.B = B; p.L = L;
-    return launch_metric<METRIC_RANK>(p, (hipStream_t)stream);
+    return metric_entry<METRIC_RANK>(scores, nullptr, 0, n, tie, 0, 0, nullptr, B, L, 0, 0, 0, ranking, kMaxListLen,
+                                     nullptr, 0, stream);
 }
 
-int ltr_rank_by_score_f32(const float *scores, const int64_t *n, int B, int L, int64_t *ranking,
-                          void *stream)
+int ltr_rank_by_score_seed_f32(const float *scores, const int64_t *n, uint64_t seed, const int64_t *seed_dev,
+                               int B, int L, int64_t *ranking, void *stream)
 {
-    LTR_CLEAR_STALE_ERROR();
-    return ltr_rank_by_score_tie_f32(scores, n, nullptr, B, L, ranking, stream);
+    return metric_entry<METRIC_RANK>(scores, nullptr, 0, n, nullptr, 1, seed, seed_dev, B, L, 0, 0, 0, ranking,
+                                     kMaxListLen, nullptr, 0, stream);
+}
+
+int ltr_dcg_f32(const float *scores, const void *rel, int rel_dtype, const int64_t *n, int B,
+                int L, int k, int use_exp, int normalize, float *out, void *stream)
+{
+    return metric_entry<METRIC_DCG>(scores, rel, rel_dtype, n, nullptr, 0, 0, nullptr, B, L, k, use_exp, normalize, out,
+                                    kMaxListLen, nullptr, 0, stream);
 }
 
 int ltr_dcg_tie_f32(const float *scores, const void *rel, int rel_dtype, const int64_t *n,
                     const int32_t *tie, int B, int L, int k, int use_exp, int normalize, float *out,
                     void *stream)
 {
-    LTR_CLEAR_STALE_ERROR();
-    if (bad_label_dtype(rel_dtype)) return LTR_ERR_KIND;
-    if (B < 0 || L <= 0 || k < 0) return LTR_ERR_SHAPE;
-    if (L > kMaxListLen) return LTR_ERR_LIST_TOO_LONG;
-    if (B == 0) return LTR_OK;
-    if (!scores || !rel || !n || !out) return LTR_ERR_NULL;
-    MetricParams p{};
-    p.scores = scores; p.rel = rel; p.n = n; p.tie = tie; p.out = out; p.B = B; p.L = L;
-    p.rel_dtype = rel_dtype; p.k = k; p.use_exp = use_exp; p.normalize = normalize;
-    return launch_metric<METRIC_DCG>(p, (hipStream_t)stream);
-}
-
-int ltr_dcg_f32(const float *scores, const void *rel, int rel_dtype, const int64_t *n, int B,
-                int L, int k, int use_exp, int normalize, float *out, void *stream)
-{
-    LTR_CLEAR_STALE_ERROR();
-    return ltr_dcg_tie_f32(scores, rel, rel_dtype, n, nullptr, B, L, k, use_exp, normalize, out, stream);
-}
-
-int ltr_arp_tie_f32(const float *scores, const void *rel, int rel_dtype, const int64_t *n,
-                    const int32_t *tie, int B, int L, float *out, void *stream)
-{
-    LTR_CLEAR_STALE_ERROR();
-    if (bad_label_dtype(rel_dtype)) return LTR_ERR_KIND;
-    if (B < 0 || L <= 0) return LTR_ERR_SHAPE;
-    if (L > kMaxListLen) return LTR_ERR_LIST_TOO_LONG;
-    if (B == 0) return LTR_OK;
-    if (!scores || !rel || !n || !out) return LTR_ERR_NULL;
-    MetricParams p{};
-    p.scores = scores; p.rel = rel; p.n = n; p.tie = tie; p.out = out; p.B = B; p.L = L;
-    p.rel_dtype = rel_dtype;
-    return launch_metric<METRIC_ARP>(p, (hipStream_t)stream);
-}
-
-int ltr_arp_f32(const float *scores, const void *rel, int rel_dtype, const int64_t *n, int B,
-                int L, float *out, void *stream)
-{
-    LTR_CLEAR_STALE_ERROR();
-    return ltr_arp_tie_f32(scores, rel, rel_dtype, n, nullptr, B, L, out, stream);
-}
-
-// ---- the same three with the tie words hashed in the kernel from a seed (see tie_hash_word) ----
-int ltr_rank_by_score_seed_f32(const float *scores, const int64_t *n, uint64_t seed, const int64_t *seed_dev,
-                               int B, int L, int64_t *ranking, void *stream)
-{
-    LTR_CLEAR_STALE_ERROR();
-    if (B < 0 || L <= 0) return LTR_ERR_SHAPE;
-    if (L > kMaxListLen || L > kTieHashMaxLen) return LTR_ERR_LIST_TOO_LONG;
-    if (B == 0) return LTR_OK;
-    if (!scores || !n || !ranking) return LTR_ERR_NULL;
-    MetricParams p{};
-    p.scores = scores; p.rel = nullptr; p.n = n; p.tie = nullptr; p.out = ranking; p.B = B; p.L = L;
-    p.use_seed = 1; p.tie_seed = seed; p.tie_seed_dev = seed_dev;
-    return launch_metric<METRIC_RANK>(p, (hipStream_t)stream);
+    return metric_entry<METRIC_DCG>(scores, rel, rel_dtype, n, tie, 0, 0, nullptr, B, L, k, use_exp, normalize, out,
+                                    kMaxListLen, nullptr, 0, stream);
 }
 
 int ltr_dcg_seed_f32(const float *scores, const void *rel, int rel_dtype, const int64_t *n, uint64_t seed,
                      const int64_t *seed_dev, int B, int L, int k, int use_exp, int normalize, float *out,
                      void *stream)
 {
-    LTR_CLEAR_STALE_ERROR();
-    if (bad_label_dtype(rel_dtype)) return LTR_ERR_KIND;
-    if (B < 0 || L <= 0 || k < 0) return LTR_ERR_SHAPE;
-    if (L > kMaxListLen || L > kTieHashMaxLen) return LTR_ERR_LIST_TOO_LONG;
-    if (B == 0) return LTR_OK;
-    if (!scores || !rel || !n || !out) return LTR_ERR_NULL;
-    MetricParams p{};
-    p.scores = scores; p.rel = rel; p.n = n; p.tie = nullptr; p.out = out; p.B = B; p.L = L;
-    p.rel_dtype = rel_dtype; p.k = k; p.use_exp = use_exp; p.normalize = normalize;
-    p.use_seed = 1; p.tie_seed = seed; p.tie_seed_dev = seed_dev;
-    return launch_metric<METRIC_DCG>(p, (hipStream_t)stream);
+    return metric_entry<METRIC_DCG>(scores, rel, rel_dtype, n, nullptr, 1, seed, seed_dev, B, L, k, use_exp, normalize,
+                                    out, kMaxListLen, nullptr, 0, stream);
+}
+
+int ltr_arp_f32(const float *scores, const void *rel, int rel_dtype, const int64_t *n, int B,
+                int L, float *out, void *stream)
+{
+    return metric_entry<METRIC_ARP>(scores, rel, rel_dtype, n, nullptr, 0, 0, nullptr, B, L, 0, 0, 0, out, kMaxListLen,
+                                    nullptr, 0, stream);
+}
+
+int ltr_arp_tie_f32(const float *scores, const void *rel, int rel_dtype, const int64_t *n,
+                    const int32_t *tie, int B, int L, float *out, void *stream)
+{
+    return metric_entry<METRIC_ARP>(scores, rel, rel_dtype, n, tie, 0, 0, nullptr, B, L, 0, 0, 0, out, kMaxListLen,
+                                    nullptr, 0, stream);
 }
 
 int ltr_arp_seed_f32(const float *scores, const void *rel, int rel_dtype, const int64_t *n, uint64_t seed,
                      const int64_t *seed_dev, int B, int L, float *out, void *stream)
 {
-    LTR_CLEAR_STALE_ERROR();
-    if (bad_label_dtype(rel_dtype)) return LTR_ERR_KIND;
-    if (B < 0 || L <= 0) return LTR_ERR_SHAPE;
-    if (L > kMaxListLen || L > kTieHashMaxLen) return LTR_ERR_LIST_TOO_LONG;
-    if (B == 0) return LTR_OK;
-    if (!scores || !rel || !n || !out) return LTR_ERR_NULL;
-    MetricParams p{};
-    p.scores = scores; p.rel = rel; p.n = n; p.tie = nullptr; p.out = out; p.B = B; p.L = L;
-    p.rel_dtype = rel_dtype;
-    p.use_seed = 1; p.tie_seed = seed; p.tie_seed_dev = seed_dev;
-    return launch_metric<METRIC_ARP>(p, (hipStream_t)stream);
+    return metric_entry<METRIC_ARP>(scores, rel, rel_dtype, n, nullptr, 1, seed, seed_dev, B, L, 0, 0, 0, out,
+                                    kMaxListLen, nullptr, 0, stream);
 }
 
 uint32_t ltr_tie_hash_word(uint64_t seed, uint32_t position) { return tie_hash_word(seed, position); }

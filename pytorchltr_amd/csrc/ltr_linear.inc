@@ -1143,16 +1143,7 @@ int launch_linear_kind(const LinearParams &p, const LinearShape &s, hipStream_t 
 template <int VEC>
 int launch_linear(int kind, const LinearParams &p, const LinearShape &s, hipStream_t stream)
 {
-    switch (kind) {
-    case LTR_HINGE: return launch_linear_kind<LTR_HINGE, VEC>(p, s, stream);
-    case LTR_DCG_HINGE: return launch_linear_kind<LTR_DCG_HINGE, VEC>(p, s, stream);
-    case LTR_LOGISTIC: return launch_linear_kind<LTR_LOGISTIC, VEC>(p, s, stream);
-    case LTR_ARP1: return launch_linear_kind<LTR_ARP1, VEC>(p, s, stream);
-    case LTR_ARP2: return launch_linear_kind<LTR_ARP2, VEC>(p, s, stream);
-    case LTR_NDCG1: return launch_linear_kind<LTR_NDCG1, VEC>(p, s, stream);
-    case LTR_NDCG2: return launch_linear_kind<LTR_NDCG2, VEC>(p, s, stream);
-    default: return LTR_ERR_KIND;
-    }
+    return with_kind(kind, [&](auto K) { return launch_linear_kind<K, VEC>(p, s, stream); });
 }
 
 
@@ -1301,16 +1292,7 @@ int launch_regtile_kind(const LinearParams &p, const RegtileShape &s, hipStream_
 
 int launch_regtile(int kind, const LinearParams &p, const RegtileShape &s, hipStream_t stream)
 {
-    switch (kind) {
-    case LTR_HINGE: return launch_regtile_kind<LTR_HINGE>(p, s, stream);
-    case LTR_DCG_HINGE: return launch_regtile_kind<LTR_DCG_HINGE>(p, s, stream);
-    case LTR_LOGISTIC: return launch_regtile_kind<LTR_LOGISTIC>(p, s, stream);
-    case LTR_ARP1: return launch_regtile_kind<LTR_ARP1>(p, s, stream);
-    case LTR_ARP2: return launch_regtile_kind<LTR_ARP2>(p, s, stream);
-    case LTR_NDCG1: return launch_regtile_kind<LTR_NDCG1>(p, s, stream);
-    case LTR_NDCG2: return launch_regtile_kind<LTR_NDCG2>(p, s, stream);
-    default: return LTR_ERR_KIND;
-    }
+    return with_kind(kind, [&](auto K) { return launch_regtile_kind<K>(p, s, stream); });
 }
 
 }  // namespace
@@ -1564,7 +1546,7 @@ int linear_partials_launch(int kind, float sigma, const float *X, const float *W
                            const LazyRequest *lazy)
 {
     LTR_CLEAR_STALE_ERROR();
-    if (kind < LTR_HINGE || kind > LTR_NDCG2 || bad_label_dtype(rel_dtype)) return LTR_ERR_KIND;
+    if (const int rc = check_kind(kind, rel_dtype)) return rc;
     if (B < 0 || L <= 0 || F <= 0) return LTR_ERR_SHAPE;
     if (L > kMaxListLen) return LTR_ERR_LIST_TOO_LONG;
     if (B == 0) return LTR_OK;

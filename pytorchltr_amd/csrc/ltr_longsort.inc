@@ -359,8 +359,6 @@ __global__ void __launch_bounds__(kEpiThreads) longsort_curve_kernel(LongMetricP
 }
 
 // ---- host side ----
-int g_long_sort_all = 0;                 // ltr_debug_long_sort_all
-
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline int long_epi_tiles(int L) { return (L + kEpiTile - 1) / kEpiTile; }
 
@@ -436,7 +434,61 @@ inline LongKeyParams long_key_params(const float *scores, const void *rel, int r
     return k;
 }
 
-inline bool long_path(int L) { return L > kMaxListLen || __atomic_load_n(&g_long_sort_all, __ATOMIC_RELAXED) != 0; }
+// The sort path of the _long_ entry points past kMaxListLen (op = METRIC_*; arguments checked by metric_entry).
+int long_metric(int op, const float *scores, const void *rel, int rel_dtype, const int64_t *n, const int32_t *tie,
+                int use_seed, uint64_t seed, const int64_t *seed_dev, int B, int L, int k, int use_exp, int normalize,
+                void *out, void *workspace, size_t workspace_bytes, hipStream_t s)
+{
+    if (!workspace || workspace_bytes < long_workspace_bytes(op, B, L)) return LTR_ERR_WORKSPACE;
+    const LongWorkspace ws = long_workspace(workspace, B, L);
+    if (op == METRIC_RANK) {
+        long_sort(long_key_params(scores, nullptr, LTR_LABEL_F32, n, tie, use_seed, seed, seed_dev, L, ws, s), B, ws,
+                  (int64_t *)out, s);
+        return (int)hipGetLastError();
+    }
+    LongMetricParams p{};
+    p.k = long_key_params(scores, rel, rel_dtype, n, tie, use_seed, seed, seed_dev, L, ws, s);
+    p.ptiles = long_epi_tiles(L);
+    p.part = ws.part;
+    p.part2 = ws.part2;
+    p.out = (float *)out;
+    if (op == METRIC_DCG) {
+        p.use_exp = use_exp;
+        p.normalize = normalize;
+        const int kk = k > 0 ? (k < L ? k : L) : 0;
+        p.lim = kk > 0 ? kk : L;
+        p.tiles = long_epi_tiles(p.lim);
+        const dim3 grid((unsigned)((size_t)B * p.tiles)), block(kEpiThreads);
+        // the ideal ranking: the same sort keyed on labels (index words; equal labels have equal gains)
+        LongMetricParams ip = p;
+        ip.k.scores = nullptr; ip.k.mode = TIE_INDEX; ip.k.tie = nullptr; ip.k.seed_dev = nullptr;
+        ip.ideal = 1;
+        ip.part = ws.part2;
+        p.sorted = long_sort(p.k, B, ws, nullptr, s);
+        if (kk > 0) {
+            hipLaunchKernelGGL(longsort_partial_kernel<METRIC_DCG>, grid, block, 0, s, p);
+            if (normalize) {
+                ip.sorted = long_sort(ip.k, B, ws, nullptr, s);
+                hipLaunchKernelGGL(longsort_partial_kernel<METRIC_DCG>, grid, block, 0, s, ip);
+            }
+            hipLaunchKernelGGL(longsort_finish_kernel<METRIC_DCG>, dim3((unsigned)B), block, 0, s, p);
+        } else {
+            hipLaunchKernelGGL(longsort_partial_kernel<METRIC_DCG>, grid, block, 0, s, p);
+            hipLaunchKernelGGL(longsort_curve_kernel<false>, grid, block, 0, s, p);
+            if (normalize) {
+                ip.sorted = long_sort(ip.k, B, ws, nullptr, s);
+                hipLaunchKernelGGL(longsort_partial_kernel<METRIC_DCG>, grid, block, 0, s, ip);
+                hipLaunchKernelGGL(longsort_curve_kernel<true>, grid, block, 0, s, ip);
+            }
+        }
+        return (int)hipGetLastError();
+    }
+    p.tiles = p.ptiles;
+    p.sorted = long_sort(p.k, B, ws, nullptr, s);
+    hipLaunchKernelGGL(longsort_partial_kernel<METRIC_ARP>, dim3((unsigned)((size_t)B * p.tiles)), dim3(kEpiThreads), 0, s, p);
+    hipLaunchKernelGGL(longsort_finish_kernel<METRIC_ARP>, dim3((unsigned)B), dim3(kEpiThreads), 0, s, p);
+    return (int)hipGetLastError();
+}
 
 }  // namespace
 
@@ -457,109 +509,29 @@ LTR_DEBUG_HOOK int ltr_debug_long_sort_all(int on)
     return __atomic_exchange_n(&g_long_sort_all, on ? 1 : 0, __ATOMIC_RELAXED);
 }
 
+// ---- rank_by_score / dcg / arp on long lists (the other forms: ltr_kernels.hip; one body, metric_entry) ----
 int ltr_rank_by_score_long_f32(const float *scores, const int64_t *n, const int32_t *tie, int use_seed, uint64_t seed,
                                const int64_t *seed_dev, int B, int L, int64_t *ranking, void *workspace,
                                size_t workspace_bytes, void *stream)
 {
-    LTR_CLEAR_STALE_ERROR();
-    if (B < 0 || L <= 0) return LTR_ERR_SHAPE;
-    if (L > kMaxSortListLen) return LTR_ERR_LIST_TOO_LONG;
-    if (B == 0) return LTR_OK;
-    if (!scores || !n || !ranking) return LTR_ERR_NULL;
-    if (!long_path(L)) {
-        if (use_seed) return ltr_rank_by_score_seed_f32(scores, n, seed, seed_dev, B, L, ranking, stream);
-        return ltr_rank_by_score_tie_f32(scores, n, tie, B, L, ranking, stream);
-    }
-    if (!workspace || workspace_bytes < long_workspace_bytes(METRIC_RANK, B, L)) return LTR_ERR_WORKSPACE;
-    const hipStream_t s = (hipStream_t)stream;
-    const LongWorkspace ws = long_workspace(workspace, B, L);
-    const LongKeyParams k = long_key_params(scores, nullptr, LTR_LABEL_F32, n, tie, use_seed, seed, seed_dev, L, ws, s);
-    long_sort(k, B, ws, ranking, s);
-    return (int)hipGetLastError();
+    return metric_entry<METRIC_RANK>(scores, nullptr, 0, n, tie, use_seed, seed, seed_dev, B, L, 0, 0, 0, ranking,
+                                     kMaxSortListLen, workspace, workspace_bytes, stream);
 }
 
 int ltr_dcg_long_f32(const float *scores, const void *rel, int rel_dtype, const int64_t *n, const int32_t *tie,
                      int use_seed, uint64_t seed, const int64_t *seed_dev, int B, int L, int k, int use_exp,
                      int normalize, float *out, void *workspace, size_t workspace_bytes, void *stream)
 {
-    LTR_CLEAR_STALE_ERROR();
-    if (bad_label_dtype(rel_dtype)) return LTR_ERR_KIND;
-    if (B < 0 || L <= 0 || k < 0) return LTR_ERR_SHAPE;
-    if (L > kMaxSortListLen) return LTR_ERR_LIST_TOO_LONG;
-    if (B == 0) return LTR_OK;
-    if (!scores || !rel || !n || !out) return LTR_ERR_NULL;
-    if (!long_path(L)) {
-        if (use_seed)
-            return ltr_dcg_seed_f32(scores, rel, rel_dtype, n, seed, seed_dev, B, L, k, use_exp, normalize, out, stream);
-        return ltr_dcg_tie_f32(scores, rel, rel_dtype, n, tie, B, L, k, use_exp, normalize, out, stream);
-    }
-    if (!workspace || workspace_bytes < long_workspace_bytes(METRIC_DCG, B, L)) return LTR_ERR_WORKSPACE;
-    const hipStream_t s = (hipStream_t)stream;
-    const LongWorkspace ws = long_workspace(workspace, B, L);
-    LongMetricParams p{};
-    p.k = long_key_params(scores, rel, rel_dtype, n, tie, use_seed, seed, seed_dev, L, ws, s);
-    p.use_exp = use_exp;
-    p.normalize = normalize;
-    p.ptiles = long_epi_tiles(L);
-    p.part = ws.part;
-    p.part2 = ws.part2;
-    p.out = out;
-    const int kk = k > 0 ? (k < L ? k : L) : 0;
-    p.lim = kk > 0 ? kk : L;
-    p.tiles = long_epi_tiles(p.lim);
-    const dim3 grid((unsigned)((size_t)B * p.tiles)), block(kEpiThreads);
-    // the ideal ranking: the same sort keyed on labels (index words; equal labels have equal gains)
-    LongMetricParams ip = p;
-    ip.k.scores = nullptr; ip.k.mode = TIE_INDEX; ip.k.tie = nullptr; ip.k.seed_dev = nullptr;
-    ip.ideal = 1;
-    ip.part = ws.part2;
-    p.sorted = long_sort(p.k, B, ws, nullptr, s);
-    if (kk > 0) {
-        hipLaunchKernelGGL(longsort_partial_kernel<METRIC_DCG>, grid, block, 0, s, p);
-        if (normalize) {
-            ip.sorted = long_sort(ip.k, B, ws, nullptr, s);
-            hipLaunchKernelGGL(longsort_partial_kernel<METRIC_DCG>, grid, block, 0, s, ip);
-        }
-        hipLaunchKernelGGL(longsort_finish_kernel<METRIC_DCG>, dim3((unsigned)B), block, 0, s, p);
-    } else {
-        hipLaunchKernelGGL(longsort_partial_kernel<METRIC_DCG>, grid, block, 0, s, p);
-        hipLaunchKernelGGL(longsort_curve_kernel<false>, grid, block, 0, s, p);
-        if (normalize) {
-            ip.sorted = long_sort(ip.k, B, ws, nullptr, s);
-            hipLaunchKernelGGL(longsort_partial_kernel<METRIC_DCG>, grid, block, 0, s, ip);
-            hipLaunchKernelGGL(longsort_curve_kernel<true>, grid, block, 0, s, ip);
-        }
-    }
-    return (int)hipGetLastError();
+    return metric_entry<METRIC_DCG>(scores, rel, rel_dtype, n, tie, use_seed, seed, seed_dev, B, L, k, use_exp, normalize,
+                                    out, kMaxSortListLen, workspace, workspace_bytes, stream);
 }
 
 int ltr_arp_long_f32(const float *scores, const void *rel, int rel_dtype, const int64_t *n, const int32_t *tie,
                      int use_seed, uint64_t seed, const int64_t *seed_dev, int B, int L, float *out, void *workspace,
                      size_t workspace_bytes, void *stream)
 {
-    LTR_CLEAR_STALE_ERROR();
-    if (bad_label_dtype(rel_dtype)) return LTR_ERR_KIND;
-    if (B < 0 || L <= 0) return LTR_ERR_SHAPE;
-    if (L > kMaxSortListLen) return LTR_ERR_LIST_TOO_LONG;
-    if (B == 0) return LTR_OK;
-    if (!scores || !rel || !n || !out) return LTR_ERR_NULL;
-    if (!long_path(L)) {
-        if (use_seed) return ltr_arp_seed_f32(scores, rel, rel_dtype, n, seed, seed_dev, B, L, out, stream);
-        return ltr_arp_tie_f32(scores, rel, rel_dtype, n, tie, B, L, out, stream);
-    }
-    if (!workspace || workspace_bytes < long_workspace_bytes(METRIC_ARP, B, L)) return LTR_ERR_WORKSPACE;
-    const hipStream_t s = (hipStream_t)stream;
-    const LongWorkspace ws = long_workspace(workspace, B, L);
-    LongMetricParams p{};
-    p.k = long_key_params(scores, rel, rel_dtype, n, tie, use_seed, seed, seed_dev, L, ws, s);
-    p.ptiles = p.tiles = long_epi_tiles(L);
-    p.part = ws.part;
-    p.part2 = ws.part2;
-    p.out = out;
-    p.sorted = long_sort(p.k, B, ws, nullptr, s);
-    hipLaunchKernelGGL(longsort_partial_kernel<METRIC_ARP>, dim3((unsigned)((size_t)B * p.tiles)), dim3(kEpiThreads), 0, s, p);
-    hipLaunchKernelGGL(longsort_finish_kernel<METRIC_ARP>, dim3((unsigned)B), dim3(kEpiThreads), 0, s, p);
-    return (int)hipGetLastError();
+    return metric_entry<METRIC_ARP>(scores, rel, rel_dtype, n, tie, use_seed, seed, seed_dev, B, L, 0, 0, 0, out,
+                                    kMaxSortListLen, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

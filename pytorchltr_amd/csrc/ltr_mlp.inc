@@ -1041,27 +1041,8 @@ int ltr_mlp_pairwise_f32(int kind, float sigma, const float *X, const float *W1,
         p.loss = loss; p.scores_out = scores_out; p.part = (float *)workspace;
         p.B = B; p.L = L; p.F = F; p.H1 = H1; p.H2 = H2;
         p.sigma = sigma; p.rel_dtype = rel_dtype; p.P = P; p.pitch = mlp_pitch(P); p.fwd_only = 0;
-        int rc;
-        if (tile) {
-            switch (kind) {
-            case LTR_HINGE: rc = launch_mlp2_kind<LTR_HINGE>(p, grid, s); break;
-            case LTR_DCG_HINGE: rc = launch_mlp2_kind<LTR_DCG_HINGE>(p, grid, s); break;
-            case LTR_LOGISTIC: rc = launch_mlp2_kind<LTR_LOGISTIC>(p, grid, s); break;
-            case LTR_ARP1: rc = launch_mlp2_kind<LTR_ARP1>(p, grid, s); break;
-            case LTR_ARP2: rc = launch_mlp2_kind<LTR_ARP2>(p, grid, s); break;
-            case LTR_NDCG1: rc = launch_mlp2_kind<LTR_NDCG1>(p, grid, s); break;
-            default: rc = launch_mlp2_kind<LTR_NDCG2>(p, grid, s); break;
-            }
-        } else
-        switch (kind) {
-        case LTR_HINGE: rc = launch_mlp_kind<LTR_HINGE>(p, grid, s); break;
-        case LTR_DCG_HINGE: rc = launch_mlp_kind<LTR_DCG_HINGE>(p, grid, s); break;
-        case LTR_LOGISTIC: rc = launch_mlp_kind<LTR_LOGISTIC>(p, grid, s); break;
-        case LTR_ARP1: rc = launch_mlp_kind<LTR_ARP1>(p, grid, s); break;
-        case LTR_ARP2: rc = launch_mlp_kind<LTR_ARP2>(p, grid, s); break;
-        case LTR_NDCG1: rc = launch_mlp_kind<LTR_NDCG1>(p, grid, s); break;
-        default: rc = launch_mlp_kind<LTR_NDCG2>(p, grid, s); break;
-        }
+        const int rc = tile ? with_kind(kind, [&](auto K) { return launch_mlp2_kind<K>(p, grid, s); })
+                            : with_kind(kind, [&](auto K) { return launch_mlp_kind<K>(p, grid, s); });
         if (rc != 0) return rc;
     }
     // (grads as float4 needs a 16-byte aligned output; otherwise the 4-byte version)

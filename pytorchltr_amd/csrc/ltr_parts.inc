@@ -1669,16 +1669,7 @@ int launch_parts(int kind, const LinearParams &p, const PartsShape &s, hipStream
     pp.gran_words = (unsigned long long)(gran_have / 8);
     pp.ctrl = reinterpret_cast<int *>(misc);
     pp.pvec = reinterpret_cast<float *>(misc + kPtCtrlBytes);
-    switch (kind) {
-    case LTR_HINGE: return launch_parts_kind<LTR_HINGE>(pp, s, stream);
-    case LTR_LOGISTIC: return launch_parts_kind<LTR_LOGISTIC>(pp, s, stream);
-    case LTR_DCG_HINGE: return launch_parts_kind<LTR_DCG_HINGE>(pp, s, stream);
-    case LTR_ARP1: return launch_parts_kind<LTR_ARP1>(pp, s, stream);
-    case LTR_ARP2: return launch_parts_kind<LTR_ARP2>(pp, s, stream);
-    case LTR_NDCG1: return launch_parts_kind<LTR_NDCG1>(pp, s, stream);
-    case LTR_NDCG2: return launch_parts_kind<LTR_NDCG2>(pp, s, stream);
-    default: return LTR_ERR_KIND;
-    }
+    return with_kind(kind, [&](auto K) { return launch_parts_kind<K>(pp, s, stream); });
 }
 
 }  // namespace

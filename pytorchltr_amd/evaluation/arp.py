@@ -21,26 +21,14 @@ def arp(scores: _torch.FloatTensor, relevance: _torch.LongTensor,
     s, r, nn = _prepare(scores, relevance, n, limit_len=False)
     B, L = s.shape
     out = _torch.empty(B, dtype=_torch.float32, device=s.device)
-    if L > _C.max_list_len():
-        # past one workgroup's LDS: the sort path (include/ltr_hip.h: ltr_arp_long_f32)
-        if L > _C.max_sort_list_len():
-            raise ValueError("list_size %d exceeds the supported maximum %d" % (L, _C.max_sort_list_len()))
-        if B > 0:
-            sd = _ties.draw_seed(L, s.device)
-            ws, nbytes = _C.sort_workspace(2, B, L, s.device)
-            with _C.device_ctx(s):
-                _C.check(_C.lib().ltr_arp_long_f32(
-                    _C.ptr(s), _C.ptr(r), _C.label_dtype(r), _C.ptr(nn), None, int(sd is not None),
-                    sd[0] if sd is not None else 0, _C.ptr(sd[1]) if sd is not None else None, B, L, _C.ptr(out),
-                    _C.ptr(ws), nbytes, _C.stream_of(s)))
-        return out
+    if L > _C.max_sort_list_len():
+        raise ValueError("list_size %d exceeds the supported maximum %d" % (L, _C.max_sort_list_len()))
     if B > 0:
         sd = _ties.draw_seed(L, s.device)             # random tie-break, as the reference (arp.py:32)
+        ws, nbytes = _C.sort_workspace(2, B, L, s.device)
         with _C.device_ctx(s):
-            if sd is None:
-                _C.check(_C.lib().ltr_arp_f32(_C.ptr(s), _C.ptr(r), _C.label_dtype(r), _C.ptr(nn), B, L,
-                                              _C.ptr(out), _C.stream_of(s)))
-            else:
-                _C.check(_C.lib().ltr_arp_seed_f32(_C.ptr(s), _C.ptr(r), _C.label_dtype(r), _C.ptr(nn), sd[0],
-                                                   _C.ptr(sd[1]), B, L, _C.ptr(out), _C.stream_of(s)))
+            _C.check(_C.lib().ltr_arp_long_f32(
+                _C.ptr(s), _C.ptr(r), _C.label_dtype(r), _C.ptr(nn), None, int(sd is not None),
+                sd[0] if sd is not None else 0, _C.ptr(sd[1]) if sd is not None else None, B, L, _C.ptr(out),
+                _C.ptr(ws), nbytes, _C.stream_of(s)))
     return out

@@ -32,29 +32,11 @@ def _run(scores, relevance, n, k, exp, normalize):
     B, L = s.shape
     kk = _cutoff(k, L)
     out = _torch.empty((B,) if kk > 0 else (B, L), dtype=_torch.float32, device=s.device)
-    if L > _C.max_list_len():
-        return _run_long(s, r, nn, kk, exp, normalize, out)
-    if B > 0:
-        # the reference ranks through rank_by_score with its global-RNG tie-break (dcg.py:85)
-        # (round 3: a seed drawn on the host, hashed into tie words inside the kernel -- no randperm launches)
-        sd = _ties.draw_seed(L, s.device)
-        with _C.device_ctx(s):
-            if sd is None:
-                _C.check(_C.lib().ltr_dcg_f32(_C.ptr(s), _C.ptr(r), _C.label_dtype(r), _C.ptr(nn), B, L, kk,
-                                              int(bool(exp)), int(normalize), _C.ptr(out), _C.stream_of(s)))
-            else:
-                _C.check(_C.lib().ltr_dcg_seed_f32(_C.ptr(s), _C.ptr(r), _C.label_dtype(r), _C.ptr(nn), sd[0],
-                                                   _C.ptr(sd[1]), B, L, kk, int(bool(exp)), int(normalize),
-                                                   _C.ptr(out), _C.stream_of(s)))
-    return out
-
-
-def _run_long(s, r, nn, kk, exp, normalize, out):
-    """Lists past one workgroup's LDS: the sort path (include/ltr_hip.h: ltr_dcg_long_f32)."""
-    B, L = s.shape
     if L > _C.max_sort_list_len():
         raise ValueError("list_size %d exceeds the supported maximum %d" % (L, _C.max_sort_list_len()))
     if B > 0:
+        # the reference ranks through rank_by_score with its global-RNG tie-break (dcg.py:85)
+        # (round 3: a seed drawn on the host, hashed into tie words inside the kernel -- no randperm launches)
         sd = _ties.draw_seed(L, s.device)
         ws, nbytes = _C.sort_workspace(1, B, L, s.device)
         with _C.device_ctx(s):

@@ -50,27 +50,15 @@ def _rank(scores2d, nn, seed=None):
     """seed: None (index order) or (seed, seed_tensor) from _ties.draw_seed."""
     B, L = scores2d.shape
     ranking = _torch.empty(B, L, dtype=_torch.int64, device=scores2d.device)
-    if L > _C.max_list_len():
-        # past one workgroup's LDS: the sort path (include/ltr_hip.h: ltr_rank_by_score_long_f32)
-        if L > _C.max_sort_list_len():
-            raise ValueError("list_size %d exceeds the supported maximum %d" % (L, _C.max_sort_list_len()))
-        if B > 0:
-            ws, nbytes = _C.sort_workspace(0, B, L, scores2d.device)
-            with _C.device_ctx(scores2d):
-                _C.check(_C.lib().ltr_rank_by_score_long_f32(
-                    _C.ptr(scores2d), _C.ptr(nn), None, int(seed is not None), seed[0] if seed is not None else 0,
-                    _C.ptr(seed[1]) if seed is not None else None, B, L, _C.ptr(ranking), _C.ptr(ws), nbytes,
-                    _C.stream_of(scores2d)))
-        return ranking
+    if L > _C.max_sort_list_len():
+        raise ValueError("list_size %d exceeds the supported maximum %d" % (L, _C.max_sort_list_len()))
     if B > 0:
+        ws, nbytes = _C.sort_workspace(0, B, L, scores2d.device)
         with _C.device_ctx(scores2d):
-            if seed is None:
-                _C.check(_C.lib().ltr_rank_by_score_f32(
-                    _C.ptr(scores2d), _C.ptr(nn), B, L, _C.ptr(ranking), _C.stream_of(scores2d)))
-            else:
-                _C.check(_C.lib().ltr_rank_by_score_seed_f32(
-                    _C.ptr(scores2d), _C.ptr(nn), seed[0], _C.ptr(seed[1]), B, L, _C.ptr(ranking),
-                    _C.stream_of(scores2d)))
+            _C.check(_C.lib().ltr_rank_by_score_long_f32(
+                _C.ptr(scores2d), _C.ptr(nn), None, int(seed is not None), seed[0] if seed is not None else 0,
+                _C.ptr(seed[1]) if seed is not None else None, B, L, _C.ptr(ranking), _C.ptr(ws), nbytes,
+                _C.stream_of(scores2d)))
     return ranking
 
 
