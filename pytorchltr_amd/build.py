@@ -16,9 +16,9 @@ LIB_PATH = os.path.join(CSRC, "libltr_hip.so")
 SOURCES = [os.path.join(CSRC, f) for f in ("ltr_kernels.hip", "ltr_linear.hip", "ltr_mlp.hip")]
 SOURCE_FLAGS = {}          # per-source compiler flags (none at present)
 OBJ_DIR = os.path.join(_ROOT, "build", "obj")
-# every .inc the translation units include, and the public header
+# every .inc the translation units include, and the public headers
 DEPENDS = SOURCES + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".inc")) + \
-    [os.path.join(_ROOT, "include", "ltr_hip.h")]
+    [os.path.join(_ROOT, "include", h) for h in ("ltr_hip.h", "ltr_eval.h")]
 ARCH = "gfx950"
 IO_LIB_PATH = os.path.join(CSRC, "libltr_io.so")
 IO_SOURCES = [os.path.join(CSRC, "svmrank_parser.cpp")]

@@ -479,15 +479,14 @@ __device__ void block_inclusive_scan(float *buf, int L, float *scan_scratch)
 
 enum { METRIC_RANK = 0, METRIC_DCG = 1, METRIC_ARP = 2 };
 
-// (the sort path, DPT <= 0, under 64 VGPRs -- eight waves per SIMD: its workgroups have up to 1024 threads, and at the 68-69 VGPRs
-// the compiler takes when left alone ONE of those fits a CU instead of two.  ndcg@10, 16 384 x 1000: 1167 -> 746 us, arp 631 -> 399,
-// 65 536 x 512: 1260 -> 1103, 8192 x 2000: 1096 -> 746; lists of 128: unchanged.  Round 6.)
-template <int OP, int DPT>
-__global__ void __launch_bounds__(1024, (DPT <= 0 ? 8 : 4))
-metric_kernel(MetricParams p)
+// The ranking of one staged query (sy: (score, label) of the first nb documents): rank_s[k] = rank of document k by
+// score, and with_y: rank_y[k] by label (the ideal ranking); ranks < nb, ties by the tie words of p.  The sort path
+// (DPT <= 0) goes through the curve region (and an inverse tie map at the end of metric_lds_bytes_sort), the counting
+// rank (DPT > 0) keeps its packed keys there.  Shared by metric_kernel and eval_kernel (ltr_eval.inc).
+template <int DPT>
+__device__ __forceinline__ void metric_ranks(const MetricParams &p, unsigned char *smem, const float2 *sy, int *rank_s,
+                                             int *rank_y, float *curve, int nb, bool with_y)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int b = blockIdx.x;
     const int L = p.L;
     const int L4 = (L + 3) & ~3;
     const int tid = threadIdx.x;
@@ -496,30 +495,9 @@ metric_kernel(MetricParams p)
     const int owners = T / msplit;
     const int o = tid % owners;
     const int slice = tid / owners;
-    const int nb = clamp_n(p.n[b], L);
-
-    float2 *sy = reinterpret_cast<float2 *>(smem);
-    int *rank_s = reinterpret_cast<int *>(smem + 8 * (size_t)L4);
-    int *rank_y = rank_s + L4;
-    float *curve = reinterpret_cast<float *>(smem + 16 * (size_t)L4);
-    float *icurve = curve + L4;
-    float *red = icurve + L4;
-    float *scan_scratch = red + 32;
-
-    const size_t row = (size_t)b * L;
-    const bool need_labels = (OP != METRIC_RANK);
-    // dcg keeps the reference's quirk: padded labels are read and counted (dcg.py:85-94)
-    const int nload = (OP == METRIC_DCG) ? L : nb;
-    for (int m = tid; m < nload; m += T)
-        sy[m] = make_float2(p.scores[row + m],
-                            need_labels ? load_label(p.rel, p.rel_dtype, row + m) : 0.f);
-    for (int m = tid; m < 2 * L4; m += T) rank_s[m] = 0;
-    __syncthreads();
-
     const int mlen = (nb + msplit - 1) / msplit;
     const int m0 = __builtin_amdgcn_readfirstlane(slice * mlen);
     const int m1 = __builtin_amdgcn_readfirstlane(min(nb, m0 + mlen));
-    const bool with_y = (OP == METRIC_DCG) && p.normalize;
     if (DPT <= 0) {
         // long lists: bitonic sort of (score, index) keys -- and of (label, index) for the ideal
         // ranking -- through the curve buffer; T = min(1024, P), E = P / T registers per thread
@@ -570,6 +548,42 @@ metric_kernel(MetricParams p)
         else
             count_ranks_keyed<(DPT > 0 ? DPT : 1), false>(keys, nb, owners, o, m0, m1, msplit > 1, rank_s, rank_y);
     }
+}
+
+// (the sort path, DPT <= 0, under 64 VGPRs -- eight waves per SIMD: its workgroups have up to 1024 threads, and at the 68-69 VGPRs
+// the compiler takes when left alone ONE of those fits a CU instead of two.  ndcg@10, 16 384 x 1000: 1167 -> 746 us, arp 631 -> 399,
+// 65 536 x 512: 1260 -> 1103, 8192 x 2000: 1096 -> 746; lists of 128: unchanged.  Round 6.)
+template <int OP, int DPT>
+__global__ void __launch_bounds__(1024, (DPT <= 0 ? 8 : 4))
+metric_kernel(MetricParams p)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int b = blockIdx.x;
+    const int L = p.L;
+    const int L4 = (L + 3) & ~3;
+    const int tid = threadIdx.x;
+    const int T = blockDim.x;
+    const int nb = clamp_n(p.n[b], L);
+
+    float2 *sy = reinterpret_cast<float2 *>(smem);
+    int *rank_s = reinterpret_cast<int *>(smem + 8 * (size_t)L4);
+    int *rank_y = rank_s + L4;
+    float *curve = reinterpret_cast<float *>(smem + 16 * (size_t)L4);
+    float *icurve = curve + L4;
+    float *red = icurve + L4;
+    float *scan_scratch = red + 32;
+
+    const size_t row = (size_t)b * L;
+    const bool need_labels = (OP != METRIC_RANK);
+    // dcg keeps the reference's quirk: padded labels are read and counted (dcg.py:85-94)
+    const int nload = (OP == METRIC_DCG) ? L : nb;
+    for (int m = tid; m < nload; m += T)
+        sy[m] = make_float2(p.scores[row + m],
+                            need_labels ? load_label(p.rel, p.rel_dtype, row + m) : 0.f);
+    for (int m = tid; m < 2 * L4; m += T) rank_s[m] = 0;
+    __syncthreads();
+
+    metric_ranks<DPT>(p, smem, sy, rank_s, rank_y, curve, nb, (OP == METRIC_DCG) && p.normalize);
     __syncthreads();
 
     if (OP == METRIC_RANK) {
@@ -1010,10 +1024,12 @@ static int launch_loss_split(const LossParams &p, int nsplit, float *ws, hipStre
     return (int)hipGetLastError();
 }
 
-template <int OP>
-int launch_metric(const MetricParams &p0, hipStream_t stream)
+// The launch shape of the one-workgroup metric kernels (metric_kernel, eval_kernel of ltr_eval.inc): the DPT
+// instantiation (0, -2, -4: the sort path with 1, 2, 4 keys per thread; 1, 2, 4: the counting rank), the
+// workgroup size and the dynamic LDS; sets p.msplit.
+struct MetricShape { int dpt; int threads; size_t lds; };
+inline MetricShape metric_shape(MetricParams &p)
 {
-    MetricParams p = p0;
     if (p.L > kSortRankMinLen) {
         const int P = sort_pow2(p.L);
         int T = P < 1024 ? P : 1024;                    // E = P / T <= 4 keys per thread
@@ -1023,19 +1039,7 @@ int launch_metric(const MetricParams &p0, hipStream_t stream)
         // keys per thread: 65 536 x 512 889, 8192 x 2000 747 -> 804 -- not taken.)
         if (P <= 1024 && P >= 128 && (long)p.B >= 16L * device_cu_count()) T = P / 2;
         p.msplit = 1;
-        const size_t lds = metric_lds_bytes_sort(p.L);
-        const dim3 sgrid((unsigned)p.B), sblock((unsigned)T);
-        if (P == T) {
-            LTR_ENSURE_LDS((metric_kernel<OP, 0>), lds);
-            hipLaunchKernelGGL((metric_kernel<OP, 0>), sgrid, sblock, lds, stream, p);
-        } else if (P == 2 * T) {
-            LTR_ENSURE_LDS((metric_kernel<OP, -2>), lds);
-            hipLaunchKernelGGL((metric_kernel<OP, -2>), sgrid, sblock, lds, stream, p);
-        } else {
-            LTR_ENSURE_LDS((metric_kernel<OP, -4>), lds);
-            hipLaunchKernelGGL((metric_kernel<OP, -4>), sgrid, sblock, lds, stream, p);
-        }
-        return (int)hipGetLastError();
+        return {P == T ? 0 : (P == 2 * T ? -2 : -4), T, metric_lds_bytes_sort(p.L)};
     }
     LaunchShape s = choose_shape(p.B, p.L);
     // (many rounds of queries per CU: ONE wave per query, two documents per thread -- what bounds the launch then is the number of
@@ -1043,14 +1047,24 @@ int launch_metric(const MetricParams &p0, hipStream_t stream)
     // 1359, arp 2^20: 1216 -> 804; at 1024 queries the two-wave shape stays, 6.6 against 8.0)
     if (p.L > 64 && p.L <= 128 && (long)p.B >= 64L * device_cu_count()) { s.owners = 64; s.dpt = 2; s.msplit = 1; }
     p.msplit = s.msplit;
-    const dim3 grid((unsigned)p.B), block((unsigned)(s.owners * s.msplit));
-    const size_t lds = metric_lds_bytes(p.L);
+    return {s.dpt == 1 || s.dpt == 2 ? s.dpt : 4, s.owners * s.msplit, metric_lds_bytes(p.L)};
+}
+
+template <int OP>
+int launch_metric(const MetricParams &p0, hipStream_t stream)
+{
+    MetricParams p = p0;
+    const MetricShape sh = metric_shape(p);
+    const dim3 grid((unsigned)p.B), block((unsigned)sh.threads);
 #define LTR_LAUNCH(D)                                                                           \
     do {                                                                                        \
-        LTR_ENSURE_LDS((metric_kernel<OP, D>), lds);          \
-        hipLaunchKernelGGL((metric_kernel<OP, D>), grid, block, lds, stream, p);                \
+        LTR_ENSURE_LDS((metric_kernel<OP, D>), sh.lds);                                         \
+        hipLaunchKernelGGL((metric_kernel<OP, D>), grid, block, sh.lds, stream, p);             \
     } while (0)
-    switch (s.dpt) {
+    switch (sh.dpt) {
+    case 0: LTR_LAUNCH(0); break;
+    case -2: LTR_LAUNCH(-2); break;
+    case -4: LTR_LAUNCH(-4); break;
     case 1: LTR_LAUNCH(1); break;
     case 2: LTR_LAUNCH(2); break;
     default: LTR_LAUNCH(4); break;
@@ -1444,3 +1458,4 @@ int ltr_collate_pad_csr_f32(const int64_t *indptr, const int32_t *indices, const
 
 #include "ltr_f64.inc"
 #include "ltr_longsort.inc"
+#include "ltr_eval.inc"
