@@ -311,28 +311,14 @@ __device__ __forceinline__ void linear_pairwise_body(const LinearParams &p)
 constexpr int kRegtileMinW = 6;       // waves/SIMD the register allocator must allow (<= 80 VGPRs)
 constexpr int kRegtileThreads = 512;       // measured sweet spot on MI355X (256..1024 swept)
 
-// LDS after the query block: gfin float[L4], then max(pd float[L*(C+1)], dred float4[R*C]).
-// (L <= 256: symmetric pair pass -- LDS rows padded to 64-wide tiles, one slice per wave)
+// the lists the register tile takes: the symmetric pair pass's (LDS rows padded to 64-wide tiles, one slice per wave)
 __host__ __device__ inline bool regtile_sym(int L) { return L <= 256; }
-__host__ __device__ inline int regtile_stride(int L) { return regtile_sym(L) ? ((L + 63) & ~63) : ((L + 3) & ~3); }
-
-__host__ __device__ inline size_t regtile_lds_bytes(int kind, int L, int F, int msplit)
-{
-    const size_t L4 = (size_t)regtile_stride(L);
-    const size_t C = (size_t)F / 4;
-    const size_t R = (size_t)kRegtileThreads / C;
-    size_t bytes = (loss_lds_bytes(kind, (int)L4, msplit) + 15) & ~(size_t)15;
-    size_t pd = 4 * (size_t)L * (C + 1);
-    size_t dr = 16 * R * C + 4 * R;
-    return bytes + 4 * L4 + (((pd > dr ? pd : dr) + 15) & ~(size_t)15);
-}
 
 __device__ __forceinline__ float4 f4_scale(float4 v, float g) { return make_float4(v.x * g, v.y * g, v.z * g, v.w * g); }
 
 // ---------------------------------------------------------------------------------
 // Register tile (lists up to 256 documents: the symmetric pair pass).  The round-1 version of this kernel
-// (linear_regtile_kernel: retired in round 4, it only still served lists of 257..512 documents with very narrow
-// rows) had the same mapping and arithmetic; what changed is everything
+// (linear_regtile_kernel, retired in round 4) had the same mapping and arithmetic; what changed is everything
 // around it, from the instruction trace of the first version (profiles/r02_regtile_trace.txt: the
 // launch was as much VALU-issue- as HBM-bound -- ~3.5 k VALU wave-instructions per query of which
 // the pair pass needs < 1 k -- and two dependent HBM round trips sat in front of the first feature
@@ -378,9 +364,8 @@ __host__ __device__ inline size_t lazy_area_words(int F)
 // two rankings + gains per query -- C3 fused kernel 19.5 -> 17.4 us; hinge 11.2 -> 11.4, so the
 // rank-free kinds keep 512)
 // NI = 19 at TT = 512 (round 4): the lists the 9- / 12-sweep tiles cannot hold, at <= 128 VGPRs (two workgroups per
-// CU) -- see choose_regtile_shape.  TT = 1024 (nine sweeps, two workgroups per CU at <= 64 VGPRs) was built for the
-// same lists first and is not instantiated any more (8-9 % slower than 19 sweeps; EXPERIMENTS.md).
-constexpr int kRegtileMinW1024 = 8;
+// CU) -- see choose_regtile_shape.  (A 1024-thread tile of nine sweeps was built for the same lists first: 8-9 % slower
+// than 19 sweeps, EXPERIMENTS.md.)
 // a * b rounded to fp32 on its own: the product is opaque to the compiler, which may not contract it with the sum behind it
 // (__fmul_rn is a plain multiplication in HIP)
 __device__ __forceinline__ float mul_rounded(float a, float b)
@@ -595,7 +580,7 @@ linear_regtile2_kernel(LinearParams p)
 }
 
 template <int KIND, int NI, int CT, int TT>
-__global__ void __launch_bounds__(TT, (TT == 512 ? (NI >= 19 ? 4 : kRegtileMinW) : (TT == 1024 ? (NI <= 9 ? kRegtileMinW1024 : 4) : 4)))
+__global__ void __launch_bounds__(TT, (TT == 512 && NI < 19 ? kRegtileMinW : 4))
 linear_regtile2w_kernel(LinearParams p)
 {
     linear_regtile2_body<KIND, NI, CT, TT>(p);
@@ -1148,22 +1133,26 @@ int launch_linear(int kind, const LinearParams &p, const LinearShape &s, hipStre
 
 
 
-struct RegtileShape { int ni, msplit; size_t lds; int v2, threads; };
+// NI sweeps of `threads` threads (512, or the NDCG kinds' 256), `lds` bytes of dynamic LDS
+struct RegtileShape { int ni, threads; size_t lds; };
 
 bool choose_regtile_shape(int kind, int L, int F, RegtileShape &s)
 {
-    if (F % 4 != 0 || L > kRegtileThreads) return false;
+    // (lists beyond the symmetric pass: cluster / parts / general kernel)
+    if (F % 4 != 0 || !regtile_sym(L)) return false;
     const int C = F / 4;
     if (C > kRegtileThreads) return false;
+    const bool ndcg = (kind == LTR_NDCG1 || kind == LTR_NDCG2);
     const int R = kRegtileThreads / C;
     const int ni = (L + R - 1) / R;
+    s.threads = kRegtileThreads;
     if (ni <= 3) s.ni = 3;
     else if (ni <= 5) s.ni = 5;
     else if (ni <= 9) s.ni = 9;
     // 12 sweeps (F = 136: lists up to 180) for the rank-free kinds: 1024 x 160 x 136 hinge 26.2 -> 21.0 us,
     // logistic 28.6 -> 23.7 against the two-pass kernel; LambdaNDCG2 35.5 -> 39.0, and 19 sweeps
     // (lists up to 285) lose for every kind (1024 x 256 x 136 hinge 35 -> 52): occupancy
-    else if (ni <= 12 && kind != LTR_NDCG1 && kind != LTR_NDCG2) s.ni = 12;
+    else if (ni <= 12 && !ndcg) s.ni = 12;
     else {
         // Round 4: NINETEEN sweeps on the 512-thread workgroups -- lists of up to 256 documents at F = 136 (171 at
         // F = 220) -- at <= 128 VGPRs, i.e. two workgroups per CU instead of four: these shapes fell to the two-pass
@@ -1178,121 +1167,86 @@ bool choose_regtile_shape(int kind, int L, int F, RegtileShape &s)
         // NDCG kinds spill 4-12 registers under the 128 there and still beat the two-pass kernel: 1024 x 200 x 220
         // LambdaNDCG1 / 2 43.9 / 44.6 -> 37.5 / 39.5 us, 512 x 200 x 220 40.9 -> 24.9)
         const int nsw = (ni <= 19) ? 19 : ((ni <= 24) ? 24 : 0);
-        if (!regtile_sym(L) || nsw == 0) return false;
-        const size_t lds19 = regtile2_lds_bytes(kind, L, F, nsw, kRegtileThreads);
-        if (lds19 > 78 * 1024) return false;
-        s.ni = nsw; s.msplit = kRegtileThreads / 64; s.lds = lds19; s.v2 = 1; s.threads = kRegtileThreads;
-        return true;
+        if (nsw == 0) return false;
+        s.ni = nsw;
+        s.lds = regtile2_lds_bytes(kind, L, F, nsw, kRegtileThreads);
+        return s.lds <= 78 * 1024;
     }
-    int owners = 64;
-    while (owners < L) owners *= 2;
-    if (owners > kRegtileThreads || kRegtileThreads % owners != 0) {
-        // non power-of-two workgroups: owners must divide T in whole waves
-        owners = 64;
-        while (owners < L && owners * 2 <= kRegtileThreads && kRegtileThreads % (owners * 2) == 0) owners *= 2;
-        if (owners < L) return false;
-    }
-    s.msplit = regtile_sym(L) ? (kRegtileThreads / 64) : (kRegtileThreads / owners);
-    s.lds = regtile_lds_bytes(kind, L, F, s.msplit);
-    s.v2 = 0;
-    s.threads = kRegtileThreads;
-    if (!regtile_sym(L)) return false;            // (lists beyond the symmetric pass: cluster / parts / general kernel)
-    {
-        if (kind == LTR_NDCG1 || kind == LTR_NDCG2) {
-            // 256-thread workgroups, up to 19 sweeps in registers
-            const int R2 = 256 / C;
-            const int ni2 = R2 > 0 ? (L + R2 - 1) / R2 : 99;
-            const int n2 = ni2 <= 5 ? 5 : (ni2 <= 9 ? 9 : (ni2 <= 12 ? 12 : (ni2 <= 19 ? 19 : 0)));
-            if (n2 > 0 && C <= 256) {
-                const size_t lds256 = regtile2_lds_bytes(kind, L, F, n2, 256);
-                if (lds256 <= 40 * 1024) { s.v2 = 1; s.threads = 256; s.ni = n2; s.lds = lds256; return true; }
-            }
+    if (ndcg && C <= 256) {
+        // 256-thread workgroups, up to 19 sweeps in registers
+        const int R2 = 256 / C;
+        const int ni2 = (L + R2 - 1) / R2;
+        const int n2 = ni2 <= 5 ? 5 : (ni2 <= 9 ? 9 : (ni2 <= 12 ? 12 : (ni2 <= 19 ? 19 : 0)));
+        if (n2 > 0) {
+            const size_t lds256 = regtile2_lds_bytes(kind, L, F, n2, 256);
+            if (lds256 <= 40 * 1024) { s.threads = 256; s.ni = n2; s.lds = lds256; return true; }
         }
-        const size_t lds2 = regtile2_lds_bytes(kind, L, F, s.ni, kRegtileThreads);
-        if (lds2 <= 64 * 1024) { s.v2 = 1; s.lds = lds2; return true; }
     }
-    return false;
+    s.lds = regtile2_lds_bytes(kind, L, F, s.ni, kRegtileThreads);
+    return s.lds <= 64 * 1024;
 }
 
 struct KernelEvents { bool armed; hipEvent_t start, stop; };
 inline KernelEvents &kernel_events() { static thread_local KernelEvents e = {false, nullptr, nullptr}; return e; }
 
-template <int KIND, int CT>
-int launch_regtile2_ct(const LinearParams &p, const RegtileShape &s, hipStream_t stream)
+// One launch of the register tile, NI sweeps of TT threads.  `ke` (or null): the start / stop event pair ltr_debug_kernel_events
+// armed -- recorded by the command processor right at the kernel's begin and end (bench.py's live duration of the lazy launch) --,
+// for the 512-thread tiles of 3 / 5 / 9 sweeps only: any other tile is a plain launch and leaves the events unrecorded.
+template <int KIND, int NI, int CT, int TT>
+int launch_regtile2_tt(const LinearParams &p, size_t lds, const KernelEvents *ke, hipStream_t stream)
 {
+    constexpr auto entry = regtile2_entry<KIND, NI, CT, TT>();
     const dim3 grid((unsigned)(p.B + (p.pend_B > 0 ? p.pend_nred : 0)));        // (a lazy step: the reducer workgroups in front)
-    if (s.threads == 256) {
-        kernel_events().armed = false;               // (the measurement hook serves the 512-thread tile only)
-        constexpr bool k256 = (KIND == LTR_NDCG1 || KIND == LTR_NDCG2);
-        if constexpr (k256) {
-            const dim3 block(256);
-            switch (s.ni) {
-            case 5: hipLaunchKernelGGL((regtile2_entry<KIND, 5, CT, 256>()), grid, block, s.lds, stream, p); break;
-            case 9: hipLaunchKernelGGL((regtile2_entry<KIND, 9, CT, 256>()), grid, block, s.lds, stream, p); break;
-            case 12: hipLaunchKernelGGL((regtile2_entry<KIND, 12, CT, 256>()), grid, block, s.lds, stream, p); break;
-            case 19: hipLaunchKernelGGL((regtile2_entry<KIND, 19, CT, 256>()), grid, block, s.lds, stream, p); break;
-            default: return LTR_ERR_CONFIG;
-            }
+    if constexpr (TT == kRegtileThreads && NI >= 19) LTR_ENSURE_LDS((*entry), lds);       // (up to 78 KiB of LDS)
+    if constexpr (TT == kRegtileThreads && NI <= 9) {
+        if (ke) {
+            hipExtLaunchKernelGGL(entry, grid, dim3(TT), (unsigned)lds, stream, ke->start, ke->stop, 0, p);
             return (int)hipGetLastError();
-        } else {
-            return LTR_ERR_CONFIG;
         }
     }
-    const dim3 block((unsigned)kRegtileThreads);
-    // (measurement: ltr_debug_kernel_events arms a start / stop event pair for the NEXT launch of the 512-thread tile --
-    // recorded by the command processor right at the kernel's begin and end: bench.py's live duration of the lazy launch)
-    KernelEvents &ke = kernel_events();
-    if (ke.armed) {
-        ke.armed = false;
-#define LTR_EXT(NI_) hipExtLaunchKernelGGL((regtile2_entry<KIND, NI_, CT, kRegtileThreads>()), grid, block, (unsigned)s.lds, stream, ke.start, ke.stop, 0, p)
-        switch (s.ni) {
-        case 3: LTR_EXT(3); return (int)hipGetLastError();
-        case 5: LTR_EXT(5); return (int)hipGetLastError();
-        case 9: LTR_EXT(9); return (int)hipGetLastError();
-        default: break;                                    // (other tiles: a plain launch below, the events stay unrecorded)
-        }
-#undef LTR_EXT
-    }
-    switch (s.ni) {
-    case 3: hipLaunchKernelGGL((regtile2_entry<KIND, 3, CT, kRegtileThreads>()), grid, block, s.lds, stream, p); break;
-    case 5: hipLaunchKernelGGL((regtile2_entry<KIND, 5, CT, kRegtileThreads>()), grid, block, s.lds, stream, p); break;
-    case 9: hipLaunchKernelGGL((regtile2_entry<KIND, 9, CT, kRegtileThreads>()), grid, block, s.lds, stream, p); break;
-    case 12:
-        // (rank-free kinds only: choose_regtile_shape sends the NDCG kinds from nine sweeps straight to nineteen)
-        if constexpr (KIND != LTR_NDCG1 && KIND != LTR_NDCG2) {
-            hipLaunchKernelGGL((regtile2_entry<KIND, 12, CT, kRegtileThreads>()), grid, block, s.lds, stream, p);
-            break;
-        } else {
-            return LTR_ERR_CONFIG;
-        }
-    case 19:
-        LTR_ENSURE_LDS((*regtile2_entry<KIND, 19, CT, kRegtileThreads>()), s.lds);
-        hipLaunchKernelGGL((regtile2_entry<KIND, 19, CT, kRegtileThreads>()), grid, block, s.lds, stream, p);
-        break;
-    case 24:
-        LTR_ENSURE_LDS((*regtile2_entry<KIND, 24, CT, kRegtileThreads>()), s.lds);
-        hipLaunchKernelGGL((regtile2_entry<KIND, 24, CT, kRegtileThreads>()), grid, block, s.lds, stream, p);
-        break;
-    default: return LTR_ERR_CONFIG;
-    }
+    hipLaunchKernelGGL(entry, grid, dim3(TT), lds, stream, p);
     return (int)hipGetLastError();
 }
 
-template <int KIND>
-int launch_regtile_kind(const LinearParams &p, const RegtileShape &s, hipStream_t stream)
+// The tiles there are: 512 threads on 3 / 5 / 9 / 19 / 24 sweeps, and on 12 for the rank-free kinds (choose_regtile_shape sends
+// the NDCG kinds from nine sweeps straight to nineteen); 256 threads on 5 / 9 / 12 / 19 sweeps for the NDCG kinds only.
+template <int KIND, int NI, int CT>
+int launch_regtile2_ni(const LinearParams &p, const RegtileShape &s, const KernelEvents *ke, hipStream_t stream)
 {
-    if (s.v2) {
-        // feature counts with compile-time loop bounds: MSLR-WEB10K/30K (136); anything else runs
-        // the same kernel with run-time bounds
-        if (p.F == 136) return launch_regtile2_ct<KIND, 34>(p, s, stream);
-        return launch_regtile2_ct<KIND, 0>(p, s, stream);
+    constexpr bool ndcg = (KIND == LTR_NDCG1 || KIND == LTR_NDCG2);
+    if (s.threads == 256) {
+        if constexpr (ndcg && NI != 3 && NI != 24) return launch_regtile2_tt<KIND, NI, CT, 256>(p, s.lds, nullptr, stream);
+        else return LTR_ERR_CONFIG;
     }
-    return LTR_ERR_CONFIG;
+    if constexpr (ndcg && NI == 12) return LTR_ERR_CONFIG;
+    else return launch_regtile2_tt<KIND, NI, CT, kRegtileThreads>(p, s.lds, ke, stream);
+}
+
+template <int KIND, int CT>
+int launch_regtile2_ct(const LinearParams &p, const RegtileShape &s, hipStream_t stream)
+{
+    // (the measurement hook serves the next launch of the tile, whichever: every launch disarms it)
+    KernelEvents &events = kernel_events();
+    const KernelEvents *ke = events.armed ? &events : nullptr;
+    events.armed = false;
+    switch (s.ni) {
+    case 3: return launch_regtile2_ni<KIND, 3, CT>(p, s, ke, stream);
+    case 5: return launch_regtile2_ni<KIND, 5, CT>(p, s, ke, stream);
+    case 9: return launch_regtile2_ni<KIND, 9, CT>(p, s, ke, stream);
+    case 12: return launch_regtile2_ni<KIND, 12, CT>(p, s, ke, stream);
+    case 19: return launch_regtile2_ni<KIND, 19, CT>(p, s, ke, stream);
+    case 24: return launch_regtile2_ni<KIND, 24, CT>(p, s, ke, stream);
+    default: return LTR_ERR_CONFIG;
+    }
 }
 
 int launch_regtile(int kind, const LinearParams &p, const RegtileShape &s, hipStream_t stream)
 {
-    return with_kind(kind, [&](auto K) { return launch_regtile_kind<K>(p, s, stream); });
+    // feature counts with compile-time loop bounds: MSLR-WEB10K/30K (136); anything else runs the same kernel with
+    // run-time bounds
+    return with_kind(kind, [&](auto K) {
+        return p.F == 136 ? launch_regtile2_ct<K, 34>(p, s, stream) : launch_regtile2_ct<K, 0>(p, s, stream);
+    });
 }
 
 }  // namespace
@@ -1445,6 +1399,26 @@ inline bool prefer_cluster()
 {
     return !parts_debug_all();          // (tests of the parts kernel: ltr_debug_parts_all puts it first)
 }
+
+// Which kernel family runs a fused Linear step of (kind, B, L, F), and its shape: the ONE copy of the fallback chain register
+// tile -> cluster (when prefer_cluster()) -> parts -> cluster -> general.  What the launch knows and the plan ABI does not is
+// an argument: vec = 4 when X's rows are whole, 16-byte aligned float4; fast = LTR_TRACE_ALLOW_FAST (no score matrix asked
+// for); labels = the cluster kernel's label kind (1 integer, 0 float, -1 unknown).  The general kernel's shape stays with its
+// launch (choose_linear_shape).
+struct LinearPlan { int family; RegtileShape rs; ClusterShape cs; PartsShape ps; };
+
+LinearPlan plan_linear(int kind, int B, int L, int F, int vec, bool fast, int labels)
+{
+    LinearPlan pl;
+    pl.family = LTR_PLAN_GENERAL;
+    if (vec != 4 || !fast) return pl;
+    const bool cluster_first = prefer_cluster();
+    if (choose_regtile_shape(kind, L, F, pl.rs)) pl.family = LTR_PLAN_REGISTER_TILE;
+    else if (cluster_first && choose_cluster_shape(kind, B, L, F, pl.cs, labels)) pl.family = LTR_PLAN_CLUSTER;
+    else if (choose_parts_shape(kind, B, L, F, pl.ps)) pl.family = LTR_PLAN_PARTS;
+    else if (!cluster_first && choose_cluster_shape(kind, B, L, F, pl.cs, labels)) pl.family = LTR_PLAN_CLUSTER;
+    return pl;
+}
 }  // namespace
 
 extern "C" {
@@ -1508,18 +1482,12 @@ int ltr_linear_fused_plan(int kind, int B, int L, int F)
     LTR_CLEAR_STALE_ERROR();
     if (kind < LTR_HINGE || kind > LTR_NDCG2 || B <= 0 || L <= 0 || F <= 0) return LTR_PLAN_NONE;
     if (L > kMaxListLen) return LTR_PLAN_NONE;
-    RegtileShape rs;
-    if (F % 4 == 0 && choose_regtile_shape(kind, L, F, rs)) return LTR_PLAN_REGISTER_TILE;
-    PartsShape ps;
-    ClusterShape cs;
-    if (prefer_cluster() && choose_cluster_shape(kind, B, L, F, cs)) return LTR_PLAN_CLUSTER;
-    if (choose_parts_shape(kind, B, L, F, ps)) return LTR_PLAN_PARTS;
-    if (choose_cluster_shape(kind, B, L, F, cs)) return LTR_PLAN_CLUSTER;
-    return LTR_PLAN_GENERAL;
+    // (the plan of a launch on 16-byte aligned rows, no score matrix asked for, the label dtype not known)
+    return plan_linear(kind, B, L, F, 4, true, -1).family;
 }
 
 namespace {
-// the pending update a lazy step hands to the register-tile launch (ltr_linear_sgd_lazy_step_f32)
+// the pending update a lazy step hands to the register-tile launch (ltr_linear_sgd_lazy_step_f32), or the flush to its reducers
 struct LazyRequest {
     int pend_B; float lr; float *W, *bias, *out; unsigned long long *gran; unsigned tag; int part_g, pend_g;
     float scale;                        // weight of a pending query's gradient row (<= 0: 1 / pend_B)
@@ -1527,6 +1495,30 @@ struct LazyRequest {
     int scale_stride;
     const MailboxDev *mb;               // data parallel: the mailbox (gran / tag are then ITS granules and the tag of its lazy half)
 };
+
+// the uniform weight of a pending query's gradient row
+inline float pending_weight(float scale, int pend_B) { return scale > 0.f ? scale : 1.0f / (float)pend_B; }
+
+// The pending update's fields of a launch that carries reducers (linear_lazy_reduce): the ONE copy of the layout they read the
+// rows in, for the lazy step's launch and for the flush alike.  queries: the lazy step -- its queries' workgroups hold their
+// bursts back and poll the reducers' granules, so the status word and the spin limit are always set; false: the flush, the
+// reducers alone, which only wait on the all-reduce of a mailbox.
+void set_pending_update(LinearParams &p, const LazyRequest &r, int F, bool queries, hipStream_t stream)
+{
+    p.pend_B = r.pend_B; p.pend_g = r.pend_g; p.pend_lr = r.lr; p.pend_w = pending_weight(r.scale, r.pend_B);
+    p.pend_mb = r.mb; p.pend_wptr = r.scale_dev; p.pend_wstride = r.scale_stride;
+    p.pend_W = r.W; p.pend_bias = r.bias; p.pend_out = r.out;
+    p.pend_gran = r.gran; p.pend_tag = r.tag; p.pend_gstride = (F + 2 + 15) & ~15;
+    // four columns per reducer + the losses' one
+    p.pend_nred = (F + 1 + 3) / 4 + 1;
+    p.pend_general = (p.pend_mb || p.pend_wptr || !p.pend_W) ? 1 : 0;
+    p.pend_sleep = queries ? 2 : 0;     // (a reducer sums ~1024 rows at most, whatever the batch size)
+    if (queries || r.mb) {
+        p.status = status_device_ptr(stream);
+        p.spin_limit = cluster_force_timeout() ? -1 : (r.mb ? 0x7fffffff : (1 << 22));
+    }
+}
+
 int linear_partials_launch(int kind, float sigma, const float *X, const float *W, const float *bias, const void *rel, int rel_dtype,
                            const int64_t *n, int B, int L, int F, float *loss, float *scores_out, float *partials, void *stream,
                            const LazyRequest *lazy);
@@ -1557,52 +1549,31 @@ int linear_partials_launch(int kind, float sigma, const float *X, const float *W
     p.X = X; p.W = W; p.bias = bias; p.rel = rel; p.n = n;
     p.loss = loss; p.scores_out = scores_out; p.part = partials;
     p.B = B; p.L = L; p.F = F; p.sigma = sigma; p.rel_dtype = rel_dtype;
-    p.sched = 0;
-    RegtileShape rs;
-    const bool allow_fast = LTR_TRACE_ALLOW_FAST(scores_out);
-    if (vec == 4 && allow_fast && choose_regtile_shape(kind, L, F, rs)) {
-        p.msplit = rs.msplit; p.rows_r = 0;
+    p.sched = 0; p.rows_r = 0;
+    const LinearPlan pl = plan_linear(kind, B, L, F, vec, LTR_TRACE_ALLOW_FAST(scores_out), rel_dtype != LTR_LABEL_F32 ? 1 : 0);
+    if (lazy && pl.family != LTR_PLAN_REGISTER_TILE) return LTR_ERR_CONFIG;        // (the caller checked: lazy_layout_g)
+    switch (pl.family) {
+    case LTR_PLAN_REGISTER_TILE:
+        p.msplit = kRegtileThreads / 64;         // (the body takes its slices from TT; the argument is eight on every tile)
         // (lists of 64 and fewer do not win the pass back: 512 x 64 x 136 6.7 -> 7.0 us; 1024 x 96: 11.3 -> 10.4)
         p.sched = (L > 64) ? sched_groups(B, kSchedMaxPerCu) : 0;
         // (snake dealing of the rounds, sched_query_sampled: measured round 6 on 1024 x 128 x 136 with four workgroups per CU resident --
         // LambdaNDCG2 16.6 -> 16.1 us, logistic 14.0 -> 13.5, hinge 11.84 -> 11.82: the kinds with compute behind their loads are
         // bound by their most loaded CU.  EXPERIMENTS.md round 6)
         if (p.sched) p.sched |= device_cu_count() << 16;
-        if (lazy) {
-            if (!rs.v2) return LTR_ERR_CONFIG;             // (the caller checked: lazy_layout_g)
-            p.part_g = lazy->part_g;
-        }
-        if (lazy && lazy->pend_B > 0) {
-            p.pend_g = lazy->pend_g;
-            p.pend_B = lazy->pend_B; p.pend_lr = lazy->lr; p.pend_w = lazy->scale > 0.f ? lazy->scale : 1.0f / (float)lazy->pend_B;
-            p.pend_mb = lazy->mb; p.pend_wptr = lazy->scale_dev; p.pend_wstride = lazy->scale_stride;
-            p.pend_W = lazy->W; p.pend_bias = lazy->bias; p.pend_out = lazy->out;
-            p.pend_gran = lazy->gran; p.pend_tag = lazy->tag; p.pend_gstride = (F + 2 + 15) & ~15;
-            // four columns per reducer + the losses' one
-            p.pend_nred = (F + 1 + 3) / 4 + 1;
-            p.pend_general = (p.pend_mb || p.pend_wptr || !p.pend_W) ? 1 : 0;
-            p.pend_sleep = 2;           // (a reducer sums ~1024 rows at most, whatever the batch size)
-            p.status = status_device_ptr((hipStream_t)stream);
-            p.spin_limit = cluster_force_timeout() ? -1 : (lazy->mb ? 0x7fffffff : (1 << 22));
-        }
-        return launch_regtile(kind, p, rs, (hipStream_t)stream);
+        if (lazy) p.part_g = lazy->part_g;
+        if (lazy && lazy->pend_B > 0) set_pending_update(p, *lazy, F, true, (hipStream_t)stream);
+        return launch_regtile(kind, p, pl.rs, (hipStream_t)stream);
+    case LTR_PLAN_PARTS:
+        p.msplit = 0;
+        return launch_parts(kind, p, pl.ps, (hipStream_t)stream);
+    case LTR_PLAN_CLUSTER: {
+        p.msplit = pl.cs.threads / 64;
+        p.sched = (B >= 16) ? (B + 63) / 64 : 0;
+        float *scratch = partials + linear_partials_bytes(B, F) / sizeof(float);
+        return launch_cluster(kind, p, pl.cs, scratch, (hipStream_t)stream);
     }
-    if (lazy) return LTR_ERR_CONFIG;
-    ClusterShape cs;
-    PartsShape ps;
-    const bool cluster_first = prefer_cluster();
-    for (int pass = 0; pass < 2; ++pass) {
-        if ((pass == 0) != cluster_first) {
-            if (vec == 4 && allow_fast && choose_parts_shape(kind, B, L, F, ps)) {
-                p.msplit = 0; p.rows_r = 0;
-                return launch_parts(kind, p, ps, (hipStream_t)stream);
-            }
-        } else if (vec == 4 && allow_fast && choose_cluster_shape(kind, B, L, F, cs, rel_dtype != LTR_LABEL_F32 ? 1 : 0)) {
-            p.msplit = cs.threads / 64; p.rows_r = 0;
-            p.sched = (B >= 16) ? (B + 63) / 64 : 0;
-            float *scratch = partials + linear_partials_bytes(B, F) / sizeof(float);
-            return launch_cluster(kind, p, cs, scratch, (hipStream_t)stream);
-        }
+    default: break;
     }
     LinearShape s;
     if (!choose_linear_shape(kind, B, L, F, vec, s)) return LTR_ERR_SHAPE;
@@ -2218,7 +2189,7 @@ static bool lazy_layout_g(int kind, int B, int L, int F)
 {
     if (B <= 0 || F % 4 != 0 || !lazy_one_round(B)) return false;
     RegtileShape rs;
-    return choose_regtile_shape(kind, L, F, rs) && rs.v2;
+    return choose_regtile_shape(kind, L, F, rs);         // (plan_linear's first choice)
 }
 // (May a launch of MORE than one round take a pending update along?  No: every workgroup of every later round still pays the
 // hold-back and the hand-over in front of its dot products -- its poll sits behind its tile burst in the in-order return queue --
@@ -2263,29 +2234,24 @@ int lazy_flush_impl(int kind, float *W, float *bias, int pending_B, int L, int F
     if (!weights) { W = nullptr; if (m) return LTR_ERR_CONFIG; }
     if (m && (!m->dev || m->count_max < F + 2 || !bias)) return LTR_ERR_CONFIG;
     if (const int st = status_peek()) return st;
-    const float scale = pending_scale > 0.f ? pending_scale : 1.0f / (float)pending_B;
     if (lazy_layout_g(kind, pending_B, L, F) && bias) {
         // rows in the lazy step's layout: the reducers of the lazy launch, on their own (data parallel: with their all-reduce)
+        LazyRequest req{pending_B, lr, W, bias, bucket, nullptr, 0u, 0, 1, pending_scale, pending_scale_dev, pending_scale_stride, nullptr};
+        if (m) {
+            if (stream_is_capturing((hipStream_t)stream)) return LTR_ERR_CONFIG;      // (host-side tags: eager launches only)
+            if (const int rc = lazy_mailbox_next(m, (hipStream_t)stream, F, &req.mb, &req.gran, &req.tag)) return rc;
+        }
         LinearParams p{};
         p.part = const_cast<float *>(reinterpret_cast<const float *>(workspace));
         p.loss = const_cast<float *>(loss);
         p.F = F; p.B = pending_B;
-        p.pend_B = pending_B; p.pend_g = 1; p.pend_lr = lr; p.pend_w = scale; p.pend_wptr = pending_scale_dev; p.pend_wstride = pending_scale_stride;
-        p.pend_W = W; p.pend_bias = bias; p.pend_out = bucket; p.pend_gran = nullptr;
-        p.pend_nred = (F + 1 + 3) / 4 + 1;
-        p.pend_gstride = (F + 2 + 15) & ~15;
-        if (m) {
-            if (stream_is_capturing((hipStream_t)stream)) return LTR_ERR_CONFIG;      // (host-side tags: eager launches only)
-            if (const int rc = lazy_mailbox_next(m, (hipStream_t)stream, F, &p.pend_mb, &p.pend_gran, &p.pend_tag)) return rc;
-            p.status = status_device_ptr((hipStream_t)stream);
-            p.spin_limit = cluster_force_timeout() ? -1 : 0x7fffffff;
-        }
-        p.pend_general = (p.pend_mb || p.pend_wptr || !p.pend_W) ? 1 : 0;
+        set_pending_update(p, req, F, false, (hipStream_t)stream);
         hipLaunchKernelGGL(linear_lazy_flush_kernel, dim3((unsigned)p.pend_nred), dim3(256), 0, (hipStream_t)stream, p);
         return (int)hipGetLastError();
     }
     // (the upstream gradient: a device scalar read with stride 0, or the uniform weight)
     const float *go = pending_scale_dev;
+    const float scale = pending_weight(pending_scale, pending_B);
     if (!m)
         return launch_linear_reduce((hipStream_t)stream, (const float *)workspace, go, scale, pending_scale_stride, pending_B, F, bucket,
                                     bucket + F, loss, bucket + F + 1, 0, W, W ? bias : nullptr, lr);
