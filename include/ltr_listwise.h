@@ -1,0 +1,47 @@
+/*
+ * ltr_listwise.h -- C ABI of ListMLE, the Plackett-Luce listwise loss (Xia et al. 2008; top-k: Xia et al. 2009).
+ *
+ * Exported by the same libltr_hip.so as include/ltr_hip.h, with its conventions: device pointers owned by the
+ * caller, work enqueued on `stream` without host synchronisation, 0 = OK, < 0 = LTR_ERR_* (ltr_hip.h),
+ * > 0 = a hipError_t; scores fp32, labels int64 / int32 / fp32 by `rel_dtype`, n int64 clamped to [0, L].
+ */
+#ifndef LTR_LISTWISE_H
+#define LTR_LISTWISE_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/*
+ * ListMLE of every query b, over its real documents j < n_b = clamp(n[b], 0, L):
+ *   pi orders them by label, descending (labels compared as fp32); equal labels by the tie mode of
+ *   ltr_rank_by_score_long_f32: use_seed != 0 hashed words from `seed` (`seed_dev`, device int64[1], overrides it
+ *   when not NULL; ltr_tie_hash_word up to ltr_max_list_len() documents, ltr_tie_hash_word_long above), else
+ *   tie != NULL explicit priorities (L), else document-index order.  Every row shares the tie words.
+ *   K_b = n_b for k <= 0, else min(k, n_b) (top-k ListMLE: the first K_b factors of the likelihood).
+ *   LSE_m = log sum_{i = m}^{n_b - 1} exp(s[pi(i)])
+ *   loss[b] = sum_{m < K_b} (LSE_m - s[pi(m)])                                  (0 for n_b <= 1)
+ *   dscores[b, pi(i)] = -[i < K_b] + sum_{m <= min(i, K_b - 1)} exp(s[pi(i)] - LSE_m),  0 for j >= n_b
+ * dscores may be NULL (forward only).  Every exp takes a non-positive argument: LSE comes from a running
+ * (max, sum) suffix scan and the gradient from the affine recurrence C_i = [i < K_b] + C_{i-1} exp(LSE_i - LSE_{i-1}),
+ * C_i <= i + 1.  Sums run in a fixed order, no atomics: bit-identical run to run for a fixed seed or tie mode.
+ *   L <= ltr_max_list_len(): one workgroup per query, one launch, no workspace (may be NULL).  Longer lists (up to
+ *   ltr_max_sort_list_len()), and every list under ltr_debug_long_sort_all: the long path's key sort on the labels,
+ *   then tile epilogues, in the caller's workspace of ltr_listmle_workspace_bytes(B, L) bytes (0 where no workspace
+ *   is needed, and for invalid arguments).  Nothing is allocated: capturable.
+ *   Errors, in this order: LTR_ERR_KIND for a bad rel_dtype, then B < 0 / L <= 0 (LTR_ERR_SHAPE),
+ *   L > ltr_max_sort_list_len() (LTR_ERR_LIST_TOO_LONG); B == 0 is a no-op; LTR_ERR_NULL (scores, rel, n, loss),
+ *   then LTR_ERR_WORKSPACE on the long path.
+ */
+size_t ltr_listmle_workspace_bytes(int B, int L);
+int ltr_listmle_f32(const float *scores, const void *rel, int rel_dtype, const int64_t *n, int k, const int32_t *tie,
+                    int use_seed, uint64_t seed, const int64_t *seed_dev, int B, int L, float *loss, float *dscores,
+                    void *workspace, size_t workspace_bytes, void *stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* LTR_LISTWISE_H */

@@ -1,4 +1,5 @@
-"""ctypes binding of the C ABI in ``include/ltr_hip.h`` and ``include/ltr_eval.h`` (pytorchltr_amd/csrc/libltr_hip.so).
+"""ctypes binding of the C ABI in ``include/ltr_hip.h``, ``include/ltr_eval.h`` and ``include/ltr_listwise.h``
+(pytorchltr_amd/csrc/libltr_hip.so).
 
 PyTorch supplies device memory and the current HIP stream; every call here hands raw device
 pointers to the library.  The library must exist -- there is deliberately no fallback.
@@ -120,6 +121,12 @@ EVAL_SIGNATURES = {
                           _sz, _vp]),
 }
 
+# name -> (restype, argtypes); mirrors include/ltr_listwise.h (ListMLE)
+LISTWISE_SIGNATURES = {
+    "ltr_listmle_workspace_bytes": (_sz, [_i, _i]),
+    "ltr_listmle_f32": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, ctypes.c_uint64, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+}
+
 _lib = None
 
 
@@ -152,7 +159,7 @@ def lib():
                 "`python -m pytorchltr_amd.build` (hipcc --offload-arch=gfx950). "
                 "There is no CPU fallback." % LIB_PATH)
         handle = _Library(LIB_PATH)
-        for name, (restype, argtypes) in list(SIGNATURES.items()) + list(EVAL_SIGNATURES.items()):
+        for name, (restype, argtypes) in list(SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(LISTWISE_SIGNATURES.items()):
             if name.startswith("ltr_debug_") and not hasattr(handle, name):
                 continue                     # a production build (-DLTR_NO_DEBUG_HOOKS) leaves the test hooks out
             fn = getattr(handle, name)       # AttributeError if the symbol is missing

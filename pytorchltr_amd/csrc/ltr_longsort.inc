@@ -81,16 +81,22 @@ __device__ __forceinline__ unsigned long long long_seed(const LongKeyParams &k)
     return k.seed_dev ? (unsigned long long)k.seed_dev[0] : k.seed;
 }
 
+// Where a key's high word comes from: KEY_SCORES, the scores (or, when k.scores is null, the labels with index words:
+// the ideal ranking); KEY_LABELS_TIED, the labels with the call's tie words (ListMLE's ranking, ltr_listmle.inc).
+enum { KEY_SCORES = 0, KEY_LABELS_TIED = 1 };
+
+template <int SRC = KEY_SCORES>
 __device__ __forceinline__ unsigned long long long_key(const LongKeyParams &k, size_t base, int j, int nb,
                                                        unsigned long long seed)
 {
     if (j >= nb) return kPadKeyHi | (unsigned)j;
-    const float v = k.scores ? k.scores[base + j] : load_label(k.rel, k.rel_dtype, base + j);
+    const bool tied = SRC == KEY_LABELS_TIED || k.scores;
+    const float v = (SRC == KEY_SCORES && k.scores) ? k.scores[base + j] : load_label(k.rel, k.rel_dtype, base + j);
     unsigned hi = (unsigned)(rank_key(v, 0) >> 32);
     hi = hi < 0xFFFFFFFFu ? hi : 0xFFFFFFFEu;    // (one NaN payload) real documents stay ahead of the padding
     unsigned w = (unsigned)j;
-    if (k.scores && k.mode == TIE_EXPLICIT) w = (unsigned)k.tie[j];
-    else if (k.scores && k.mode == TIE_SEED) w = tie_hash_word_long(seed, (unsigned)j);
+    if (tied && k.mode == TIE_EXPLICIT) w = (unsigned)k.tie[j];
+    else if (tied && k.mode == TIE_SEED) w = tie_hash_word_long(seed, (unsigned)j);
     return ((unsigned long long)hi << 32) | w;
 }
 
@@ -122,8 +128,8 @@ __global__ void __launch_bounds__(256) longsort_inverse_tie_kernel(const int32_t
 }
 
 // 1. one sorted run of kSortChunk keys per workgroup.  RANK_OUT (a query that is one chunk): the
-// ranking is written instead of the keys.
-template <bool RANK_OUT>
+// ranking is written instead of the keys.  SRC: long_key's key source.
+template <bool RANK_OUT, int SRC = KEY_SCORES>
 __global__ void __launch_bounds__(kChunkThreads)
 longsort_chunk_kernel(LongKeyParams k, int chunks, unsigned long long *__restrict__ keys_out, int64_t *__restrict__ ranking)
 {
@@ -137,7 +143,7 @@ longsort_chunk_kernel(LongKeyParams k, int chunks, unsigned long long *__restric
     const unsigned long long seed = long_seed(k);
     int P = 64;
     while (P < len) P <<= 1;
-    for (int x = tid; x < P; x += kChunkThreads) s[x] = x < len ? long_key(k, base, j0 + x, nb, seed) : ~0ull;
+    for (int x = tid; x < P; x += kChunkThreads) s[x] = x < len ? long_key<SRC>(k, base, j0 + x, nb, seed) : ~0ull;
     __syncthreads();
     for (int kk = 2; kk <= P; kk <<= 1) {
         for (int j = kk >> 1; j > 0; j >>= 1) {
@@ -389,8 +395,9 @@ inline LongWorkspace long_workspace(void *ws, int B, int L)
     return r;
 }
 
-// Sorts every query's keys.  ranking != null: the ranking is written by the last launch and
-// nothing is returned; else the buffer that holds the sorted keys.
+// Sorts every query's keys (SRC: long_key's key source).  ranking != null: the ranking is written by the last
+// launch and nothing is returned; else the buffer that holds the sorted keys.
+template <int SRC = KEY_SCORES>
 inline const unsigned long long *long_sort(const LongKeyParams &k, int B, const LongWorkspace &ws, int64_t *ranking,
                                            hipStream_t stream)
 {
@@ -401,8 +408,8 @@ inline const unsigned long long *long_sort(const LongKeyParams &k, int B, const 
                            (unsigned long long *)nullptr, ranking);
         return nullptr;
     }
-    hipLaunchKernelGGL(longsort_chunk_kernel<false>, dim3((unsigned)((size_t)B * chunks)), dim3(kChunkThreads), 0, stream,
-                       k, chunks, ws.k0, (int64_t *)nullptr);
+    hipLaunchKernelGGL((longsort_chunk_kernel<false, SRC>), dim3((unsigned)((size_t)B * chunks)), dim3(kChunkThreads), 0,
+                       stream, k, chunks, ws.k0, (int64_t *)nullptr);
     unsigned long long *src = ws.k0, *dst = ws.k1;
     const int tiles = (L + kMergeTile - 1) / kMergeTile;
     const dim3 grid((unsigned)((size_t)B * tiles));

@@ -1,4 +1,4 @@
-"""Listwise softmax cross-entropy (ListNet top-one) on MI355X.
+"""Listwise losses on MI355X: softmax cross-entropy (ListNet top-one) and ListMLE (the Plackett-Luce likelihood).
 
 NOT part of the reference: ``pytorchltr/loss/__init__.py:1-7`` exports the seven pairwise classes
 only and nothing in the reference's code, tests or docs defines a listwise loss.  The project
@@ -12,6 +12,7 @@ import torch as _torch
 from torch.autograd.function import once_differentiable as _once
 
 from pytorchltr_amd import _C
+from pytorchltr_amd import _ties
 from pytorchltr_amd._prepare import prepare as _prepare
 
 
@@ -69,3 +70,81 @@ class ListwiseSoftmaxLoss(_torch.nn.Module):
 
 
 ListNetLoss = ListwiseSoftmaxLoss
+
+
+class _ListMLEFunction(_torch.autograd.Function):
+    """ltr_listmle_f32 (include/ltr_listwise.h): loss and d loss / d scores in one forward; backward is a row scale.
+    Computes in fp32 whatever the score dtype, like _ListwiseSoftmaxFunction."""
+
+    @staticmethod
+    def forward(ctx, scores, relevance, n, k):
+        s, r, nn = _prepare(scores, relevance, n, allow_f64=False, limit_len=False)
+        B, L = s.shape
+        if L > _C.max_sort_list_len():
+            raise ValueError("list_size %d exceeds the supported maximum %d" % (L, _C.max_sort_list_len()))
+        need_grad = ctx.needs_input_grad[0]
+        loss = _torch.empty(B, dtype=_torch.float32, device=s.device)
+        ds = _torch.empty(B, L, dtype=_torch.float32, device=s.device) if need_grad else None
+        if B > 0:
+            lib = _C.lib()
+            sd = _ties.draw_seed(L, s.device)
+            nbytes = int(lib.ltr_listmle_workspace_bytes(B, L))       # 0: one workgroup per query, no workspace
+            ws = _torch.empty(nbytes, dtype=_torch.uint8, device=s.device) if nbytes > 0 else None
+            with _C.device_ctx(s):
+                _C.check(lib.ltr_listmle_f32(
+                    _C.ptr(s), _C.ptr(r), _C.label_dtype(r), _C.ptr(nn), int(k or 0), None, int(sd is not None),
+                    sd[0] if sd is not None else 0, _C.ptr(sd[1]) if sd is not None else None, B, L, _C.ptr(loss),
+                    _C.ptr(ds), _C.ptr(ws), nbytes, _C.stream_of(s)))
+        if need_grad:
+            ctx.save_for_backward(ds)
+        ctx.in_shape, ctx.in_dtype = scores.shape, scores.dtype
+        return loss if scores.dtype is _torch.float32 else loss.to(scores.dtype)
+
+    @staticmethod
+    @_once
+    def backward(ctx, grad_out):
+        (ds,) = ctx.saved_tensors
+        out = ds * grad_out.reshape(-1, 1).to(ds.dtype)
+        return out.reshape(ctx.in_shape).to(ctx.in_dtype), None, None, None
+
+
+class ListMLELoss(_torch.nn.Module):
+    r"""ListMLE (Xia et al. 2008): the negative log-likelihood of the label ordering under a Plackett-Luce model of
+    the scores; with ``k``, top-k ListMLE (Xia et al. 2009), the first ``k`` factors of the likelihood only.
+
+    With :math:`\pi` the real documents (:math:`j < n`) ordered by label, descending, and
+    :math:`K = \min(k, n)` (:math:`K = n` without ``k``):
+
+    .. math::
+        l(\mathbf{s}, \mathbf{y}) = \sum_{m < K} \Big( \ln \sum_{i = m}^{n - 1} e^{s_{\pi(i)}} - s_{\pi(m)} \Big)
+
+    Padded documents take no part; ``n <= 1`` gives 0.  Equal labels are ordered by the tie-breaking mode of
+    :mod:`pytorchltr_amd.utils` (``tie_breaking``): one random order per call by default, document index in mode
+    ``"index"``.  Any list length up to ``ltr_max_sort_list_len()``; fp16, bf16 and fp64 scores are computed in fp32.
+
+    Shape:
+        - scores: :math:`(N, \texttt{list\_size})` or :math:`(N, \texttt{list\_size}, 1)`
+        - relevance: :math:`(N, \texttt{list\_size})`
+        - n: :math:`(N)`
+        - output: :math:`(N)`
+    """
+
+    def __init__(self, k=None):
+        super().__init__()
+        if k is not None:
+            if isinstance(k, bool) or int(k) != k or k < 1:
+                raise ValueError("k must be a positive integer or None, got %r" % (k,))
+            k = int(k)
+        self.k = k
+
+    def forward(self, scores: _torch.FloatTensor, relevance: _torch.LongTensor,
+                n: _torch.LongTensor) -> _torch.FloatTensor:
+        # there is no fused scorer kernel for this loss: scores a LinearScorer has not computed yet are computed here,
+        # autograd-connected to the layer (fused.LazyScores)
+        materialize = getattr(scores, "materialize", None)
+        if materialize is not None:
+            scores = materialize()
+        return _ListMLEFunction.apply(scores, relevance, n, self.k)
+
+    def extra_repr(self):
+        return "" if self.k is None else "k=%d" % self.k
