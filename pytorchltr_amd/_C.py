@@ -233,13 +233,17 @@ def max_sort_list_len():
     return _max_sort_len
 
 
+def workspace(nbytes, device):
+    """A workspace of `nbytes` bytes on `device` for an ltr_*_workspace_bytes count: (tensor, bytes), or (None, 0)
+    where the entry point needs none."""
+    nbytes = int(nbytes)
+    return (torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes > 0 else None), nbytes
+
+
 def sort_workspace(op, B, L, device):
     """Workspace of the ltr_*_long_f32 entry points (op 0 rank, 1 dcg / ndcg, 2 arp): (tensor, bytes).
     (None, 0) for lists of at most max_list_len(): the entry points do not read it there."""
-    if L <= max_list_len():
-        return None, 0
-    nbytes = int(lib().ltr_sort_workspace_bytes(op, B, L))
-    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device), nbytes
+    return workspace(lib().ltr_sort_workspace_bytes(op, B, L) if L > max_list_len() else 0, device)
 
 
 def max_list_len_f64():

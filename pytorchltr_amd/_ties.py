@@ -75,6 +75,13 @@ def draw_seed(L, device, generator=None):
     return 0, t.to(device)
 
 
+def tie_args(sd):
+    """The four tie arguments of the C ABI (tie, use_seed, seed, seed_dev) for a draw_seed() result."""
+    if sd is None:
+        return None, 0, 0, None
+    return None, 1, sd[0], (None if sd[1] is None else sd[1].data_ptr())
+
+
 def hash_words(seed, L):
     """The tie words the kernels make from `seed` for positions 0..L-1 (numpy int32; for tests / oracles)."""
     import numpy as np

@@ -221,6 +221,28 @@ __device__ __forceinline__ float block_sum(float v, float *red)
     return t;
 }
 
+// Scalar operators of the workgroup reductions and scans below and in ltr_ranked.inc: the identity and the combination.
+struct OpAdd { static constexpr float id = 0.f; static __device__ __forceinline__ float f(float a, float b) { return a + b; } };
+struct OpMul { static constexpr float id = 1.f; static __device__ __forceinline__ float f(float a, float b) { return a * b; } };
+struct OpMin { static constexpr float id = 3.0e38f; static __device__ __forceinline__ float f(float a, float b) { return fminf(a, b); } };
+
+// block_sum for another operator (OpMul, OpMin): a butterfly within the wave, then the waves in order; every thread
+// gets the result.  `red`: LDS of >= 16 floats.  Contains barriers: call from uniform code.
+template <typename Op>
+__device__ __forceinline__ float block_reduce(float v, float *red)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = Op::f(v, __shfl_xor(v, o, kWave));
+    const int nw = blockDim.x >> 6;
+    if (nw == 1) return v;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float t = red[0];
+    for (int i = 1; i < nw; ++i) t = Op::f(t, red[i]);
+    return t;
+}
+
 // Two sums in one pass (same barriers): used for (loss, sum of gradients).
 __device__ __forceinline__ void block_sum2(float &a, float &b, float *red)
 {

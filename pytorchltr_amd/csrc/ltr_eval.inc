@@ -1,10 +1,9 @@
 // ltr_eval.inc -- evaluate(): M ranking metrics of every query from ONE ranking of it
 // (included by ltr_kernels.hip after ltr_longsort.inc; C ABI: include/ltr_eval.h).
 //
-// Up to kMaxListLen documents: eval_kernel, one workgroup per query in metric_kernel's launch shape
-// (metric_shape).  It stages the row, ranks it with metric_ranks (the labels too when an NDCG is
-// asked for) and forms the DCG-family metrics and ARP exactly as metric_kernel does, term for term
-// and in the same order of summation, so they equal dcg / ndcg / arp bit for bit.  Then it scatters
+// Up to kMaxListLen documents: eval_kernel, one workgroup per query on the ranked-row core (ltr_ranked.inc): its
+// launch shape, LDS layout and ranking (the labels too when an NDCG is asked for), and its ranked_dcg / ranked_arp --
+// the very functions metric_kernel calls, so the DCG-family metrics and ARP equal dcg / ndcg / arp bit for bit.  Then it scatters
 // the real documents' labels into LDS in rank order and takes only the prefix data the request
 // needs: one inclusive scan of the relevance indicator (MAP, P, recall, R; the first relevant rank is
 // the number of leading zeros of that scan) and one multiplicative scan of (1 - R_i) (ERR).  The
@@ -47,58 +46,6 @@ __device__ __forceinline__ float err_prob(float y, float gmax)
     return (exp2f(g) - 1.0f) / exp2f(gmax);
 }
 
-// Inclusive scan of buf[0..len) in place, sum or (MUL) product; thread t owns a contiguous chunk.
-// `scratch`: LDS of >= 16 floats.  Contains barriers: call from uniform code, after buf is written.
-template <bool MUL>
-__device__ void block_scan(float *buf, int len, float *scratch)
-{
-    const int T = blockDim.x, tid = threadIdx.x;
-    const float id = MUL ? 1.f : 0.f;
-    const int ch = (len + T - 1) / T;
-    const int lo = min(len, tid * ch), hi = min(len, lo + ch);
-    float s = id;
-    for (int i = lo; i < hi; ++i) s = MUL ? s * buf[i] : s + buf[i];
-    float incl = s;
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) {
-        const float up = __shfl_up(incl, off, kWave);
-        if ((tid & 63) >= off) incl = MUL ? incl * up : incl + up;
-    }
-    float excl = __shfl_up(incl, 1, kWave);
-    if ((tid & 63) == 0) excl = id;
-    __syncthreads();
-    if ((tid & 63) == 63) scratch[tid >> 6] = incl;
-    __syncthreads();
-    float run = id;
-    for (int i = 0; i < (tid >> 6); ++i) run = MUL ? run * scratch[i] : run + scratch[i];
-    run = MUL ? run * excl : run + excl;
-    for (int i = lo; i < hi; ++i) {
-        run = MUL ? run * buf[i] : run + buf[i];
-        buf[i] = run;
-    }
-    __syncthreads();
-}
-
-// Product (MUL) or minimum over the workgroup, every thread gets it; fixed order (a butterfly, then the
-// waves in order).  `red`: LDS of >= 16 floats.  Contains barriers: call from uniform code.
-template <bool MUL>
-__device__ __forceinline__ float block_reduce(float v, float *red)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float u = __shfl_xor(v, o, kWave);
-        v = MUL ? v * u : fminf(v, u);
-    }
-    const int nw = blockDim.x >> 6;
-    if (nw == 1) return v;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float t = red[0];
-    for (int i = 1; i < nw; ++i) t = MUL ? t * red[i] : fminf(t, red[i]);
-    return t;
-}
-
 // A trec_eval metric from its parts: s = the summed terms (MAP, ERR) or the relevant count in the top
 // min(k, n) (P, recall); R = relevant documents; first = 0-based rank of the first of them; kc = min(k, n).
 __device__ __forceinline__ float eval_rel_metric(int op, int k, int L, int kc, float s, float R, int first)
@@ -113,7 +60,7 @@ __device__ __forceinline__ float eval_rel_metric(int op, int k, int L, int kc, f
     }
 }
 
-// (the launch bounds, and so the register budgets, of metric_kernel: same shapes, same occupancy)
+// (the launch bounds, and so the register budgets, of the ranked-row core's kernels: same shapes, same occupancy)
 template <int DPT>
 __global__ void __launch_bounds__(1024, (DPT <= 0 ? 8 : 4))
 eval_kernel(EvalParams p)
@@ -126,85 +73,38 @@ eval_kernel(EvalParams p)
     const int tid = threadIdx.x;
     const int T = blockDim.x;
     const int nb = clamp_n(m.n[b], L);
-
-    // metric_kernel's LDS layout
-    float2 *sy = reinterpret_cast<float2 *>(smem);
-    int *rank_s = reinterpret_cast<int *>(smem + 8 * (size_t)L4);
-    int *rank_y = rank_s + L4;
-    float *curve = reinterpret_cast<float *>(smem + 16 * (size_t)L4);
-    float *icurve = curve + L4;
-    float *red = icurve + L4;
-    float *scan_scratch = red + 32;
-    // the spec, staged behind metric_kernel's layout (launch_eval adds its bytes), read one wave-uniform entry at a time
+    const RankedRowLds q = ranked_row_lds(smem, L, DPT <= 0);
+    // the spec, staged behind the core's layout (launch_eval adds its bytes), read one wave-uniform entry at a time
     // (indexed in the kernel arguments, the sort path's eight-wave bound of 80 SGPRs spilled three more of them
     // into VGPR lanes)
-    int2 *spec = reinterpret_cast<int2 *>(smem + (DPT <= 0 ? metric_lds_bytes_sort(L) : metric_lds_bytes(L)));
+    int2 *spec = reinterpret_cast<int2 *>(q.free);
     if (tid < p.M) spec[tid] = p.spec[tid];
 
     const size_t row = (size_t)b * L;
     const int nload = (p.need & EVAL_NEED_DCG) ? L : nb;
-    for (int j = tid; j < nload; j += T) sy[j] = make_float2(m.scores[row + j], load_label(m.rel, m.rel_dtype, row + j));
-    for (int j = tid; j < 2 * L4; j += T) rank_s[j] = 0;
+    for (int j = tid; j < nload; j += T) q.sy[j] = make_float2(m.scores[row + j], load_label(m.rel, m.rel_dtype, row + j));
+    for (int j = tid; j < 2 * L4; j += T) q.rank_s[j] = 0;
     __syncthreads();
-    metric_ranks<DPT>(m, smem, sy, rank_s, rank_y, curve, nb, (p.need & EVAL_NEED_IDEAL) != 0);
+    metric_ranks<DPT>(m, q, nb, (p.need & EVAL_NEED_IDEAL) != 0);
     __syncthreads();
 
-    // ---- dcg / ndcg / arp: metric_kernel's terms and sums ----
+    // ---- dcg / ndcg / arp ----
     for (int i = 0; i < p.M; ++i) {
         const int op = __builtin_amdgcn_readfirstlane(spec[i].x);
         if (op > LTR_EVAL_ARP) continue;
         float v;
         if (op == LTR_EVAL_ARP) {
-            float srp = 0.f, nrp = 0.f;
-            for (int k = tid; k < nb; k += T) {
-                const float y = sy[k].y;
-                srp += (float)(rank_s[k] + 1) * y;
-                nrp += y;
-            }
-            srp = block_sum(srp, red);
-            nrp = block_sum(nrp, red);
-            if (nrp == 0.0f) nrp = 1.0f;
-            v = srp / nrp;
+            v = ranked_arp(q, nb);
         } else {
             const bool norm = op == LTR_EVAL_NDCG;
             const int k = __builtin_amdgcn_readfirstlane(spec[i].y);
             const int kk = k > 0 ? min(k, L) : 0;
-            float part = 0.f, ipart = 0.f;
-            for (int k = tid; k < L; k += T) {
-                const float y = sy[k].y;
-                const float gain = m.use_exp ? (exp2f(y) - 1.0f) : y;
-                const int r = k < nb ? rank_s[k] : k;
-                const float term = gain / log2f((float)r + 2.0f);
-                int ry = 0;
-                float iterm = 0.f;
+            v = ranked_dcg(q, L, nb, kk, norm, m.use_exp);
+            if (kk == 0) {
+                // the last column of dcg / ndcg's curve
+                v = q.curve[L - 1];
                 if (norm) {
-                    ry = k < nb ? rank_y[k] : k;
-                    iterm = gain / log2f((float)ry + 2.0f);
-                }
-                if (kk > 0) {
-                    part += (r < kk) ? term : 0.f;
-                    ipart += (norm && ry < kk) ? iterm : 0.f;
-                } else {
-                    curve[r] = term;
-                    if (norm) icurve[ry] = iterm;
-                }
-            }
-            if (kk > 0) {
-                part = block_sum(part, red);
-                if (norm) {
-                    ipart = block_sum(ipart, red);
-                    if (ipart == 0.0f) ipart = 1.0f;
-                    part = part / ipart;
-                }
-                v = part;
-            } else {
-                // the last column of dcg / ndcg's curve: the same scan
-                __syncthreads();
-                block_inclusive_scan(curve, L, scan_scratch);
-                if (norm) block_inclusive_scan(icurve, L, scan_scratch);
-                v = curve[L - 1];
-                if (norm) {
-                    float id = icurve[L - 1];
+                    float id = q.icurve[L - 1];
                     if (id == 0.0f) id = 1.0f;
                     v /= id;
                 }
@@ -216,24 +116,24 @@ eval_kernel(EvalParams p)
     if (!(p.need & EVAL_NEED_REL)) return;
 
     // ---- trec_eval metrics: labels of the real documents in rank order, then the scans they need ----
-    float *lab = curve, *cnt = icurve;
-    float *keep = reinterpret_cast<float *>(rank_y);                   // prod_{i <= r} (1 - R_i)
+    float *lab = q.curve, *cnt = q.icurve;
+    float *keep = reinterpret_cast<float *>(q.rank_y);                 // prod_{i <= r} (1 - R_i)
     __syncthreads();
-    for (int k = tid; k < nb; k += T) lab[rank_s[k]] = sy[k].y;
+    for (int k = tid; k < nb; k += T) lab[q.rank_s[k]] = q.sy[k].y;
     __syncthreads();
     for (int r = tid; r < nb; r += T) {
         cnt[r] = lab[r] >= p.rel_level ? 1.f : 0.f;
         if (p.need & EVAL_NEED_ERR) keep[r] = 1.f - err_prob(lab[r], p.err_gmax);
     }
     __syncthreads();
-    block_scan<false>(cnt, nb, scan_scratch);
-    if (p.need & EVAL_NEED_ERR) block_scan<true>(keep, nb, scan_scratch);
+    block_scan<OpAdd>(cnt, nb, q.scan);
+    if (p.need & EVAL_NEED_ERR) block_scan<OpMul>(keep, nb, q.scan);
     const float R = nb > 0 ? cnt[nb - 1] : 0.f;
     int first = nb;
     if (p.need & EVAL_NEED_MRR) {
         float lead = 0.f;                                              // ranks before the first relevant one
         for (int r = tid; r < nb; r += T) lead += cnt[r] == 0.0f ? 1.f : 0.f;
-        first = (int)block_sum(lead, red);
+        first = (int)block_sum(lead, q.red);
     }
     for (int i = 0; i < p.M; ++i) {
         const int op = __builtin_amdgcn_readfirstlane(spec[i].x), k = __builtin_amdgcn_readfirstlane(spec[i].y);
@@ -246,7 +146,7 @@ eval_kernel(EvalParams p)
                 if (op == LTR_EVAL_MAP) s += y >= p.rel_level ? cnt[r] / (float)(r + 1) : 0.f;
                 else s += err_prob(y, p.err_gmax) / (float)(r + 1) * (r > 0 ? keep[r - 1] : 1.f);
             }
-            s = block_sum(s, red);
+            s = block_sum(s, q.red);
         } else if (op != LTR_EVAL_MRR) {
             s = kc > 0 ? cnt[kc - 1] : 0.f;
         }
@@ -277,25 +177,22 @@ __global__ void __launch_bounds__(kEpiThreads) eval_long_partial_kernel(EvalLong
     __shared__ float lab[kEpiTile];          // labels of the tile's ranks (real documents)
     __shared__ float term[kEpiTile];         // DCG terms of the tile's ranks (padded documents included)
     __shared__ float red[32];
-    const int q = blockIdx.x / p.tiles, tile = blockIdx.x - q * p.tiles;
+    const EpiTile t = epi_tile(p.l.k, p.tiles);
     const int L = p.l.k.L, tid = threadIdx.x;
-    const size_t base = (size_t)q * L;
-    const int nb = clamp_n(p.l.k.n[q], L);
-    const unsigned long long seed = long_seed(p.l.k);
-    const int r0 = tile * kEpiTile;
-    const int len = min(kEpiTile, L - r0);
+    const int nb = t.nb, r0 = t.r0;
     const bool dcg = (p.need & EVAL_NEED_DCG) != 0;
-    float c = 0.f, keep = 1.f, first = 3.0e38f;
+    float c = 0.f, keep = 1.f, first = OpMin::id;
     for (int x = tid; x < kEpiTile; x += kEpiThreads) {
         const int r = r0 + x;
-        float y = 0.f, t = 0.f;
-        if (x < len) {
+        float y = 0.f, dt = 0.f;
+        if (x < t.span) {
             if (IDEAL) {
-                t = long_dcg_term(p.l, base, r, nb, seed);
+                dt = long_dcg_term(p.l, t.base, r, nb, t.seed);
             } else {
-                y = r < nb ? eval_long_label(p, base, r, seed) : (dcg ? load_label(p.l.k.rel, p.l.k.rel_dtype, base + r) : 0.f);
-                if (dcg) t = (p.l.use_exp ? (exp2f(y) - 1.0f) : y) / log2f((float)r + 2.0f);   // long_dcg_term
-                if (r < nb) {
+                // (the label once for the term and the counts: long_dcg_term's label and dcg_term)
+                y = x < t.real ? eval_long_label(p, t.base, r, t.seed) : (dcg ? load_label(p.l.k.rel, p.l.k.rel_dtype, t.base + r) : 0.f);
+                if (dcg) dt = dcg_term(y, r, p.l.use_exp);
+                if (x < t.real) {
                     const bool rel = y >= p.rel_level;
                     c += rel ? 1.f : 0.f;
                     if (rel) first = fminf(first, (float)r);
@@ -304,13 +201,13 @@ __global__ void __launch_bounds__(kEpiThreads) eval_long_partial_kernel(EvalLong
             }
         }
         lab[x] = y;
-        term[x] = t;
+        term[x] = dt;
     }
-    const size_t tslot = (size_t)q * p.tiles + tile;
+    const size_t tslot = (size_t)t.q * p.tiles + t.tile;
     if (!IDEAL) {
         c = block_sum(c, red);
-        if (p.need & EVAL_NEED_ERR) keep = block_reduce<true>(keep, red);
-        if (p.need & EVAL_NEED_MRR) first = block_reduce<false>(first, red);
+        if (p.need & EVAL_NEED_ERR) keep = block_reduce<OpMul>(keep, red);
+        if (p.need & EVAL_NEED_MRR) first = block_reduce<OpMin>(first, red);
         if (tid == 0) {
             p.cnt[tslot] = c;
             p.keep[tslot] = keep;
@@ -328,9 +225,8 @@ __global__ void __launch_bounds__(kEpiThreads) eval_long_partial_kernel(EvalLong
             for (int x = tid; x < kEpiTile; x += kEpiThreads) a += (r0 + x < lim) ? term[x] : 0.f;   // longsort_partial_kernel's order
         } else if (op == LTR_EVAL_ARP) {
             for (int x = tid; x < kEpiTile; x += kEpiThreads) {
-                const int r = r0 + x;
-                if (r < nb) {
-                    a += (float)(r + 1) * lab[x];
+                if (x < t.real) {
+                    a += (float)(r0 + x + 1) * lab[x];
                     a2 += lab[x];
                 }
             }
@@ -356,31 +252,28 @@ __global__ void __launch_bounds__(kEpiThreads) eval_long_prefix_kernel(EvalLongP
     __shared__ float cnt[kEpiTile];          // relevant documents in the top r + 1, within the tile
     __shared__ float keep[kEpiTile];         // prod (1 - R_i) over the tile's ranks <= r
     __shared__ float red[32];
-    const int q = blockIdx.x / p.tiles, tile = blockIdx.x - q * p.tiles;
-    const int L = p.l.k.L, tid = threadIdx.x;
-    const size_t base = (size_t)q * L;
-    const int nb = clamp_n(p.l.k.n[q], L);
-    const unsigned long long seed = long_seed(p.l.k);
-    const int r0 = tile * kEpiTile;
+    const EpiTile t = epi_tile(p.l.k, p.tiles);
+    const int tid = threadIdx.x;
+    const int nb = t.nb, r0 = t.r0;
     const bool err = (p.need & EVAL_NEED_ERR) != 0;
     for (int x = tid; x < kEpiTile; x += kEpiThreads) {
-        const int r = r0 + x;
-        const float y = r < nb ? eval_long_label(p, base, r, seed) : 0.f;
+        const bool real = x < t.real;
+        const float y = real ? eval_long_label(p, t.base, r0 + x, t.seed) : 0.f;
         lab[x] = y;
-        cnt[x] = (r < nb && y >= p.rel_level) ? 1.f : 0.f;
-        keep[x] = r < nb ? 1.f - err_prob(y, p.err_gmax) : 1.f;
+        cnt[x] = (real && y >= p.rel_level) ? 1.f : 0.f;
+        keep[x] = real ? 1.f - err_prob(y, p.err_gmax) : 1.f;
     }
     float c0 = 0.f, k0 = 1.f;
-    for (int t = tid; t < tile; t += kEpiThreads) {
-        c0 += p.cnt[(size_t)q * p.tiles + t];
-        k0 *= p.keep[(size_t)q * p.tiles + t];
+    for (int i = tid; i < t.tile; i += kEpiThreads) {
+        c0 += p.cnt[(size_t)t.q * p.tiles + i];
+        k0 *= p.keep[(size_t)t.q * p.tiles + i];
     }
     c0 = block_sum(c0, red);
-    if (err) k0 = block_reduce<true>(k0, red);
+    if (err) k0 = block_reduce<OpMul>(k0, red);
     __syncthreads();
-    block_scan<false>(cnt, kEpiTile, red);
-    if (err) block_scan<true>(keep, kEpiTile, red);
-    const size_t tslot = (size_t)q * p.tiles + tile;
+    block_scan<OpAdd>(cnt, kEpiTile, red);
+    if (err) block_scan<OpMul>(keep, kEpiTile, red);
+    const size_t tslot = (size_t)t.q * p.tiles + t.tile;
     const size_t mstride = (size_t)p.B * p.tiles;
     for (int i = 0; i < p.M; ++i) {
         const int op = p.spec[i].x, k = p.spec[i].y;
@@ -407,13 +300,13 @@ __global__ void __launch_bounds__(kEpiThreads) eval_long_finish_kernel(EvalLongP
     const int nb = clamp_n(p.l.k.n[q], L);
     const size_t row = (size_t)q * p.tiles;
     const size_t mstride = (size_t)p.B * p.tiles;
-    float R = 0.f, first = 3.0e38f;
+    float R = 0.f, first = OpMin::id;
     for (int t = tid; t < p.tiles; t += kEpiThreads) {
         R += p.cnt[row + t];
         first = fminf(first, p.first[row + t]);
     }
     R = block_sum(R, red);
-    if (p.need & EVAL_NEED_MRR) first = block_reduce<false>(first, red);
+    if (p.need & EVAL_NEED_MRR) first = block_reduce<OpMin>(first, red);
     for (int i = 0; i < p.M; ++i) {
         const int op = p.spec[i].x, k = p.spec[i].y;
         float a = 0.f, c = 0.f;
@@ -457,11 +350,18 @@ inline int eval_needs(const int32_t *spec, int M)
     return need;
 }
 
-// the byte formula of include/ltr_eval.h: the long path's keys and inverse tie map, then 2 M + 3 (B, tiles) arrays
-inline size_t eval_long_workspace_bytes(int B, int L, int M)
+// The workspace of ltr_eval_workspace_bytes (include/ltr_eval.h states the byte formula): the long path's keys and
+// inverse tie map, then 2 M + 3 (B, tiles) arrays, into p.
+inline LongWorkspace eval_long_workspace(Carver &c, int B, int L, int M, EvalLongParams &p)
 {
-    return align256(16 * (size_t)B * (size_t)L) + align256(4 * (size_t)L) +
-           4 * (size_t)B * (size_t)long_epi_tiles(L) * (size_t)(2 * M + 3);
+    const LongWorkspace ws = long_workspace(c, B, L, false);
+    const size_t arr = (size_t)B * (size_t)long_epi_tiles(L);
+    p.part = c.take<float>((size_t)M * arr);
+    p.ipart = c.take<float>((size_t)M * arr);
+    p.cnt = c.take<float>(arr);
+    p.keep = c.take<float>(arr);
+    p.first = c.take<float>(arr);
+    return ws;
 }
 
 int long_eval(const float *scores, const void *rel, int rel_dtype, const int64_t *n, const int32_t *tie, int use_seed,
@@ -469,9 +369,10 @@ int long_eval(const float *scores, const void *rel, int rel_dtype, const int64_t
               float relevance_level, int use_exp, float err_max_grade, float *out, void *workspace,
               size_t workspace_bytes, hipStream_t s)
 {
-    if (!workspace || workspace_bytes < eval_long_workspace_bytes(B, L, M)) return LTR_ERR_WORKSPACE;
-    const LongWorkspace ws = long_workspace(workspace, B, L);
     EvalLongParams p{};
+    Carver carver(workspace);
+    const LongWorkspace ws = eval_long_workspace(carver, B, L, M, p);
+    if (!workspace || workspace_bytes < carver.off) return LTR_ERR_WORKSPACE;
     p.l.k = long_key_params(scores, rel, rel_dtype, n, tie, use_seed, seed, seed_dev, L, ws, s);
     p.l.use_exp = use_exp;
     p.M = M; p.need = need; p.B = B;
@@ -479,11 +380,6 @@ int long_eval(const float *scores, const void *rel, int rel_dtype, const int64_t
     p.rel_level = relevance_level;
     p.err_gmax = err_max_grade;
     const size_t arr = (size_t)B * p.tiles;
-    p.part = reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(ws.inv) + align256(4 * (size_t)L));
-    p.ipart = p.part + (size_t)M * arr;
-    p.cnt = p.ipart + (size_t)M * arr;
-    p.keep = p.cnt + arr;
-    p.first = p.keep + arr;
     p.out = out;
     for (int i = 0; i < M; ++i) p.spec[i] = make_int2(spec[2 * i], spec[2 * i + 1]);
     const dim3 grid((unsigned)arr), block(kEpiThreads);
@@ -506,23 +402,8 @@ int launch_eval(const EvalParams &p0, hipStream_t stream)
 {
     EvalParams p = p0;
     const MetricShape sh = metric_shape(p.m);
-    const dim3 grid((unsigned)p.m.B), block((unsigned)sh.threads);
-    const size_t lds = sh.lds + sizeof(p.spec);            // + the spec (eval_kernel)
-#define LTR_LAUNCH(D)                                                                           \
-    do {                                                                                        \
-        LTR_ENSURE_LDS((eval_kernel<D>), lds);                                                  \
-        hipLaunchKernelGGL((eval_kernel<D>), grid, block, lds, stream, p);                      \
-    } while (0)
-    switch (sh.dpt) {
-    case 0: LTR_LAUNCH(0); break;
-    case -2: LTR_LAUNCH(-2); break;
-    case -4: LTR_LAUNCH(-4); break;
-    case 1: LTR_LAUNCH(1); break;
-    case 2: LTR_LAUNCH(2); break;
-    default: LTR_LAUNCH(4); break;
-    }
-#undef LTR_LAUNCH
-    return (int)hipGetLastError();
+    // (+ the spec, staged behind the core's layout)
+    return launch_ranked(sh, p.m.B, sizeof(p.spec), stream, p, [](auto D) { return &eval_kernel<decltype(D)::value>; });
 }
 
 // The host checks of ltr_eval_f32 up to the lists (include/ltr_eval.h states the order).
@@ -547,7 +428,11 @@ extern "C" {
 size_t ltr_eval_workspace_bytes(int B, int L, const int32_t *spec, int M)
 {
     if (!spec || eval_check(LTR_LABEL_I64, spec, M) != LTR_OK || check_lists(B, L, kMaxSortListLen) != LTR_OK) return 0;
-    return long_path(L) ? eval_long_workspace_bytes(B, L, M) : 0;
+    if (!long_path(L)) return 0;
+    EvalLongParams p{};
+    Carver sizes(nullptr);
+    eval_long_workspace(sizes, B, L, M, p);
+    return sizes.off;
 }
 
 int ltr_eval_f32(const float *scores, const void *rel, int rel_dtype, const int64_t *n, const int32_t *tie, int use_seed,
@@ -566,8 +451,7 @@ int ltr_eval_f32(const float *scores, const void *rel, int rel_dtype, const int6
                          use_exp, err_max_grade, out, workspace, workspace_bytes, s);
     EvalParams p{};
     p.m.scores = scores; p.m.rel = rel; p.m.n = n; p.m.B = B; p.m.L = L; p.m.rel_dtype = rel_dtype; p.m.use_exp = use_exp;
-    if (use_seed) { p.m.use_seed = 1; p.m.tie_seed = seed; p.m.tie_seed_dev = seed_dev; }
-    else p.m.tie = tie;
+    set_tie(p.m, tie, use_seed, seed, seed_dev);
     p.out = out;
     p.M = M; p.need = need;
     p.rel_level = relevance_level;

@@ -418,247 +418,6 @@ listwise_softmax_kernel(const float *__restrict__ scores, const LabelT *__restri
 }
 
 // ---------------------------------------------------------------------------------
-// rank_by_score / dcg / ndcg / arp
-// ---------------------------------------------------------------------------------
-struct MetricParams {
-    const float *scores;
-    const void *rel;
-    const int64_t *n;
-    const int32_t *tie;   // (L) tie priorities (a permutation of 0..L-1) or null = index order
-    unsigned long long tie_seed;   // use_seed: tie words hashed from (seed, position), see tie_hash_word
-    const int64_t *tie_seed_dev;   //   the seed read from device memory instead (a device generator's draw)
-    int use_seed;
-    void *out;
-    int B, L;
-    int rel_dtype;
-    int k;           // dcg: cutoff (0 = full curve)
-    int use_exp;
-    int normalize;
-    int msplit;
-};
-
-__host__ __device__ inline size_t metric_lds_bytes(int L)
-{
-    const size_t L4 = (size_t)((L + 3) & ~3);
-    return 8 * L4 + 8 * L4 + 16 * L4 + 32 * 4 + 64 * 4;  // sy, ranks, two curves (also: packed keys), red, scan
-}
-
-__host__ __device__ inline size_t metric_lds_bytes_sort(int L)
-{
-    const size_t L4 = (size_t)((L + 3) & ~3);
-    // ... + the inverse tie map int[L4] behind everything else
-    return 8 * L4 + 8 * L4 + 8 * (size_t)sort_pow2(L) + 32 * 4 + 64 * 4 + 4 * L4;
-}
-
-// Inclusive prefix sum of buf[0..L) in place (LDS).  Thread t owns a contiguous chunk.
-__device__ void block_inclusive_scan(float *buf, int L, float *scan_scratch)
-{
-    const int T = blockDim.x, tid = threadIdx.x;
-    const int ch = (L + T - 1) / T;
-    const int lo = min(L, tid * ch), hi = min(L, lo + ch);
-    float s = 0.f;
-    for (int i = lo; i < hi; ++i) s += buf[i];
-    // exclusive scan of per-thread sums: wave scan + cross-wave offsets
-    float incl = s;
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) {
-        const float up = __shfl_up(incl, off, kWave);
-        if ((tid & 63) >= off) incl += up;
-    }
-    const int w = tid >> 6, nw = T >> 6;
-    __syncthreads();
-    if ((tid & 63) == 63) scan_scratch[w] = incl;
-    __syncthreads();
-    float woff = 0.f;
-    for (int i = 0; i < w; ++i) woff += scan_scratch[i];
-    (void)nw;
-    float run = woff + incl - s;
-    for (int i = lo; i < hi; ++i) { run += buf[i]; buf[i] = run; }
-    __syncthreads();
-}
-
-enum { METRIC_RANK = 0, METRIC_DCG = 1, METRIC_ARP = 2 };
-
-// The ranking of one staged query (sy: (score, label) of the first nb documents): rank_s[k] = rank of document k by
-// score, and with_y: rank_y[k] by label (the ideal ranking); ranks < nb, ties by the tie words of p.  The sort path
-// (DPT <= 0) goes through the curve region (and an inverse tie map at the end of metric_lds_bytes_sort), the counting
-// rank (DPT > 0) keeps its packed keys there.  Shared by metric_kernel and eval_kernel (ltr_eval.inc).
-template <int DPT>
-__device__ __forceinline__ void metric_ranks(const MetricParams &p, unsigned char *smem, const float2 *sy, int *rank_s,
-                                             int *rank_y, float *curve, int nb, bool with_y)
-{
-    const int L = p.L;
-    const int L4 = (L + 3) & ~3;
-    const int tid = threadIdx.x;
-    const int T = blockDim.x;
-    const int msplit = p.msplit;
-    const int owners = T / msplit;
-    const int o = tid % owners;
-    const int slice = tid / owners;
-    const int mlen = (nb + msplit - 1) / msplit;
-    const int m0 = __builtin_amdgcn_readfirstlane(slice * mlen);
-    const int m1 = __builtin_amdgcn_readfirstlane(min(nb, m0 + mlen));
-    if (DPT <= 0) {
-        // long lists: bitonic sort of (score, index) keys -- and of (label, index) for the ideal
-        // ranking -- through the curve buffer; T = min(1024, P), E = P / T registers per thread
-        // (DPT = 0, -2, -4 stands for E = 1, 2, 4)
-        constexpr int E = DPT == 0 ? 1 : (DPT == -2 ? 2 : 4);
-        unsigned long long *xbuf = reinterpret_cast<unsigned long long *>(curve);
-        int Pq = 64;                                    // smallest power of two >= n of this query
-        while (Pq < nb) Pq <<= 1;
-        // random tie-break: the low key word is the document's tie priority; the inverse map
-        // (priority -> document) sits behind the other arrays
-        int *invt = nullptr;
-        const unsigned long long seed = p.use_seed ? (p.tie_seed_dev ? (unsigned long long)p.tie_seed_dev[0] : p.tie_seed) : 0ull;
-        const int low_mask = p.use_seed ? 0xFFF : 0;
-        auto tie_word = [&](int i) { return p.use_seed ? (int)tie_hash_word(seed, (unsigned)i) : (p.tie ? p.tie[i] : i); };
-        if (p.tie && !p.use_seed) {
-            invt = reinterpret_cast<int *>(smem + metric_lds_bytes_sort(L) - 4 * (size_t)L4);
-            for (int j = tid; j < L; j += T) invt[p.tie[j]] = j;
-            __syncthreads();
-        }
-        unsigned long long v[E];
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const int i = e * T + tid;
-            v[e] = (i < nb) ? rank_key(sy[i].x, tie_word(i)) : ~0ull;
-        }
-        sort_ranks<E>(v, Pq, nb, rank_s, xbuf, invt, low_mask);
-        if (with_y) {
-#pragma unroll
-            for (int e = 0; e < E; ++e) {
-                const int i = e * T + tid;
-                v[e] = (i < nb) ? rank_key(sy[i].y, tie_word(i)) : ~0ull;
-            }
-            sort_ranks<E>(v, Pq, nb, rank_y, xbuf, invt, low_mask);
-        }
-    } else {
-        // counting rank on packed keys (see count_ranks_keyed); the keys live in the curve region
-        ulonglong2 *keys = reinterpret_cast<ulonglong2 *>(curve);
-        for (int k = tid; k < nb; k += T) {
-            const float2 v = sy[k];
-            // tie word: hashed from the seed, a caller-drawn priority, or the index
-            const int t = p.use_seed ? (int)tie_hash_word(p.tie_seed_dev ? (unsigned long long)p.tie_seed_dev[0] : p.tie_seed, (unsigned)k)
-                                     : (p.tie ? p.tie[k] : k);
-            keys[k] = make_ulonglong2(rank_key(v.x, t), rank_key(v.y, t));
-        }
-        __syncthreads();
-        if (with_y)
-            count_ranks_keyed<(DPT > 0 ? DPT : 1), true>(keys, nb, owners, o, m0, m1, msplit > 1, rank_s, rank_y);
-        else
-            count_ranks_keyed<(DPT > 0 ? DPT : 1), false>(keys, nb, owners, o, m0, m1, msplit > 1, rank_s, rank_y);
-    }
-}
-
-// (the sort path, DPT <= 0, under 64 VGPRs -- eight waves per SIMD: its workgroups have up to 1024 threads, and at the 68-69 VGPRs
-// the compiler takes when left alone ONE of those fits a CU instead of two.  ndcg@10, 16 384 x 1000: 1167 -> 746 us, arp 631 -> 399,
-// 65 536 x 512: 1260 -> 1103, 8192 x 2000: 1096 -> 746; lists of 128: unchanged.  Round 6.)
-template <int OP, int DPT>
-__global__ void __launch_bounds__(1024, (DPT <= 0 ? 8 : 4))
-metric_kernel(MetricParams p)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int b = blockIdx.x;
-    const int L = p.L;
-    const int L4 = (L + 3) & ~3;
-    const int tid = threadIdx.x;
-    const int T = blockDim.x;
-    const int nb = clamp_n(p.n[b], L);
-
-    float2 *sy = reinterpret_cast<float2 *>(smem);
-    int *rank_s = reinterpret_cast<int *>(smem + 8 * (size_t)L4);
-    int *rank_y = rank_s + L4;
-    float *curve = reinterpret_cast<float *>(smem + 16 * (size_t)L4);
-    float *icurve = curve + L4;
-    float *red = icurve + L4;
-    float *scan_scratch = red + 32;
-
-    const size_t row = (size_t)b * L;
-    const bool need_labels = (OP != METRIC_RANK);
-    // dcg keeps the reference's quirk: padded labels are read and counted (dcg.py:85-94)
-    const int nload = (OP == METRIC_DCG) ? L : nb;
-    for (int m = tid; m < nload; m += T)
-        sy[m] = make_float2(p.scores[row + m],
-                            need_labels ? load_label(p.rel, p.rel_dtype, row + m) : 0.f);
-    for (int m = tid; m < 2 * L4; m += T) rank_s[m] = 0;
-    __syncthreads();
-
-    metric_ranks<DPT>(p, smem, sy, rank_s, rank_y, curve, nb, (OP == METRIC_DCG) && p.normalize);
-    __syncthreads();
-
-    if (OP == METRIC_RANK) {
-        // invert: ranking[rank_k] = k; padded documents keep their index (tail in index order)
-        int *inv = rank_y;
-        for (int k = tid; k < L; k += T) inv[k < nb ? rank_s[k] : k] = k;
-        __syncthreads();
-        int64_t *out = reinterpret_cast<int64_t *>(p.out) + row;
-        for (int r = tid; r < L; r += T) out[r] = (int64_t)inv[r];
-        return;
-    }
-
-    if (OP == METRIC_ARP) {
-        // arp.py:31-42: sum((r+1) * rel_r) / sum(rel_r) over ranks r < n; 0 -> 1 guard
-        float srp = 0.f, nrp = 0.f;
-        for (int k = tid; k < nb; k += T) {
-            const float y = sy[k].y;
-            srp += (float)(rank_s[k] + 1) * y;
-            nrp += y;
-        }
-        srp = block_sum(srp, red);
-        nrp = block_sum(nrp, red);
-        if (nrp == 0.0f) nrp = 1.0f;
-        if (tid == 0) reinterpret_cast<float *>(p.out)[b] = srp / nrp;
-        return;
-    }
-
-    // ---- dcg / ndcg ----
-    const int kk = p.k > 0 ? min(p.k, L) : 0;
-    float part = 0.f, ipart = 0.f;
-    for (int k = tid; k < L; k += T) {
-        const float y = sy[k].y;
-        const float gain = p.use_exp ? (exp2f(y) - 1.0f) : y;        // dcg.py:91-92
-        const int r = k < nb ? rank_s[k] : k;
-        const float term = gain / log2f((float)r + 2.0f);             // dcg.py:93
-        int ry = 0;
-        float iterm = 0.f;
-        if (p.normalize) {
-            ry = k < nb ? rank_y[k] : k;                              // ideal ranking, dcg.py:36
-            iterm = gain / log2f((float)ry + 2.0f);
-        }
-        if (kk > 0) {
-            part += (r < kk) ? term : 0.f;
-            ipart += (p.normalize && ry < kk) ? iterm : 0.f;
-        } else {
-            curve[r] = term;
-            if (p.normalize) icurve[ry] = iterm;
-        }
-    }
-    if (kk > 0) {
-        part = block_sum(part, red);
-        if (p.normalize) {
-            ipart = block_sum(ipart, red);
-            if (ipart == 0.0f) ipart = 1.0f;                           // dcg.py:37
-            part = part / ipart;
-        }
-        if (tid == 0) reinterpret_cast<float *>(p.out)[b] = part;
-        return;
-    }
-    __syncthreads();
-    block_inclusive_scan(curve, L, scan_scratch);                      // cumsum, dcg.py:94
-    if (p.normalize) block_inclusive_scan(icurve, L, scan_scratch);
-    float *out = reinterpret_cast<float *>(p.out) + row;
-    for (int r = tid; r < L; r += T) {
-        float v = curve[r];
-        if (p.normalize) {
-            float id = icurve[r];
-            if (id == 0.0f) id = 1.0f;
-            v /= id;
-        }
-        out[r] = v;
-    }
-}
-
-// ---------------------------------------------------------------------------------
 // mask_padded_values / batch_pairs
 // ---------------------------------------------------------------------------------
 __global__ void mask_padded_kernel(const float *__restrict__ xs, const int64_t *__restrict__ n,
@@ -1024,30 +783,75 @@ static int launch_loss_split(const LossParams &p, int nsplit, float *ws, hipStre
     return (int)hipGetLastError();
 }
 
-// The launch shape of the one-workgroup metric kernels (metric_kernel, eval_kernel of ltr_eval.inc): the DPT
-// instantiation (0, -2, -4: the sort path with 1, 2, 4 keys per thread; 1, 2, 4: the counting rank), the
-// workgroup size and the dynamic LDS; sets p.msplit.
-struct MetricShape { int dpt; int threads; size_t lds; };
-inline MetricShape metric_shape(MetricParams &p)
+// ---------------------------------------------------------------------------------
+// rank_by_score / dcg / ndcg / arp: one workgroup per query on the ranked-row core
+// ---------------------------------------------------------------------------------
+#include "ltr_ranked.inc"
+
+enum { METRIC_RANK = 0, METRIC_DCG = 1, METRIC_ARP = 2 };
+
+// (the sort path, DPT <= 0, under 64 VGPRs -- eight waves per SIMD: its workgroups have up to 1024 threads, and at the 68-69 VGPRs
+// the compiler takes when left alone ONE of those fits a CU instead of two.  ndcg@10, 16 384 x 1000: 1167 -> 746 us, arp 631 -> 399,
+// 65 536 x 512: 1260 -> 1103, 8192 x 2000: 1096 -> 746; lists of 128: unchanged.  Round 6.)
+template <int OP, int DPT>
+__global__ void __launch_bounds__(1024, (DPT <= 0 ? 8 : 4))
+metric_kernel(MetricParams p)
 {
-    if (p.L > kSortRankMinLen) {
-        const int P = sort_pow2(p.L);
-        int T = P < 1024 ? P : 1024;                    // E = P / T <= 4 keys per thread
-        // (many rounds of queries per CU: half the threads with two keys each -- narrower workgroups, more queries in flight, see
-        // choose_loss_shape.  Round 6, us: ndcg@10 65 536 x 512 1105 -> 854, 65 536 x 300 953 -> 737, 16 384 x 1000 749 -> 552,
-        // arp 65 536 x 300 530 -> 384; 1024 x 512: 25.9 / 25.5, 256 x 1000: 21.7 -> 26.7 -- hence from 16 queries per CU on.  Four
-        // keys per thread: 65 536 x 512 889, 8192 x 2000 747 -> 804 -- not taken.)
-        if (P <= 1024 && P >= 128 && (long)p.B >= 16L * device_cu_count()) T = P / 2;
-        p.msplit = 1;
-        return {P == T ? 0 : (P == 2 * T ? -2 : -4), T, metric_lds_bytes_sort(p.L)};
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int b = blockIdx.x;
+    const int L = p.L;
+    const int L4 = (L + 3) & ~3;
+    const int tid = threadIdx.x;
+    const int T = blockDim.x;
+    const int nb = clamp_n(p.n[b], L);
+    const RankedRowLds q = ranked_row_lds(smem, L, DPT <= 0);
+
+    const size_t row = (size_t)b * L;
+    const bool need_labels = (OP != METRIC_RANK);
+    // dcg keeps the reference's quirk: padded labels are read and counted (dcg.py:85-94)
+    const int nload = (OP == METRIC_DCG) ? L : nb;
+    for (int m = tid; m < nload; m += T)
+        q.sy[m] = make_float2(p.scores[row + m],
+                              need_labels ? load_label(p.rel, p.rel_dtype, row + m) : 0.f);
+    for (int m = tid; m < 2 * L4; m += T) q.rank_s[m] = 0;
+    __syncthreads();
+
+    metric_ranks<DPT>(p, q, nb, (OP == METRIC_DCG) && p.normalize);
+    __syncthreads();
+
+    if (OP == METRIC_RANK) {
+        // invert: ranking[rank_k] = k; padded documents keep their index (tail in index order)
+        int *inv = q.rank_y;
+        for (int k = tid; k < L; k += T) inv[k < nb ? q.rank_s[k] : k] = k;
+        __syncthreads();
+        int64_t *out = reinterpret_cast<int64_t *>(p.out) + row;
+        for (int r = tid; r < L; r += T) out[r] = (int64_t)inv[r];
+        return;
     }
-    LaunchShape s = choose_shape(p.B, p.L);
-    // (many rounds of queries per CU: ONE wave per query, two documents per thread -- what bounds the launch then is the number of
-    // queries a CU has in flight, see choose_loss_shape.  Lists of 128, round 6: ndcg@10 65 536 queries 116 -> 99 us, 2^20: 1667 ->
-    // 1359, arp 2^20: 1216 -> 804; at 1024 queries the two-wave shape stays, 6.6 against 8.0)
-    if (p.L > 64 && p.L <= 128 && (long)p.B >= 64L * device_cu_count()) { s.owners = 64; s.dpt = 2; s.msplit = 1; }
-    p.msplit = s.msplit;
-    return {s.dpt == 1 || s.dpt == 2 ? s.dpt : 4, s.owners * s.msplit, metric_lds_bytes(p.L)};
+
+    if (OP == METRIC_ARP) {
+        const float arp = ranked_arp(q, nb);
+        if (tid == 0) reinterpret_cast<float *>(p.out)[b] = arp;
+        return;
+    }
+
+    // ---- dcg / ndcg ----
+    const int kk = p.k > 0 ? min(p.k, L) : 0;
+    const float at_k = ranked_dcg(q, L, nb, kk, p.normalize != 0, p.use_exp);
+    if (kk > 0) {
+        if (tid == 0) reinterpret_cast<float *>(p.out)[b] = at_k;
+        return;
+    }
+    float *out = reinterpret_cast<float *>(p.out) + row;
+    for (int r = tid; r < L; r += T) {
+        float v = q.curve[r];
+        if (p.normalize) {
+            float id = q.icurve[r];
+            if (id == 0.0f) id = 1.0f;
+            v /= id;
+        }
+        out[r] = v;
+    }
 }
 
 template <int OP>
@@ -1055,22 +859,7 @@ int launch_metric(const MetricParams &p0, hipStream_t stream)
 {
     MetricParams p = p0;
     const MetricShape sh = metric_shape(p);
-    const dim3 grid((unsigned)p.B), block((unsigned)sh.threads);
-#define LTR_LAUNCH(D)                                                                           \
-    do {                                                                                        \
-        LTR_ENSURE_LDS((metric_kernel<OP, D>), sh.lds);                                         \
-        hipLaunchKernelGGL((metric_kernel<OP, D>), grid, block, sh.lds, stream, p);             \
-    } while (0)
-    switch (sh.dpt) {
-    case 0: LTR_LAUNCH(0); break;
-    case -2: LTR_LAUNCH(-2); break;
-    case -4: LTR_LAUNCH(-4); break;
-    case 1: LTR_LAUNCH(1); break;
-    case 2: LTR_LAUNCH(2); break;
-    default: LTR_LAUNCH(4); break;
-    }
-#undef LTR_LAUNCH
-    return (int)hipGetLastError();
+    return launch_ranked(sh, p.B, 0, stream, p, [](auto D) { return &metric_kernel<OP, decltype(D)::value>; });
 }
 
 int g_long_sort_all = 0;                 // ltr_debug_long_sort_all
@@ -1104,8 +893,7 @@ int metric_entry(const float *scores, const void *rel, int rel_dtype, const int6
         MetricParams p{};
         p.scores = scores; p.rel = rel; p.n = n; p.out = out; p.B = B; p.L = L;
         p.rel_dtype = rel_dtype; p.k = k; p.use_exp = use_exp; p.normalize = normalize;
-        if (use_seed) { p.use_seed = 1; p.tie_seed = seed; p.tie_seed_dev = seed_dev; }
-        else p.tie = tie;
+        set_tie(p, tie, use_seed, seed, seed_dev);
         return launch_metric<OP>(p, s);
     }
     return long_metric(OP, scores, rel, rel_dtype, n, tie, use_seed, seed, seed_dev, B, L, k, use_exp, normalize, out,

@@ -8,11 +8,11 @@
 //   2. the gradient scan: D_i = [i < K] + D_{i-1} exp(LSE_i - LSE_{i-1}) (D_{-1} = 0), an affine recurrence
 //      D_i = a_i D_{i-1} + b_i scanned as the composition of the maps (a_i, b_i); D_i <= i + 1, every a_i <= 1.  Then
 //      dscores[pi(i)] = exp(x_i - LSE_i) D_i - [i < K].
-// Both scans are one pass per thread over a contiguous chunk, a DPP wave scan of the chunk aggregates and one LDS hop
-// across waves; every sum runs in a fixed order (no atomics): bit-identical run to run.
+// Both scans are one pass per thread over a contiguous chunk, then block_pair_scan of the chunk aggregates (the ranked-row
+// core's pair scan, ltr_ranked.inc); every sum runs in a fixed order (no atomics): bit-identical run to run.
 //
-// Up to kMaxListLen documents: listmle_kernel, one workgroup per query in metric_kernel's launch shape (metric_shape),
-// its ranking (metric_ranks, with the labels in the score slot) and LDS layout.
+// Up to kMaxListLen documents: listmle_kernel, one workgroup per query on the ranked-row core: its launch shape, its
+// ranking (with the labels in the score slot) and its LDS layout.
 // Longer lists (and every list under ltr_debug_long_sort_all): the long path's key sort on label keys with the call's
 // tie words (long_sort<KEY_LABELS_TIED>), then per tile of kEpiTile ranks:
 //   1. listmle_long_gather_kernel: the ranked scores x_r, and the tile's (max, sum) aggregate;
@@ -45,78 +45,19 @@ __device__ __forceinline__ void aff_then(float &a, float &b, float a2, float b2)
     a = a * a2;
 }
 
-// the value of lane (lane - shift) within the DPP pattern CTRL, or `idle` where there is none
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_from(float idle, float v)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(idle), __float_as_int(v), CTRL, ROW_MASK, 0xF, false));
-}
-
-// Inclusive wave scans in lane order: row_shr 1, 2, 4, 8 within the rows of 16 lanes, then row_bcast15 / row_bcast31
-// carry the rows' totals forward (rows 1, 3 take row 0, 2; rows 2, 3 take rows 0-1).
-#define LTR_MS_STEP(CTRL, RM)                                                                                        \
-    do {                                                                                                             \
-        const float m2_ = dpp_from<CTRL, RM>(-INFINITY, m), s2_ = dpp_from<CTRL, RM>(0.f, s);                       \
-        ms_add(m, s, m2_, s2_);                                                                                      \
-    } while (0)
-__device__ __forceinline__ void wave_scan_ms(float &m, float &s)
-{
-    LTR_MS_STEP(0x111, 0xF); LTR_MS_STEP(0x112, 0xF); LTR_MS_STEP(0x114, 0xF); LTR_MS_STEP(0x118, 0xF);
-    LTR_MS_STEP(0x142, 0xA); LTR_MS_STEP(0x143, 0xC);
-}
-#undef LTR_MS_STEP
-
-#define LTR_AFF_STEP(CTRL, RM)                                                                                       \
-    do {                                                                                                             \
-        float a1_ = dpp_from<CTRL, RM>(1.f, a), b1_ = dpp_from<CTRL, RM>(0.f, b);                                    \
-        aff_then(a1_, b1_, a, b);                                                                                    \
-        a = a1_; b = b1_;                                                                                            \
-    } while (0)
-__device__ __forceinline__ void wave_scan_aff(float &a, float &b)
-{
-    LTR_AFF_STEP(0x111, 0xF); LTR_AFF_STEP(0x112, 0xF); LTR_AFF_STEP(0x114, 0xF); LTR_AFF_STEP(0x118, 0xF);
-    LTR_AFF_STEP(0x142, 0xA); LTR_AFF_STEP(0x143, 0xC);
-}
-#undef LTR_AFF_STEP
-
-// Workgroup scans in thread order of one value per thread: (x, y) becomes the combination of the threads before it
-// (exclusive), (tx, ty) the whole workgroup's, the same bits in every thread.  `pair`: LDS of 2 x 16 floats.
-// Contain barriers: call from uniform code.
-__device__ __forceinline__ void block_scan_ms(float &x, float &y, float &tx, float &ty, float *pair)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    float im = x, is = y;
-    wave_scan_ms(im, is);
-    float em = __shfl_up(im, 1, kWave), es = __shfl_up(is, 1, kWave);
-    if (lane == 0) { em = -INFINITY; es = 0.f; }
-    __syncthreads();
-    if (lane == 63) { pair[2 * w] = im; pair[2 * w + 1] = is; }
-    __syncthreads();
-    float m = -INFINITY, s = 0.f;
-    for (int i = 0; i < w; ++i) ms_add(m, s, pair[2 * i], pair[2 * i + 1]);
-    tx = m; ty = s;
-    for (int i = w; i < nw; ++i) ms_add(tx, ty, pair[2 * i], pair[2 * i + 1]);
-    ms_add(m, s, em, es);
-    x = m; y = s;
-}
-
-__device__ __forceinline__ void block_scan_aff(float &x, float &y, float &tx, float &ty, float *pair)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    float ia = x, ib = y;
-    wave_scan_aff(ia, ib);
-    float ea = __shfl_up(ia, 1, kWave), eb = __shfl_up(ib, 1, kWave);
-    if (lane == 0) { ea = 1.f; eb = 0.f; }
-    __syncthreads();
-    if (lane == 63) { pair[2 * w] = ia; pair[2 * w + 1] = ib; }
-    __syncthreads();
-    float a = 1.f, b = 0.f;
-    for (int i = 0; i < w; ++i) aff_then(a, b, pair[2 * i], pair[2 * i + 1]);
-    tx = a; ty = b;
-    for (int i = w; i < nw; ++i) aff_then(tx, ty, pair[2 * i], pair[2 * i + 1]);
-    aff_then(a, b, ea, eb);
-    x = a; y = b;
-}
+// The two as operators of block_pair_scan.  ms_add's rounding depends on which argument is the larger, so each
+// states the order it has always been called in: a lane's own pair first in the wave ladder of (max, sum), the
+// predecessor's map first in that of the affine maps.
+struct MaxSum {
+    static constexpr float idx = -INFINITY, idy = 0.f;
+    static __device__ __forceinline__ void then(float &m, float &s, float m2, float s2) { ms_add(m, s, m2, s2); }
+    static __device__ __forceinline__ void after(float &m, float &s, float pm, float ps) { ms_add(m, s, pm, ps); }
+};
+struct Affine {
+    static constexpr float idx = 1.f, idy = 0.f;
+    static __device__ __forceinline__ void then(float &a, float &b, float a2, float b2) { aff_then(a, b, a2, b2); }
+    static __device__ __forceinline__ void after(float &a, float &b, float pa, float pb) { aff_then(pa, pb, a, b); a = pa; b = pb; }
+};
 
 // a_i = exp(LSE_i - LSE_{i-1}) from the (M, log S) pairs of ranks i and i - 1 (<= 1; clamped against rounding)
 __device__ __forceinline__ float lse_step(float m, float ls, float mp, float lsp)
@@ -134,7 +75,7 @@ struct ListMLEParams {
     int k;                   // <= 0: every factor
 };
 
-// (metric_kernel's launch bounds and so its register budgets: same shapes, same occupancy)
+// (the launch bounds, and so the register budgets, of the ranked-row core's kernels: same shapes, same occupancy)
 template <int DPT>
 __global__ void __launch_bounds__(1024, (DPT <= 0 ? 8 : 4))
 listmle_kernel(ListMLEParams p)
@@ -149,20 +90,20 @@ listmle_kernel(ListMLEParams p)
     const int nb = clamp_n(m.n[b], L);
     const int K = p.k > 0 ? min(p.k, nb) : nb;
 
-    // metric_kernel's LDS layout: (label, score) pairs where it keeps (score, label) -- metric_ranks ranks the x slot
-    float2 *sy = reinterpret_cast<float2 *>(smem);
-    int *rank_s = reinterpret_cast<int *>(smem + 8 * (size_t)L4);
-    float *xs = reinterpret_cast<float *>(rank_s + L4);                // ranked scores (rank_y's slot)
-    float *curve = reinterpret_cast<float *>(smem + 16 * (size_t)L4);
-    float *red = curve + 2 * L4;
-    float *pair = red + 32;
-    float *mx = reinterpret_cast<float *>(smem), *ls = mx + L4;        // (M_i, log S_i), over sy once it is read
+    // the core's LDS layout, with (label, score) pairs where the metrics keep (score, label): metric_ranks ranks the x slot
+    const RankedRowLds q = ranked_row_lds(smem, L, DPT <= 0);
+    float2 *sy = q.sy;
+    int *rank_s = q.rank_s;
+    float *xs = reinterpret_cast<float *>(q.rank_y);                   // ranked scores (rank_y's slot)
+    float *curve = q.curve;                                            // the gradient by rank
+    float *red = q.red, *pair = q.scan;
+    float *mx = reinterpret_cast<float *>(q.sy), *ls = mx + L4;        // (M_i, log S_i), over sy once it is read
 
     const size_t row = (size_t)b * L;
     for (int j = tid; j < nb; j += T) sy[j] = make_float2(load_label(m.rel, m.rel_dtype, row + j), p.scores[row + j]);
     for (int j = tid; j < L4; j += T) rank_s[j] = 0;
     __syncthreads();
-    metric_ranks<DPT>(m, smem, sy, rank_s, reinterpret_cast<int *>(xs), curve, nb, false);
+    metric_ranks<DPT>(m, q, nb, false);
     __syncthreads();
     for (int j = tid; j < nb; j += T) xs[rank_s[j]] = sy[j].y;
     __syncthreads();
@@ -171,10 +112,10 @@ listmle_kernel(ListMLEParams p)
     const int ch = (nb + T - 1) / T;
     const int lo = min(nb, tid * ch), hi = min(nb, lo + ch);
     float cm = -INFINITY, cs = 0.f, tm, ts;
-    for (int q = lo; q < hi; ++q) ms_add(cm, cs, xs[nb - 1 - q], 1.f);
-    block_scan_ms(cm, cs, tm, ts, pair);
-    for (int q = lo; q < hi; ++q) {
-        const int i = nb - 1 - q;
+    for (int u = lo; u < hi; ++u) ms_add(cm, cs, xs[nb - 1 - u], 1.f);
+    block_pair_scan<MaxSum>(cm, cs, tm, ts, pair);
+    for (int u = lo; u < hi; ++u) {
+        const int i = nb - 1 - u;
         ms_add(cm, cs, xs[i], 1.f);
         mx[i] = cm;
         ls[i] = logf(cs);
@@ -190,7 +131,7 @@ listmle_kernel(ListMLEParams p)
     float ca = 1.f, cb = 0.f, ta, tb;
     for (int i = lo; i < hi; ++i)
         aff_then(ca, cb, i > 0 ? lse_step(mx[i], ls[i], mx[i - 1], ls[i - 1]) : 0.f, i < K ? 1.f : 0.f);
-    block_scan_aff(ca, cb, ta, tb, pair);
+    block_pair_scan<Affine>(ca, cb, ta, tb, pair);
     float d = cb;                                                      // D before the chunk (D_{-1} = 0)
     for (int i = lo; i < hi; ++i) {
         const float bi = i < K ? 1.f : 0.f;
@@ -220,26 +161,21 @@ __global__ void __launch_bounds__(kEpiThreads) listmle_long_gather_kernel(ListML
 {
     __shared__ float t[kEpiTile];
     __shared__ float pair[32];
-    const int q = blockIdx.x / p.tiles, tile = blockIdx.x - q * p.tiles;
-    const int L = p.key.L, tid = threadIdx.x;
-    const size_t base = (size_t)q * L;
-    const int nb = clamp_n(p.key.n[q], L);
-    const unsigned long long seed = long_seed(p.key);
-    const int r0 = tile * kEpiTile;
-    const int len = max(0, min(kEpiTile, nb - r0));
-    for (int x = tid; x < len; x += kEpiThreads) {
-        const float v = p.scores[base + long_doc(p.key, p.sorted[base + r0 + x], seed)];
+    const EpiTile et = epi_tile(p.key, p.tiles);
+    const int tid = threadIdx.x;
+    for (int x = tid; x < et.real; x += kEpiThreads) {
+        const float v = p.scores[et.base + long_doc(p.key, p.sorted[et.base + et.r0 + x], et.seed)];
         t[x] = v;
-        p.xs[base + r0 + x] = v;
+        p.xs[et.base + et.r0 + x] = v;
     }
     __syncthreads();
     float m = -INFINITY, s = 0.f, tm, ts;
     for (int e = 0; e < kEpiE; ++e) {
         const int x = tid * kEpiE + e;
-        if (x < len) ms_add(m, s, t[x], 1.f);
+        if (x < et.real) ms_add(m, s, t[x], 1.f);
     }
-    block_scan_ms(m, s, tm, ts, pair);
-    if (tid == 0) p.tagg[(size_t)q * p.tiles + tile] = make_float2(tm, ts);
+    block_pair_scan<MaxSum>(m, s, tm, ts, pair);
+    if (tid == 0) p.tagg[(size_t)et.q * p.tiles + et.tile] = make_float2(tm, ts);
 }
 
 // 2. (M_r, log S_r) of the tile's ranks: the tiles after it first (in a fixed order), then the in-tile suffix scan
@@ -248,44 +184,40 @@ __global__ void __launch_bounds__(kEpiThreads) listmle_long_lse_kernel(ListMLELo
     __shared__ float t[kEpiTile];
     __shared__ float pair[32];
     __shared__ float red[32];
-    const int q = blockIdx.x / p.tiles, tile = blockIdx.x - q * p.tiles;
-    const int L = p.key.L, tid = threadIdx.x;
-    const size_t base = (size_t)q * L;
-    const int nb = clamp_n(p.key.n[q], L);
-    const int K = listmle_k(p, nb);
-    const int r0 = tile * kEpiTile;
-    const int len = max(0, min(kEpiTile, nb - r0));
-    for (int x = tid; x < len; x += kEpiThreads) t[x] = p.xs[base + r0 + x];
+    const EpiTile et = epi_tile(p.key, p.tiles);
+    const int tid = threadIdx.x;
+    const int K = listmle_k(p, et.nb);
+    for (int x = tid; x < et.real; x += kEpiThreads) t[x] = p.xs[et.base + et.r0 + x];
     // the tiles after this one: thread-contiguous runs of them, then the workgroup's combination
-    const int after = max(0, min(p.tiles, (nb + kEpiTile - 1) / kEpiTile) - tile - 1);
+    const int after = max(0, min(p.tiles, (et.nb + kEpiTile - 1) / kEpiTile) - et.tile - 1);
     const int ach = (after + kEpiThreads - 1) / kEpiThreads;
     float im = -INFINITY, is = 0.f, inm, ins;
     for (int i = tid * ach; i < min(after, (tid + 1) * ach); ++i) {
-        const float2 a = p.tagg[(size_t)q * p.tiles + tile + 1 + i];
+        const float2 a = p.tagg[(size_t)et.q * p.tiles + et.tile + 1 + i];
         ms_add(im, is, a.x, a.y);
     }
-    block_scan_ms(im, is, inm, ins, pair);                             // (its barriers publish t)
+    block_pair_scan<MaxSum>(im, is, inm, ins, pair);                   // (its barriers publish t)
     // the tile: thread t owns the reversed ranks [t kEpiE, (t + 1) kEpiE)
     float m = -INFINITY, s = 0.f, tm, ts;
     for (int e = 0; e < kEpiE; ++e) {
-        const int x = len - 1 - (tid * kEpiE + e);
+        const int x = et.real - 1 - (tid * kEpiE + e);
         if (x >= 0) ms_add(m, s, t[x], 1.f);
     }
-    block_scan_ms(m, s, tm, ts, pair);
+    block_pair_scan<MaxSum>(m, s, tm, ts, pair);
     float rm = inm, rs = ins, acc = 0.f;
     ms_add(rm, rs, m, s);
     for (int e = 0; e < kEpiE; ++e) {
-        const int x = len - 1 - (tid * kEpiE + e);
+        const int x = et.real - 1 - (tid * kEpiE + e);
         if (x >= 0) {
             ms_add(rm, rs, t[x], 1.f);
             const float l = logf(rs);
-            p.mx[base + r0 + x] = rm;
-            p.ls[base + r0 + x] = l;
-            if (r0 + x < K) acc += (rm - t[x]) + l;
+            p.mx[et.base + et.r0 + x] = rm;
+            p.ls[et.base + et.r0 + x] = l;
+            if (et.r0 + x < K) acc += (rm - t[x]) + l;
         }
     }
     acc = block_sum(acc, red);
-    if (tid == 0) p.tloss[(size_t)q * p.tiles + tile] = acc;
+    if (tid == 0) p.tloss[(size_t)et.q * p.tiles + et.tile] = acc;
 }
 
 // the map (a_r, b_r) of rank r < nb (the arrays of listmle_long_lse_kernel)
@@ -299,66 +231,57 @@ __device__ __forceinline__ float2 listmle_long_map(const ListMLELongParams &p, s
 __global__ void __launch_bounds__(kEpiThreads) listmle_long_affine_kernel(ListMLELongParams p)
 {
     __shared__ float pair[32];
-    const int q = blockIdx.x / p.tiles, tile = blockIdx.x - q * p.tiles;
-    const int L = p.key.L, tid = threadIdx.x;
-    const size_t base = (size_t)q * L;
-    const int nb = clamp_n(p.key.n[q], L);
-    const int K = listmle_k(p, nb);
-    const int r0 = tile * kEpiTile;
-    const int len = max(0, min(kEpiTile, nb - r0));
+    const EpiTile et = epi_tile(p.key, p.tiles);
+    const int tid = threadIdx.x;
+    const int K = listmle_k(p, et.nb);
     float a = 1.f, b = 0.f, ta, tb;
     for (int e = 0; e < kEpiE; ++e) {
         const int x = tid * kEpiE + e;
-        if (x < len) {
-            const float2 f = listmle_long_map(p, base, r0 + x, K);
+        if (x < et.real) {
+            const float2 f = listmle_long_map(p, et.base, et.r0 + x, K);
             aff_then(a, b, f.x, f.y);
         }
     }
-    block_scan_aff(a, b, ta, tb, pair);
-    if (tid == 0) p.taff[(size_t)q * p.tiles + tile] = make_float2(ta, tb);
+    block_pair_scan<Affine>(a, b, ta, tb, pair);
+    if (tid == 0) p.taff[(size_t)et.q * p.tiles + et.tile] = make_float2(ta, tb);
 }
 
 // 4. D_r of the tile's ranks (the maps of the tiles before it composed in order), dscores through the ranking
 __global__ void __launch_bounds__(kEpiThreads) listmle_long_grad_kernel(ListMLELongParams p)
 {
     __shared__ float pair[32];
-    const int q = blockIdx.x / p.tiles, tile = blockIdx.x - q * p.tiles;
-    const int L = p.key.L, tid = threadIdx.x;
-    const size_t base = (size_t)q * L;
-    const int nb = clamp_n(p.key.n[q], L);
-    const int K = listmle_k(p, nb);
-    const unsigned long long seed = long_seed(p.key);
-    const int r0 = tile * kEpiTile;
-    const int len = max(0, min(kEpiTile, nb - r0));
+    const EpiTile et = epi_tile(p.key, p.tiles);
+    const int tid = threadIdx.x;
+    const int K = listmle_k(p, et.nb);
     // padded documents sit at their own index past the real ones
-    for (int x = max(len, 0) + tid; x < min(kEpiTile, L - r0); x += kEpiThreads) p.dscores[base + r0 + x] = 0.f;
-    const int before = min(tile, (nb + kEpiTile - 1) / kEpiTile);
+    for (int x = et.real + tid; x < et.span; x += kEpiThreads) p.dscores[et.base + et.r0 + x] = 0.f;
+    const int before = min(et.tile, (et.nb + kEpiTile - 1) / kEpiTile);
     const int bch = (before + kEpiThreads - 1) / kEpiThreads;
     float pa = 1.f, pb = 0.f, ta, tb;
     for (int i = tid * bch; i < min(before, (tid + 1) * bch); ++i) {
-        const float2 f = p.taff[(size_t)q * p.tiles + i];
+        const float2 f = p.taff[(size_t)et.q * p.tiles + i];
         aff_then(pa, pb, f.x, f.y);
     }
-    block_scan_aff(pa, pb, ta, tb, pair);
+    block_pair_scan<Affine>(pa, pb, ta, tb, pair);
     const float din = tb;                                              // D at the end of the tiles before (D_{-1} = 0)
     float a = 1.f, b = 0.f, ea, eb;
     for (int e = 0; e < kEpiE; ++e) {
         const int x = tid * kEpiE + e;
-        if (x < len) {
-            const float2 f = listmle_long_map(p, base, r0 + x, K);
+        if (x < et.real) {
+            const float2 f = listmle_long_map(p, et.base, et.r0 + x, K);
             aff_then(a, b, f.x, f.y);
         }
     }
-    block_scan_aff(a, b, ea, eb, pair);
+    block_pair_scan<Affine>(a, b, ea, eb, pair);
     float d = __builtin_fmaf(a, din, b);
     for (int e = 0; e < kEpiE; ++e) {
         const int x = tid * kEpiE + e;
-        if (x < len) {
-            const int r = r0 + x;
-            const float2 f = listmle_long_map(p, base, r, K);
+        if (x < et.real) {
+            const int r = et.r0 + x;
+            const float2 f = listmle_long_map(p, et.base, r, K);
             d = __builtin_fmaf(f.x, d, f.y);
-            const float g = lse_prob(p.xs[base + r], p.mx[base + r], p.ls[base + r]) * d - f.y;
-            p.dscores[base + long_doc(p.key, p.sorted[base + r], seed)] = g;
+            const float g = lse_prob(p.xs[et.base + r], p.mx[et.base + r], p.ls[et.base + r]) * d - f.y;
+            p.dscores[et.base + long_doc(p.key, p.sorted[et.base + r], et.seed)] = g;
         }
     }
 }
@@ -375,32 +298,34 @@ __global__ void __launch_bounds__(kEpiThreads) listmle_long_finish_kernel(ListML
 }
 
 // ---- host side ----
-// the long path's keys and inverse tie map, three (B, L) float arrays, two (B, tiles) float2 and one float array
-inline size_t listmle_long_workspace_bytes(int B, int L)
+// The workspace of ltr_listmle_workspace_bytes (include/ltr_listwise.h states the byte formula): the long path's keys
+// and inverse tie map, three (B, L) float arrays, two (B, tiles) float2 and one float array, into p.
+inline LongWorkspace listmle_long_workspace(Carver &c, int B, int L, ListMLELongParams &p)
 {
+    const LongWorkspace ws = long_workspace(c, B, L, false);
     const size_t BL = (size_t)B * (size_t)L, bt = (size_t)B * (size_t)long_epi_tiles(L);
-    return align256(16 * BL) + align256(4 * (size_t)L) + 3 * align256(4 * BL) + align256(16 * bt) + 4 * bt;
+    p.xs = c.take<float>(BL); c.align256();
+    p.mx = c.take<float>(BL); c.align256();
+    p.ls = c.take<float>(BL); c.align256();
+    p.tagg = c.take<float2>(bt);
+    p.taff = c.take<float2>(bt); c.align256();
+    p.tloss = c.take<float>(bt);
+    return ws;
 }
 
 int long_listmle(const float *scores, const void *rel, int rel_dtype, const int64_t *n, int k, const int32_t *tie,
                  int use_seed, uint64_t seed, const int64_t *seed_dev, int B, int L, float *loss, float *dscores,
                  void *workspace, size_t workspace_bytes, hipStream_t s)
 {
-    if (!workspace || workspace_bytes < listmle_long_workspace_bytes(B, L)) return LTR_ERR_WORKSPACE;
-    const LongWorkspace ws = long_workspace(workspace, B, L);
     ListMLELongParams p{};
+    Carver carver(workspace);
+    const LongWorkspace ws = listmle_long_workspace(carver, B, L, p);
+    if (!workspace || workspace_bytes < carver.off) return LTR_ERR_WORKSPACE;
     p.key = long_key_params(nullptr, rel, rel_dtype, n, tie, use_seed, seed, seed_dev, L, ws, s);
     p.scores = scores; p.loss = loss; p.dscores = dscores;
     p.k = k; p.B = B;
     p.tiles = long_epi_tiles(L);
-    const size_t BL = (size_t)B * (size_t)L, bt = (size_t)B * (size_t)p.tiles;
-    unsigned char *w = reinterpret_cast<unsigned char *>(ws.inv) + align256(4 * (size_t)L);
-    p.xs = reinterpret_cast<float *>(w);
-    p.mx = reinterpret_cast<float *>(w + align256(4 * BL));
-    p.ls = reinterpret_cast<float *>(w + 2 * align256(4 * BL));
-    p.tagg = reinterpret_cast<float2 *>(w + 3 * align256(4 * BL));
-    p.taff = p.tagg + bt;
-    p.tloss = reinterpret_cast<float *>(w + 3 * align256(4 * BL) + align256(16 * bt));
+    const size_t bt = (size_t)B * (size_t)p.tiles;
     p.sorted = long_sort<KEY_LABELS_TIED>(p.key, B, ws, nullptr, s);
     const dim3 grid((unsigned)bt), block(kEpiThreads);
     hipLaunchKernelGGL(listmle_long_gather_kernel, grid, block, 0, s, p);
@@ -417,22 +342,7 @@ int launch_listmle(const ListMLEParams &p0, hipStream_t stream)
 {
     ListMLEParams p = p0;
     const MetricShape sh = metric_shape(p.m);
-    const dim3 grid((unsigned)p.m.B), block((unsigned)sh.threads);
-#define LTR_LAUNCH(D)                                                                           \
-    do {                                                                                        \
-        LTR_ENSURE_LDS((listmle_kernel<D>), sh.lds);                                            \
-        hipLaunchKernelGGL((listmle_kernel<D>), grid, block, sh.lds, stream, p);                \
-    } while (0)
-    switch (sh.dpt) {
-    case 0: LTR_LAUNCH(0); break;
-    case -2: LTR_LAUNCH(-2); break;
-    case -4: LTR_LAUNCH(-4); break;
-    case 1: LTR_LAUNCH(1); break;
-    case 2: LTR_LAUNCH(2); break;
-    default: LTR_LAUNCH(4); break;
-    }
-#undef LTR_LAUNCH
-    return (int)hipGetLastError();
+    return launch_ranked(sh, p.m.B, 0, stream, p, [](auto D) { return &listmle_kernel<decltype(D)::value>; });
 }
 
 }  // namespace
@@ -442,7 +352,11 @@ extern "C" {
 size_t ltr_listmle_workspace_bytes(int B, int L)
 {
     if (check_lists(B, L, kMaxSortListLen) != LTR_OK) return 0;
-    return long_path(L) ? listmle_long_workspace_bytes(B, L) : 0;
+    if (!long_path(L)) return 0;
+    ListMLELongParams p{};
+    Carver sizes(nullptr);
+    listmle_long_workspace(sizes, B, L, p);
+    return sizes.off;
 }
 
 int ltr_listmle_f32(const float *scores, const void *rel, int rel_dtype, const int64_t *n, int k, const int32_t *tie,
@@ -460,8 +374,7 @@ int ltr_listmle_f32(const float *scores, const void *rel, int rel_dtype, const i
                             workspace_bytes, s);
     ListMLEParams p{};
     p.m.rel = rel; p.m.n = n; p.m.B = B; p.m.L = L; p.m.rel_dtype = rel_dtype;
-    if (use_seed) { p.m.use_seed = 1; p.m.tie_seed = seed; p.m.tie_seed_dev = seed_dev; }
-    else p.m.tie = tie;
+    set_tie(p.m, tie, use_seed, seed, seed_dev);
     p.scores = scores; p.loss = loss; p.dscores = dscores; p.k = k;
     return launch_listmle(p, s);
 }

@@ -236,8 +236,25 @@ longsort_merge_kernel(LongKeyParams k, int tiles, int W, const unsigned long lon
     }
 }
 
-// 3. epilogues (the metric_kernel semantics: padded labels counted by dcg, gains 2^y - 1 or y,
+// 3. epilogues (the semantics of the one-workgroup kernels: padded labels counted by dcg, gains 2^y - 1 or y,
 // discount 1 / log2(r + 2), arp over the real documents).
+// The tile of one epilogue workgroup: query q (its row at `base`, nb real documents, tie seed), tile `tile` of the
+// `tiles` per query of the launch: sorted positions [r0, r0 + span) of the row, the first `real` of them real documents.
+struct EpiTile { int q, tile, r0, span, real, nb; size_t base; unsigned long long seed; };
+__device__ __forceinline__ EpiTile epi_tile(const LongKeyParams &k, int tiles)
+{
+    EpiTile t;
+    t.q = blockIdx.x / tiles;
+    t.tile = blockIdx.x - t.q * tiles;
+    t.base = (size_t)t.q * k.L;
+    t.nb = clamp_n(k.n[t.q], k.L);
+    t.seed = long_seed(k);
+    t.r0 = t.tile * kEpiTile;
+    t.span = min(kEpiTile, k.L - t.r0);
+    t.real = max(0, min(kEpiTile, t.nb - t.r0));
+    return t;
+}
+
 struct LongMetricParams {
     LongKeyParams k;                     // the keys `sorted` holds
     const unsigned long long *sorted;    // (B, L)
@@ -250,6 +267,14 @@ struct LongMetricParams {
     float *out;
 };
 
+// the DCG term of label y at position r (dcg.py:91-93)
+__device__ __forceinline__ float dcg_term(float y, int r, int use_exp)
+{
+    const float gain = use_exp ? (exp2f(y) - 1.0f) : y;
+    return gain / log2f((float)r + 2.0f);
+}
+
+// ... of sorted position r: a padded document's own label, else the label behind the key (ideal: in the key)
 __device__ __forceinline__ float long_dcg_term(const LongMetricParams &p, size_t base, int r, int nb,
                                                unsigned long long seed)
 {
@@ -257,38 +282,33 @@ __device__ __forceinline__ float long_dcg_term(const LongMetricParams &p, size_t
     if (r >= nb) y = load_label(p.k.rel, p.k.rel_dtype, base + r);
     else if (p.ideal) y = long_key_value(p.sorted[base + r]);
     else y = load_label(p.k.rel, p.k.rel_dtype, base + long_doc(p.k, p.sorted[base + r], seed));
-    const float gain = p.use_exp ? (exp2f(y) - 1.0f) : y;
-    return gain / log2f((float)r + 2.0f);
+    return dcg_term(y, r, p.use_exp);
 }
 
 template <int OP>
 __global__ void __launch_bounds__(kEpiThreads) longsort_partial_kernel(LongMetricParams p)
 {
     __shared__ float red[32];
-    const int q = blockIdx.x / p.tiles, tile = blockIdx.x - q * p.tiles;
-    const int L = p.k.L, tid = threadIdx.x;
-    const size_t base = (size_t)q * L;
-    const int nb = clamp_n(p.k.n[q], L);
-    const unsigned long long seed = long_seed(p.k);
-    const int lim = OP == METRIC_ARP ? nb : min(p.lim, L);
-    const int r0 = tile * kEpiTile;
+    const EpiTile t = epi_tile(p.k, p.tiles);
+    const int tid = threadIdx.x;
+    const int lim = OP == METRIC_ARP ? t.nb : min(p.lim, p.k.L);
     float a = 0.f, c = 0.f;
     for (int x = tid; x < kEpiTile; x += kEpiThreads) {
-        const int r = r0 + x;
+        const int r = t.r0 + x;
         if (r >= lim) break;
         if (OP == METRIC_ARP) {
-            const float y = load_label(p.k.rel, p.k.rel_dtype, base + long_doc(p.k, p.sorted[base + r], seed));
+            const float y = load_label(p.k.rel, p.k.rel_dtype, t.base + long_doc(p.k, p.sorted[t.base + r], t.seed));
             a += (float)(r + 1) * y;                                   // arp.py:31-42
             c += y;
         } else {
-            a += long_dcg_term(p, base, r, nb, seed);
+            a += long_dcg_term(p, t.base, r, t.nb, t.seed);
         }
     }
     a = block_sum(a, red);
     if (OP == METRIC_ARP) c = block_sum(c, red);
     if (tid == 0) {
-        p.part[(size_t)q * p.ptiles + tile] = a;
-        if (OP == METRIC_ARP) p.part2[(size_t)q * p.ptiles + tile] = c;
+        p.part[(size_t)t.q * p.ptiles + t.tile] = a;
+        if (OP == METRIC_ARP) p.part2[(size_t)t.q * p.ptiles + t.tile] = c;
     }
 }
 
@@ -317,55 +337,30 @@ __global__ void __launch_bounds__(kEpiThreads) longsort_finish_kernel(LongMetric
 template <bool DIVIDE>
 __global__ void __launch_bounds__(kEpiThreads) longsort_curve_kernel(LongMetricParams p)
 {
-    __shared__ float t[kEpiTile];
+    __shared__ float term[kEpiTile];
     __shared__ float red[32];
-    const int q = blockIdx.x / p.tiles, tile = blockIdx.x - q * p.tiles;
-    const int L = p.k.L, tid = threadIdx.x;
-    const size_t base = (size_t)q * L;
-    const int nb = clamp_n(p.k.n[q], L);
-    const unsigned long long seed = long_seed(p.k);
-    const int r0 = tile * kEpiTile;
-    const int len = min(kEpiTile, L - r0);
-    for (int x = tid; x < kEpiTile; x += kEpiThreads) t[x] = x < len ? long_dcg_term(p, base, r0 + x, nb, seed) : 0.f;
+    const EpiTile t = epi_tile(p.k, p.tiles);
+    const int tid = threadIdx.x;
+    for (int x = tid; x < kEpiTile; x += kEpiThreads)
+        term[x] = x < t.span ? long_dcg_term(p, t.base, t.r0 + x, t.nb, t.seed) : 0.f;
     float off = 0.f;
-    for (int i = tid; i < tile; i += kEpiThreads) off += p.part[(size_t)q * p.ptiles + i];
+    for (int i = tid; i < t.tile; i += kEpiThreads) off += p.part[(size_t)t.q * p.ptiles + i];
     off = block_sum(off, red);
     __syncthreads();
-    float s = 0.f;
-#pragma unroll
-    for (int e = 0; e < kEpiE; ++e) s += t[tid * kEpiE + e];
-    float incl = s;
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-        const float up = __shfl_up(incl, o, kWave);
-        if ((tid & 63) >= o) incl += up;
-    }
-    __syncthreads();                                                   // block_sum's readers of red are done
-    if ((tid & 63) == 63) red[tid >> 6] = incl;
-    __syncthreads();
-    float woff = 0.f;
-    for (int i = 0; i < (tid >> 6); ++i) woff += red[i];
-    float run = off + (woff + incl - s);
-#pragma unroll
-    for (int e = 0; e < kEpiE; ++e) {
-        run += t[tid * kEpiE + e];
-        t[tid * kEpiE + e] = run;
-    }
-    __syncthreads();
-    for (int x = tid; x < len; x += kEpiThreads) {
-        float *o = p.out + base + r0 + x;
+    block_inclusive_scan(term, kEpiTile, red, off);                    // (kEpiE positions per thread)
+    for (int x = tid; x < t.span; x += kEpiThreads) {
+        float *o = p.out + t.base + t.r0 + x;
         if (DIVIDE) {
-            float id = t[x];
+            float id = term[x];
             if (id == 0.0f) id = 1.0f;                                 // dcg.py:37
             *o = *o / id;
         } else {
-            *o = t[x];
+            *o = term[x];
         }
     }
 }
 
 // ---- host side ----
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline int long_epi_tiles(int L) { return (L + kEpiTile - 1) / kEpiTile; }
 
 struct LongWorkspace {
@@ -374,24 +369,18 @@ struct LongWorkspace {
     float *part, *part2;
 };
 
-// the byte formula of include/ltr_hip.h (ltr_sort_workspace_bytes)
-inline size_t long_workspace_bytes(int op, int B, int L)
+// The workspace of ltr_sort_workspace_bytes (include/ltr_hip.h states the byte formula): the key ping-pong and the
+// inverse tie map, each rounded up to 256 bytes -- evaluate() and ListMLE carve theirs on behind these --, then
+// (parts) the two (B, tiles) tile sums of dcg / arp.
+inline LongWorkspace long_workspace(Carver &c, int B, int L, bool parts)
 {
-    const size_t keys = align256(16 * (size_t)B * (size_t)L);
-    const size_t inv = align256(4 * (size_t)L);
-    const size_t part = op == METRIC_RANK ? 0 : 8 * (size_t)B * (size_t)long_epi_tiles(L);
-    return keys + inv + part;
-}
-
-inline LongWorkspace long_workspace(void *ws, int B, int L)
-{
-    unsigned char *w = reinterpret_cast<unsigned char *>(ws);
+    const size_t BL = (size_t)B * (size_t)L, bt = parts ? (size_t)B * (size_t)long_epi_tiles(L) : 0;
     LongWorkspace r;
-    r.k0 = reinterpret_cast<unsigned long long *>(w);
-    r.k1 = r.k0 + (size_t)B * L;
-    r.inv = reinterpret_cast<int *>(w + align256(16 * (size_t)B * (size_t)L));
-    r.part = reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(r.inv) + align256(4 * (size_t)L));
-    r.part2 = r.part + (size_t)B * long_epi_tiles(L);
+    r.k0 = c.take<unsigned long long>(BL);
+    r.k1 = c.take<unsigned long long>(BL); c.align256();
+    r.inv = c.take<int>((size_t)L); c.align256();
+    r.part = c.take<float>(bt);
+    r.part2 = c.take<float>(bt);
     return r;
 }
 
@@ -446,8 +435,9 @@ int long_metric(int op, const float *scores, const void *rel, int rel_dtype, con
                 int use_seed, uint64_t seed, const int64_t *seed_dev, int B, int L, int k, int use_exp, int normalize,
                 void *out, void *workspace, size_t workspace_bytes, hipStream_t s)
 {
-    if (!workspace || workspace_bytes < long_workspace_bytes(op, B, L)) return LTR_ERR_WORKSPACE;
-    const LongWorkspace ws = long_workspace(workspace, B, L);
+    Carver carver(workspace);
+    const LongWorkspace ws = long_workspace(carver, B, L, op != METRIC_RANK);
+    if (!workspace || workspace_bytes < carver.off) return LTR_ERR_WORKSPACE;
     if (op == METRIC_RANK) {
         long_sort(long_key_params(scores, nullptr, LTR_LABEL_F32, n, tie, use_seed, seed, seed_dev, L, ws, s), B, ws,
                   (int64_t *)out, s);
@@ -506,7 +496,9 @@ int ltr_max_sort_list_len(void) { return kMaxSortListLen; }
 size_t ltr_sort_workspace_bytes(int op, int B, int L)
 {
     if (op < METRIC_RANK || op > METRIC_ARP || B < 0 || L <= 0 || L > kMaxSortListLen) return 0;
-    return long_workspace_bytes(op, B, L);
+    Carver sizes(nullptr);
+    long_workspace(sizes, B, L, op != METRIC_RANK);
+    return sizes.off;
 }
 
 uint32_t ltr_tie_hash_word_long(uint64_t seed, uint32_t position) { return tie_hash_word_long(seed, position); }

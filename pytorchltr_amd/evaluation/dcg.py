@@ -41,8 +41,7 @@ def _run(scores, relevance, n, k, exp, normalize):
         ws, nbytes = _C.sort_workspace(1, B, L, s.device)
         with _C.device_ctx(s):
             _C.check(_C.lib().ltr_dcg_long_f32(
-                _C.ptr(s), _C.ptr(r), _C.label_dtype(r), _C.ptr(nn), None, int(sd is not None),
-                sd[0] if sd is not None else 0, _C.ptr(sd[1]) if sd is not None else None, B, L, kk,
+                _C.ptr(s), _C.ptr(r), _C.label_dtype(r), _C.ptr(nn), *_ties.tie_args(sd), B, L, kk,
                 int(bool(exp)), int(normalize), _C.ptr(out), _C.ptr(ws), nbytes, _C.stream_of(s)))
     return out
 

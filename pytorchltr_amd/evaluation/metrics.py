@@ -107,12 +107,10 @@ def evaluate(scores: _torch.Tensor, relevance: _torch.Tensor, n: _torch.Tensor,
     if B > 0:
         lib = _C.lib()
         sd = _ties.draw_seed(L, s.device)            # one draw per call: every metric sees the same ranking
-        nbytes = int(lib.ltr_eval_workspace_bytes(B, L, spec, M))
-        ws = _torch.empty(nbytes, dtype=_torch.uint8, device=s.device) if nbytes > 0 else None
+        ws, nbytes = _C.workspace(lib.ltr_eval_workspace_bytes(B, L, spec, M), s.device)
         with _C.device_ctx(s):
             _C.check(lib.ltr_eval_f32(
-                _C.ptr(s), _C.ptr(r), _C.label_dtype(r), _C.ptr(nn), None, int(sd is not None),
-                sd[0] if sd is not None else 0, _C.ptr(sd[1]) if sd is not None else None, B, L, spec, M,
+                _C.ptr(s), _C.ptr(r), _C.label_dtype(r), _C.ptr(nn), *_ties.tie_args(sd), B, L, spec, M,
                 float(relevance_level), int(bool(exp)), float(err_max_grade), _C.ptr(out), _C.ptr(ws), nbytes,
                 _C.stream_of(s)))
     return {name: out[i] for i, name in enumerate(names)}

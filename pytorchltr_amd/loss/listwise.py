@@ -88,13 +88,12 @@ class _ListMLEFunction(_torch.autograd.Function):
         if B > 0:
             lib = _C.lib()
             sd = _ties.draw_seed(L, s.device)
-            nbytes = int(lib.ltr_listmle_workspace_bytes(B, L))       # 0: one workgroup per query, no workspace
-            ws = _torch.empty(nbytes, dtype=_torch.uint8, device=s.device) if nbytes > 0 else None
+            # (0 bytes: one workgroup per query, no workspace)
+            ws, nbytes = _C.workspace(lib.ltr_listmle_workspace_bytes(B, L), s.device)
             with _C.device_ctx(s):
                 _C.check(lib.ltr_listmle_f32(
-                    _C.ptr(s), _C.ptr(r), _C.label_dtype(r), _C.ptr(nn), int(k or 0), None, int(sd is not None),
-                    sd[0] if sd is not None else 0, _C.ptr(sd[1]) if sd is not None else None, B, L, _C.ptr(loss),
-                    _C.ptr(ds), _C.ptr(ws), nbytes, _C.stream_of(s)))
+                    _C.ptr(s), _C.ptr(r), _C.label_dtype(r), _C.ptr(nn), int(k or 0), *_ties.tie_args(sd), B, L,
+                    _C.ptr(loss), _C.ptr(ds), _C.ptr(ws), nbytes, _C.stream_of(s)))
         if need_grad:
             ctx.save_for_backward(ds)
         ctx.in_shape, ctx.in_dtype = scores.shape, scores.dtype

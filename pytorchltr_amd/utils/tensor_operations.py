@@ -56,8 +56,7 @@ def _rank(scores2d, nn, seed=None):
         ws, nbytes = _C.sort_workspace(0, B, L, scores2d.device)
         with _C.device_ctx(scores2d):
             _C.check(_C.lib().ltr_rank_by_score_long_f32(
-                _C.ptr(scores2d), _C.ptr(nn), None, int(seed is not None), seed[0] if seed is not None else 0,
-                _C.ptr(seed[1]) if seed is not None else None, B, L, _C.ptr(ranking), _C.ptr(ws), nbytes,
+                _C.ptr(scores2d), _C.ptr(nn), *_ties.tie_args(seed), B, L, _C.ptr(ranking), _C.ptr(ws), nbytes,
                 _C.stream_of(scores2d)))
     return ranking
 

@@ -224,6 +224,19 @@ def test_listmle_workspace_bytes(lib):
         lib.ltr_debug_long_sort_all(prev)
 
 
+@pytest.mark.parametrize("B", [1, 24])
+def test_listmle_workspace_bytes_grid(lib, B):
+    """The header's byte formula where the tile and chunk counts change (one tile more at 4097, 8193; several at 20000):
+    the workspace is stated once, as a carving, and its size must stay what the header says."""
+    ws = lib.ltr_listmle_workspace_bytes
+    al = lambda x: -(-x // 256) * 256                                  # noqa: E731
+    for L in (1, 256, 4095, 4096):
+        assert ws(B, L) == 0, L
+    for L in (4097, 8192, 8193, 20000):
+        tiles = -(-L // 4096)
+        assert ws(B, L) == al(16 * B * L) + al(4 * L) + 3 * al(4 * B * L) + al(16 * B * tiles) + 4 * B * tiles, L
+
+
 def test_listmle_header_matches_the_ctypes_table(lib):
     import re
     from pytorchltr_amd import _C

@@ -94,6 +94,18 @@ def test_workspace_formula(lib):
     assert lib.ltr_sort_workspace_bytes(1, 1024, 5000) < 32 * 1024 * 5000
 
 
+@pytest.mark.parametrize("B", [1, 24])
+def test_workspace_formula_grid(lib, B):
+    """The header's byte formula where the tile and chunk counts change (one tile more at 4097, 8193; several at 20000).
+    ltr_sort_workspace_bytes states it for every valid L (the callers pass no workspace up to ltr_max_list_len())."""
+    def a(x):
+        return (x + 255) // 256 * 256
+    for op in (0, 1, 2):
+        for L in (1, 4096, 4097, 8192, 8193, 20000):
+            want = a(16 * B * L) + a(4 * L) + (8 * B * ((L + 4095) // 4096) if op else 0)
+            assert lib.ltr_sort_workspace_bytes(op, B, L) == want, (op, L)
+
+
 @pytest.mark.parametrize("seed", [0, 12345, (1 << 62) - 7])
 def test_hash_words_long_is_the_library_word_and_a_permutation(lib, seed):
     from pytorchltr_amd import _ties
