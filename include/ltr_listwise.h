@@ -1,5 +1,6 @@
 /*
- * ltr_listwise.h -- C ABI of ListMLE, the Plackett-Luce listwise loss (Xia et al. 2008; top-k: Xia et al. 2009).
+ * ltr_listwise.h -- C ABI of ListMLE, the Plackett-Luce listwise loss (Xia et al. 2008; top-k: Xia et al. 2009), and
+ * of the Linear(F, 1) scorer fused with the two listwise losses, ListNet and ListMLE.
  *
  * Exported by the same libltr_hip.so as include/ltr_hip.h, with its conventions: device pointers owned by the
  * caller, work enqueued on `stream` without host synchronisation, 0 = OK, < 0 = LTR_ERR_* (ltr_hip.h),
@@ -40,6 +41,35 @@ size_t ltr_listmle_workspace_bytes(int B, int L);
 int ltr_listmle_f32(const float *scores, const void *rel, int rel_dtype, const int64_t *n, int k, const int32_t *tie,
                     int use_seed, uint64_t seed, const int64_t *seed_dev, int B, int L, float *loss, float *dscores,
                     void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * The Linear(F, 1) scorer fused with a listwise loss: scores, loss, gradient and the per-query weight-gradient rows
+ * in ONE launch, one workgroup per query.  The rows of a query are read twice, for the scores and for the
+ * weight-gradient row; the second read is meant to hit the L2 / last-level cache (not measured yet).
+ *   loss = LTR_LISTWISE_LISTNET: the listwise softmax cross-entropy of ltr_listwise_softmax_f32 (ltr_hip.h); k and
+ *     the tie arguments are ignored.  LTR_LISTWISE_LISTMLE: ltr_listmle_f32 above, same k, same tie modes -- the
+ *     same row function, so loss_out equals ltr_listmle_f32 on the scores of this call bit for bit.
+ *   s[b, j] = X[b, j, :] . W + bias[0] (bias may be NULL: 0) for j < n_b; rows j >= n_b of X and rel are never read.
+ *   X (B, L, F) fp32 with F % 4 == 0, 16-byte aligned; W (F).
+ *   loss_out (B); scores_out (B, L) or NULL: s[b, j], 0 for j >= n_b (the convention of ltr_linear_scores_f32 with n).
+ *   partials: B rows of (F + 4) & ~3 floats, 16-byte aligned: [d loss[b] / dW_0 .. dW_{F-1} | d loss[b] / d bias |
+ *     zeros] -- the per-query rows ltr_linear_reduce_f32 / _bcast_f32 / _loss_f32 / _accum_f32 (ltr_hip.h) take;
+ *     ltr_linear_workspace_bytes(B, L, F) bytes are enough.  A query with n_b = 0 gets a row of zeros and loss 0.
+ *   No atomics, every sum in a fixed order: bit-identical run to run for a fixed tie mode.  Nothing is allocated:
+ *   capturable.
+ * ltr_linear_listwise_plan: 1 where the fused kernel takes (loss, B, L, F), else 0: a bad loss, B, L or F <= 0,
+ *   L > ltr_max_list_len(), F % 4 != 0, or the query's LDS (the ranked row, W, the cross-row buffer) does not fit.
+ *   Errors, in this order: LTR_ERR_KIND for a bad loss or rel_dtype, then B < 0 / L <= 0 / F <= 0 (LTR_ERR_SHAPE),
+ *   L > ltr_max_list_len() (LTR_ERR_LIST_TOO_LONG); B == 0 is a no-op; LTR_ERR_NULL (X, W, rel, n, loss_out,
+ *   partials), LTR_ERR_CONFIG for a shape the plan declines or X / partials not 16-byte aligned, then the sticky
+ *   device status (ltr_device_status).
+ */
+enum { LTR_LISTWISE_LISTNET = 0, LTR_LISTWISE_LISTMLE = 1 };
+int ltr_linear_listwise_plan(int loss, int B, int L, int F);
+int ltr_linear_listwise_partials_f32(int loss, int k, const float *X, const float *W, const float *bias,
+                                     const void *rel, int rel_dtype, const int64_t *n, const int32_t *tie, int use_seed,
+                                     uint64_t seed, const int64_t *seed_dev, int B, int L, int F, float *loss_out,
+                                     float *scores_out, float *partials, void *stream);
 
 #ifdef __cplusplus
 }

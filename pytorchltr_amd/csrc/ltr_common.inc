@@ -1296,6 +1296,12 @@ inline unsigned grid_for(size_t items, int block)
     return (unsigned)g;
 }
 
+// Per-query partials of the fused Linear steps (ltr_linear.inc, ltr_linear_listwise.inc): row b of a (B, PF) row-major matrix, PF = partial_pitch(F) floats:
+// [d loss[b]/dW_0 .. dW_{F-1} | d loss[b]/d bias | zero padding to a multiple of 4].  A query's row is
+// ONE contiguous, 16-byte aligned run, so a workgroup stores it with a single coalesced wave-store
+// (round 1 kept it column-major in b: 137 scattered 4-byte stores per query, 5.4x write amplification).
+__host__ __device__ inline int partial_pitch(int F) { return (F + 4) & ~3; }
+
 // small vector helpers shared by the fused scorer kernels
 typedef unsigned int ltr_u32x4 __attribute__((ext_vector_type(4)));
 template <int VEC> struct VecT;

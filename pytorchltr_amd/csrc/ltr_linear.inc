@@ -27,11 +27,7 @@ constexpr int kP1Unr = 4;
 constexpr int kP3Unr = 4;
 constexpr int kLinearThreads = 512;
 
-// Per-query partials: row b of a (B, PF) row-major matrix, PF = partial_pitch(F) floats:
-// [d loss[b]/dW_0 .. dW_{F-1} | d loss[b]/d bias | zero padding to a multiple of 4].  A query's row is
-// ONE contiguous, 16-byte aligned run, so a workgroup stores it with a single coalesced wave-store
-// (round 1 kept it column-major in b: 137 scattered 4-byte stores per query, 5.4x write amplification).
-__host__ __device__ inline int partial_pitch(int F) { return (F + 4) & ~3; }
+// (the per-query partial rows: partial_pitch, ltr_common.inc)
 
 // The mailbox of a data-parallel lazy step as the device sees it (ltr_mailbox_*, further down): a small struct in this rank's
 // own device memory -- every rank's mailbox mapped into THIS address space, who I am, the granules per (parity, rank) slot.

@@ -12,7 +12,8 @@
 // core's pair scan, ltr_ranked.inc); every sum runs in a fixed order (no atomics): bit-identical run to run.
 //
 // Up to kMaxListLen documents: listmle_kernel, one workgroup per query on the ranked-row core: its launch shape, its
-// ranking (with the labels in the score slot) and its LDS layout.
+// ranking (with the labels in the score slot) and its LDS layout; the row itself is listmle_row, which the fused Linear
+// step (ltr_linear_listwise.inc) runs on scores it has just computed.
 // Longer lists (and every list under ltr_debug_long_sort_all): the long path's key sort on label keys with the call's
 // tie words (long_sort<KEY_LABELS_TIED>), then per tile of kEpiTile ranks:
 //   1. listmle_long_gather_kernel: the ranked scores x_r, and the tile's (max, sum) aggregate;
@@ -75,23 +76,16 @@ struct ListMLEParams {
     int k;                   // <= 0: every factor
 };
 
-// (the launch bounds, and so the register budgets, of the ranked-row core's kernels: same shapes, same occupancy)
+// The ListMLE row of one staged query: q.sy holds the (label, score) pairs of the first nb documents (metric_ranks ranks
+// the x slot).  Ranks by label, scans, stores the loss of the first K factors to *loss and, `grad`, leaves the gradient
+// BY RANK in q.curve, published: document j's is q.curve[q.rank_s[j]].  What listmle_kernel and linear_listwise_kernel
+// (ltr_linear_listwise.inc) share.  Contains barriers: call from uniform code, behind the barrier that publishes q.sy.
 template <int DPT>
-__global__ void __launch_bounds__(1024, (DPT <= 0 ? 8 : 4))
-listmle_kernel(ListMLEParams p)
+__device__ __forceinline__ void listmle_row(const MetricParams &m, const RankedRowLds &q, int nb, int K, float *loss, bool grad)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const MetricParams &m = p.m;
-    const int b = blockIdx.x;
-    const int L = m.L;
-    const int L4 = (L + 3) & ~3;
+    const int L4 = (m.L + 3) & ~3;
     const int tid = threadIdx.x;
     const int T = blockDim.x;
-    const int nb = clamp_n(m.n[b], L);
-    const int K = p.k > 0 ? min(p.k, nb) : nb;
-
-    // the core's LDS layout, with (label, score) pairs where the metrics keep (score, label): metric_ranks ranks the x slot
-    const RankedRowLds q = ranked_row_lds(smem, L, DPT <= 0);
     float2 *sy = q.sy;
     int *rank_s = q.rank_s;
     float *xs = reinterpret_cast<float *>(q.rank_y);                   // ranked scores (rank_y's slot)
@@ -99,8 +93,6 @@ listmle_kernel(ListMLEParams p)
     float *red = q.red, *pair = q.scan;
     float *mx = reinterpret_cast<float *>(q.sy), *ls = mx + L4;        // (M_i, log S_i), over sy once it is read
 
-    const size_t row = (size_t)b * L;
-    for (int j = tid; j < nb; j += T) sy[j] = make_float2(load_label(m.rel, m.rel_dtype, row + j), p.scores[row + j]);
     for (int j = tid; j < L4; j += T) rank_s[j] = 0;
     __syncthreads();
     metric_ranks<DPT>(m, q, nb, false);
@@ -124,8 +116,8 @@ listmle_kernel(ListMLEParams p)
     float acc = 0.f;
     for (int i = tid; i < K; i += T) acc += (mx[i] - xs[i]) + ls[i];
     acc = block_sum(acc, red);
-    if (tid == 0) p.loss[b] = acc;
-    if (!p.dscores) return;
+    if (tid == 0) *loss = acc;
+    if (!grad) return;
 
     // 2. gradient scan: thread t owns ranks [t ch, (t + 1) ch), walked upwards
     float ca = 1.f, cb = 0.f, ta, tb;
@@ -139,7 +131,29 @@ listmle_kernel(ListMLEParams p)
         curve[i] = lse_prob(xs[i], mx[i], ls[i]) * d - bi;
     }
     __syncthreads();
-    for (int j = tid; j < L; j += T) p.dscores[row + j] = j < nb ? curve[rank_s[j]] : 0.f;
+}
+
+// (the launch bounds, and so the register budgets, of the ranked-row core's kernels: same shapes, same occupancy)
+template <int DPT>
+__global__ void __launch_bounds__(1024, (DPT <= 0 ? 8 : 4))
+listmle_kernel(ListMLEParams p)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const MetricParams &m = p.m;
+    const int b = blockIdx.x;
+    const int L = m.L;
+    const int tid = threadIdx.x;
+    const int T = blockDim.x;
+    const int nb = clamp_n(m.n[b], L);
+    const int K = p.k > 0 ? min(p.k, nb) : nb;
+
+    // the core's LDS layout, with (label, score) pairs where the metrics keep (score, label): metric_ranks ranks the x slot
+    const RankedRowLds q = ranked_row_lds(smem, L, DPT <= 0);
+    const size_t row = (size_t)b * L;
+    for (int j = tid; j < nb; j += T) q.sy[j] = make_float2(load_label(m.rel, m.rel_dtype, row + j), p.scores[row + j]);
+    listmle_row<DPT>(m, q, nb, K, p.loss + b, p.dscores != nullptr);
+    if (!p.dscores) return;
+    for (int j = tid; j < L; j += T) p.dscores[row + j] = j < nb ? q.curve[q.rank_s[j]] : 0.f;
 }
 
 // ---- the sort path ----

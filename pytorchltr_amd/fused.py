@@ -7,6 +7,7 @@ parameters (``weight`` (1, F), ``bias`` (1,), state_dict-compatible with ``nn.Li
 same per-query output -- computed by ``ltr_linear_partials_f32`` so the (B, L, F) feature
 tensor crosses HBM once instead of twice plus the score round trip.
 """
+import collections
 import ctypes
 import math
 
@@ -22,14 +23,40 @@ _KIND_BY_NAME = {
 }
 
 
+class _ListwiseKind(collections.namedtuple("_ListwiseKind", "loss k", defaults=(None,))):
+    """A listwise loss where the pairwise ones are an ``enum ltr_loss_kind`` value: the loss code of
+    ``include/ltr_listwise.h`` (ListNet, ListMLE) and ListMLE's ``k``."""
+    __slots__ = ()
+
+
+_LISTWISE_BY_NAME = {"softmax": _C.LISTWISE_LISTNET, "listnet": _C.LISTWISE_LISTNET, "listmle": _C.LISTWISE_LISTMLE}
+
+
 def _resolve_loss(loss):
-    """Accepts a kind name or an instance of a pytorchltr_amd loss module."""
+    """Accepts a kind name or an instance of a pytorchltr_amd loss module: (kind, sigma); a listwise loss ("softmax" /
+    "listnet" / "listmle", ListwiseSoftmaxLoss, ListMLELoss(k)) resolves to a :class:`_ListwiseKind`."""
     if isinstance(loss, str):
+        if loss in _LISTWISE_BY_NAME:
+            return _ListwiseKind(_LISTWISE_BY_NAME[loss]), 1.0
         return _KIND_BY_NAME[loss], 1.0
+    from .loss import listwise as _lw
+    if isinstance(loss, _lw.ListMLELoss):
+        return _ListwiseKind(_C.LISTWISE_LISTMLE, loss.k), 1.0
+    if isinstance(loss, _lw.ListwiseSoftmaxLoss):
+        return _ListwiseKind(_C.LISTWISE_LISTNET), 1.0
     kind = getattr(loss, "_kind", None)
     if kind is None:
         raise TypeError("loss must be a kind name or a pytorchltr_amd.loss module")
     return kind, float(getattr(loss, "sigma", 1.0))
+
+
+def _resolve_pairwise_loss(loss):
+    """_resolve_loss for the entry points that have kernels for the seven pairwise kinds only."""
+    kind, sigma = _resolve_loss(loss)
+    if isinstance(kind, _ListwiseKind):
+        raise TypeError("this entry point takes the pairwise losses only (the listwise ones: FusedLinearLoss, "
+                        "linear_loss_step, LinearScorer)")
+    return kind, sigma
 
 
 def _padded_rows(xs):
@@ -198,21 +225,123 @@ class _LinearLossFunction(torch.autograd.Function):
                     _LABEL_CODE[r.dtype], nn.data_ptr(), B, L, F, scratch.data_ptr(), None, ws.data_ptr(), _C.stream_of(X)))
         else:
             (ws,) = ctx.saved_tensors
-        B, F = ctx.dims
-        go = grad_loss
-        dW = torch.empty(F, dtype=torch.float32, device=ws.device)
-        db = torch.empty(1, dtype=torch.float32, device=ws.device)
-        # `.mean().backward()` / `.sum().backward()`: autograd hands over an expanded scalar (stride 0) -- the reduction
-        # reads it where it is instead of a (B,) copy being made first
-        bcast = go.dtype is torch.float32 and go.dim() == 1 and go.stride(0) == 0
-        if not bcast and (go.dtype is not torch.float32 or go.dim() != 1 or not go.is_contiguous()):
-            go = go.reshape(B).float().contiguous()
-        with _C.device_ctx(ws):
-            entry = _C.lib().ltr_linear_reduce_bcast_f32 if bcast else _C.lib().ltr_linear_reduce_f32
-            rc = entry(ws.data_ptr(), go.data_ptr(), B, F, dW.data_ptr(), db.data_ptr(), _C.stream_of(ws))
-            if rc != 0:
-                _C.check(rc)
-        return (None, dW[:ctx.Fw].reshape(ctx.w_shape), db if ctx.has_bias else None, None, None, None, None, None)
+        dW, db = _reduce_rows(ctx, ws, grad_loss)
+        return (None, dW, db, None, None, None, None, None)
+
+
+def _reduce_rows(ctx, ws, grad_loss):
+    """The backward pass of a fused Linear step: (weight.grad, bias.grad) = the per-query rows `ws` of the forward pass
+    summed with the upstream gradient as weights (ctx: dims, Fw, w_shape, has_bias)."""
+    B, F = ctx.dims
+    go = grad_loss
+    dW = torch.empty(F, dtype=torch.float32, device=ws.device)
+    db = torch.empty(1, dtype=torch.float32, device=ws.device)
+    # `.mean().backward()` / `.sum().backward()`: autograd hands over an expanded scalar (stride 0) -- the reduction
+    # reads it where it is instead of a (B,) copy being made first
+    bcast = go.dtype is torch.float32 and go.dim() == 1 and go.stride(0) == 0
+    if not bcast and (go.dtype is not torch.float32 or go.dim() != 1 or not go.is_contiguous()):
+        go = go.reshape(B).float().contiguous()
+    with _C.device_ctx(ws):
+        entry = _C.lib().ltr_linear_reduce_bcast_f32 if bcast else _C.lib().ltr_linear_reduce_f32
+        rc = entry(ws.data_ptr(), go.data_ptr(), B, F, dW.data_ptr(), db.data_ptr(), _C.stream_of(ws))
+        if rc != 0:
+            _C.check(rc)
+    return dW[:ctx.Fw].reshape(ctx.w_shape), (db if ctx.has_bias else None)
+
+
+# ---------------------------------------------------------------------------------------------
+# The listwise losses (ListNet, ListMLE): ltr_linear_listwise_partials_f32, include/ltr_listwise.h
+# ---------------------------------------------------------------------------------------------
+_listwise_plan_cache = {}
+
+
+def _listwise_fused(kind, X):
+    """True where the one-launch listwise step takes the prepared feature batch X (ltr_linear_listwise_plan: lists of
+    at most max_list_len() documents, rows of whole float4 that fit the LDS next to the ranked row), else the three
+    kernels -- scorer, listwise loss, weight gradient -- compute the same.  (The plan depends on the device: its launch
+    shapes follow the CU count.)"""
+    B, L, F = X.shape
+    key = (kind.loss, X.device.index, B, L, F)
+    v = _listwise_plan_cache.get(key)
+    if v is None:
+        if len(_listwise_plan_cache) > 1024:
+            _listwise_plan_cache.clear()
+        with _C.device_ctx(X):
+            v = _listwise_plan_cache[key] = bool(_C.lib().ltr_linear_listwise_plan(kind.loss, B, L, F))
+    return v and X.data_ptr() % 16 == 0
+
+
+def _listwise_launch(kind, X, W, bvec, r, nn, loss, scores, ws):
+    """One ltr_linear_listwise_partials_f32 call; ListMLE draws its tie seed here, one per forward pass."""
+    from . import _ties
+    B, L, F = X.shape
+    sd = _ties.draw_seed(L, X.device) if kind.loss == _C.LISTWISE_LISTMLE else None
+    with _C.device_ctx(X):
+        _C.check(_C.lib().ltr_linear_listwise_partials_f32(
+            kind.loss, int(kind.k or 0), _C.ptr(X), _C.ptr(W), _C.ptr(bvec), _C.ptr(r), _LABEL_CODE[r.dtype], _C.ptr(nn),
+            *_ties.tie_args(sd), B, L, F, _C.ptr(loss), _C.ptr(scores), _C.ptr(ws), _C.stream_of(X)))
+
+
+def _listwise_pieces(scores, relevance, n, kind):
+    """The stand-alone listwise loss on computed scores (autograd-connected to them)."""
+    from .loss import listwise as _lw
+    if kind.loss == _C.LISTWISE_LISTMLE:
+        return _lw._ListMLEFunction.apply(scores, relevance, n, kind.k)
+    return _lw._ListwiseSoftmaxFunction.apply(scores, relevance, n)
+
+
+class _LinearListwiseFunction(torch.autograd.Function):
+    """loss[b] of a listwise kind on Linear(F, 1)(X) as ONE launch; backward is the cross-query reduction of
+    _LinearLossFunction.  X: a prepared batch that _listwise_fused takes."""
+
+    @staticmethod
+    def forward(ctx, X, weight, bias, relevance, n, kind, want_scores):
+        B, L, F = X.shape                           # (F: the row width in memory, >= the logical feature count)
+        Fw = weight.numel()
+        if not F - 4 < Fw <= F:
+            raise ValueError("weight has %d elements, the feature rows %d" % (Fw, F))
+        dev = X.device
+        r, nn = _labels_and_n(relevance, n, B, L, dev)
+        # parameters that pytorchltr_amd.optim.SGD updates lazily: there is no lazy one-launch step for the listwise
+        # losses; this launch reads the weights, so no update may be pending
+        st = getattr(weight, "_ltr_lazy", None)
+        if st is not None:
+            st.settle()
+        W = _pad_weight(_flat_f32(weight, Fw), F)
+        bvec = None if bias is None else _flat_f32(bias, 1)
+        loss = torch.empty(B, dtype=torch.float32, device=dev)
+        ws = torch.empty(_linear_ws_bytes(B, L, F) // 4, dtype=torch.float32, device=dev)
+        scores = torch.empty((B, L), dtype=torch.float32, device=dev) if want_scores else None
+        _listwise_launch(kind, X, W, bvec, r, nn, loss, scores, ws)
+        ctx.save_for_backward(ws)
+        ctx.dims = (B, F)
+        ctx.Fw = Fw
+        ctx.w_shape = weight.shape
+        ctx.has_bias = bias is not None
+        if want_scores:
+            ctx.mark_non_differentiable(scores)
+            return loss, scores
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss, *unused):
+        (ws,) = ctx.saved_tensors
+        dW, db = _reduce_rows(ctx, ws, grad_loss)
+        return (None, dW, db, None, None, None, None)
+
+
+def _listwise_linear_loss(xs, weight, bias, relevance, n, kind, want_scores):
+    """``loss_fn(Linear(F, 1)(xs), relevance, n)`` of a listwise loss: the fused launch where it applies, else the
+    three kernels with autograd between them."""
+    if weight.numel() != xs.shape[-1]:
+        raise ValueError("weight has %d elements, features have %d" % (weight.numel(), xs.shape[-1]))
+    X = _prepare_features(xs)
+    if _listwise_fused(kind, X):
+        return _LinearListwiseFunction.apply(X, weight, bias, relevance, n, kind, want_scores)
+    scores = _LinearScoreFunction.apply(xs, weight, bias, n)
+    loss = _listwise_pieces(scores, relevance, n, kind)
+    return (loss, scores.detach().squeeze(-1)) if want_scores else loss
 
 
 _pieces_cache = {}
@@ -256,6 +385,8 @@ class FusedLinearLoss(torch.nn.Module):
             torch.nn.init.uniform_(self.bias, -bound, bound)
 
     def forward(self, xs, relevance, n, return_scores=False):
+        if isinstance(self.kind, _ListwiseKind):
+            return _listwise_linear_loss(xs, self.weight, self.bias, relevance, n, self.kind, bool(return_scores))
         if xs.dim() == 3 and xs.is_cuda and self._pieces_cached(xs.shape[0], xs.shape[1]):
             # a few long lists: one workgroup per query cannot fill the GPU; the balanced pieces
             # (streaming scorer, split-query loss, streaming weight gradient) are faster
@@ -289,6 +420,9 @@ def linear_loss_step(xs, weight, bias, relevance, n, loss="hinge", grad_out=None
     scorer+loss kernel and the cross-query reduction (which also totals the loss)."""
     kind, sigma = _resolve_loss(loss)
     X = _prepare_features(xs)
+    listwise = isinstance(kind, _ListwiseKind)
+    if listwise and not _listwise_fused(kind, X):
+        return _listwise_step_pieces(xs, weight, bias, relevance, n, kind, grad_out, return_scores, return_loss_sum)
     B, L, F = X.shape                               # (F: the row width in memory -- a padded view's F4)
     Fw = xs.shape[2]
     W = _pad_weight(_flat_f32(weight, Fw), F)
@@ -304,9 +438,12 @@ def linear_loss_step(xs, weight, bias, relevance, n, loss="hinge", grad_out=None
     go = None if grad_out is None else grad_out.reshape(B).float().contiguous()
     with _C.device_ctx(X):
         st = _C.stream_of(X)
-        _C.check(_C.lib().ltr_linear_partials_f32(
-            kind, float(sigma), _C.ptr(X), _C.ptr(W), _C.ptr(bvec), _C.ptr(r), _C.label_dtype(r),
-            _C.ptr(nn), B, L, F, _C.ptr(lossv), _C.ptr(scores), _C.ptr(ws), st))
+        if listwise:
+            _listwise_launch(kind, X, W, bvec, r, nn, lossv, scores, ws)
+        else:
+            _C.check(_C.lib().ltr_linear_partials_f32(
+                kind, float(sigma), _C.ptr(X), _C.ptr(W), _C.ptr(bvec), _C.ptr(r), _C.label_dtype(r),
+                _C.ptr(nn), B, L, F, _C.ptr(lossv), _C.ptr(scores), _C.ptr(ws), st))
         _C.check(_C.lib().ltr_linear_reduce_loss_f32(
             _C.ptr(ws), _C.ptr(go), _C.ptr(lossv), B, F, _C.ptr(dW), _C.ptr(db), _C.ptr(lsum), st))
     out = (lossv, dW[:Fw], db)
@@ -314,6 +451,28 @@ def linear_loss_step(xs, weight, bias, relevance, n, loss="hinge", grad_out=None
         out = out + (scores,)
     if return_loss_sum:
         out = out + (lsum,)
+    return out
+
+
+def _listwise_step_pieces(xs, weight, bias, relevance, n, kind, grad_out, return_scores, return_loss_sum):
+    """linear_loss_step of a listwise loss on a shape the fused launch does not take: the scorer, the stand-alone loss
+    and the weight-gradient kernel, chained by autograd on detached copies of the parameters."""
+    B = xs.shape[0]
+    with torch.enable_grad():
+        w = weight.detach().float().reshape(1, -1).requires_grad_(True)
+        b = (torch.zeros(1, dtype=torch.float32, device=xs.device) if bias is None
+             else bias.detach().float().reshape(1)).requires_grad_(True)
+        scores = _LinearScoreFunction.apply(xs, w, b, n)
+        lossv = _listwise_pieces(scores, relevance, n, kind)
+        go = (torch.full((B,), 1.0 / max(B, 1), dtype=torch.float32, device=xs.device) if grad_out is None
+              else grad_out.reshape(B).float())
+        (lossv * go).sum().backward()
+    lossv = lossv.detach()
+    out = (lossv, w.grad.reshape(-1), b.grad)
+    if return_scores:
+        out = out + (scores.detach().squeeze(-1),)
+    if return_loss_sum:
+        out = out + (lossv.sum().reshape(1),)
     return out
 
 
@@ -339,7 +498,7 @@ class LazySGD:
     the update is the gradient of the mean over the GLOBAL batch (`mailbox.global_count` queries)."""
 
     def __init__(self, weight, bias, lr, loss="hinge", mailbox=None):
-        self.kind, self.sigma = _resolve_loss(loss)
+        self.kind, self.sigma = _resolve_pairwise_loss(loss)
         if weight.dtype is not torch.float32 or not weight.is_contiguous() or not weight.is_cuda:
             raise ValueError("weight must be a contiguous fp32 device tensor (it is updated in place)")
         if bias is None or bias.dtype is not torch.float32 or bias.numel() != 1 or not bias.is_cuda:
@@ -478,10 +637,19 @@ class LazyScores(torch.Tensor):
                                "scores; use the scores (or call .materialize()) before the optimizer step")
 
     def fused_loss(self, relevance, n, kind, sigma):
-        """loss[b] of the pairwise loss `kind` on these scores, or None when the scores have to be computed anyway."""
-        if self._real is not None or kind == _LISTWISE_SOFTMAX:
+        """loss[b] of the loss `kind` (a pairwise kind or a _ListwiseKind) on these scores, or None when the scores have
+        to be computed anyway."""
+        if self._real is not None:
             return None
         xs = self._xs
+        if isinstance(kind, _ListwiseKind):
+            X = _prepare_features(xs)
+            if not _listwise_fused(kind, X):
+                return None
+            self._check_versions()
+            return _LinearListwiseFunction.apply(X, self._weight, self._bias, relevance, n, kind, False)
+        if kind == _LISTWISE_SOFTMAX:
+            return None
         B, L, F = xs.shape
         if _prefer_pieces(kind, B, L, (F + 3) & ~3 if not xs.is_contiguous() else F):
             return None
@@ -521,7 +689,7 @@ class LazyScores(torch.Tensor):
         return func(*[real(a) for a in args], **{k: real(v) for k, v in (kwargs or {}).items()})
 
 
-_LISTWISE_SOFTMAX = 100                  # (_autograd.LISTWISE_SOFTMAX: not a pairwise kind, no fused kernel)
+_LISTWISE_SOFTMAX = 100                  # (_autograd.LISTWISE_SOFTMAX as a plain kind: the stand-alone kernel on real scores)
 _REQUIRES_GRAD_GET = torch.Tensor.requires_grad.__get__
 _LAZY_METADATA = {
     torch.Tensor.shape.__get__, torch.Tensor.dtype.__get__, torch.Tensor.device.__get__, torch.Tensor.is_cuda.__get__,
@@ -699,7 +867,7 @@ def mlp_loss_step(xs, params, relevance, n, loss="hinge", grad_out=None, return_
         buffer (available as ``grads[0].base`` / the ``out`` argument), then optionally the scores
         (valid for documents < n only) and ``loss_sum`` (1,).
     """
-    kind, sigma = _resolve_loss(loss)
+    kind, sigma = _resolve_pairwise_loss(loss)
     X = _prepare_features(xs)
     B, L, F = X.shape
     flat_params, H1, H2 = _flat_params(params, F)
@@ -821,7 +989,7 @@ class FusedMLPLoss(torch.nn.Module):
             raise ValueError("reduction must be 'mean' or 'sum'")
         self.in_features = in_features
         self.reduction = reduction
-        self.kind, self.sigma = _resolve_loss(loss)
+        self.kind, self.sigma = _resolve_pairwise_loss(loss)
         self.l1 = torch.nn.Linear(in_features, hidden[0])
         self.l2 = torch.nn.Linear(hidden[0], hidden[1])
         self.l3 = torch.nn.Linear(hidden[1], 1)

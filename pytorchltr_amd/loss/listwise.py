@@ -16,6 +16,19 @@ from pytorchltr_amd import _ties
 from pytorchltr_amd._prepare import prepare as _prepare
 
 
+def _fused_step(scores, relevance, n, loss, k):
+    """Scores a LinearScorer has not computed yet (fused.LazyScores) are asked for the fused Linear step first --
+    scorer, loss and weight-gradient rows in one launch, no score matrix written: (loss[b], None).  Where that step does
+    not apply (ltr_linear_listwise_plan declines the shape, the scores were computed already) they are computed here,
+    autograd-connected to the layer: (None, scores), as for any other scores."""
+    fused = getattr(scores, "fused_loss", None)
+    if fused is None:
+        return None, scores
+    from pytorchltr_amd.fused import _ListwiseKind
+    out = fused(relevance, n, _ListwiseKind(loss, k), 1.0)
+    return (None, scores.materialize()) if out is None else (out, None)
+
+
 class _ListwiseSoftmaxFunction(_torch.autograd.Function):
     """Its own small Function: the pairwise plumbing does not apply -- the kernel has no
     LDS-bound list limit (one wave walks the list), and it computes in fp32 whatever the score dtype
@@ -66,7 +79,8 @@ class ListwiseSoftmaxLoss(_torch.nn.Module):
 
     def forward(self, scores: _torch.FloatTensor, relevance: _torch.LongTensor,
                 n: _torch.LongTensor) -> _torch.FloatTensor:
-        return _ListwiseSoftmaxFunction.apply(scores, relevance, n)
+        out, scores = _fused_step(scores, relevance, n, _C.LISTWISE_LISTNET, None)
+        return out if out is not None else _ListwiseSoftmaxFunction.apply(scores, relevance, n)
 
 
 ListNetLoss = ListwiseSoftmaxLoss
@@ -138,12 +152,8 @@ class ListMLELoss(_torch.nn.Module):
 
     def forward(self, scores: _torch.FloatTensor, relevance: _torch.LongTensor,
                 n: _torch.LongTensor) -> _torch.FloatTensor:
-        # there is no fused scorer kernel for this loss: scores a LinearScorer has not computed yet are computed here,
-        # autograd-connected to the layer (fused.LazyScores)
-        materialize = getattr(scores, "materialize", None)
-        if materialize is not None:
-            scores = materialize()
-        return _ListMLEFunction.apply(scores, relevance, n, self.k)
+        out, scores = _fused_step(scores, relevance, n, _C.LISTWISE_LISTMLE, self.k)
+        return out if out is not None else _ListMLEFunction.apply(scores, relevance, n, self.k)
 
     def extra_repr(self):
         return "" if self.k is None else "k=%d" % self.k
