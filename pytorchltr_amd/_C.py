@@ -1,5 +1,5 @@
-"""ctypes binding of the C ABI in ``include/ltr_hip.h``, ``include/ltr_eval.h`` and ``include/ltr_listwise.h``
-(pytorchltr_amd/csrc/libltr_hip.so).
+"""ctypes binding of the C ABI in ``include/ltr_hip.h``, ``include/ltr_eval.h``, ``include/ltr_listwise.h`` and
+``include/ltr_longpair.h`` (pytorchltr_amd/csrc/libltr_hip.so).
 
 PyTorch supplies device memory and the current HIP stream; every call here hands raw device
 pointers to the library.  The library must exist -- there is deliberately no fallback.
@@ -133,6 +133,15 @@ LISTWISE_SIGNATURES = {
                                               _vp, _vp, _vp, _vp]),
 }
 
+# name -> (restype, argtypes); mirrors include/ltr_longpair.h (the pairwise losses past max_list_len() documents)
+LONGPAIR_SIGNATURES = {
+    "ltr_max_pair_list_len": (_i, []),
+    "ltr_long_pair_geometry": (None, [_vp, _vp]),
+    "ltr_pairwise_loss_long_workspace_bytes": (_sz, [_i, _i, _i]),
+    "ltr_pairwise_loss_long_f32": (_i, [_i, _f, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "ltr_debug_long_pairs_all": (_i, [_i]),
+}
+
 _lib = None
 
 
@@ -165,7 +174,8 @@ def lib():
                 "`python -m pytorchltr_amd.build` (hipcc --offload-arch=gfx950). "
                 "There is no CPU fallback." % LIB_PATH)
         handle = _Library(LIB_PATH)
-        for name, (restype, argtypes) in list(SIGNATURES.items()) + list(EVAL_SIGNATURES.items()) + list(LISTWISE_SIGNATURES.items()):
+        for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(EVAL_SIGNATURES.items())
+                                          + list(LISTWISE_SIGNATURES.items()) + list(LONGPAIR_SIGNATURES.items())):
             if name.startswith("ltr_debug_") and not hasattr(handle, name):
                 continue                     # a production build (-DLTR_NO_DEBUG_HOOKS) leaves the test hooks out
             fn = getattr(handle, name)       # AttributeError if the symbol is missing
@@ -226,6 +236,24 @@ def max_list_len():
     if _max_len is None:
         _max_len = int(lib().ltr_max_list_len())
     return _max_len
+
+
+_max_pair_len = None
+
+
+def max_pair_list_len():
+    """Longest list the pairwise losses take with ``long_lists=True`` (ltr_max_pair_list_len)."""
+    global _max_pair_len
+    if _max_pair_len is None:
+        _max_pair_len = int(lib().ltr_max_pair_list_len())
+    return _max_pair_len
+
+
+def long_pair_geometry():
+    """(owner_docs, chunk_docs) of the long pairwise path: documents per workgroup, documents per LDS chunk."""
+    own, ch = ctypes.c_int(0), ctypes.c_int(0)
+    lib().ltr_long_pair_geometry(ctypes.byref(own), ctypes.byref(ch))
+    return own.value, ch.value
 
 
 _max_sort_len = None

@@ -14,6 +14,7 @@ from ._prepare import prepare
 
 _LABEL_CODE = {torch.int64: _C.LABEL_I64, torch.float32: _C.LABEL_F32, torch.int32: _C.LABEL_I32}
 _ws_cache = {}          # (kind, B, L) -> workspace bytes of ltr_pairwise_loss_ws_f32 (0 = plain path)
+_long_ws_cache = {}     # (kind, B, L) -> workspace bytes of ltr_pairwise_loss_long_f32
 LISTWISE_SOFTMAX = 100  # pseudo-kind of this module: ltr_listwise_softmax_f32 (not a pairwise loss)
 
 
@@ -50,23 +51,56 @@ def _workspace_bytes(kind, B, L):
     return ws
 
 
+class LongKind(int):
+    """A pairwise ``enum ltr_loss_kind`` value whose owner opted into lists past ``max_list_len()`` documents
+    (``long_lists=True``): an int wherever a kind is expected, and the flag travels with it (fused._resolve_loss,
+    LazyScores.fused_loss)."""
+    long_lists = True
+
+
+def _long_workspace_bytes(kind, B, L):
+    key = (kind, B, L)
+    ws = _long_ws_cache.get(key)
+    if ws is None:
+        ws = _long_ws_cache[key] = int(_C.lib().ltr_pairwise_loss_long_workspace_bytes(kind, B, L))
+    return ws
+
+
+def _check_list_len(L, long_lists):
+    """The pairwise losses' bound on the list length: max_list_len(), or max_pair_list_len() for a caller that opted in."""
+    if L <= _C.max_list_len():
+        return
+    if not long_lists:
+        raise ValueError("list_size %d exceeds the supported maximum %d of the pairwise losses; long_lists=True takes "
+                         "lists of up to %d documents (quadratic work: list_size^2 pair evaluations per query)"
+                         % (L, _C.max_list_len(), _C.max_pair_list_len()))
+    if L > _C.max_pair_list_len():
+        raise ValueError("list_size %d exceeds max_pair_list_len() = %d, the bound of the pairwise losses with "
+                         "long_lists=True (ListMLELoss and ListwiseSoftmaxLoss take longer lists)"
+                         % (L, _C.max_pair_list_len()))
+
+
 class PairwiseLossFunction(torch.autograd.Function):
-    """loss[b] = L_kind(scores[b,:], relevance[b,:], n[b]); gradient only w.r.t. scores."""
+    """loss[b] = L_kind(scores[b,:], relevance[b,:], n[b]); gradient only w.r.t. scores.  `long_lists`: fp32 scores on
+    lists past max_list_len() documents take ltr_pairwise_loss_long_f32 (include/ltr_longpair.h)."""
 
     @staticmethod
-    def forward(ctx, scores, relevance, n, kind, sigma):
+    def forward(ctx, scores, relevance, n, kind, sigma, long_lists):
+        long_lists = bool(long_lists) and kind != LISTWISE_SOFTMAX
         fast = _fast_args(scores, relevance, n)
         if fast is not None:
             s, r, nn = scores, relevance, n
             B, L = fast
         else:
-            s, r, nn = prepare(scores, relevance, n, allow_f64=True)
+            s, r, nn = prepare(scores, relevance, n, allow_f64=True, limit_len=False)
             B, L = s.shape
+            if s.dtype is not torch.float64:
+                _check_list_len(L, long_lists)
         need_grad = ctx.needs_input_grad[0]
         f64 = s.dtype is torch.float64          # fp64 in -> fp64 arithmetic, like the reference
         if f64 and L > _C.max_list_len_f64():
-            raise ValueError("list_size %d exceeds the fp64 maximum %d (fp32 scores: %d)"
-                             % (L, _C.max_list_len_f64(), _C.max_list_len()))
+            raise ValueError("list_size %d exceeds the fp64 maximum %d (fp32 scores: %d; long_lists=True applies to "
+                             "fp32 scores only)" % (L, _C.max_list_len_f64(), _C.max_list_len()))
         dev = s.device
         loss = torch.empty(B, dtype=s.dtype, device=dev)
         ds = torch.empty((B, L), dtype=s.dtype, device=dev) if need_grad else None
@@ -84,6 +118,13 @@ class PairwiseLossFunction(torch.autograd.Function):
                     rc = lib.ltr_pairwise_loss_f64(kind, float(sigma), s.data_ptr(), r.data_ptr(),
                                                    _LABEL_CODE[r.dtype], nn.data_ptr(), B, L,
                                                    loss.data_ptr(), dsp, st)
+                elif L > _C.max_list_len():
+                    # past one workgroup's LDS (long_lists=True): owner tiles against the streamed query
+                    ws_bytes = _long_workspace_bytes(kind, B, L)
+                    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+                    rc = lib.ltr_pairwise_loss_long_f32(
+                        kind, float(sigma), s.data_ptr(), r.data_ptr(), _LABEL_CODE[r.dtype],
+                        nn.data_ptr(), B, L, loss.data_ptr(), dsp, ws.data_ptr(), ws_bytes, st)
                 else:
                     # long lists on a small batch: several workgroups share a query (needs scratch)
                     ws_bytes = _workspace_bytes(kind, B, L)
@@ -132,26 +173,35 @@ class PairwiseLossFunction(torch.autograd.Function):
             out = out.reshape(ctx.in_shape)
         if ctx.in_dtype is not out.dtype:
             out = out.to(ctx.in_dtype)
-        return out, None, None, None, None
+        return out, None, None, None, None, None
 
 
-def pairwise_loss(scores, relevance, n, kind, sigma=1.0):
+def pairwise_loss(scores, relevance, n, kind, sigma=1.0, long_lists=False):
     # scores that have not been computed yet (fused.LazyScores, what LinearScorer returns in a training step): scores,
     # loss and weight-gradient rows in ONE pass over the features instead of scorer kernel + loss kernel + gradient kernel
     fused = getattr(scores, "fused_loss", None)
     if fused is not None:
-        out = fused(relevance, n, kind, sigma)
+        out = fused(relevance, n, LongKind(kind) if long_lists else kind, sigma)
         if out is not None:
             return out
         scores = scores.materialize()
-    return PairwiseLossFunction.apply(scores, relevance, n, kind, sigma)
+    return PairwiseLossFunction.apply(scores, relevance, n, int(kind), sigma, bool(long_lists))
 
 
-def pairwise_loss_and_grad(scores, relevance, n, kind, sigma=1.0, cfg=None):
+def pairwise_loss_and_grad(scores, relevance, n, kind, sigma=1.0, cfg=None, long_lists=False):
     """Direct (no autograd) call: returns (loss[B], dscores[B,L]).  `cfg` = (owners, dpt,
     msplit) forces a launch shape (tests / tuning); cfg = "split" takes the workspace entry point
-    (several workgroups per query when the library decides that pays)."""
-    s, r, nn = prepare(scores, relevance, n)
+    (several workgroups per query when the library decides that pays).  `long_lists` takes
+    ltr_pairwise_loss_long_f32 (lists of up to max_pair_list_len() documents; not together with `cfg`)."""
+    if long_lists:
+        if cfg is not None:
+            raise ValueError("`cfg` forces a launch shape of the one-workgroup kernels; it does not go with long_lists=True")
+        if kind == LISTWISE_SOFTMAX:
+            raise ValueError("long_lists applies to the pairwise losses")
+        s, r, nn = prepare(scores, relevance, n, limit_len=False)
+        _check_list_len(s.shape[1], True)
+    else:
+        s, r, nn = prepare(scores, relevance, n)
     B, L = s.shape
     loss = torch.empty(B, dtype=torch.float32, device=s.device)
     ds = torch.empty(B, L, dtype=torch.float32, device=s.device)
@@ -161,6 +211,11 @@ def pairwise_loss_and_grad(scores, relevance, n, kind, sigma=1.0, cfg=None):
                 rc = _C.lib().ltr_listwise_softmax_f32(
                     _C.ptr(s), _C.ptr(r), _C.label_dtype(r), _C.ptr(nn), B, L, _C.ptr(loss),
                     _C.ptr(ds), _C.stream_of(s))
+            elif long_lists:
+                ws, ws_bytes = _C.workspace(_C.lib().ltr_pairwise_loss_long_workspace_bytes(kind, B, L), s.device)
+                rc = _C.lib().ltr_pairwise_loss_long_f32(
+                    kind, float(sigma), _C.ptr(s), _C.ptr(r), _C.label_dtype(r), _C.ptr(nn),
+                    B, L, _C.ptr(loss), _C.ptr(ds), _C.ptr(ws), ws_bytes, _C.stream_of(s))
             elif cfg == "split":
                 ws_bytes = _C.lib().ltr_pairwise_loss_workspace_bytes(kind, B, L)
                 ws = torch.empty(max(ws_bytes, 4) // 4, dtype=torch.float32, device=s.device)

@@ -1246,6 +1246,7 @@ int ltr_collate_pad_csr_f32(const int64_t *indptr, const int32_t *indices, const
 
 #include "ltr_f64.inc"
 #include "ltr_longsort.inc"
+#include "ltr_longpair.inc"
 #include "ltr_eval.inc"
 #include "ltr_listmle.inc"
 #include "ltr_linear_listwise.inc"

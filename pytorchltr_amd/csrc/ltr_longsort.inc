@@ -259,7 +259,7 @@ struct LongMetricParams {
     LongKeyParams k;                     // the keys `sorted` holds
     const unsigned long long *sorted;    // (B, L)
     int ideal;                           // label keys: the gain comes from the key itself
-    int lim;                             // dcg: positions [0, lim) count
+    int lim;                             // dcg: positions [0, lim) count; < 0: the real documents, [0, n[b])
     int use_exp, normalize;
     int tiles;                           // tiles per query in this launch
     int ptiles;                          // row stride of the partials: ceil(L / kEpiTile)
@@ -291,7 +291,7 @@ __global__ void __launch_bounds__(kEpiThreads) longsort_partial_kernel(LongMetri
     __shared__ float red[32];
     const EpiTile t = epi_tile(p.k, p.tiles);
     const int tid = threadIdx.x;
-    const int lim = OP == METRIC_ARP ? t.nb : min(p.lim, p.k.L);
+    const int lim = (OP == METRIC_ARP || p.lim < 0) ? t.nb : min(p.lim, p.k.L);
     float a = 0.f, c = 0.f;
     for (int x = tid; x < kEpiTile; x += kEpiThreads) {
         const int r = t.r0 + x;

@@ -34,7 +34,8 @@ _LISTWISE_BY_NAME = {"softmax": _C.LISTWISE_LISTNET, "listnet": _C.LISTWISE_LIST
 
 def _resolve_loss(loss):
     """Accepts a kind name or an instance of a pytorchltr_amd loss module: (kind, sigma); a listwise loss ("softmax" /
-    "listnet" / "listmle", ListwiseSoftmaxLoss, ListMLELoss(k)) resolves to a :class:`_ListwiseKind`."""
+    "listnet" / "listmle", ListwiseSoftmaxLoss, ListMLELoss(k)) resolves to a :class:`_ListwiseKind`; a pairwise module
+    built with ``long_lists=True`` to a :class:`_autograd.LongKind` (the same int, and the flag with it)."""
     if isinstance(loss, str):
         if loss in _LISTWISE_BY_NAME:
             return _ListwiseKind(_LISTWISE_BY_NAME[loss]), 1.0
@@ -47,7 +48,22 @@ def _resolve_loss(loss):
     kind = getattr(loss, "_kind", None)
     if kind is None:
         raise TypeError("loss must be a kind name or a pytorchltr_amd.loss module")
+    if getattr(loss, "long_lists", False):
+        from ._autograd import LongKind
+        kind = LongKind(kind)
     return kind, float(getattr(loss, "sigma", 1.0))
+
+
+def _long_pair_shape(kind, L):
+    """True for a pairwise kind that opted into long lists (long_lists=True) on a list past max_list_len(): no fused
+    kernel holds such a query; the scorer, ltr_pairwise_loss_long_f32 and the streaming weight-gradient kernel do."""
+    return getattr(kind, "long_lists", False) and L > _C.max_list_len()
+
+
+def _pairwise_pieces(scores, relevance, n, kind, sigma):
+    """The stand-alone pairwise loss on computed scores (autograd-connected to them)."""
+    from ._autograd import PairwiseLossFunction
+    return PairwiseLossFunction.apply(scores, relevance, n, int(kind), sigma, bool(getattr(kind, "long_lists", False)))
 
 
 def _resolve_pairwise_loss(loss):
@@ -387,12 +403,13 @@ class FusedLinearLoss(torch.nn.Module):
     def forward(self, xs, relevance, n, return_scores=False):
         if isinstance(self.kind, _ListwiseKind):
             return _listwise_linear_loss(xs, self.weight, self.bias, relevance, n, self.kind, bool(return_scores))
-        if xs.dim() == 3 and xs.is_cuda and self._pieces_cached(xs.shape[0], xs.shape[1]):
+        if xs.dim() == 3 and xs.is_cuda and (_long_pair_shape(self.kind, xs.shape[1])
+                                             or self._pieces_cached(xs.shape[0], xs.shape[1])):
             # a few long lists: one workgroup per query cannot fill the GPU; the balanced pieces
-            # (streaming scorer, split-query loss, streaming weight gradient) are faster
-            from ._autograd import PairwiseLossFunction
+            # (streaming scorer, split-query loss, streaming weight gradient) are faster -- and past
+            # max_list_len() documents (long_lists=True) they are the only path
             scores = _LinearScoreFunction.apply(xs, self.weight, self.bias, n)
-            loss = PairwiseLossFunction.apply(scores, relevance, n, self.kind, self.sigma)
+            loss = _pairwise_pieces(scores, relevance, n, self.kind, self.sigma)
             return (loss, scores.detach().squeeze(-1)) if return_scores else loss
         return _LinearLossFunction.apply(xs, self.weight, self.bias, relevance, n, self.kind,
                                          self.sigma, bool(return_scores))
@@ -422,7 +439,9 @@ def linear_loss_step(xs, weight, bias, relevance, n, loss="hinge", grad_out=None
     X = _prepare_features(xs)
     listwise = isinstance(kind, _ListwiseKind)
     if listwise and not _listwise_fused(kind, X):
-        return _listwise_step_pieces(xs, weight, bias, relevance, n, kind, grad_out, return_scores, return_loss_sum)
+        return _step_pieces(xs, weight, bias, relevance, n, kind, sigma, grad_out, return_scores, return_loss_sum)
+    if not listwise and _long_pair_shape(kind, X.shape[1]):
+        return _step_pieces(xs, weight, bias, relevance, n, kind, sigma, grad_out, return_scores, return_loss_sum)
     B, L, F = X.shape                               # (F: the row width in memory -- a padded view's F4)
     Fw = xs.shape[2]
     W = _pad_weight(_flat_f32(weight, Fw), F)
@@ -454,16 +473,18 @@ def linear_loss_step(xs, weight, bias, relevance, n, loss="hinge", grad_out=None
     return out
 
 
-def _listwise_step_pieces(xs, weight, bias, relevance, n, kind, grad_out, return_scores, return_loss_sum):
-    """linear_loss_step of a listwise loss on a shape the fused launch does not take: the scorer, the stand-alone loss
-    and the weight-gradient kernel, chained by autograd on detached copies of the parameters."""
+def _step_pieces(xs, weight, bias, relevance, n, kind, sigma, grad_out, return_scores, return_loss_sum):
+    """linear_loss_step on a shape no fused launch takes (a listwise loss off its plan; a pairwise loss with
+    long_lists=True past max_list_len() documents): the scorer, the stand-alone loss and the weight-gradient kernel,
+    chained by autograd on detached copies of the parameters."""
     B = xs.shape[0]
     with torch.enable_grad():
         w = weight.detach().float().reshape(1, -1).requires_grad_(True)
         b = (torch.zeros(1, dtype=torch.float32, device=xs.device) if bias is None
              else bias.detach().float().reshape(1)).requires_grad_(True)
         scores = _LinearScoreFunction.apply(xs, w, b, n)
-        lossv = _listwise_pieces(scores, relevance, n, kind)
+        lossv = (_listwise_pieces(scores, relevance, n, kind) if isinstance(kind, _ListwiseKind)
+                 else _pairwise_pieces(scores, relevance, n, kind, sigma))
         go = (torch.full((B,), 1.0 / max(B, 1), dtype=torch.float32, device=xs.device) if grad_out is None
               else grad_out.reshape(B).float())
         (lossv * go).sum().backward()
@@ -651,7 +672,7 @@ class LazyScores(torch.Tensor):
         if kind == _LISTWISE_SOFTMAX:
             return None
         B, L, F = xs.shape
-        if _prefer_pieces(kind, B, L, (F + 3) & ~3 if not xs.is_contiguous() else F):
+        if _long_pair_shape(kind, L) or _prefer_pieces(kind, B, L, (F + 3) & ~3 if not xs.is_contiguous() else F):
             return None
         self._check_versions()
         return _LinearLossFunction.apply(xs, self._weight, self._bias, relevance, n, kind, sigma, False)
@@ -1021,6 +1042,6 @@ class FusedMLPLoss(torch.nn.Module):
             self.last_losses = per_query
             return total
         from ._autograd import PairwiseLossFunction
-        per_query = PairwiseLossFunction.apply(self.score(xs), relevance, n, self.kind, self.sigma)
+        per_query = PairwiseLossFunction.apply(self.score(xs), relevance, n, int(self.kind), self.sigma, False)
         self.last_losses = per_query.detach()
         return per_query.mean() if self.reduction == "mean" else per_query.sum()

@@ -13,11 +13,17 @@ from pytorchltr_amd._autograd import pairwise_loss as _pairwise_loss
 
 
 class _PairwiseAdditiveLoss(_torch.nn.Module):
-    """Base of the linearly decomposable pairwise losses (reference :5-90)."""
+    """Base of the linearly decomposable pairwise losses (reference :5-90).
+
+    ``long_lists=True`` (keyword only; the reference has no such bound) takes lists of more than
+    ``_C.max_list_len()`` = 4096 documents, up to ``_C.max_pair_list_len()`` = 65 536, through
+    ``ltr_pairwise_loss_long_f32``: the work is quadratic in the list length, so the default keeps
+    raising ``ValueError`` there instead of silently taking milliseconds to seconds of GPU time."""
     _kind = None
 
-    def __init__(self):
+    def __init__(self, *, long_lists: bool = False):
         super().__init__()
+        self.long_lists = bool(long_lists)
 
     def _sigma(self):
         return 1.0
@@ -33,7 +39,7 @@ class _PairwiseAdditiveLoss(_torch.nn.Module):
         """
         if self._kind is None:
             raise NotImplementedError
-        return _pairwise_loss(scores, relevance, n, self._kind, self._sigma())
+        return _pairwise_loss(scores, relevance, n, self._kind, self._sigma(), self.long_lists)
 
 
 class PairwiseHingeLoss(_PairwiseAdditiveLoss):
@@ -53,12 +59,13 @@ class PairwiseLogisticLoss(_PairwiseAdditiveLoss):
     :math:`l(s, y) = \sum_{y_i > y_j} \log_2(1 + e^{-\sigma (s_i - s_j)})`."""
     _kind = _C.LOGISTIC
 
-    def __init__(self, sigma: float = 1.0):
+    def __init__(self, sigma: float = 1.0, *, long_lists: bool = False):
         """
         Args:
             sigma: Steepness of the logistic curve.
+            long_lists: Take lists of more than 4096 documents (see the base class).
         """
-        super().__init__()
+        super().__init__(long_lists=long_lists)
         self.sigma = sigma
 
     def _sigma(self):

@@ -19,20 +19,24 @@ class LambdaLoss(_torch.nn.Module):
     """LambdaLoss base (reference :6-92)."""
     _kind = None
 
-    def __init__(self, sigma: float = 1.0):
+    def __init__(self, sigma: float = 1.0, *, long_lists: bool = False):
         """
         Args:
             sigma: Steepness of the logistic curve.
+            long_lists: Take lists of more than ``_C.max_list_len()`` = 4096 documents, up to
+                ``_C.max_pair_list_len()`` = 65 536 (``ltr_pairwise_loss_long_f32``; the reference has no such
+                bound).  The work is quadratic in the list length, so the default keeps raising ``ValueError``.
         """
         super().__init__()
         self.sigma = sigma
+        self.long_lists = bool(long_lists)
 
     def forward(self, scores: _torch.FloatTensor, relevance: _torch.LongTensor,
                 n: _torch.LongTensor) -> _torch.FloatTensor:
         """Per-query loss; arguments as for the additive losses."""
         if self._kind is None:
             raise NotImplementedError
-        return _pairwise_loss(scores, relevance, n, self._kind, self.sigma)
+        return _pairwise_loss(scores, relevance, n, self._kind, self.sigma, self.long_lists)
 
 
 class LambdaARPLoss1(LambdaLoss):
