@@ -10,8 +10,12 @@ split of the same shape (136 features, ragged queries, 5 relevance grades that d
 features through a fixed random network), so the printed ndcg@10 must RISE from its untrained
 value.  Pass an SVMrank file pair to train on real data instead:
 
-    python examples/02_mlp_getting_started.py [train.txt test.txt]
+    python examples/02_mlp_getting_started.py [--loss {hinge,listnet,listmle}] [train.txt test.txt]
+
+--loss listnet / listmle trains the same network on a listwise loss (FusedMLPListwiseLoss: the same kernel with
+ListNet or ListMLE in its loss slot); the default is the guide's hinge loss.
 """
+import argparse
 import os
 import sys
 
@@ -21,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from pytorchltr_amd.datasets import RaggedQueries, UniformSampler, load_svmrank  # noqa: E402
 from pytorchltr_amd.evaluation import ndcg  # noqa: E402
-from pytorchltr_amd.fused import FusedMLPLoss  # noqa: E402
+from pytorchltr_amd.fused import FusedMLPListwiseLoss, FusedMLPLoss  # noqa: E402
 from pytorchltr_amd.loss import PairwiseHingeLoss  # noqa: E402
 
 
@@ -38,7 +42,7 @@ def synthetic_split(queries, features, seed, device):
     return RaggedQueries(xs, ys, offsets, device=device)
 
 
-def run(train_path=None, test_path=None, epochs=5, device="cuda", log=print):
+def run(train_path=None, test_path=None, epochs=5, device="cuda", log=print, loss="hinge"):
     torch.manual_seed(42)
     if train_path:
         train = load_svmrank(train_path, normalize=True, filter_queries=True, device=device)
@@ -46,7 +50,10 @@ def run(train_path=None, test_path=None, epochs=5, device="cuda", log=print):
     else:
         train = synthetic_split(600, 136, 1, device)
         test = synthetic_split(200, 136, 2, device)
-    model = FusedMLPLoss(train.features.shape[1], PairwiseHingeLoss()).to(device)
+    if loss == "hinge":
+        model = FusedMLPLoss(train.features.shape[1], PairwiseHingeLoss()).to(device)
+    else:
+        model = FusedMLPListwiseLoss(train.features.shape[1], loss=loss).to(device)
     optimizer = torch.optim.Adagrad(model.parameters(), lr=0.1)
 
     def evaluate():
@@ -75,5 +82,8 @@ def run(train_path=None, test_path=None, epochs=5, device="cuda", log=print):
 
 
 if __name__ == "__main__":
-    args = sys.argv[1:]
-    run(*(args[:2] if len(args) >= 2 else ()))
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--loss", choices=("hinge", "listnet", "listmle"), default="hinge")
+    ap.add_argument("files", nargs="*", help="train.txt test.txt (SVMrank); default: a synthetic split")
+    args = ap.parse_args()
+    run(*(args.files[:2] if len(args.files) >= 2 else ()), loss=args.loss)

@@ -1,6 +1,6 @@
 /*
  * ltr_listwise.h -- C ABI of ListMLE, the Plackett-Luce listwise loss (Xia et al. 2008; top-k: Xia et al. 2009), and
- * of the Linear(F, 1) scorer fused with the two listwise losses, ListNet and ListMLE.
+ * of the Linear(F, 1) scorer and the MLP scorer fused with the two listwise losses, ListNet and ListMLE.
  *
  * Exported by the same libltr_hip.so as include/ltr_hip.h, with its conventions: device pointers owned by the
  * caller, work enqueued on `stream` without host synchronisation, 0 = OK, < 0 = LTR_ERR_* (ltr_hip.h),
@@ -70,6 +70,39 @@ int ltr_linear_listwise_partials_f32(int loss, int k, const float *X, const floa
                                      const void *rel, int rel_dtype, const int64_t *n, const int32_t *tie, int use_seed,
                                      uint64_t seed, const int64_t *seed_dev, int B, int L, int F, float *loss_out,
                                      float *scores_out, float *partials, void *stream);
+
+/*
+ * The guide's MLP scorer, Linear(F, H1) / ReLU / Linear(H1, H2) / ReLU / Linear(H2, 1), fused with a listwise loss:
+ * the training step of ltr_mlp_pairwise_f32 (ltr_hip.h) with ListNet or ListMLE in the loss slot of the same two f32
+ * MFMA kernels -- scores, per-query losses and the gradient of sum_b weight[b] * loss[b] w.r.t. all six parameter
+ * tensors in one launch plus the cross-workgroup reduction.  Conventions, parameter layout and workspace are those of
+ * ltr_mlp_pairwise_f32: ltr_mlp_param_count(F, H1, H2) floats of `grads` as [dW1 | db1 | dW2 | db2 | dW3 | db3],
+ * ltr_mlp_workspace_bytes(B, F, H1, H2) bytes of workspace, weight[b] = grad_out[b] or 1 / B for grad_out == NULL,
+ * loss_sum (may be NULL) = sum_b loss[b] written by the reduction launch, scores_out (may be NULL) valid for j < n_b.
+ *   loss = LTR_LISTWISE_LISTNET: the listwise softmax cross-entropy of ltr_listwise_softmax_f32; k and the tie
+ *     arguments are ignored; a query with n_b = 0 has loss 0 and a zero gradient.  LTR_LISTWISE_LISTMLE:
+ *     ltr_listmle_f32 above -- the same row function, same k ("first K factors"), same tie modes (seed, device seed,
+ *     explicit priorities, index order); n_b <= 1 gives loss 0 and a zero gradient.  The scans are chunked by the
+ *     workgroup size (256 or 512 threads), so the loss agrees with ltr_listmle_f32 on scores_out to rounding, not bit
+ *     for bit.  Rows j >= n_b of X and rel never reach a result.
+ *   Shapes: F % 4 == 0, F <= 224, H1 <= 64, H2 <= 16; L <= 256 for F <= 144 (the 4-wave tile layout), L <= 128 above
+ *     (the 8-wave layout).  ltr_debug_mlp_layout steers the layout as it does for ltr_mlp_pairwise_f32.
+ *   No atomics on floats, every sum in a fixed order: bit-identical run to run for a fixed tie mode.  Nothing is
+ *   allocated: capturable.
+ * ltr_mlp_listwise_plan: 1 where the fused kernels take (loss, B, L, F, H1, H2), else 0: a bad loss, B, L, H1 or
+ *   H2 <= 0, H1 > 64, H2 > 16, F <= 0, F % 4 != 0, F > 224, L past the layout's longest list, or the LDS of a layout
+ *   the call may run on (its static part plus the ranked row) does not fit.
+ *   Errors, in this order: LTR_ERR_KIND for a bad loss or rel_dtype, then LTR_ERR_SHAPE (B < 0, L / F / H1 / H2 <= 0,
+ *   F % 4 != 0, F > 224, H1 > 64, H2 > 16), LTR_ERR_LIST_TOO_LONG; B == 0 is a no-op (nothing is written);
+ *   LTR_ERR_NULL (X, the six parameters, rel, n, loss_out, grads), LTR_ERR_WORKSPACE, then LTR_ERR_CONFIG for a shape
+ *   the plan declines.
+ */
+int ltr_mlp_listwise_plan(int loss, int B, int L, int F, int H1, int H2);
+int ltr_mlp_listwise_f32(int loss, int k, const float *X, const float *W1, const float *b1, const float *W2,
+                         const float *b2, const float *W3, const float *b3, const void *rel, int rel_dtype,
+                         const int64_t *n, const int32_t *tie, int use_seed, uint64_t seed, const int64_t *seed_dev,
+                         const float *grad_out, int B, int L, int F, int H1, int H2, float *loss_out, float *scores_out,
+                         float *grads, float *loss_sum, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -124,13 +124,16 @@ EVAL_SIGNATURES = {
 # enum of include/ltr_listwise.h: the losses of the fused listwise Linear step
 LISTWISE_LISTNET, LISTWISE_LISTMLE = 0, 1
 
-# name -> (restype, argtypes); mirrors include/ltr_listwise.h (ListMLE, the fused listwise Linear step)
+# name -> (restype, argtypes); mirrors include/ltr_listwise.h (ListMLE, the fused listwise Linear and MLP steps)
 LISTWISE_SIGNATURES = {
     "ltr_listmle_workspace_bytes": (_sz, [_i, _i]),
     "ltr_listmle_f32": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, ctypes.c_uint64, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "ltr_linear_listwise_plan": (_i, [_i, _i, _i, _i]),
     "ltr_linear_listwise_partials_f32": (_i, [_i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, ctypes.c_uint64, _vp, _i, _i, _i,
                                               _vp, _vp, _vp, _vp]),
+    "ltr_mlp_listwise_plan": (_i, [_i, _i, _i, _i, _i, _i]),
+    "ltr_mlp_listwise_f32": (_i, [_i, _i] + [_vp] * 7 + [_vp, _i, _vp, _vp, _i, ctypes.c_uint64, _vp, _vp]
+                             + [_i] * 5 + [_vp] * 5 + [_sz, _vp]),
 }
 
 # name -> (restype, argtypes); mirrors include/ltr_longpair.h (the pairwise losses past max_list_len() documents)

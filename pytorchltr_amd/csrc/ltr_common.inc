@@ -378,7 +378,7 @@ __device__ __forceinline__ void pair_rowweight(float sk, float ak, float sm, flo
 
 // lists longer than this take the sort path (DPT == 0 instantiation of metric_kernel)
 constexpr int kSortRankMinLen = 256;
-__host__ __device__ inline int sort_pow2(int L)
+__host__ __device__ constexpr int sort_pow2(int L)
 {
     int P = 64;
     while (P < L) P <<= 1;
@@ -542,14 +542,24 @@ struct LossParams {
 //                             path twice as long, zero beyond the list (see fill_ndcg2_delta)
 //   gpart float [msplit*L4]   per-slice gradient partials; aliased by the two int rank arrays
 //   red   float [32]
-__host__ __device__ inline size_t ndcg2_delta_floats(size_t L4)
+__host__ __device__ constexpr size_t ndcg2_delta_floats(size_t L4)
 {
     return (L4 <= (size_t)kLossSymMaxLen ? 2 * L4 : L4) + 4;
 }
 
-__host__ __device__ inline size_t loss_lds_bytes(int kind, int L, int msplit)
+// KIND codes of the fused MLP step's listwise loss slot (ltr_mlp_listwise.inc), outside enum ltr_loss_kind: internal to
+// the MLP kernels' KIND parameter, never part of the C ABI (whose listwise codes are LTR_LISTWISE_*, ltr_listwise.h).
+constexpr int LTR_MLP_LISTNET = 16;
+constexpr int LTR_MLP_LISTMLE = 17;
+constexpr size_t kRowScratchBytes = (32 + 64) * 4;      // red + scan of the ranked-row layout (ltr_ranked.inc)
+
+__host__ __device__ constexpr size_t loss_lds_bytes(int kind, int L, int msplit)
 {
     const size_t L4 = (size_t)((L + 3) & ~3);
+    // the listwise slot of the MLP kernels: ListNet keeps sy and the reduction scratch, ListMLE the whole ranked-row
+    // layout of the counting rank (ranked_row_layout(L, false).end: sy, two rank arrays, 16 B of keys per document)
+    if (kind == LTR_MLP_LISTNET) return 8 * L4 + kRowScratchBytes;
+    if (kind == LTR_MLP_LISTMLE) return 32 * L4 + kRowScratchBytes;
     size_t bytes = 8 * L4;
     if (kind == LTR_NDCG2) bytes += 16 * L4 + 4 * ndcg2_delta_floats(L4);
     size_t g = 4 * L4 * (size_t)msplit;
@@ -579,6 +589,12 @@ __device__ __forceinline__ QueryLds carve_query_lds(unsigned char *base, int L4,
     unsigned char *cur = base + 8 * (size_t)L4;
     q.q4 = nullptr;
     q.delta = nullptr;
+    if (KIND == LTR_MLP_LISTNET || KIND == LTR_MLP_LISTMLE) {
+        // (label, score) pairs in sy; the rest of the block is carved by mlp_listwise_slot (ltr_mlp_listwise.inc)
+        q.gpart = nullptr; q.rank_s = nullptr; q.rank_y = nullptr; q.gbytes = 0;
+        q.red = nullptr;
+        return q;
+    }
     if (KIND == LTR_NDCG2) {
         q.q4 = reinterpret_cast<float4 *>(cur);
         cur += 16 * (size_t)L4;

@@ -33,6 +33,9 @@
 #pragma once
 #include <type_traits>
 
+#include "ltr_listwise.h"
+#include "ltr_mlp_listwise.inc"
+
 typedef float mlp_f4 __attribute__((ext_vector_type(4)));
 
 constexpr int kMlpThreads = 512;      // 8 waves = two per SIMD: one wave's MFMA stream covers the
@@ -60,6 +63,7 @@ struct MlpParams {
     int P;                           // parameter count = length of one partial vector
     int pitch;                       // floats between consecutive partial vectors (P rounded up to 4)
     int fwd_only;                    // 1: scores only (evaluation) -- no pair pass, no backward
+    MlpListwiseArgs lw{};            // KIND = LTR_MLP_LISTNET / LTR_MLP_LISTMLE only (ltr_mlp_listwise.inc)
 };
 
 __host__ __device__ inline int mlp_param_count(int F, int H1, int H2)
@@ -321,6 +325,7 @@ mlp_pairwise_kernel(MlpParams p)
     const int L = p.L, F = p.F, H1 = p.H1, H2 = p.H2;
     constexpr int FS = 16 * NT + 4;                 // LDS pitch of W1 (zero padded to the bucket)
     constexpr int Lt = kMlpMaxLen;
+    constexpr bool kListwise = KIND == LTR_MLP_LISTNET || KIND == LTR_MLP_LISTMLE;   // sy holds (label, score)
 
     float *W1s = reinterpret_cast<float *>(smem);                 // [64][FS]
     float *H1s = W1s + (size_t)kMlpH1 * FS;                       // [128][72]  H1, later dH1
@@ -461,7 +466,7 @@ mlp_pairwise_kernel(MlpParams p)
         const int b = __builtin_amdgcn_readfirstlane(query_at(qi));
         const int nb = __builtin_amdgcn_readfirstlane(nb_next);
         const size_t row0 = (size_t)b * L;
-        if (tid < nb) q.sy[tid].y = ynext;
+        if (tid < nb) { if (kListwise) q.sy[tid].x = ynext; else q.sy[tid].y = ynext; }
         if (KIND == LTR_NDCG1 || KIND == LTR_NDCG2)
             for (int m = tid; m < 2 * Lt; m += T) q.rank_s[m] = 0;
         const bool on = __builtin_amdgcn_readfirstlane(16 * w < nb);    // this wave has documents
@@ -523,7 +528,7 @@ mlp_pairwise_kernel(MlpParams p)
             s += __shfl_xor(s, 32);
             s += b3;
             if (g == 0 && rowA < nb) {
-                q.sy[rowA].x = s;
+                if (kListwise) q.sy[rowA].y = s; else q.sy[rowA].x = s;
 #ifndef LTR_MLP_TRACE
                 if (p.scores_out) p.scores_out[row0 + rowA] = s;
 #endif
@@ -546,26 +551,31 @@ mlp_pairwise_kernel(MlpParams p)
         __syncthreads();
         MLP_STAMP(3);                              // layers 2, 3 + barrier
 
-        // ---- pair pass over the whole query ----
-        float gscale;
-        if (KIND == LTR_NDCG1 || KIND == LTR_NDCG2) {
-            constexpr int owners = 128;
-            constexpr int ms = T / owners;
-            const int mlen = (nb + ms - 1) / ms;
-            const int m0 = __builtin_amdgcn_readfirstlane(min(nb, (tid / owners) * mlen));
-            const int m1 = __builtin_amdgcn_readfirstlane(min(nb, m0 + mlen));
-            prepare_ndcg<KIND, 1>(q, nb, owners, tid % owners, m0, m1, ms > 1);
-        }
-        const float total = pairwise_core_sym<KIND, kMlpWaves>(q, nb, Lt, p.sigma, gscale);
-        if (tid == 0) p.loss[b] = total;
-        const float weight = (p.grad_out ? p.grad_out[b] : 1.0f / (float)p.B) * gscale;
-        for (int k = tid; k < Lt; k += T) {
-            float gk = 0.f;
-            if (k < nb) {
-#pragma unroll
-                for (int s = 0; s < kMlpWaves; ++s) gk += q.gpart[(size_t)s * Lt + k];
+        // ---- the loss slot over the whole query: the pair pass, or the listwise row (ltr_mlp_listwise.inc) ----
+        if constexpr (kListwise) {
+            mlp_listwise_slot<KIND, T, Lt>(smem + qoff, p.lw, nb, p.grad_out ? p.grad_out[b] : 1.0f / (float)p.B,
+                                           p.loss + b, gfin);
+        } else {
+            float gscale;
+            if (KIND == LTR_NDCG1 || KIND == LTR_NDCG2) {
+                constexpr int owners = 128;
+                constexpr int ms = T / owners;
+                const int mlen = (nb + ms - 1) / ms;
+                const int m0 = __builtin_amdgcn_readfirstlane(min(nb, (tid / owners) * mlen));
+                const int m1 = __builtin_amdgcn_readfirstlane(min(nb, m0 + mlen));
+                prepare_ndcg<KIND, 1>(q, nb, owners, tid % owners, m0, m1, ms > 1);
             }
-            gfin[k] = gk * weight;
+            const float total = pairwise_core_sym<KIND, kMlpWaves>(q, nb, Lt, p.sigma, gscale);
+            if (tid == 0) p.loss[b] = total;
+            const float weight = (p.grad_out ? p.grad_out[b] : 1.0f / (float)p.B) * gscale;
+            for (int k = tid; k < Lt; k += T) {
+                float gk = 0.f;
+                if (k < nb) {
+#pragma unroll
+                    for (int s = 0; s < kMlpWaves; ++s) gk += q.gpart[(size_t)s * Lt + k];
+                }
+                gfin[k] = gk * weight;
+            }
         }
         __syncthreads();
         MLP_STAMP(4);                              // pair pass
@@ -990,6 +1000,39 @@ int launch_mlp_kind(const MlpParams &p, int grid, hipStream_t stream)
     }
 }
 
+// the cross-workgroup sum of the partial vectors (and loss_sum) behind a training step of either entry point
+inline int mlp_reduce_launch(void *workspace, int grid, int P, float *grads, const float *loss, int B, float *loss_sum,
+                             hipStream_t s)
+{
+    // (grads as float4 needs a 16-byte aligned output; otherwise the 4-byte version)
+    if ((reinterpret_cast<uintptr_t>(grads) & 15) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0) {
+        const int P4 = mlp_pitch(P) >> 2;
+        hipLaunchKernelGGL(mlp_reduce4_kernel<kMlpRedCols4>, dim3((unsigned)((P4 + kMlpRedCols4 - 1) / kMlpRedCols4)),
+                           dim3(1024), 0, s, (const float *)workspace, grid, P, mlp_pitch(P), grads, loss, B, loss_sum);
+        return (int)hipGetLastError();
+    }
+    hipLaunchKernelGGL(mlp_reduce_kernel, dim3((unsigned)((P + kMlpRedCols - 1) / kMlpRedCols)),
+                       dim3(kMlpRedCols * kMlpRedSlices), 0, s,
+                       (const float *)workspace, grid, P, mlp_pitch(P), grads, loss, B, loss_sum);
+    return (int)hipGetLastError();
+}
+
+// ---- the listwise step (ltr_mlp_listwise_f32) ----
+inline bool bad_mlp_listwise_loss(int loss) { return loss != LTR_LISTWISE_LISTNET && loss != LTR_LISTWISE_LISTMLE; }
+
+// The plan rule behind the shape checks: the list fits the layouts that take F, and the LDS of every layout the call
+// may be steered to (ltr_debug_mlp_layout) -- the static part and the loss slot's row -- fits the workgroup.
+inline bool mlp_listwise_fits(int loss, int L, int F)
+{
+    const int kind = loss == LTR_LISTWISE_LISTNET ? LTR_MLP_LISTNET : LTR_MLP_LISTMLE;
+    if (L > (mlp2_takes(F) ? kM2MaxLen : kMlpMaxLen)) return false;
+    if (mlp2_takes(F) &&
+        mlp2_lds_bytes(kind, mlp_bucket(F), L <= kM2ParkLen ? kM2ParkLen : kM2MaxLen) > kLdsBudget / kM2Wgs)
+        return false;
+    if (L <= kMlpMaxLen && mlp_lds_bytes(kind, F) > kLdsBudget) return false;
+    return true;
+}
+
 extern "C" {
 
 LTR_DEBUG_HOOK void ltr_debug_mlp_layout(int layout) { mlp_layout_choice() = layout; }
@@ -1045,17 +1088,53 @@ int ltr_mlp_pairwise_f32(int kind, float sigma, const float *X, const float *W1,
                             : with_kind(kind, [&](auto K) { return launch_mlp_kind<K>(p, grid, s); });
         if (rc != 0) return rc;
     }
-    // (grads as float4 needs a 16-byte aligned output; otherwise the 4-byte version)
-    if ((reinterpret_cast<uintptr_t>(grads) & 15) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0) {
-        const int P4 = mlp_pitch(P) >> 2;
-        hipLaunchKernelGGL(mlp_reduce4_kernel<kMlpRedCols4>, dim3((unsigned)((P4 + kMlpRedCols4 - 1) / kMlpRedCols4)),
-                           dim3(1024), 0, s, (const float *)workspace, grid, P, mlp_pitch(P), grads, loss, B, loss_sum);
-        return (int)hipGetLastError();
+    return mlp_reduce_launch(workspace, grid, P, grads, loss, B, loss_sum, s);
+}
+
+int ltr_mlp_listwise_plan(int loss, int B, int L, int F, int H1, int H2)
+{
+    if (bad_mlp_listwise_loss(loss) || B <= 0 || L <= 0 || H1 <= 0 || H2 <= 0 || H1 > kMlpH1 || H2 > kMlpH2) return 0;
+    if (F <= 0 || (F & 3) || F > 16 * 14) return 0;
+    return mlp_listwise_fits(loss, L, F) ? 1 : 0;
+}
+
+int ltr_mlp_listwise_f32(int loss, int k, const float *X, const float *W1, const float *b1, const float *W2,
+                         const float *b2, const float *W3, const float *b3, const void *rel, int rel_dtype,
+                         const int64_t *n, const int32_t *tie, int use_seed, uint64_t seed, const int64_t *seed_dev,
+                         const float *grad_out, int B, int L, int F, int H1, int H2, float *loss_out, float *scores_out,
+                         float *grads, float *loss_sum, void *workspace, size_t workspace_bytes, void *stream)
+{
+    LTR_CLEAR_STALE_ERROR();
+    if (bad_mlp_listwise_loss(loss) || bad_label_dtype(rel_dtype)) return LTR_ERR_KIND;
+    if (B < 0 || L <= 0 || F <= 0 || H1 <= 0 || H2 <= 0) return LTR_ERR_SHAPE;
+    if ((F & 3) || F > 16 * 14 || H1 > kMlpH1 || H2 > kMlpH2) return LTR_ERR_SHAPE;
+    if (L > (mlp2_takes(F) ? kM2MaxLen : kMlpMaxLen)) return LTR_ERR_LIST_TOO_LONG;
+    if (B == 0) return LTR_OK;
+    if (!X || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !rel || !n || !loss_out || !grads) return LTR_ERR_NULL;
+    const int P = mlp_param_count(F, H1, H2);
+    const bool tile = mlp_use_tile_layout(F, B, L);
+    const int grid = tile ? mlp2_grid(B) : mlp_grid(B);
+    if (!workspace || workspace_bytes < (size_t)grid * mlp_pitch(P) * sizeof(float)) return LTR_ERR_WORKSPACE;
+    if (!mlp_listwise_fits(loss, L, F)) return LTR_ERR_CONFIG;
+    hipStream_t s = (hipStream_t)stream;
+    MlpParams p;
+    p.X = X; p.W1 = W1; p.b1 = b1; p.W2 = W2; p.b2 = b2; p.W3 = W3; p.b3 = b3;
+    p.rel = rel; p.n = n; p.grad_out = grad_out;
+    p.loss = loss_out; p.scores_out = scores_out; p.part = (float *)workspace;
+    p.B = B; p.L = L; p.F = F; p.H1 = H1; p.H2 = H2;
+    p.sigma = 1.0f; p.rel_dtype = rel_dtype; p.P = P; p.pitch = mlp_pitch(P); p.fwd_only = 0;
+    p.lw.k = k;
+    if (loss == LTR_LISTWISE_LISTMLE) {           // (ListNet ranks nothing: the tie arguments are ignored)
+        if (use_seed) { p.lw.use_seed = 1; p.lw.tie_seed = seed; p.lw.tie_seed_dev = seed_dev; }
+        else p.lw.tie = tie;
     }
-    hipLaunchKernelGGL(mlp_reduce_kernel, dim3((unsigned)((P + kMlpRedCols - 1) / kMlpRedCols)),
-                       dim3(kMlpRedCols * kMlpRedSlices), 0, s,
-                       (const float *)workspace, grid, P, mlp_pitch(P), grads, loss, B, loss_sum);
-    return (int)hipGetLastError();
+    int rc;
+    if (loss == LTR_LISTWISE_LISTNET)
+        rc = tile ? launch_mlp2_kind<LTR_MLP_LISTNET>(p, grid, s) : launch_mlp_kind<LTR_MLP_LISTNET>(p, grid, s);
+    else
+        rc = tile ? launch_mlp2_kind<LTR_MLP_LISTMLE>(p, grid, s) : launch_mlp_kind<LTR_MLP_LISTMLE>(p, grid, s);
+    if (rc != 0) return rc;
+    return mlp_reduce_launch(workspace, grid, P, grads, loss_out, B, loss_sum, s);
 }
 
 // bench.py `extra.mlp_scorer_fused.launch_ceiling` (include/ltr_hip.h): the launch geometry of the fused MLP training

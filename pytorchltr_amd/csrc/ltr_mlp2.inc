@@ -96,7 +96,7 @@ __global__ void __launch_bounds__(kM2Threads, kM2Wgs)
 mlp_tile_kernel(MlpParams p)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x;
+    int tid = threadIdx.x;                         // (not const, like c16 and g: see the top of the query loop)
     constexpr int T = kM2Threads;
 #ifdef LTR_MLP_TRACE
     long long last_ = (long long)__builtin_readcyclecounter();
@@ -104,12 +104,13 @@ mlp_tile_kernel(MlpParams p)
 #endif
     const int lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int c16 = lane & 15;
-    const int g = lane >> 4;
+    int c16 = lane & 15;
+    int g = lane >> 4;
     const int L = p.L, F = p.F, H1 = p.H1, H2 = p.H2;
     const int C = CT > 0 ? CT : (F >> 2);           // float4 units per feature row
     constexpr int IP = 16 * NT + 4;                 // image pitch (floats): odd number of 16-byte units
     constexpr int Lt = LT;
+    constexpr bool kListwise = KIND == LTR_MLP_LISTNET || KIND == LTR_MLP_LISTMLE;   // sy holds (label, score)
     constexpr bool kPark = LT <= kM2ParkLen;        // else: forward again in the backward pass
     constexpr int kSlots = kPark ? kM2ParkLen / kM2Docs - 1 : 0;
     constexpr int KP = (kM2Docs * 4 * NT + T - 1) / T;     // float4 units of a fill per thread
@@ -264,7 +265,7 @@ mlp_tile_kernel(MlpParams p)
         s += b3;
         const int k = kM2Docs * fill + doc;
         if (publish && g == 0 && k < nb) {
-            if (!FWD) q.sy[k].x = s;
+            if (!FWD) { if (kListwise) q.sy[k].y = s; else q.sy[k].x = s; }
 #ifndef LTR_MLP_TRACE
             if (p.scores_out) p.scores_out[row0 + k] = s;
 #endif
@@ -348,6 +349,11 @@ mlp_tile_kernel(MlpParams p)
     M2_STAMP(8);                                   // first fill and weight fragments requested
 
     for (int qi = 0; qi < nqueries; ++qi) {
+        // The listwise rows bring their own lane-derived addresses; with those of the chains below hoisted out of this
+        // loop as well, the register allocator spills (ListNet at F = 136: 6 VGPRs, ListMLE: 28).  Opaque lane indices
+        // keep the address arithmetic inside the loop: a few VALU instructions per query, no spill (the row functions'
+        // own reads of the thread index: ltr_mlp.hip).
+        if constexpr (kListwise) asm volatile("" : "+v"(c16), "+v"(g), "+v"(tid));
         const int b = __builtin_amdgcn_readfirstlane(query_at(qi));
         const int nb = __builtin_amdgcn_readfirstlane(nb_next);
         const size_t row0 = (size_t)b * L;
@@ -358,7 +364,7 @@ mlp_tile_kernel(MlpParams p)
 
         if (PROBE) {
         } else if (!FWD) {
-            if (tid < nb) q.sy[tid].y = ynext;
+            if (tid < nb) { if (kListwise) q.sy[tid].x = ynext; else q.sy[tid].y = ynext; }
             if (KIND == LTR_NDCG1 || KIND == LTR_NDCG2)
                 for (int m = tid; m < 2 * Lt; m += T) q.rank_s[m] = 0;
             // the next query's label goes out ahead of the fills in the in-order vmcnt queue
@@ -424,26 +430,31 @@ mlp_tile_kernel(MlpParams p)
             }
             continue;
         }
-        // ---- pair pass over the whole query ----
-        float gscale;
-        if (KIND == LTR_NDCG1 || KIND == LTR_NDCG2) {
-            constexpr int owners = 128;
-            constexpr int ms = T / owners;
-            const int mlen = (nb + ms - 1) / ms;
-            const int m0 = __builtin_amdgcn_readfirstlane(min(nb, (tid / owners) * mlen));
-            const int m1 = __builtin_amdgcn_readfirstlane(min(nb, m0 + mlen));
-            prepare_ndcg<KIND, 1, kM2Waves, true>(q, nb, owners, tid % owners, m0, m1, ms > 1);
-        }
-        const float total = pairwise_core_sym<KIND, kM2Waves, true>(q, nb, Lt, p.sigma, gscale);
-        if (tid == 0) p.loss[b] = total;
-        const float weight = (p.grad_out ? p.grad_out[b] : 1.0f / (float)p.B) * gscale;
-        if (tid < Lt) {
-            float gk = 0.f;
-            if (tid < nb) {
-#pragma unroll
-                for (int s = 0; s < kM2Waves; ++s) gk += q.gpart[(size_t)s * Lt + tid];
+        // ---- the loss slot over the whole query: the pair pass, or the listwise row (ltr_mlp_listwise.inc) ----
+        if constexpr (kListwise) {
+            mlp_listwise_slot<KIND, T, Lt>(smem + qoff, p.lw, nb, p.grad_out ? p.grad_out[b] : 1.0f / (float)p.B,
+                                           p.loss + b, gfin);
+        } else {
+            float gscale;
+            if (KIND == LTR_NDCG1 || KIND == LTR_NDCG2) {
+                constexpr int owners = 128;
+                constexpr int ms = T / owners;
+                const int mlen = (nb + ms - 1) / ms;
+                const int m0 = __builtin_amdgcn_readfirstlane(min(nb, (tid / owners) * mlen));
+                const int m1 = __builtin_amdgcn_readfirstlane(min(nb, m0 + mlen));
+                prepare_ndcg<KIND, 1, kM2Waves, true>(q, nb, owners, tid % owners, m0, m1, ms > 1);
             }
-            gfin[tid] = gk * weight;
+            const float total = pairwise_core_sym<KIND, kM2Waves, true>(q, nb, Lt, p.sigma, gscale);
+            if (tid == 0) p.loss[b] = total;
+            const float weight = (p.grad_out ? p.grad_out[b] : 1.0f / (float)p.B) * gscale;
+            if (tid < Lt) {
+                float gk = 0.f;
+                if (tid < nb) {
+#pragma unroll
+                    for (int s = 0; s < kM2Waves; ++s) gk += q.gpart[(size_t)s * Lt + tid];
+                }
+                gfin[tid] = gk * weight;
+            }
         }
         lds_barrier();
         M2_STAMP(4);                              // pair pass

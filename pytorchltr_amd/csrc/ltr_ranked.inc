@@ -4,6 +4,18 @@
 // LDS layout and ranking of a staged query, three workgroup scans, the ARP and DCG / NDCG terms, the launch shape and
 // its one dispatch, and the workspace carver.
 
+// The thread index as the row helpers of this file and of ltr_listmle_row.inc read it: threadIdx.x.  A translation unit
+// that inlines them into a long persistent loop may define LTR_ROW_TID_OPAQUE (ltr_mlp.hip does, and says why): the read
+// then goes through an empty asm, the same value, which the optimiser cannot hoist out of that loop.
+__device__ __forceinline__ unsigned row_tid()
+{
+    unsigned t = threadIdx.x;
+#ifdef LTR_ROW_TID_OPAQUE
+    asm volatile("" : "+v"(t));
+#endif
+    return t;
+}
+
 struct MetricParams {
     const float *scores;
     const void *rel;
@@ -46,10 +58,10 @@ __device__ __forceinline__ int tie_word(const MetricParams &p, unsigned long lon
 // keys, 16 B per document, or the sort's 8 B x sort_pow2(L) -- and once the ranks are taken it holds, from its start:
 // curve float[L4] | icurve float[L4] | red float[32] | scan float[64].
 struct RankedRowLayout { size_t ranks, work, red, invt, end; };
-__host__ __device__ inline RankedRowLayout ranked_row_layout(int L, bool sort)
+__host__ __device__ constexpr RankedRowLayout ranked_row_layout(int L, bool sort)
 {
     const size_t L4 = (size_t)((L + 3) & ~3);
-    RankedRowLayout o;
+    RankedRowLayout o{};
     o.ranks = 8 * L4;
     o.work = o.ranks + 8 * L4;
     o.red = o.work + 8 * L4;
@@ -93,7 +105,7 @@ template <int DPT>
 __device__ __forceinline__ void metric_ranks(const MetricParams &p, const RankedRowLds &q, int nb, bool with_y)
 {
     const int L = p.L;
-    const int tid = threadIdx.x;
+    const int tid = row_tid();
     const int T = blockDim.x;
     const int msplit = p.msplit;
     const int owners = T / msplit;
@@ -157,7 +169,7 @@ __device__ __forceinline__ void metric_ranks(const MetricParams &p, const Ranked
 // `scan_scratch`: LDS of >= 16 floats.
 __device__ void block_inclusive_scan(float *buf, int L, float *scan_scratch, float carry = 0.f)
 {
-    const int T = blockDim.x, tid = threadIdx.x;
+    const int T = blockDim.x, tid = row_tid();
     const int ch = (L + T - 1) / T;
     const int lo = min(L, tid * ch), hi = min(L, lo + ch);
     float s = 0.f;
@@ -185,7 +197,7 @@ __device__ void block_inclusive_scan(float *buf, int L, float *scan_scratch, flo
 template <typename Op>
 __device__ void block_scan(float *buf, int len, float *scratch)
 {
-    const int T = blockDim.x, tid = threadIdx.x;
+    const int T = blockDim.x, tid = row_tid();
     const int ch = (len + T - 1) / T;
     const int lo = min(len, tid * ch), hi = min(len, lo + ch);
     float s = Op::id;
@@ -242,7 +254,8 @@ __device__ __forceinline__ void wave_pair_scan(float &x, float &y)
 template <typename Op>
 __device__ __forceinline__ void block_pair_scan(float &x, float &y, float &tx, float &ty, float *pair)
 {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const unsigned t = row_tid();
+    const int lane = t & 63, w = t >> 6, nw = blockDim.x >> 6;
     float ix = x, iy = y;
     wave_pair_scan<Op>(ix, iy);
     float ex = __shfl_up(ix, 1, kWave), ey = __shfl_up(iy, 1, kWave);
@@ -264,7 +277,7 @@ __device__ __forceinline__ void block_pair_scan(float &x, float &y, float &tx, f
 // arp.py:31-42: sum((r+1) * rel_r) / sum(rel_r) over ranks r < n; 0 -> 1 guard
 __device__ __forceinline__ float ranked_arp(const RankedRowLds &q, int nb)
 {
-    const int tid = threadIdx.x, T = blockDim.x;
+    const int tid = row_tid(), T = blockDim.x;
     float srp = 0.f, nrp = 0.f;
     for (int k = tid; k < nb; k += T) {
         const float y = q.sy[k].y;
@@ -281,7 +294,7 @@ __device__ __forceinline__ float ranked_arp(const RankedRowLds &q, int nb)
 // kk > 0: returns the metric at kk.  kk == 0: leaves the cumulative curves in q.curve (and, norm, q.icurve).
 __device__ __forceinline__ float ranked_dcg(const RankedRowLds &q, int L, int nb, int kk, bool norm, int use_exp)
 {
-    const int tid = threadIdx.x, T = blockDim.x;
+    const int tid = row_tid(), T = blockDim.x;
     float part = 0.f, ipart = 0.f;
     for (int k = tid; k < L; k += T) {
         const float y = q.sy[k].y;
@@ -317,6 +330,7 @@ __device__ __forceinline__ float ranked_dcg(const RankedRowLds &q, int L, int nb
     return 0.f;
 }
 
+#ifndef LTR_RANKED_ROW_ONLY      // (ltr_mlp.hip takes the row above -- layout, ranking, scans -- without the core's launches)
 // ---- the launch ----
 // The launch shape of the one-workgroup kernels: the DPT instantiation (0, -2, -4: the sort path with 1, 2, 4 keys
 // per thread; 1, 2, 4: the counting rank), the workgroup size and the dynamic LDS; sets p.msplit.
@@ -365,6 +379,8 @@ int launch_ranked(const MetricShape &sh, int B, size_t extra_lds, hipStream_t st
     }
     return launch(std::integral_constant<int, 4>{});
 }
+
+#endif  // LTR_RANKED_ROW_ONLY
 
 // ---- workspaces ----
 // A bump allocator over a caller's workspace.  A consumer states its workspace once, as a sequence of take / align256

@@ -71,7 +71,7 @@ def _resolve_pairwise_loss(loss):
     kind, sigma = _resolve_loss(loss)
     if isinstance(kind, _ListwiseKind):
         raise TypeError("this entry point takes the pairwise losses only (the listwise ones: FusedLinearLoss, "
-                        "linear_loss_step, LinearScorer)")
+                        "linear_loss_step, LinearScorer; on the MLP scorer: FusedMLPListwiseLoss, mlp_loss_step)")
     return kind, sigma
 
 
@@ -871,12 +871,23 @@ def _mlp_workspace(dev, stream, ws_bytes):
     return ws
 
 
+def mlp_listwise_supported(kind, B, L, F, H1, H2):
+    """True where the fused MLP kernels take a listwise loss at this shape (ltr_mlp_listwise_plan: the shapes of
+    :func:`mlp_supported` whose ranked row fits the LDS next to the network's).  An empty batch counts as taken."""
+    if not mlp_supported(L, F, H1, H2):
+        return False
+    return B == 0 or bool(_C.lib().ltr_mlp_listwise_plan(kind.loss, B, L, F, H1, H2))
+
+
 def mlp_loss_step(xs, params, relevance, n, loss="hinge", grad_out=None, return_scores=False,
                   return_loss_sum=False, out=None):
     """One fused forward+backward step of ``loss_fn(mlp(xs), relevance, n)`` without autograd.
 
     Args:
         xs: (B, L, F) float32 features on the device.
+        loss: a pairwise kind name or module, or a listwise loss -- ``"listnet"`` / ``"softmax"``, ``"listmle"``,
+            ``ListwiseSoftmaxLoss()``, ``ListMLELoss(k)`` (ltr_mlp_listwise_f32; ListMLE draws one tie seed per call,
+            as ``ListMLELoss`` does, and ``utils.tie_breaking("index")`` turns it off).
         params: ``(W1, b1, W2, b2, W3, b3)`` of ``Linear(F,H1) / ReLU / Linear(H1,H2) / ReLU /
             Linear(H2,1)`` in torch layout.
         grad_out: (B,) weights of the per-query losses; None = 1/B (the ``.mean()`` of the guide's
@@ -888,11 +899,12 @@ def mlp_loss_step(xs, params, relevance, n, loss="hinge", grad_out=None, return_
         buffer (available as ``grads[0].base`` / the ``out`` argument), then optionally the scores
         (valid for documents < n only) and ``loss_sum`` (1,).
     """
-    kind, sigma = _resolve_pairwise_loss(loss)
+    kind, sigma = _resolve_loss(loss)
+    listwise = isinstance(kind, _ListwiseKind)
     X = _prepare_features(xs)
     B, L, F = X.shape
     flat_params, H1, H2 = _flat_params(params, F)
-    if not mlp_supported(L, F, H1, H2):
+    if not mlp_supported(L, F, H1, H2) or (listwise and not mlp_listwise_supported(kind, B, L, F, H1, H2)):
         raise ValueError("fused MLP kernel takes L <= %d (F <= 144: %d), F <= %d with F %% 4 == 0, "
                          "hidden <= %s; got L=%d F=%d hidden=(%d, %d)"
                          % (MLP_MAX_LIST_LEN, MLP_MAX_LIST_LEN_NARROW, MLP_MAX_FEATURES,
@@ -914,13 +926,25 @@ def mlp_loss_step(xs, params, relevance, n, loss="hinge", grad_out=None, return_
     with _C.device_ctx(X):
         st = _C.stream_of(X)
         ws = _mlp_workspace(dev, st, ws_bytes)
-        rc = lib.ltr_mlp_pairwise_f32(
-            kind, float(sigma), X.data_ptr(), flat_params[0].data_ptr(), flat_params[1].data_ptr(),
-            flat_params[2].data_ptr(), flat_params[3].data_ptr(), flat_params[4].data_ptr(),
-            flat_params[5].data_ptr(), r.data_ptr(), _LABEL_CODE[r.dtype], nn.data_ptr(),
-            None if go is None else go.data_ptr(), B, L, F, H1, H2, lossv.data_ptr(),
-            None if scores is None else scores.data_ptr(), flat.data_ptr(),
-            None if lsum is None else lsum.data_ptr(), ws.data_ptr(), ws_bytes, st)
+        if listwise:
+            from . import _ties
+            if B == 0:
+                flat.zero_()                # (the listwise entry point launches nothing for an empty batch)
+            sd = _ties.draw_seed(L, dev) if kind.loss == _C.LISTWISE_LISTMLE else None
+            rc = lib.ltr_mlp_listwise_f32(
+                kind.loss, int(kind.k or 0), X.data_ptr(), *[t.data_ptr() for t in flat_params],
+                r.data_ptr(), _LABEL_CODE[r.dtype], nn.data_ptr(), *_ties.tie_args(sd),
+                None if go is None else go.data_ptr(), B, L, F, H1, H2, lossv.data_ptr(),
+                None if scores is None else scores.data_ptr(), flat.data_ptr(),
+                None if lsum is None else lsum.data_ptr(), ws.data_ptr(), ws_bytes, st)
+        else:
+            rc = lib.ltr_mlp_pairwise_f32(
+                kind, float(sigma), X.data_ptr(), flat_params[0].data_ptr(), flat_params[1].data_ptr(),
+                flat_params[2].data_ptr(), flat_params[3].data_ptr(), flat_params[4].data_ptr(),
+                flat_params[5].data_ptr(), r.data_ptr(), _LABEL_CODE[r.dtype], nn.data_ptr(),
+                None if go is None else go.data_ptr(), B, L, F, H1, H2, lossv.data_ptr(),
+                None if scores is None else scores.data_ptr(), flat.data_ptr(),
+                None if lsum is None else lsum.data_ptr(), ws.data_ptr(), ws_bytes, st)
         if rc != 0:
             _C.check(rc)
     res = (lossv, _split_grads(flat, F, H1, H2))
@@ -991,26 +1015,17 @@ class _KindProxy:
         self.sigma = sigma
 
 
-class FusedMLPLoss(torch.nn.Module):
-    """The guide's scorer and loss as one module: ``l1``/``l2``/``l3`` are ordinary
-    ``torch.nn.Linear`` layers (state_dict-compatible with the ``Model`` class of
-    docs/source/getting-started.rst:40-50), and ``forward(xs, relevance, n)`` returns the
-    *reduced* loss ``loss_fn(model(xs), relevance, n).mean()`` (or ``.sum()``) whose backward
-    fills the six parameter gradients -- computed by one fused MFMA kernel.
+class _FusedMLPBase(torch.nn.Module):
+    """What FusedMLPLoss and FusedMLPListwiseLoss share: the three ``nn.Linear`` layers, ``score()``, the fused step
+    where ``_fused_shape`` takes the batch and the unfused composition (``_pieces``) where it does not."""
 
-    Feature counts that are not a multiple of 4 are zero-padded on the fly.  Shapes the kernel
-    does not take (lists longer than 256 -- 128 beyond 144 features --, more than 224 features, ...) run as the unfused
-    composition: rocBLAS layers + the HIP loss kernel.  ``score(xs)`` evaluates the
-    network alone (for the metrics).
-    """
-
-    def __init__(self, in_features, loss="hinge", hidden=(50, 10), reduction="mean"):
+    def __init__(self, in_features, loss, hidden, reduction):
         super().__init__()
         if reduction not in ("mean", "sum"):
             raise ValueError("reduction must be 'mean' or 'sum'")
         self.in_features = in_features
         self.reduction = reduction
-        self.kind, self.sigma = _resolve_pairwise_loss(loss)
+        self.kind, self.sigma = self._resolve(loss)
         self.l1 = torch.nn.Linear(in_features, hidden[0])
         self.l2 = torch.nn.Linear(hidden[0], hidden[1])
         self.l3 = torch.nn.Linear(hidden[1], 1)
@@ -1033,15 +1048,68 @@ class FusedMLPLoss(torch.nn.Module):
         return (self.l1.weight, self.l1.bias, self.l2.weight, self.l2.bias, self.l3.weight,
                 self.l3.bias)
 
+    def _fused_shape(self, B, L, F4):
+        return mlp_supported(L, F4, self.l1.out_features, self.l2.out_features)
+
     def forward(self, xs, relevance, n):
         _C.require_device(xs, "xs")
         B, L, F = xs.shape
-        if mlp_supported(L, (F + 3) & ~3, self.l1.out_features, self.l2.out_features):
+        if self._fused_shape(B, L, (F + 3) & ~3):
             total, per_query = _MLPLossFunction.apply(
                 xs, relevance, n, (self.kind, self.sigma), self.reduction == "mean", *self._params())
             self.last_losses = per_query
             return total
-        from ._autograd import PairwiseLossFunction
-        per_query = PairwiseLossFunction.apply(self.score(xs), relevance, n, int(self.kind), self.sigma, False)
+        per_query = self._pieces(self.score(xs), relevance, n)
         self.last_losses = per_query.detach()
         return per_query.mean() if self.reduction == "mean" else per_query.sum()
+
+
+class FusedMLPLoss(_FusedMLPBase):
+    """The guide's scorer and loss as one module: ``l1``/``l2``/``l3`` are ordinary
+    ``torch.nn.Linear`` layers (state_dict-compatible with the ``Model`` class of
+    docs/source/getting-started.rst:40-50), and ``forward(xs, relevance, n)`` returns the
+    *reduced* loss ``loss_fn(model(xs), relevance, n).mean()`` (or ``.sum()``) whose backward
+    fills the six parameter gradients -- computed by one fused MFMA kernel.
+
+    Feature counts that are not a multiple of 4 are zero-padded on the fly.  Shapes the kernel
+    does not take (lists longer than 256 -- 128 beyond 144 features --, more than 224 features, ...) run as the unfused
+    composition: rocBLAS layers + the HIP loss kernel.  ``score(xs)`` evaluates the
+    network alone (for the metrics).  The seven pairwise losses; the listwise ones: :class:`FusedMLPListwiseLoss`.
+    """
+
+    def __init__(self, in_features, loss="hinge", hidden=(50, 10), reduction="mean"):
+        super().__init__(in_features, loss, hidden, reduction)
+
+    _resolve = staticmethod(_resolve_pairwise_loss)
+
+    def _pieces(self, scores, relevance, n):
+        from ._autograd import PairwiseLossFunction
+        return PairwiseLossFunction.apply(scores, relevance, n, int(self.kind), self.sigma, False)
+
+
+def _resolve_listwise_loss(loss):
+    kind, sigma = _resolve_loss(loss)
+    if not isinstance(kind, _ListwiseKind):
+        raise TypeError("FusedMLPListwiseLoss takes the listwise losses only (\"listnet\" / \"softmax\", \"listmle\", "
+                        "ListwiseSoftmaxLoss, ListMLELoss); the pairwise ones: FusedMLPLoss")
+    return kind, sigma
+
+
+class FusedMLPListwiseLoss(_FusedMLPBase):
+    """:class:`FusedMLPLoss` for the listwise losses: ``loss`` is ``"listnet"`` (``"softmax"``), ``"listmle"``,
+    ``ListwiseSoftmaxLoss()`` or ``ListMLELoss(k)``.  Same layers, ``state_dict``, ``score()``, ``last_losses`` and
+    feature padding; the fused step is ``ltr_mlp_listwise_f32`` (include/ltr_listwise.h), ListNet or ListMLE in the
+    loss slot of the same two MFMA kernels.  Shapes its plan declines -- lists longer than 256 (128 beyond 144
+    features), hidden sizes past (64, 16), ... -- run as the unfused composition: ``score()`` with autograd and the
+    stand-alone listwise loss kernel.  ListMLE breaks label ties as :class:`pytorchltr_amd.loss.ListMLELoss` does."""
+
+    def __init__(self, in_features, loss="listnet", hidden=(50, 10), reduction="mean"):
+        super().__init__(in_features, loss, hidden, reduction)
+
+    _resolve = staticmethod(_resolve_listwise_loss)
+
+    def _fused_shape(self, B, L, F4):
+        return mlp_listwise_supported(self.kind, B, L, F4, self.l1.out_features, self.l2.out_features)
+
+    def _pieces(self, scores, relevance, n):
+        return _listwise_pieces(scores, relevance, n, self.kind)
