@@ -879,6 +879,137 @@ def mlp_listwise_supported(kind, B, L, F, H1, H2):
     return B == 0 or bool(_C.lib().ltr_mlp_listwise_plan(kind.loss, B, L, F, H1, H2))
 
 
+_mlp_rows_ws = {}        # (device index, B, L, F, H1, H2) -> ltr_mlp_rows_grad_workspace_bytes (grows with the CU count)
+
+
+def _mlp_rows_network(F, H1, H2):
+    """Networks the stand-alone MLP kernels take (include/ltr_mlp_rows.h), at any list length."""
+    return (0 < F <= MLP_MAX_FEATURES and F % 4 == 0 and 0 < H1 <= MLP_MAX_HIDDEN[0] and 0 < H2 <= MLP_MAX_HIDDEN[1])
+
+
+def _mlp_rows_scores(X, flat_params, H1, H2, nn):
+    """ltr_mlp_rows_scores_f32 on prepared arguments: (B, L) scores, 0 on the padded documents."""
+    B, L, F = X.shape
+    scores = torch.empty(B, L, dtype=torch.float32, device=X.device)
+    if B > 0:
+        with _C.device_ctx(X):
+            _C.check(_C.lib().ltr_mlp_rows_scores_f32(
+                _C.ptr(X), *[_C.ptr(t) for t in flat_params], _C.ptr(nn), B, L, F, H1, H2, _C.ptr(scores),
+                _C.stream_of(X)))
+    return scores
+
+
+def mlp_grad(xs, params, grad_scores, n=None, out=None):
+    """The parameter gradients of ``sum_{b, j < n[b]} grad_scores[b, j] * mlp(xs)[b, j]`` as one row-streaming MFMA
+    kernel plus the fixed-order reduction (ltr_mlp_rows_grad_f32; no autograd, any list length): what
+    ``scores.backward(grad_scores)`` leaves in the six ``.grad``s.  The activations are recomputed from ``xs``.
+
+    Args:
+        xs: (B, L, F) float32 features on the device, F a multiple of 4 and at most 224.
+        params: ``(W1, b1, W2, b2, W3, b3)`` in torch layout, hidden sizes up to (64, 16).
+        grad_scores: (B, L) or (B, L, 1); entries of padded documents are not read.
+        n: (B,) list lengths, or None: every document is real.
+        out: optional preallocated flat gradient buffer of ``ltr_mlp_param_count`` floats.
+
+    Returns:
+        ``(dW1, db1, dW2, db2, dW3, db3)``, views of one flat buffer as :func:`mlp_loss_step` returns them.
+    """
+    X = _prepare_features(xs)
+    B, L, F = X.shape
+    flat_params, H1, H2 = _flat_params(params, F)
+    if not _mlp_rows_network(F, H1, H2) or L == 0:
+        raise ValueError("the MLP row kernels take F <= %d with F %% 4 == 0, hidden <= %s and L >= 1; got L=%d F=%d "
+                         "hidden=(%d, %d)" % (MLP_MAX_FEATURES, MLP_MAX_HIDDEN, L, F, H1, H2))
+    dev = X.device
+    if grad_scores.numel() != B * L or grad_scores.device != dev:
+        raise ValueError("grad_scores must hold one value per document of xs, on its device")
+    g = grad_scores.detach().reshape(B, L)
+    if g.dtype is not torch.float32 or not g.is_contiguous():
+        g = g.float().contiguous()
+    nn = None if n is None else prepare_n(n, B)
+    lib = _C.lib()
+    P = _mlp_sizes_for(max(B, 1), F, H1, H2)[0]
+    flat = out if out is not None else torch.empty(P, dtype=torch.float32, device=dev)
+    if flat.numel() != P or flat.dtype != torch.float32 or not flat.is_contiguous():
+        raise ValueError("out must be a contiguous float32 tensor of %d elements" % P)
+    key = (dev.index, B, L, F, H1, H2)
+    with _C.device_ctx(X):
+        ws_bytes = _mlp_rows_ws.get(key)
+        if ws_bytes is None:                # (asked with X's device current: the grid follows its CU count)
+            ws_bytes = _mlp_rows_ws[key] = int(lib.ltr_mlp_rows_grad_workspace_bytes(B, L, F, H1, H2))
+        st = _C.stream_of(X)
+        ws = _mlp_workspace(dev, st, ws_bytes)
+        _C.check(lib.ltr_mlp_rows_grad_f32(
+            _C.ptr(X), *[_C.ptr(t) for t in flat_params], _C.ptr(g), _C.ptr(nn), B, L, F, H1, H2, _C.ptr(flat),
+            _C.ptr(ws), ws_bytes, st))
+    return _split_grads(flat, F, H1, H2)
+
+
+class _MLPScoreFunction(torch.autograd.Function):
+    """``mlp(xs)`` with parameter gradients: forward is the row score kernel, backward the row gradient kernel on
+    ``grad_scores`` (the activations are recomputed; nothing but the features and the parameters is kept).  The
+    features get no gradient (they are data; callers route an input that requires one to the torch layers)."""
+
+    @staticmethod
+    def forward(ctx, xs, n, *params):
+        xp, w1, extra = _pad_features(xs, params[0].detach())
+        X = _prepare_features(xp)
+        B, L, F = X.shape
+        flat_params, H1, H2 = _flat_params((w1,) + tuple(t.detach() for t in params[1:]), F)
+        nn = None if n is None else prepare_n(n, B)
+        scores = _mlp_rows_scores(X, flat_params, H1, H2, nn)
+        ctx.save_for_backward(X, nn if nn is not None else torch.empty(0, device=X.device), *flat_params)
+        ctx.has_n = nn is not None
+        ctx.extra = extra
+        ctx.shapes = [t.shape for t in params]
+        return scores.unsqueeze(-1)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_scores):
+        X, nn, *flat_params = ctx.saved_tensors
+        parts = list(mlp_grad(X, flat_params, grad_scores, nn if ctx.has_n else None))
+        if ctx.extra:
+            parts[0] = parts[0][:, :X.shape[2] - ctx.extra]
+        return (None, None) + tuple(g if g.shape == s else g.reshape(s) for g, s in zip(parts, ctx.shapes))
+
+
+def _mlp_rows_usable(xs, H1, H2):
+    """True where ``_MLPScoreFunction`` computes ``mlp(xs)``: an fp32 (B, L, F) batch on the device that needs no
+    gradient itself, a network within the kernels' limits (F counted after the padding to a multiple of 4)."""
+    return (torch.is_tensor(xs) and xs.dim() == 3 and xs.is_cuda and xs.dtype is torch.float32 and not xs.requires_grad
+            and xs.shape[1] > 0 and not torch.is_autocast_enabled()
+            and _mlp_rows_network((xs.shape[2] + 3) & ~3, H1, H2))
+
+
+# Set to False by scripts/bench_mlp_rows.py alone: the routes past the fused limits as they were before the row kernels
+# (torch layers + autograd), timed in the same process as the new ones.
+_MLP_ROWS_ENABLED = True
+
+
+def _mlp_step_pieces(X, flat_params, H1, H2, relevance, n, kind, sigma, grad_out, return_scores, return_loss_sum, out):
+    """mlp_loss_step past the limits of the fused kernels, as `_step_pieces` is for the Linear scorer: the row score
+    kernel, the stand-alone loss kernel (its d loss / d score scaled by `grad_out`), the row gradient kernel."""
+    B, L, F = X.shape
+    dev = X.device
+    r, nn = _labels_and_n(relevance, n, B, L, dev)
+    scores = _mlp_rows_scores(X, flat_params, H1, H2, nn)
+    with torch.enable_grad():
+        s = scores.unsqueeze(-1).requires_grad_(True)
+        lossv = (_listwise_pieces(s, r, nn, kind) if isinstance(kind, _ListwiseKind)
+                 else _pairwise_pieces(s, r, nn, kind, sigma))
+        go = (torch.full((B,), 1.0 / max(B, 1), dtype=torch.float32, device=dev) if grad_out is None
+              else grad_out.reshape(B).float())
+        (ds,) = torch.autograd.grad((lossv * go).sum(), s)
+    lossv = lossv.detach()
+    res = (lossv, mlp_grad(X, flat_params, ds, nn, out=out))
+    if return_scores:
+        res = res + (scores,)
+    if return_loss_sum:
+        res = res + (lossv.sum().reshape(1),)
+    return res
+
+
 def mlp_loss_step(xs, params, relevance, n, loss="hinge", grad_out=None, return_scores=False,
                   return_loss_sum=False, out=None):
     """One fused forward+backward step of ``loss_fn(mlp(xs), relevance, n)`` without autograd.
@@ -894,6 +1025,10 @@ def mlp_loss_step(xs, params, relevance, n, loss="hinge", grad_out=None, return_
             training loop, docs/source/getting-started.rst:95).
         out: optional preallocated flat gradient buffer of ``ltr_mlp_param_count`` floats.
 
+    Lists longer than the fused kernels hold (:func:`mlp_max_list_len`; a listwise loss off its plan) run as three
+    pieces instead of one launch -- the row score kernel, the stand-alone loss kernel, the row gradient kernel
+    (:func:`mlp_grad`) -- with the same results; a pairwise module needs ``long_lists=True`` past ``max_list_len()``.
+
     Returns:
         ``(loss[B], grads)`` with ``grads = (dW1, db1, dW2, db2, dW3, db3)`` views of one flat
         buffer (available as ``grads[0].base`` / the ``out`` argument), then optionally the scores
@@ -905,6 +1040,10 @@ def mlp_loss_step(xs, params, relevance, n, loss="hinge", grad_out=None, return_
     B, L, F = X.shape
     flat_params, H1, H2 = _flat_params(params, F)
     if not mlp_supported(L, F, H1, H2) or (listwise and not mlp_listwise_supported(kind, B, L, F, H1, H2)):
+        if _mlp_rows_network(F, H1, H2) and L > 0:
+            # past the list lengths the fused kernels hold (or their listwise plan): the same step from three pieces
+            return _mlp_step_pieces(X, flat_params, H1, H2, relevance, n, kind, sigma, grad_out, return_scores,
+                                    return_loss_sum, out)
         raise ValueError("fused MLP kernel takes L <= %d (F <= 144: %d), F <= %d with F %% 4 == 0, "
                          "hidden <= %s; got L=%d F=%d hidden=(%d, %d)"
                          % (MLP_MAX_LIST_LEN, MLP_MAX_LIST_LEN_NARROW, MLP_MAX_FEATURES,
@@ -958,10 +1097,14 @@ def mlp_loss_step(xs, params, relevance, n, loss="hinge", grad_out=None, return_
 def mlp_scores(xs, params, n=None):
     """``model(xs)`` of the guide's network as one fused kernel (no autograd): (B, L) float32
     scores for documents < n[b] and 0 for the padded ones; n=None scores every document.
-    Shapes outside the kernel's limits raise ValueError (see :func:`mlp_supported`)."""
+    Lists up to :func:`mlp_max_list_len` run the per-query kernel (ltr_mlp_scores_f32), longer ones the row kernel
+    (ltr_mlp_rows_scores_f32: any length).  Feature counts and hidden sizes outside the kernels' limits raise
+    ValueError (see :func:`mlp_supported`)."""
     X = _prepare_features(xs)
     B, L, F = X.shape
     flat_params, H1, H2 = _flat_params(params, F)
+    if L > mlp_max_list_len(F) and _mlp_rows_network(F, H1, H2):
+        return _mlp_rows_scores(X, flat_params, H1, H2, None if n is None else prepare_n(n, B))
     if not mlp_supported(L, F, H1, H2):
         raise ValueError("fused MLP kernel takes L <= %d (F <= 144: %d), F <= %d with F %% 4 == 0, "
                          "hidden <= %s" % (MLP_MAX_LIST_LEN, MLP_MAX_LIST_LEN_NARROW, MLP_MAX_FEATURES,
@@ -1032,14 +1175,22 @@ class _FusedMLPBase(torch.nn.Module):
         self.last_losses = None
 
     def score(self, xs, n=None):
-        """``model(xs)``: (B, L, 1) scores.  Under ``torch.no_grad()`` (evaluation) and for shapes
-        the fused kernel takes it is one launch (padded documents, when ``n`` is given, score 0);
-        otherwise the three ``nn.Linear`` layers, with autograd."""
-        if (not torch.is_grad_enabled() and xs.dim() == 3 and xs.is_cuda
-                and mlp_supported(xs.shape[1], (xs.shape[2] + 3) & ~3, self.l1.out_features,
-                                  self.l2.out_features)):
-            xp, w1, _ = _pad_features(xs, self.l1.weight.detach())
-            return mlp_scores(xp, (w1,) + self._params()[1:], n).unsqueeze(-1)
+        """``model(xs)``: (B, L, 1) scores (padded documents, when ``n`` is given, score 0) from the HIP kernels:
+        under ``torch.no_grad()`` (evaluation) one launch -- the per-query kernel up to :func:`mlp_max_list_len`
+        documents, the row kernel past it --, with gradients enabled the row score kernel, whose backward is the row
+        gradient kernel (:class:`MLPScorer`).  The three ``nn.Linear`` layers, with autograd, serve what those do not
+        take: more than 224 features, hidden sizes past (64, 16), features that require a gradient, other dtypes."""
+        H1, H2 = self.l1.out_features, self.l2.out_features
+        if torch.is_tensor(xs) and xs.dim() == 3 and xs.is_cuda:
+            if not torch.is_grad_enabled():
+                # evaluation: mlp_scores (the per-query kernel up to mlp_max_list_len documents, the row kernel past it)
+                F4, L = (xs.shape[2] + 3) & ~3, xs.shape[1]
+                if mlp_supported(L, F4, H1, H2) or (_MLP_ROWS_ENABLED and L > 0 and _mlp_rows_network(F4, H1, H2)):
+                    xp, w1, _ = _pad_features(xs, self.l1.weight.detach())
+                    return mlp_scores(xp, (w1,) + self._params()[1:], n).unsqueeze(-1)
+            elif _MLP_ROWS_ENABLED and _mlp_rows_usable(xs, H1, H2):
+                return _MLPScoreFunction.apply(xs, n, *self._params())
+        # everything else: the torch layers
         o1 = torch.nn.functional.relu(self.l1(xs))
         o2 = torch.nn.functional.relu(self.l2(o1))
         return self.l3(o2)
@@ -1059,7 +1210,7 @@ class _FusedMLPBase(torch.nn.Module):
                 xs, relevance, n, (self.kind, self.sigma), self.reduction == "mean", *self._params())
             self.last_losses = per_query
             return total
-        per_query = self._pieces(self.score(xs), relevance, n)
+        per_query = self._pieces(self.score(xs, n), relevance, n)
         self.last_losses = per_query.detach()
         return per_query.mean() if self.reduction == "mean" else per_query.sum()
 
@@ -1072,8 +1223,10 @@ class FusedMLPLoss(_FusedMLPBase):
     fills the six parameter gradients -- computed by one fused MFMA kernel.
 
     Feature counts that are not a multiple of 4 are zero-padded on the fly.  Shapes the kernel
-    does not take (lists longer than 256 -- 128 beyond 144 features --, more than 224 features, ...) run as the unfused
-    composition: rocBLAS layers + the HIP loss kernel.  ``score(xs)`` evaluates the
+    does not take run as the unfused composition.  Lists longer than 256 (128 beyond 144 features), of any length:
+    the row score kernel, the HIP loss kernel and the row gradient kernel (ltr_mlp_rows_*_f32, :class:`MLPScorer`) --
+    a loss module built with ``long_lists=True`` takes them past ``max_list_len()`` documents.  More than 224
+    features or hidden sizes past (64, 16): the torch layers + the HIP loss kernel.  ``score(xs)`` evaluates the
     network alone (for the metrics).  The seven pairwise losses; the listwise ones: :class:`FusedMLPListwiseLoss`.
     """
 
@@ -1083,8 +1236,7 @@ class FusedMLPLoss(_FusedMLPBase):
     _resolve = staticmethod(_resolve_pairwise_loss)
 
     def _pieces(self, scores, relevance, n):
-        from ._autograd import PairwiseLossFunction
-        return PairwiseLossFunction.apply(scores, relevance, n, int(self.kind), self.sigma, False)
+        return _pairwise_pieces(scores, relevance, n, self.kind, self.sigma)
 
 
 def _resolve_listwise_loss(loss):
@@ -1099,9 +1251,10 @@ class FusedMLPListwiseLoss(_FusedMLPBase):
     """:class:`FusedMLPLoss` for the listwise losses: ``loss`` is ``"listnet"`` (``"softmax"``), ``"listmle"``,
     ``ListwiseSoftmaxLoss()`` or ``ListMLELoss(k)``.  Same layers, ``state_dict``, ``score()``, ``last_losses`` and
     feature padding; the fused step is ``ltr_mlp_listwise_f32`` (include/ltr_listwise.h), ListNet or ListMLE in the
-    loss slot of the same two MFMA kernels.  Shapes its plan declines -- lists longer than 256 (128 beyond 144
-    features), hidden sizes past (64, 16), ... -- run as the unfused composition: ``score()`` with autograd and the
-    stand-alone listwise loss kernel.  ListMLE breaks label ties as :class:`pytorchltr_amd.loss.ListMLELoss` does."""
+    loss slot of the same two MFMA kernels.  Shapes its plan declines run as the unfused composition of ``score()``
+    with autograd and the stand-alone listwise loss kernel: lists longer than 256 (128 beyond 144 features), ListMLE
+    at any length, on the row score and row gradient kernels (ltr_mlp_rows_*_f32); hidden sizes past (64, 16) or more
+    than 224 features on the torch layers.  ListMLE breaks label ties as :class:`pytorchltr_amd.loss.ListMLELoss` does."""
 
     def __init__(self, in_features, loss="listnet", hidden=(50, 10), reduction="mean"):
         super().__init__(in_features, loss, hidden, reduction)
@@ -1113,3 +1266,33 @@ class FusedMLPListwiseLoss(_FusedMLPBase):
 
     def _pieces(self, scores, relevance, n):
         return _listwise_pieces(scores, relevance, n, self.kind)
+
+
+class MLPScorer(torch.nn.Module):
+    """The guide's scorer ``Linear(F, H1) / ReLU / Linear(H1, H2) / ReLU / Linear(H2, 1)`` on its own -- what
+    :class:`LinearScorer` is to ``nn.Linear(F, 1)``: ``loss_fn(scorer(xs), ys, n)`` with any loss, at any list length.
+    ``l1`` / ``l2`` / ``l3`` are ordinary ``torch.nn.Linear`` layers (the state_dict of :class:`FusedMLPLoss` and of
+    the guide's ``Model``).  ``forward(xs, n=None)`` returns (B, L, 1) scores from the row score kernel
+    (ltr_mlp_rows_scores_f32; with ``n`` the padded documents score 0 and their features are not read); its backward
+    runs the row gradient kernel on ``grad_scores`` and fills the six ``.grad``s (activations are recomputed, nothing
+    but the features is kept).  Feature counts that are not a multiple of 4 are zero-padded on the fly.  Features
+    that require a gradient, inputs that are not fp32, more than 224 features or hidden sizes past (64, 16) run the
+    torch layers.  CPU tensors are refused: there is no CPU fallback."""
+
+    def __init__(self, in_features, hidden=(50, 10)):
+        super().__init__()
+        self.in_features = in_features
+        self.l1 = torch.nn.Linear(in_features, hidden[0])
+        self.l2 = torch.nn.Linear(hidden[0], hidden[1])
+        self.l3 = torch.nn.Linear(hidden[1], 1)
+
+    def _params(self):
+        return (self.l1.weight, self.l1.bias, self.l2.weight, self.l2.bias, self.l3.weight, self.l3.bias)
+
+    def forward(self, xs, n=None):
+        _C.require_device(xs, "xs")
+        if _mlp_rows_usable(xs, self.l1.out_features, self.l2.out_features):
+            return _MLPScoreFunction.apply(xs, n, *self._params())
+        o1 = torch.nn.functional.relu(self.l1(xs))
+        o2 = torch.nn.functional.relu(self.l2(o1))
+        return self.l3(o2)
