@@ -800,6 +800,7 @@ MLP_MAX_LIST_LEN = 128           # feature rows wider than 144 floats
 MLP_MAX_LIST_LEN_NARROW = 256    # F <= 144
 MLP_NARROW_FEATURES = 144
 MLP_MAX_FEATURES = 224
+MLP_WIDE_MAX_FEATURES = 704      # the K-streamed kernels of include/ltr_mlp_wide.h (Yahoo: 699 -> 700)
 MLP_MAX_HIDDEN = (64, 16)
 
 
@@ -887,15 +888,23 @@ def _mlp_rows_network(F, H1, H2):
     return (0 < F <= MLP_MAX_FEATURES and F % 4 == 0 and 0 < H1 <= MLP_MAX_HIDDEN[0] and 0 < H2 <= MLP_MAX_HIDDEN[1])
 
 
-def _mlp_rows_scores(X, flat_params, H1, H2, nn):
-    """ltr_mlp_rows_scores_f32 on prepared arguments: (B, L) scores, 0 on the padded documents."""
+def _mlp_wide_network(F, H1, H2):
+    """Networks the wide-row MLP kernels are routed (include/ltr_mlp_wide.h): more features than the row kernels take,
+    up to 704, at any list length."""
+    return (MLP_MAX_FEATURES < F <= MLP_WIDE_MAX_FEATURES and F % 4 == 0
+            and 0 < H1 <= MLP_MAX_HIDDEN[0] and 0 < H2 <= MLP_MAX_HIDDEN[1])
+
+
+def _mlp_rows_scores(X, flat_params, H1, H2, nn, wide=False):
+    """ltr_mlp_rows_scores_f32 (`wide`: ltr_mlp_wide_scores_f32) on prepared arguments: (B, L) scores, 0 on the
+    padded documents."""
     B, L, F = X.shape
     scores = torch.empty(B, L, dtype=torch.float32, device=X.device)
     if B > 0:
+        fn = _C.lib().ltr_mlp_wide_scores_f32 if wide else _C.lib().ltr_mlp_rows_scores_f32
         with _C.device_ctx(X):
-            _C.check(_C.lib().ltr_mlp_rows_scores_f32(
-                _C.ptr(X), *[_C.ptr(t) for t in flat_params], _C.ptr(nn), B, L, F, H1, H2, _C.ptr(scores),
-                _C.stream_of(X)))
+            _C.check(fn(_C.ptr(X), *[_C.ptr(t) for t in flat_params], _C.ptr(nn), B, L, F, H1, H2, _C.ptr(scores),
+                        _C.stream_of(X)))
     return scores
 
 
@@ -920,6 +929,12 @@ def mlp_grad(xs, params, grad_scores, n=None, out=None):
     if not _mlp_rows_network(F, H1, H2) or L == 0:
         raise ValueError("the MLP row kernels take F <= %d with F %% 4 == 0, hidden <= %s and L >= 1; got L=%d F=%d "
                          "hidden=(%d, %d)" % (MLP_MAX_FEATURES, MLP_MAX_HIDDEN, L, F, H1, H2))
+    return _mlp_grad_call(X, flat_params, H1, H2, grad_scores, n, out, False)
+
+
+def _mlp_grad_call(X, flat_params, H1, H2, grad_scores, n, out, wide):
+    """ltr_mlp_rows_grad_f32 (`wide`: ltr_mlp_wide_grad_f32) behind the shape checks of its caller."""
+    B, L, F = X.shape
     dev = X.device
     if grad_scores.numel() != B * L or grad_scores.device != dev:
         raise ValueError("grad_scores must hold one value per document of xs, on its device")
@@ -932,23 +947,50 @@ def mlp_grad(xs, params, grad_scores, n=None, out=None):
     flat = out if out is not None else torch.empty(P, dtype=torch.float32, device=dev)
     if flat.numel() != P or flat.dtype != torch.float32 or not flat.is_contiguous():
         raise ValueError("out must be a contiguous float32 tensor of %d elements" % P)
-    key = (dev.index, B, L, F, H1, H2)
+    key = (dev.index, B, L, F, H1, H2, wide)
+    ws_fn, grad_fn = ((lib.ltr_mlp_wide_grad_workspace_bytes, lib.ltr_mlp_wide_grad_f32) if wide
+                      else (lib.ltr_mlp_rows_grad_workspace_bytes, lib.ltr_mlp_rows_grad_f32))
     with _C.device_ctx(X):
         ws_bytes = _mlp_rows_ws.get(key)
         if ws_bytes is None:                # (asked with X's device current: the grid follows its CU count)
-            ws_bytes = _mlp_rows_ws[key] = int(lib.ltr_mlp_rows_grad_workspace_bytes(B, L, F, H1, H2))
+            ws_bytes = _mlp_rows_ws[key] = int(ws_fn(B, L, F, H1, H2))
         st = _C.stream_of(X)
         ws = _mlp_workspace(dev, st, ws_bytes)
-        _C.check(lib.ltr_mlp_rows_grad_f32(
+        _C.check(grad_fn(
             _C.ptr(X), *[_C.ptr(t) for t in flat_params], _C.ptr(g), _C.ptr(nn), B, L, F, H1, H2, _C.ptr(flat),
             _C.ptr(ws), ws_bytes, st))
     return _split_grads(flat, F, H1, H2)
 
 
+def _mlp_wide_checked(xs, params):
+    X = _prepare_features(xs)
+    B, L, F = X.shape
+    flat_params, H1, H2 = _flat_params(params, F)
+    if not _mlp_wide_network(F, H1, H2) or L == 0:
+        raise ValueError("the wide-row MLP kernels take %d < F <= %d with F %% 4 == 0, hidden <= %s and L >= 1; got L=%d "
+                         "F=%d hidden=(%d, %d)" % (MLP_MAX_FEATURES, MLP_WIDE_MAX_FEATURES, MLP_MAX_HIDDEN, L, F, H1, H2))
+    return X, flat_params, H1, H2
+
+
+def mlp_wide_scores(xs, params, n=None):
+    """:func:`mlp_scores` for feature rows wider than 224 floats, up to 704 (ltr_mlp_wide_scores_f32: the feature
+    dimension is streamed in chunks; any list length; no autograd): (B, L) float32 scores for documents < n[b] and 0 for
+    the padded ones, whose features are not read; n=None scores every document.  Other networks raise ValueError."""
+    X, flat_params, H1, H2 = _mlp_wide_checked(xs, params)
+    return _mlp_rows_scores(X, flat_params, H1, H2, None if n is None else prepare_n(n, X.shape[0]), wide=True)
+
+
+def mlp_wide_grad(xs, params, grad_scores, n=None, out=None):
+    """:func:`mlp_grad` for feature rows wider than 224 floats, up to 704 (ltr_mlp_wide_grad_f32): same arguments, same
+    ``(dW1, db1, dW2, db2, dW3, db3)`` views of one flat buffer.  Other networks raise ValueError."""
+    X, flat_params, H1, H2 = _mlp_wide_checked(xs, params)
+    return _mlp_grad_call(X, flat_params, H1, H2, grad_scores, n, out, True)
+
+
 class _MLPScoreFunction(torch.autograd.Function):
     """``mlp(xs)`` with parameter gradients: forward is the row score kernel, backward the row gradient kernel on
-    ``grad_scores`` (the activations are recomputed; nothing but the features and the parameters is kept).  The
-    features get no gradient (they are data; callers route an input that requires one to the torch layers)."""
+    ``grad_scores`` (the activations are recomputed; nothing but the features and the parameters is kept); rows wider
+    than 224 features run the wide-row pair of kernels (ltr_mlp_wide_*_f32).  The features get no gradient (they are data; callers route an input that requires one to the torch layers)."""
 
     @staticmethod
     def forward(ctx, xs, n, *params):
@@ -957,7 +999,7 @@ class _MLPScoreFunction(torch.autograd.Function):
         B, L, F = X.shape
         flat_params, H1, H2 = _flat_params((w1,) + tuple(t.detach() for t in params[1:]), F)
         nn = None if n is None else prepare_n(n, B)
-        scores = _mlp_rows_scores(X, flat_params, H1, H2, nn)
+        scores = _mlp_rows_scores(X, flat_params, H1, H2, nn, wide=_mlp_wide_network(F, H1, H2))
         ctx.save_for_backward(X, nn if nn is not None else torch.empty(0, device=X.device), *flat_params)
         ctx.has_n = nn is not None
         ctx.extra = extra
@@ -968,7 +1010,9 @@ class _MLPScoreFunction(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad_scores):
         X, nn, *flat_params = ctx.saved_tensors
-        parts = list(mlp_grad(X, flat_params, grad_scores, nn if ctx.has_n else None))
+        H1, H2 = flat_params[0].shape[0], flat_params[2].shape[0]
+        parts = list(_mlp_grad_call(X, flat_params, H1, H2, grad_scores, nn if ctx.has_n else None, None,
+                                    _mlp_wide_network(X.shape[2], H1, H2)))
         if ctx.extra:
             parts[0] = parts[0][:, :X.shape[2] - ctx.extra]
         return (None, None) + tuple(g if g.shape == s else g.reshape(s) for g, s in zip(parts, ctx.shapes))
@@ -979,12 +1023,16 @@ def _mlp_rows_usable(xs, H1, H2):
     gradient itself, a network within the kernels' limits (F counted after the padding to a multiple of 4)."""
     return (torch.is_tensor(xs) and xs.dim() == 3 and xs.is_cuda and xs.dtype is torch.float32 and not xs.requires_grad
             and xs.shape[1] > 0 and not torch.is_autocast_enabled()
-            and _mlp_rows_network((xs.shape[2] + 3) & ~3, H1, H2))
+            and (_mlp_rows_network((xs.shape[2] + 3) & ~3, H1, H2)
+                 or (_MLP_WIDE_ENABLED and _mlp_wide_network((xs.shape[2] + 3) & ~3, H1, H2))))
 
 
 # Set to False by scripts/bench_mlp_rows.py alone: the routes past the fused limits as they were before the row kernels
 # (torch layers + autograd), timed in the same process as the new ones.
 _MLP_ROWS_ENABLED = True
+# Set to False by scripts/bench_mlp_wide.py alone: rows wider than 224 features on the torch layers, as before the
+# wide-row kernels, timed in the same process as the new route.
+_MLP_WIDE_ENABLED = True
 
 
 def _mlp_step_pieces(X, flat_params, H1, H2, relevance, n, kind, sigma, grad_out, return_scores, return_loss_sum, out):
@@ -1178,8 +1226,10 @@ class _FusedMLPBase(torch.nn.Module):
         """``model(xs)``: (B, L, 1) scores (padded documents, when ``n`` is given, score 0) from the HIP kernels:
         under ``torch.no_grad()`` (evaluation) one launch -- the per-query kernel up to :func:`mlp_max_list_len`
         documents, the row kernel past it --, with gradients enabled the row score kernel, whose backward is the row
-        gradient kernel (:class:`MLPScorer`).  The three ``nn.Linear`` layers, with autograd, serve what those do not
-        take: more than 224 features, hidden sizes past (64, 16), features that require a gradient, other dtypes."""
+        gradient kernel (:class:`MLPScorer`).  Rows wider than 224 features, up to 704, take the wide-row kernels
+        (ltr_mlp_wide_*_f32) in both cases, at every list length.  The three ``nn.Linear`` layers, with autograd, serve
+        what those do not take: more than 704 features, hidden sizes past (64, 16), features that require a gradient,
+        other dtypes, autocast."""
         H1, H2 = self.l1.out_features, self.l2.out_features
         if torch.is_tensor(xs) and xs.dim() == 3 and xs.is_cuda:
             if not torch.is_grad_enabled():
@@ -1188,7 +1238,11 @@ class _FusedMLPBase(torch.nn.Module):
                 if mlp_supported(L, F4, H1, H2) or (_MLP_ROWS_ENABLED and L > 0 and _mlp_rows_network(F4, H1, H2)):
                     xp, w1, _ = _pad_features(xs, self.l1.weight.detach())
                     return mlp_scores(xp, (w1,) + self._params()[1:], n).unsqueeze(-1)
-            elif _MLP_ROWS_ENABLED and _mlp_rows_usable(xs, H1, H2):
+                if (_MLP_WIDE_ENABLED and L > 0 and _mlp_wide_network(F4, H1, H2) and xs.dtype is torch.float32
+                        and not torch.is_autocast_enabled()):
+                    xp, w1, _ = _pad_features(xs, self.l1.weight.detach())
+                    return mlp_wide_scores(xp, (w1,) + self._params()[1:], n).unsqueeze(-1)
+            elif _mlp_rows_usable(xs, H1, H2) and (_MLP_ROWS_ENABLED or _mlp_wide_network((xs.shape[2] + 3) & ~3, H1, H2)):
                 return _MLPScoreFunction.apply(xs, n, *self._params())
         # everything else: the torch layers
         o1 = torch.nn.functional.relu(self.l1(xs))
@@ -1226,7 +1280,8 @@ class FusedMLPLoss(_FusedMLPBase):
     does not take run as the unfused composition.  Lists longer than 256 (128 beyond 144 features), of any length:
     the row score kernel, the HIP loss kernel and the row gradient kernel (ltr_mlp_rows_*_f32, :class:`MLPScorer`) --
     a loss module built with ``long_lists=True`` takes them past ``max_list_len()`` documents.  More than 224
-    features or hidden sizes past (64, 16): the torch layers + the HIP loss kernel.  ``score(xs)`` evaluates the
+    features, up to 704 (Yahoo: 699), at every list length: the same three pieces on the wide-row kernels
+    (ltr_mlp_wide_*_f32).  More than 704 features or hidden sizes past (64, 16): the torch layers + the HIP loss kernel.  ``score(xs)`` evaluates the
     network alone (for the metrics).  The seven pairwise losses; the listwise ones: :class:`FusedMLPListwiseLoss`.
     """
 
@@ -1253,8 +1308,9 @@ class FusedMLPListwiseLoss(_FusedMLPBase):
     feature padding; the fused step is ``ltr_mlp_listwise_f32`` (include/ltr_listwise.h), ListNet or ListMLE in the
     loss slot of the same two MFMA kernels.  Shapes its plan declines run as the unfused composition of ``score()``
     with autograd and the stand-alone listwise loss kernel: lists longer than 256 (128 beyond 144 features), ListMLE
-    at any length, on the row score and row gradient kernels (ltr_mlp_rows_*_f32); hidden sizes past (64, 16) or more
-    than 224 features on the torch layers.  ListMLE breaks label ties as :class:`pytorchltr_amd.loss.ListMLELoss` does."""
+    at any length, on the row score and row gradient kernels (ltr_mlp_rows_*_f32); more than 224 features, up to 704,
+    at every list length on the wide-row kernels (ltr_mlp_wide_*_f32); hidden sizes past (64, 16) or more than 704
+    features on the torch layers.  ListMLE breaks label ties as :class:`pytorchltr_amd.loss.ListMLELoss` does."""
 
     def __init__(self, in_features, loss="listnet", hidden=(50, 10), reduction="mean"):
         super().__init__(in_features, loss, hidden, reduction)
@@ -1276,8 +1332,9 @@ class MLPScorer(torch.nn.Module):
     (ltr_mlp_rows_scores_f32; with ``n`` the padded documents score 0 and their features are not read); its backward
     runs the row gradient kernel on ``grad_scores`` and fills the six ``.grad``s (activations are recomputed, nothing
     but the features is kept).  Feature counts that are not a multiple of 4 are zero-padded on the fly.  Features
-    that require a gradient, inputs that are not fp32, more than 224 features or hidden sizes past (64, 16) run the
-    torch layers.  CPU tensors are refused: there is no CPU fallback."""
+    that require a gradient, inputs that are not fp32, more than 704 features or hidden sizes past (64, 16) run the
+    torch layers; 228 to 704 features (Yahoo: 699, padded to 700) run the wide-row kernels (ltr_mlp_wide_*_f32), which
+    stream the feature dimension in chunks.  CPU tensors are refused: there is no CPU fallback."""
 
     def __init__(self, in_features, hidden=(50, 10)):
         super().__init__()
