@@ -53,12 +53,20 @@ class LambdaARPLoss2(LambdaLoss):
 
 class LambdaNDCGLoss1(LambdaLoss):
     r"""NDCG Loss 1 (reference :143-173): exponent :math:`G_{\pi_i} / D_i` with
-    :math:`G = (2^y - 1) / \mathrm{maxDCG}` and :math:`D_i = \log_2(2 + i)` (0-based rank)."""
+    :math:`G = (2^y - 1) / \mathrm{maxDCG}` and :math:`D_i = \log_2(2 + i)` (0-based rank).
+
+    Negative integer grades take the float formula :math:`2^y - 1` (a grade of -1 has the gain -0.5, whatever the label
+    dtype); the reference computes ``2 ** y`` on the integer tensor, where ``2 ** -1 == 0`` and the gain is -1.  Float
+    labels of the same values agree with the reference."""
     _kind = _C.NDCG1
 
 
 class LambdaNDCGLoss2(LambdaLoss):
     r"""NDCG Loss 2 (reference :176-218): exponent :math:`\delta_{ij} |G_{\pi_i} - G_{\pi_j}|`
     over pairs with :math:`y_i > y_j`, :math:`\delta_{ij} = |1/D_{|i-j|} - 1/D_{|i-j|+1}|`,
-    :math:`D_k = \log_2(2 + k)` as the reference code (not its docstring) has it."""
+    :math:`D_k = \log_2(2 + k)` as the reference code (not its docstring) has it.
+
+    Negative integer grades take the float formula :math:`2^y - 1` (a grade of -1 has the gain -0.5, whatever the label
+    dtype); the reference computes ``2 ** y`` on the integer tensor, where ``2 ** -1 == 0`` and the gain is -1.  Float
+    labels of the same values agree with the reference."""
     _kind = _C.NDCG2
