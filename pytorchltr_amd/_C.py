@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI in ``include/ltr_hip.h``, ``include/ltr_eval.h``, ``include/ltr_listwise.h``,
-``include/ltr_longpair.h``, ``include/ltr_mlp_rows.h`` and ``include/ltr_mlp_wide.h`` (pytorchltr_amd/csrc/libltr_hip.so).
+``include/ltr_longpair.h``, ``include/ltr_mlp_rows.h``, ``include/ltr_mlp_wide.h`` and ``include/ltr_sched.h`` (pytorchltr_amd/csrc/libltr_hip.so).
 
 PyTorch supplies device memory and the current HIP stream; every call here hands raw device
 pointers to the library.  The library must exist -- there is deliberately no fallback.
@@ -159,6 +159,12 @@ LONGPAIR_SIGNATURES = {
     "ltr_debug_long_pairs_all": (_i, [_i]),
 }
 
+# name -> (restype, argtypes); mirrors include/ltr_sched.h (hooks of the list-length scheduling and the lazy launch's hold-backs)
+SCHED_SIGNATURES = {
+    "ltr_debug_sched_slots": (_i, [_i, _i, _i, _i, _vp, _vp]),
+    "ltr_debug_lazy_holdback": (_i, [_i]),
+}
+
 _lib = None
 
 
@@ -193,7 +199,8 @@ def lib():
         handle = _Library(LIB_PATH)
         for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(EVAL_SIGNATURES.items())
                                           + list(LISTWISE_SIGNATURES.items()) + list(LONGPAIR_SIGNATURES.items())
-                                          + list(MLP_ROWS_SIGNATURES.items()) + list(MLP_WIDE_SIGNATURES.items())):
+                                          + list(MLP_ROWS_SIGNATURES.items()) + list(MLP_WIDE_SIGNATURES.items())
+                                          + list(SCHED_SIGNATURES.items())):
             if name.startswith("ltr_debug_") and not hasattr(handle, name):
                 continue                     # a production build (-DLTR_NO_DEBUG_HOOKS) leaves the test hooks out
             fn = getattr(handle, name)       # AttributeError if the symbol is missing

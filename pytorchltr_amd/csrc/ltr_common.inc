@@ -126,28 +126,81 @@ __device__ __forceinline__ int clamp_n(int64_t n, int L)
 constexpr int kSchedMaxPerCu = 4;        // register-tile kernel (B = 8 x #CUs: 22.1 -> 23.9 us with it)
 constexpr int kLossSchedMaxPerCu = 16;   // loss kernel, general fused kernel
 constexpr int kSchedLowBits = 3;         // low bits of n the selection ignores
+
+// Block id -> place in the list-length order: the sample group and the member rank (0 = the group's longest list) block `id` of a
+// grid of `nred` leading workgroups without a query + B query workgroups takes.  Host and device: the ONE copy of the arithmetic
+// (the CPU tier enumerates it through ltr_debug_sched_slots).  A bijection of the ids nred .. nred + B - 1 onto the
+// (group, rank < the group's size) pairs for every B, G = ceil(B / 64), cus >= 0 and nred >= 0.
+struct SchedSlot { int group, rank; };
+// (nred > 0, a lazy launch: block id i sits on CU slot i mod cus and the reducers -- ids below nred, fewer than the CUs -- leave
+// theirs first, so the query workgroups with i mod cus < nred share a CU with a reducer at work or take its place: the QUIET ones)
+// id = t * cus + r for id < 8 cus, by three compares: a grid is a few rounds of `cus` workgroups, and an integer division is some
+// forty scalar instructions and a reciprocal's latency in front of the tile burst of every workgroup (a subtraction LOOP is
+// turned back into that division by the compiler)
+__host__ __device__ inline int sched_round(int id, int cus, int &r)
+{
+    int t = 0;
+    r = id;
+    if (r >= 4 * cus) { r -= 4 * cus; t += 4; }
+    if (r >= 2 * cus) { r -= 2 * cus; t += 2; }
+    if (r >= cus) { r -= cus; t += 1; }
+    return t;
+}
+__host__ __device__ inline bool sched_quiet(int id, int cus, int nred)
+{
+    if (nred <= 0 || nred >= cus || id < cus) return false;
+    int r;
+    sched_round(id, cus, r);
+    return r < nred;
+}
+__host__ __device__ inline SchedSlot sched_slot(int id, int B, int G, int cus, int nred)
+{
+    int pos = id - nred;
+    // (the quiet workgroups take the last places of the order -- the batch's shortest lists --, everybody else the places in front
+    // of them, both in id order)
+    if (nred > 0 && nred < cus) {
+        int r, re;
+        const int t = sched_round(id, cus, r);
+        const int below = t > 0 ? (t - 1) * nred + (r < nred ? r : nred) : 0;      // quiet ids below `id`
+        if (t > 0 && r < nred) {
+            const int te = sched_round(nred + B, cus, re);
+            const int Q = te > 0 ? (te - 1) * nred + (re < nred ? re : nred) : 0;  // quiet ids in the grid
+            pos = B - Q + below;
+        } else {
+            pos -= below;
+        }
+    }
+    const int u = pos >> 3;
+    int jp = u / G;
+    SchedSlot s;
+    s.group = u - jp * G;
+    // (cus > 0: snake over the rounds of one workgroup per CU.  8 G block ids take one eighth of every group -- `jp`,
+    // the jp-th longest eighth --, a round of `cus` CUs is `per` of those steps, and a CU hosts ids i, i + #CUs, ...:
+    // dealt straight, the CUs of the first half of every round get the longer half of EVERY round's lists (B = 1024,
+    // n ~ U[1,128]: 288 rows against 224 per CU); with the odd rounds dealt backwards every CU's queries sum to the same bytes)
+    if (cus > 0) {
+        const int per = cus / (8 * G);                           // steps per round (256 CUs, G = 16: 2)
+        if (per >= 2) {
+            const int rd = jp / per, base = rd * per;
+            const int back = (rd ^ (rd >> 1)) & 1;               // straight, back, back, straight: the last round ends on the shortest lists
+            // (only a round in which EVERY group is complete: dealt backwards, an incomplete one sends blocks to member ranks its
+            // short groups do not have -- B = 385 .. 447 and 449 .. 511 on 256 CUs took a query index no lane had written)
+            if (back && (base + per) * 8 * G <= B) jp = base + (per - 1 - (jp - base));
+        }
+    }
+    s.rank = jp * 8 + (pos & 7);
+    return s;
+}
+
 __device__ __forceinline__ int sched_query_sampled(const int64_t *__restrict__ n, int B, int L, int G, int tid,
-                                                   int &nb_out, int pos, int round_cus = 0)
+                                                   int &nb_out, int pos, int round_cus = 0, int nred = 0)
 {
     __shared__ int s_sel[2];
     if (tid < 64) {
         const int lane = tid;
-        const int u = pos >> 3;
-        int jp = u / G;
-        const int gam = u - jp * G;
-        // (round_cus > 0: snake over the rounds of one workgroup per CU.  8 G block ids take one eighth of every group -- `jp`,
-        // the jp-th longest eighth --, a round of round_cus CUs is `per` of those steps, and a CU hosts ids i, i + #CUs, ...:
-        // dealt straight, the CUs of the first half of every round get the longer half of EVERY round's lists (B = 1024,
-        // n ~ U[1,128]: 288 rows against 224 per CU); with the odd rounds dealt backwards every CU's queries sum to the same bytes)
-        if (round_cus > 0) {
-            const int per = round_cus / (8 * G);                 // steps per round (256 CUs, G = 16: 2)
-            if (per >= 2) {
-                const int rd = jp / per, base = rd * per;
-                const int back = (rd ^ (rd >> 1)) & 1;           // straight, back, back, straight: the last round ends on the shortest lists
-                if (back && base + per <= 8) jp = base + (per - 1 - (jp - base));
-            }
-        }
-        int rho = jp * 8 + (pos & 7);                            // this block's member number
+        const SchedSlot slot = sched_slot(pos, B, G, round_cus, nred);
+        const int gam = slot.group;
+        int rho = slot.rank;                                     // this block's member number
         const int id = ((lane >> 3) * G + gam) * 8 + (lane & 7); // member `lane` of the group
         unsigned long long cand = __ballot(id < B);              // a prefix of the lanes (ids grow with lane)
         const int key = clamp_n(n[min(id, B - 1)], L);

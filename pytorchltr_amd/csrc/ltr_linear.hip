@@ -9,4 +9,5 @@
 #include <thread>
 
 #include "ltr_common.inc"
+#include "ltr_sched.h"
 #include "ltr_linear.inc"

@@ -617,16 +617,26 @@ __device__ __forceinline__ void linear_regtile2_body(const LinearParams &p)
         LTR_KA(pend_wptr); LTR_KA(pend_wstride); LTR_KA(pend_general); LTR_KA(pend_W); LTR_KA(pend_bias); LTR_KA(pend_out);
         LTR_KA(pend_gran); LTR_KA(pend_gstride); LTR_KA(pend_tag); LTR_KA(status); LTR_KA(spin_limit); LTR_KA(pend_mb);
 #undef LTR_KA
+        LTR_TRACE_REDUCER(0);
         linear_lazy_reduce(pr, reinterpret_cast<float *>(smem), TT);
+        LTR_TRACE_REDUCER(1);
         return;
     }
     // (a head start for the reducers: their scattered 4-byte loads take microseconds once a thousand tile bursts are in the
     // queues in front of them, and every workgroup then waits for the weights -- C2 14.9 -> 15.9 us; on an idle memory
     // system they are done in about one, which is what the queries' bursts are held back for)
-    if (lazy) for (int i = 0; i < p.pend_sleep; ++i) __builtin_amdgcn_s_sleep(8);
+    // (two hold-backs in one word: the low byte for everybody, the next one -- != 0: the quiet rule is on -- for the QUIET
+    // workgroups, the ones on the reducers' own CUs, sched_quiet, whose bursts would sit in the very memory queue the reducer's
+    // loads and granule stores go through; they carry the batch's shortest lists, sched_slot, and can afford to start last)
+    const int qhold = lazy ? p.pend_sleep >> 8 : 0;
+    if (lazy) {
+        const int hold = (qhold && sched_quiet((int)blockIdx.x, p.sched >> 16, p.pend_nred)) ? qhold : (p.pend_sleep & 0xff);
+        for (int i = 0; i < hold; ++i) __builtin_amdgcn_s_sleep(8);
+    }
     int b, nb;
     if (p.sched) {
-        b = sched_query_sampled(p.n, p.B, L, p.sched & 0xffff, (int)threadIdx.x, nb, qblock, p.sched >> 16);
+        b = sched_query_sampled(p.n, p.B, L, p.sched & 0xffff, (int)threadIdx.x, nb, qhold ? (int)blockIdx.x : qblock, p.sched >> 16,
+                                qhold ? p.pend_nred : 0);
     } else {
         b = qblock;
         nb = clamp_n(p.n[b], L);
@@ -691,6 +701,7 @@ __device__ __forceinline__ void linear_regtile2_body(const LinearParams &p)
     }
     if (KIND == LTR_NDCG1 || KIND == LTR_NDCG2)
         for (int m = tid; m < 2 * L4; m += T) q.rank_s[m] = 0;
+    LTR_STAMP2(7);
 
     if (lazy) {
         // the weights: F + 2 granules (columns, bias, the losses' column -- read, so that nothing of the pending batch is
@@ -704,6 +715,7 @@ __device__ __forceinline__ void linear_regtile2_body(const LinearParams &p)
             asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
             linear_lazy_poll_weights<T>(p, wst, xcc, tid);
             lds_barrier();
+            LTR_STAMP2(11);
             w = reinterpret_cast<const float4 *>(wst)[c];
             bias = wst[F];
         }
@@ -1415,6 +1427,19 @@ LinearPlan plan_linear(int kind, int B, int L, int F, int vec, bool fast, int la
     else if (!cluster_first && choose_cluster_shape(kind, B, L, F, pl.cs, labels)) pl.family = LTR_PLAN_CLUSTER;
     return pl;
 }
+
+// hold-backs of a lazy launch's query workgroups in units of 512 cycles (LinearParams::pend_sleep): without quiet workgroups,
+// and with them -- everybody else's and the quiet ones' own (profiles/r07_lazy_quiet.txt)
+constexpr int kLazyHoldPlain = 2, kLazyHold = 0, kLazyHoldQuiet = 8;
+inline int &lazy_holdback() { static int v = -1; return v; }       // ltr_debug_lazy_holdback: >= 0 replaces the packed word
+// Where the quiet rule was measured to pay (profiles/r07_lazy_quiet.txt): the hinge kinds -- their launch is bound by the memory
+// system all CUs share, the others by their most loaded CU, which the reducers' CUs taking the shortest lists unbalances (C3,
+// LambdaNDCG2: 17.3 -> 18.2 us; logistic 14.4 -> 15.2) --, a grid that fills the CUs (a fourth workgroup on some: at 600 queries
+// the quiet ones' wait is the launch's tail, 10.4 -> 11.0) and rows of at least 64 features (8 features: 19.8 -> 20.1)
+inline bool lazy_quiet_pays(int kind, int B, int F)
+{
+    return (kind == LTR_HINGE || kind == LTR_DCG_HINGE) && B > 3 * device_cu_count() && F >= 64;
+}
 }  // namespace
 
 extern "C" {
@@ -1499,7 +1524,7 @@ inline float pending_weight(float scale, int pend_B) { return scale > 0.f ? scal
 // rows in, for the lazy step's launch and for the flush alike.  queries: the lazy step -- its queries' workgroups hold their
 // bursts back and poll the reducers' granules, so the status word and the spin limit are always set; false: the flush, the
 // reducers alone, which only wait on the all-reduce of a mailbox.
-void set_pending_update(LinearParams &p, const LazyRequest &r, int F, bool queries, hipStream_t stream)
+void set_pending_update(LinearParams &p, const LazyRequest &r, int F, bool queries, hipStream_t stream, bool quiet_pays = false)
 {
     p.pend_B = r.pend_B; p.pend_g = r.pend_g; p.pend_lr = r.lr; p.pend_w = pending_weight(r.scale, r.pend_B);
     p.pend_mb = r.mb; p.pend_wptr = r.scale_dev; p.pend_wstride = r.scale_stride;
@@ -1508,7 +1533,11 @@ void set_pending_update(LinearParams &p, const LazyRequest &r, int F, bool queri
     // four columns per reducer + the losses' one
     p.pend_nred = (F + 1 + 3) / 4 + 1;
     p.pend_general = (p.pend_mb || p.pend_wptr || !p.pend_W) ? 1 : 0;
-    p.pend_sleep = queries ? 2 : 0;     // (a reducer sums ~1024 rows at most, whatever the batch size)
+    // (a reducer sums ~1024 rows at most, whatever the batch size.  Low byte: every query workgroup's hold-back; next byte: the
+    // quiet ones' -- under the list-length order with fewer reducers than CUs, sched_quiet, on the kinds where it pays; 0: nobody
+    // is quiet)
+    const bool quiet = quiet_pays && p.sched != 0 && p.pend_nred < (p.sched >> 16);
+    p.pend_sleep = !queries ? 0 : lazy_holdback() >= 0 ? lazy_holdback() : quiet ? kLazyHoldQuiet << 8 | kLazyHold : kLazyHoldPlain;
     if (queries || r.mb) {
         p.status = status_device_ptr(stream);
         p.spin_limit = cluster_force_timeout() ? -1 : (r.mb ? 0x7fffffff : (1 << 22));
@@ -1558,7 +1587,8 @@ int linear_partials_launch(int kind, float sigma, const float *X, const float *W
         // bound by their most loaded CU.  EXPERIMENTS.md round 6)
         if (p.sched) p.sched |= device_cu_count() << 16;
         if (lazy) p.part_g = lazy->part_g;
-        if (lazy && lazy->pend_B > 0) set_pending_update(p, *lazy, F, true, (hipStream_t)stream);
+        p.scores_out = LTR_TRACE_BUFFER(p.scores_out);      // (trace builds: the lazy step's launches have no score matrix to stamp)
+        if (lazy && lazy->pend_B > 0) set_pending_update(p, *lazy, F, true, (hipStream_t)stream, lazy_quiet_pays(kind, B, F));
         return launch_regtile(kind, p, pl.rs, (hipStream_t)stream);
     case LTR_PLAN_PARTS:
         p.msplit = 0;
@@ -1579,6 +1609,31 @@ int linear_partials_launch(int kind, float sigma, const float *X, const float *W
                       : launch_linear<1>(kind, p, s, (hipStream_t)stream);
 }
 }  // namespace
+
+LTR_DEBUG_HOOK int ltr_debug_sched_slots(int B, int G, int cus, int nred, int *group, int *rank)
+{
+    if (B <= 0 || G <= 0 || cus < 0 || nred < 0) return LTR_ERR_SHAPE;
+    if (nred > 0 && nred < cus && (long long)B + nred >= 8ll * cus) return LTR_ERR_SHAPE;        // (sched_round)
+    if (!group || !rank) return LTR_ERR_NULL;
+    for (int i = 0; i < B; ++i) {
+        const SchedSlot s = sched_slot(nred + i, B, G, cus, nred);
+        group[i] = s.group;
+        rank[i] = s.rank;
+    }
+    return LTR_OK;
+}
+
+#ifdef LTR_TRACE
+// Trace builds only: the stamp buffer of the launches that are given no score matrix (the lazy step's), or null.
+int ltr_debug_trace_buffer(void *buf) { trace_buffer() = (float *)buf; return LTR_OK; }
+#endif
+
+LTR_DEBUG_HOOK int ltr_debug_lazy_holdback(int packed)
+{
+    const int old = lazy_holdback();
+    lazy_holdback() = packed < 0 ? -1 : (packed & 0xffff);
+    return old;
+}
 
 // Measurement aid (bench.py `roofline`): the next launch of the 512-thread register tile on this thread records `start` right
 // before and `stop` right behind the kernel (hipExtLaunchKernelGGL) -- the kernel's own duration, as a profiler sees it.
