@@ -896,12 +896,15 @@ def _mlp_wide_network(F, H1, H2):
 
 
 def _mlp_rows_scores(X, flat_params, H1, H2, nn, wide=False):
-    """ltr_mlp_rows_scores_f32 (`wide`: ltr_mlp_wide_scores_f32) on prepared arguments: (B, L) scores, 0 on the
-    padded documents."""
+    """ltr_mlp_rows_scores_f32 (`wide`: ltr_mlp_wide_scores_f32; a bf16 `X`: ltr_mlp_bf16_scores) on prepared
+    arguments: (B, L) scores, 0 on the padded documents."""
     B, L, F = X.shape
     scores = torch.empty(B, L, dtype=torch.float32, device=X.device)
     if B > 0:
-        fn = _C.lib().ltr_mlp_wide_scores_f32 if wide else _C.lib().ltr_mlp_rows_scores_f32
+        if X.dtype is torch.bfloat16:
+            fn = _C.lib().ltr_mlp_bf16_scores
+        else:
+            fn = _C.lib().ltr_mlp_wide_scores_f32 if wide else _C.lib().ltr_mlp_rows_scores_f32
         with _C.device_ctx(X):
             _C.check(fn(_C.ptr(X), *[_C.ptr(t) for t in flat_params], _C.ptr(nn), B, L, F, H1, H2, _C.ptr(scores),
                         _C.stream_of(X)))
@@ -933,7 +936,8 @@ def mlp_grad(xs, params, grad_scores, n=None, out=None):
 
 
 def _mlp_grad_call(X, flat_params, H1, H2, grad_scores, n, out, wide):
-    """ltr_mlp_rows_grad_f32 (`wide`: ltr_mlp_wide_grad_f32) behind the shape checks of its caller."""
+    """ltr_mlp_rows_grad_f32 (`wide`: ltr_mlp_wide_grad_f32; a bf16 `X`: ltr_mlp_bf16_grad) behind the shape checks of
+    its caller."""
     B, L, F = X.shape
     dev = X.device
     if grad_scores.numel() != B * L or grad_scores.device != dev:
@@ -947,9 +951,13 @@ def _mlp_grad_call(X, flat_params, H1, H2, grad_scores, n, out, wide):
     flat = out if out is not None else torch.empty(P, dtype=torch.float32, device=dev)
     if flat.numel() != P or flat.dtype != torch.float32 or not flat.is_contiguous():
         raise ValueError("out must be a contiguous float32 tensor of %d elements" % P)
-    key = (dev.index, B, L, F, H1, H2, wide)
-    ws_fn, grad_fn = ((lib.ltr_mlp_wide_grad_workspace_bytes, lib.ltr_mlp_wide_grad_f32) if wide
-                      else (lib.ltr_mlp_rows_grad_workspace_bytes, lib.ltr_mlp_rows_grad_f32))
+    bf16 = X.dtype is torch.bfloat16
+    key = (dev.index, B, L, F, H1, H2, "bf16" if bf16 else wide)
+    if bf16:
+        ws_fn, grad_fn = lib.ltr_mlp_bf16_grad_workspace_bytes, lib.ltr_mlp_bf16_grad
+    else:
+        ws_fn, grad_fn = ((lib.ltr_mlp_wide_grad_workspace_bytes, lib.ltr_mlp_wide_grad_f32) if wide
+                          else (lib.ltr_mlp_rows_grad_workspace_bytes, lib.ltr_mlp_rows_grad_f32))
     with _C.device_ctx(X):
         ws_bytes = _mlp_rows_ws.get(key)
         if ws_bytes is None:                # (asked with X's device current: the grid follows its CU count)
@@ -1018,6 +1026,99 @@ class _MLPScoreFunction(torch.autograd.Function):
         return (None, None) + tuple(g if g.shape == s else g.reshape(s) for g, s in zip(parts, ctx.shapes))
 
 
+def _mlp_bf16_network(F, H1, H2):
+    """Networks the bf16-feature MLP kernels take (include/ltr_mlp_bf16.h), at any list length."""
+    return (0 < F <= MLP_MAX_FEATURES and F % 8 == 0 and 0 < H1 <= MLP_MAX_HIDDEN[0] and 0 < H2 <= MLP_MAX_HIDDEN[1])
+
+
+def _pad_features_bf16(xs, w1):
+    """:func:`_pad_features` for the bf16 kernels, whose rows are whole 16-byte pieces of 8 values (Istella: 220 ->
+    224): zero columns are appended to the features and to W1, the extra dW1 columns are dropped.  One copy of the
+    batch; pad the stored split once to avoid it."""
+    extra = (-xs.shape[-1]) % 8
+    if extra == 0:
+        return xs, w1, 0
+    return (torch.nn.functional.pad(xs, (0, extra)), torch.nn.functional.pad(w1, (0, extra)), extra)
+
+
+def _mlp_bf16_checked(xs, params):
+    """The arguments of the bf16 kernels: the contiguous bf16 batch (zero-padded to F % 8 == 0), the fp32 parameters
+    (W1 padded to match), the hidden sizes and the number of padding columns; ValueError for anything else."""
+    if not torch.is_tensor(xs) or xs.dtype is not torch.bfloat16:
+        raise ValueError("the bf16 MLP kernels take torch.bfloat16 features (fp32 features: mlp_scores / mlp_grad)")
+    if xs.dim() != 3:
+        raise ValueError("features must have shape (batch, list_size, features)")
+    B, L, F = xs.shape
+    flat_params, H1, H2 = _flat_params([t.detach() for t in params], F)
+    F8 = (F + 7) & ~7
+    if not _mlp_bf16_network(F8, H1, H2) or L == 0:
+        raise ValueError("the bf16 MLP kernels take F <= %d (after zero-padding to a multiple of 8), hidden <= %s and "
+                         "L >= 1; got L=%d F=%d hidden=(%d, %d)" % (MLP_MAX_FEATURES, MLP_MAX_HIDDEN, L, F, H1, H2))
+    _C.require_device(xs, "xs")
+    xp, w1, extra = _pad_features_bf16(xs, flat_params[0])
+    X = xp if xp.is_contiguous() else xp.contiguous()
+    flat_params = (w1 if w1.is_contiguous() else w1.contiguous(),) + tuple(flat_params[1:])
+    return X, flat_params, H1, H2, extra
+
+
+def mlp_scores_bf16(xs, params, n=None):
+    """:func:`mlp_scores` on a batch kept as ``torch.bfloat16`` (half the bytes of the fp32 batch; any list length; no
+    autograd): (B, L) float32 scores for documents < n[b] and 0 for the padded ones, whose features are not read.  One
+    row-streaming kernel whose first layer runs on the bf16 MFMA (ltr_mlp_bf16_scores).  The parameters stay fp32; the
+    kernel rounds W1 to bf16 (nearest even) for the first layer -- the scores are those of the network with
+    ``W1.bfloat16()``, accumulated in fp32 -- everything behind the first layer is fp32.  Feature counts that are not a
+    multiple of 8 are zero-padded with one copy.  Other networks raise ValueError."""
+    X, flat_params, H1, H2, _ = _mlp_bf16_checked(xs, params)
+    return _mlp_rows_scores(X, flat_params, H1, H2, None if n is None else prepare_n(n, X.shape[0]))
+
+
+def mlp_grad_bf16(xs, params, grad_scores, n=None, out=None):
+    """:func:`mlp_grad` on a ``torch.bfloat16`` batch (ltr_mlp_bf16_grad): the fp32 gradients of
+    ``sum grad_scores * mlp_scores_bf16(xs, params)``, ``dW1`` being the gradient with respect to the rounded W1 the
+    forward uses (a straight-through update of the fp32 master weights).  Same arguments and the same
+    ``(dW1, db1, dW2, db2, dW3, db3)`` views of one flat buffer; with a feature count that is not a multiple of 8, `out`
+    holds the padded network's parameters and ``dW1`` is the view of its first F columns."""
+    X, flat_params, H1, H2, extra = _mlp_bf16_checked(xs, params)
+    parts = _mlp_grad_call(X, flat_params, H1, H2, grad_scores, n, out, False)
+    if extra:
+        parts = (parts[0][:, :X.shape[2] - extra],) + tuple(parts[1:])
+    return parts
+
+
+class _MLPScoreBf16Function(torch.autograd.Function):
+    """:class:`_MLPScoreFunction` on a bf16 batch: forward is the bf16 score kernel, backward the bf16 gradient kernel;
+    the bf16 batch itself is what is saved (a copy only where the feature count had to be padded to 8)."""
+
+    @staticmethod
+    def forward(ctx, xs, n, *params):
+        X, flat_params, H1, H2, extra = _mlp_bf16_checked(xs, params)
+        nn = None if n is None else prepare_n(n, X.shape[0])
+        scores = _mlp_rows_scores(X, flat_params, H1, H2, nn)
+        ctx.save_for_backward(X, nn if nn is not None else torch.empty(0, device=X.device), *flat_params)
+        ctx.has_n = nn is not None
+        ctx.extra = extra
+        ctx.shapes = [t.shape for t in params]
+        return scores.unsqueeze(-1)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_scores):
+        X, nn, *flat_params = ctx.saved_tensors
+        H1, H2 = flat_params[0].shape[0], flat_params[2].shape[0]
+        parts = list(_mlp_grad_call(X, flat_params, H1, H2, grad_scores, nn if ctx.has_n else None, None, False))
+        if ctx.extra:
+            parts[0] = parts[0][:, :X.shape[2] - ctx.extra]
+        return (None, None) + tuple(g if g.shape == s else g.reshape(s) for g, s in zip(parts, ctx.shapes))
+
+
+def _mlp_bf16_batch(xs):
+    """True for the batches the modules hand to the bf16 kernels: a bf16 (B, L, F) batch on the device that needs no
+    gradient itself, outside autocast.  (The torch layers cannot take it: their weights are fp32.  A network outside
+    the kernels' limits raises ValueError there.)"""
+    return (torch.is_tensor(xs) and xs.dim() == 3 and xs.is_cuda and xs.dtype is torch.bfloat16 and not xs.requires_grad
+            and xs.shape[1] > 0 and not torch.is_autocast_enabled())
+
+
 def _mlp_rows_usable(xs, H1, H2):
     """True where ``_MLPScoreFunction`` computes ``mlp(xs)``: an fp32 (B, L, F) batch on the device that needs no
     gradient itself, a network within the kernels' limits (F counted after the padding to a multiple of 4)."""
@@ -1041,7 +1142,7 @@ def _mlp_step_pieces(X, flat_params, H1, H2, relevance, n, kind, sigma, grad_out
     B, L, F = X.shape
     dev = X.device
     r, nn = _labels_and_n(relevance, n, B, L, dev)
-    scores = _mlp_rows_scores(X, flat_params, H1, H2, nn)
+    scores = _mlp_rows_scores(X, flat_params, H1, H2, nn)       # (a bf16 X: the bf16 kernels, here and below)
     with torch.enable_grad():
         s = scores.unsqueeze(-1).requires_grad_(True)
         lossv = (_listwise_pieces(s, r, nn, kind) if isinstance(kind, _ListwiseKind)
@@ -1050,7 +1151,7 @@ def _mlp_step_pieces(X, flat_params, H1, H2, relevance, n, kind, sigma, grad_out
               else grad_out.reshape(B).float())
         (ds,) = torch.autograd.grad((lossv * go).sum(), s)
     lossv = lossv.detach()
-    res = (lossv, mlp_grad(X, flat_params, ds, nn, out=out))
+    res = (lossv, _mlp_grad_call(X, flat_params, H1, H2, ds, nn, out, False))
     if return_scores:
         res = res + (scores,)
     if return_loss_sum:
@@ -1063,7 +1164,8 @@ def mlp_loss_step(xs, params, relevance, n, loss="hinge", grad_out=None, return_
     """One fused forward+backward step of ``loss_fn(mlp(xs), relevance, n)`` without autograd.
 
     Args:
-        xs: (B, L, F) float32 features on the device.
+        xs: (B, L, F) float32 features on the device; a ``torch.bfloat16`` batch with F % 8 == 0 runs, at every list
+            length, as the three pieces below on the bf16 kernels (:func:`mlp_scores_bf16`, :func:`mlp_grad_bf16`).
         loss: a pairwise kind name or module, or a listwise loss -- ``"listnet"`` / ``"softmax"``, ``"listmle"``,
             ``ListwiseSoftmaxLoss()``, ``ListMLELoss(k)`` (ltr_mlp_listwise_f32; ListMLE draws one tie seed per call,
             as ``ListMLELoss`` does, and ``utils.tie_breaking("index")`` turns it off).
@@ -1084,6 +1186,11 @@ def mlp_loss_step(xs, params, relevance, n, loss="hinge", grad_out=None, return_
     """
     kind, sigma = _resolve_loss(loss)
     listwise = isinstance(kind, _ListwiseKind)
+    if _mlp_bf16_batch(xs) and xs.shape[2] % 8 == 0:
+        # a bf16 batch: the three pieces on the bf16 kernels at every list length (the fused kernels are fp32-only)
+        X, flat_params, H1, H2, _ = _mlp_bf16_checked(xs, params)
+        return _mlp_step_pieces(X, flat_params, H1, H2, relevance, n, kind, sigma, grad_out, return_scores,
+                                return_loss_sum, out)
     X = _prepare_features(xs)
     B, L, F = X.shape
     flat_params, H1, H2 = _flat_params(params, F)
@@ -1229,8 +1336,14 @@ class _FusedMLPBase(torch.nn.Module):
         gradient kernel (:class:`MLPScorer`).  Rows wider than 224 features, up to 704, take the wide-row kernels
         (ltr_mlp_wide_*_f32) in both cases, at every list length.  The three ``nn.Linear`` layers, with autograd, serve
         what those do not take: more than 704 features, hidden sizes past (64, 16), features that require a gradient,
-        other dtypes, autocast."""
+        other dtypes, autocast.  A ``torch.bfloat16`` batch (outside autocast, no gradient of its own) runs the bf16
+        kernels (ltr_mlp_bf16_*: W1 rounded to bf16 for the first layer, fp32 behind it) at every list length, with
+        and without gradients; more than 224 features (after padding to 8) or hidden sizes past (64, 16) raise
+        ValueError there."""
         H1, H2 = self.l1.out_features, self.l2.out_features
+        if _mlp_bf16_batch(xs):
+            # a bf16 batch: the bf16 score kernel (its backward: the bf16 gradient kernel), at every list length
+            return _MLPScoreBf16Function.apply(xs, n, *self._params())
         if torch.is_tensor(xs) and xs.dim() == 3 and xs.is_cuda:
             if not torch.is_grad_enabled():
                 # evaluation: mlp_scores (the per-query kernel up to mlp_max_list_len documents, the row kernel past it)
@@ -1259,7 +1372,8 @@ class _FusedMLPBase(torch.nn.Module):
     def forward(self, xs, relevance, n):
         _C.require_device(xs, "xs")
         B, L, F = xs.shape
-        if self._fused_shape(B, L, (F + 3) & ~3):
+        # (a bf16 batch: score() on the bf16 kernels + the loss kernel, the fused per-query kernels are fp32-only)
+        if not _mlp_bf16_batch(xs) and self._fused_shape(B, L, (F + 3) & ~3):
             total, per_query = _MLPLossFunction.apply(
                 xs, relevance, n, (self.kind, self.sigma), self.reduction == "mean", *self._params())
             self.last_losses = per_query
@@ -1281,7 +1395,8 @@ class FusedMLPLoss(_FusedMLPBase):
     the row score kernel, the HIP loss kernel and the row gradient kernel (ltr_mlp_rows_*_f32, :class:`MLPScorer`) --
     a loss module built with ``long_lists=True`` takes them past ``max_list_len()`` documents.  More than 224
     features, up to 704 (Yahoo: 699), at every list length: the same three pieces on the wide-row kernels
-    (ltr_mlp_wide_*_f32).  More than 704 features or hidden sizes past (64, 16): the torch layers + the HIP loss kernel.  ``score(xs)`` evaluates the
+    (ltr_mlp_wide_*_f32).  A ``torch.bfloat16`` batch (up to 224 features): the same three pieces on the bf16 kernels
+    (ltr_mlp_bf16_*, :func:`mlp_scores_bf16`) at every list length -- the one-launch fused step is fp32-only.  More than 704 features or hidden sizes past (64, 16): the torch layers + the HIP loss kernel.  ``score(xs)`` evaluates the
     network alone (for the metrics).  The seven pairwise losses; the listwise ones: :class:`FusedMLPListwiseLoss`.
     """
 
@@ -1332,8 +1447,9 @@ class MLPScorer(torch.nn.Module):
     (ltr_mlp_rows_scores_f32; with ``n`` the padded documents score 0 and their features are not read); its backward
     runs the row gradient kernel on ``grad_scores`` and fills the six ``.grad``s (activations are recomputed, nothing
     but the features is kept).  Feature counts that are not a multiple of 4 are zero-padded on the fly.  Features
-    that require a gradient, inputs that are not fp32, more than 704 features or hidden sizes past (64, 16) run the
-    torch layers; 228 to 704 features (Yahoo: 699, padded to 700) run the wide-row kernels (ltr_mlp_wide_*_f32), which
+    that require a gradient, inputs that are neither fp32 nor bf16, more than 704 features or hidden sizes past (64, 16)
+    run the torch layers; a ``torch.bfloat16`` batch runs the bf16 kernels (ltr_mlp_bf16_*, :func:`mlp_scores_bf16`:
+    half the bytes, W1 rounded to bf16 for the first layer; up to 224 features, ValueError past that); 228 to 704 features (Yahoo: 699, padded to 700) run the wide-row kernels (ltr_mlp_wide_*_f32), which
     stream the feature dimension in chunks.  CPU tensors are refused: there is no CPU fallback."""
 
     def __init__(self, in_features, hidden=(50, 10)):
@@ -1348,6 +1464,8 @@ class MLPScorer(torch.nn.Module):
 
     def forward(self, xs, n=None):
         _C.require_device(xs, "xs")
+        if _mlp_bf16_batch(xs):
+            return _MLPScoreBf16Function.apply(xs, n, *self._params())
         if _mlp_rows_usable(xs, self.l1.out_features, self.l2.out_features):
             return _MLPScoreFunction.apply(xs, n, *self._params())
         o1 = torch.nn.functional.relu(self.l1(xs))
