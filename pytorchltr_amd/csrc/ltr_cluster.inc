@@ -414,10 +414,12 @@ __device__ __forceinline__ float cluster_hinge_from_runs(const QueryLds &q, cons
     __syncthreads();
     RUNS_STAMP(6);
     // my rows' gradients and my share of the pair sum: #active (counted at the higher-graded side) + sum (s - c) g with c =
-    // the query's first score (any constant every member agrees on: the gradients sum to zero); fixed order
+    // the median score of the first run (any constant every member agrees on: the gradients sum to zero -- but fl(s - c)
+    // must keep the scores' digits: with the query's first score for c, one outlier at 1e5 in that place cost the loss
+    // up to 2e-3; half a run of outliers is no outlier); fixed order
     float term = 0.f;
     {
-        const float c = (nb > 0) ? q.sy[0].x : 0.0f;
+        const float c = (nb > 0) ? u.ss[min(rpw, nb) >> 1] : 0.0f;
         for (int lr = tid; lr < rows; lr += T) {
             const int below = u.cnts[2 * lr], above = u.cnts[2 * lr + 1];
             const float g = (float)(above - below);

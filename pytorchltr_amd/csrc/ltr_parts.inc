@@ -456,7 +456,14 @@ __device__ __forceinline__ float pt_wave_minmax(float v)
 // scr: 64 words of LDS scratch.  Returns false (nothing written) when the query does not qualify.
 // Everything that is summed in an order the hardware chooses (LDS atomics, the documents of a bucket in
 // scatter order) is summed in FIXED POINT, so the result does not depend on that order: scores as
-// 30-bit fractions of the query's score range, margins as 24-bit fractions of range + 2.
+// 30-bit fractions of the query's score range (64-bit sums), the margins met in the edge buckets as 32-bit
+// fractions of 3 bucket widths + 2, summed in 64 bits.  A visited document lies less than two bucket widths (and
+// the rounding of the bucket index: under half a width, by `need`) above the window edge, or above the query's
+// minimum where the edge is clamped to it: its margin is below 1 + 2.5 widths, so a term fits 32 bits and 2048 of
+// them 43.  The quantum follows the margins that are summed, not the range: one far outlier puts every other
+// document into bucket 0, and as 24-bit fractions of range + 2 each margin lost ~range / 2^24 (2e-3 of the loss at
+// 1e5); and a 32-bit sum of those wrapped once some 600 lower-graded documents with margins near 1 shared the edge
+// buckets -- a cluster of tied scores at the query's minimum, the loss 18-37 % low.
 #ifdef LTR_TRACE
 #define RK_STAMP(i) do { if (trace && threadIdx.x == 0) trace[i] = (long long)wall_clock64(); } while (0)
 #else
@@ -518,8 +525,9 @@ int nb, int r0, int rows, int rpw, unsigned rk_off,
     };
     const float qs = 1073741824.0f / span;                    // scores -> 30-bit fractions of the range
     const float qs_inv = span * (1.0f / 1073741824.0f);
-    const float qu = 16777216.0f / (span + 2.0f);             // margins (0 .. range + 1) -> 24-bit fractions
-    const float qu_inv = (span + 2.0f) * (1.0f / 16777216.0f);
+    const float mmax = 3.0f * span / (float)NB + 2.0f;        // above every margin the visits of S5 meet
+    const float qu = 4294967296.0f / mmax;                    // those margins -> 32-bit fractions of it
+    const float qu_inv = mmax * (1.0f / 4294967296.0f);
     RK_STAMP(10);
 
     // ---- S2: histogram + per-bucket counts / sums in one pass over the documents ----
@@ -640,7 +648,7 @@ int nb, int r0, int rows, int rpw, unsigned rk_off,
                 Bc = all_above - ge_above;
                 // sum of 1 - (s - s_m) over them = Bc * (1 - s + lo) + (sum of s_m - lo), the latter in fixed point
                 float lk = (float)Bc * ((1.0f - s) + lo) + (float)(long long)aggS[(size_t)(y - 1) * (NB + 1) + b1] * qs_inv;
-                unsigned uq = 0u;
+                unsigned long long uq = 0ull;
                 const int e1 = start[b1];
                 for (int e = start[b0]; e < e1; e += 4) {
                     int2 x[4];

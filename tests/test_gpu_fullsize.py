@@ -332,7 +332,8 @@ def test_parts_kernel_ranked_hinge_all_rows(shape):
 @pytest.mark.parametrize("variant", ["float_labels", "grade_7", "tied_scores", "tiny_spread", "constant"])
 def test_parts_kernel_ranked_hinge_falls_back(variant):
     """Queries the counting formulation does not take (labels that are not the integers 0..4, scores without
-    spread) fall back to the pair pass, per query, and queries full of tied scores stay exact."""
+    spread) fall back to the pair pass, per query, and queries full of tied scores stay exact (ties spread over the range;
+    ties that CLUSTER at one score, and shapes that really carry the counting tables: tests/test_gpu_hinge_counting.py)."""
     from pytorchltr_amd import _C
     from pytorchltr_amd.fused import linear_loss_step
     dev = _dev()

@@ -66,7 +66,7 @@ def _by_runs(s, y, rpw):
                     above += (ln - pos) - (tl - tp)
         g[i] = above - below
         active += below
-    c = f32(s[0])
+    c = f32(ss[min(rpw, n) // 2])                         # the median score of the first run
     raw = float(active) + float(np.sum((s.astype(np.float32) - c).astype(np.float64) * g))
     return g, raw
 
