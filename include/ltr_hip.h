@@ -482,7 +482,12 @@ int ltr_linear_sgd_flush_f32(int kind, float *W, float *bias, int pending_B, int
  * Every rank makes the same sequence of calls with B > 0; eager launches only (a stream under capture: LTR_ERR_CONFIG when an
  * update is pending).  Shapes the launch does not take along flush first (below).  One process per GPU: a launch's reducers wait
  * for the peers' reducers INSIDE the kernel, so the ranks' launches must be resident at the same time -- ranks that share one
- * device (functional tests) must fit it together, B + (F + 4) / 4 + 1 workgroups each at four per CU. */
+ * device (functional tests) must fit it together, B + (F + 4) / 4 + 1 workgroups each at four per CU.
+ * `loss`: the launch that takes the update along sums the PENDING batch's losses through THIS call's pointer before its queries
+ * overwrite them, so `loss` must hold at least max(B, pending_B) floats (B and pending_B may differ from call to call: a short
+ * last batch, the longer first one of the next epoch), and bucket[F + 1] is the pending batch's loss sum only when `loss` is the
+ * buffer the pending step wrote; a caller that hands every step a buffer of its own (pytorchltr_amd.optim.SGD: the user keeps
+ * the per-query losses) gets dW / db / the weights as documented and a bucket[F + 1] that means nothing. */
 int ltr_linear_sgd_lazy_step_dp_f32(int kind, float sigma, const float *X, float *W, float *bias, const void *rel,
                                     int rel_dtype, const int64_t *n, int B, int L, int F, float lr, float *loss,
                                     float *bucket /* F + 2 */, void *workspace, size_t workspace_bytes, int pending_B,

@@ -229,7 +229,12 @@ class _LazyLinear:
         pg_old = self.grad() if self.grad is not None else None
         if pg_old is not None and pg_old.real is None and not pg_old.consumed and pg_old.gen == self.gen:
             pg_old.materialize()                            # somebody still holds the last gradient: its rows go now
-        loss = torch.empty(B, dtype=torch.float32, device=X.device)
+        # (a launch that takes the update along also sums the PENDING batch's losses -- pending_B floats -- through THIS call's
+        # loss pointer (include/ltr_hip.h): the buffer holds max(B, pending_B) floats so that the read stays inside it, the
+        # caller gets its first B.  Every step has a buffer of its own -- the user may keep the losses -- so what that sum
+        # reads is not the pending batch's losses: bucket[F + 1] is NOT meaningful on this path, and nothing here reads it.)
+        pending_B = pend.pg.shape[1] if pend is not None else 0
+        loss = torch.empty(max(B, pending_B), dtype=torch.float32, device=X.device)[:B]
         with _C.device_ctx(X):
             rc = lib.ltr_linear_sgd_lazy_step_dp_f32(
                 kind, float(sigma), X.data_ptr(), self.w_raw.data_ptr(), self.b_raw.data_ptr(), r.data_ptr(), rcode,

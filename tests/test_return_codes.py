@@ -170,6 +170,28 @@ def test_every_entry_point_is_pinned():
     assert sorted(name for name, _, _ in _declarations()) == sorted(EXPECTED)
 
 
+def _lazy_step(lib, B, pending_B, ws_for, dp, L=72, F=136):
+    """The lazy step with dummy pointers, a batch of B queries, pending_B pending and a workspace sized for `ws_for` queries."""
+    ws_bytes = lib.ltr_linear_workspace_bytes(ws_for, L, F)
+    head = (0, 1.0, P, P, P, P, 0, P, B, L, F, 0.05, P, P, P, ws_bytes, pending_B)
+    if dp:
+        return lib.ltr_linear_sgd_lazy_step_dp_f32(*head, 0.0, None, 0, None, None)
+    return lib.ltr_linear_sgd_lazy_step_f32(*head, None)
+
+
+@pytest.mark.parametrize("dp", [False, True], ids=["lazy_step", "lazy_step_dp"])
+def test_lazy_step_checks_the_pending_batch_too(lib, dp):
+    """The pending batch may have another size than this call's: a negative pending_B is LTR_ERR_SHAPE, and the ONE workspace
+    has to take the larger of the two batches -- LTR_ERR_WORKSPACE whichever of them it is too small for (before any launch:
+    every pointer here is a dummy)."""
+    ERR_SHAPE, ERR_WORKSPACE = -2, -5
+    assert lib.ltr_linear_workspace_bytes(300, 72, 136) > lib.ltr_linear_workspace_bytes(77, 72, 136) > 0
+    assert _lazy_step(lib, 77, -1, 300, dp) == ERR_SHAPE
+    assert _lazy_step(lib, 77, 300, 77, dp) == ERR_WORKSPACE          # large enough for B, not for the larger pending batch
+    assert _lazy_step(lib, 300, 77, 77, dp) == ERR_WORKSPACE          # ... and with B and pending_B swapped
+    assert _lazy_step(lib, 0, 300, 77, dp) == ERR_WORKSPACE           # the empty batch that only applies the pending update
+
+
 @pytest.mark.parametrize("name", sorted(EXPECTED))
 def test_return_codes(lib, name):
     decl = {n: (r, a) for n, r, a in _declarations()}
