@@ -1,5 +1,6 @@
 // ltr_mlp.hip -- translation unit of the fused MLP scorer + loss kernels (ltr_mlp.inc, ltr_mlp2.inc, ltr_mlp_listwise.inc),
-// the stand-alone MLP scorer (ltr_mlp_rows.inc; bf16 features: ltr_mlp_bf16.inc; wide rows: ltr_mlp_wide.inc) and the stand-alone Linear scorer layer (ltr_scorer.inc, which shares
+// the stand-alone MLP scorer (shared layer: ltr_mlp_stream.inc; f32 rows: ltr_mlp_rows.inc; bf16 features: ltr_mlp_bf16.inc;
+// wide rows: ltr_mlp_wide.inc) and the stand-alone Linear scorer layer (ltr_scorer.inc, which shares
 // the MLP's reduction kernel).
 #include "ltr_common.inc"
 // the listwise slot of the training step: the ranked row (layout, ranking, scans) and the ListMLE row function
@@ -13,6 +14,7 @@
 #include "ltr_ranked.inc"
 #include "ltr_listmle_row.inc"
 #include "ltr_mlp.inc"
+#include "ltr_mlp_stream.inc"
 #include "ltr_mlp_rows.inc"
 #include "ltr_mlp_bf16.inc"
 #include "ltr_mlp_wide.inc"

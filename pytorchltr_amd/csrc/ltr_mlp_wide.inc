@@ -1,12 +1,13 @@
 // ltr_mlp_wide.inc -- the ReLU-MLP scorer (F -> H1 -> H2 -> 1) on WIDE feature rows, up to 704 features: K-streamed
 // score and parameter-gradient kernels on v_mfma_f32_16x16x4_f32 for lists of any length (include/ltr_mlp_wide.h).
-// Included by ltr_mlp.hip behind ltr_mlp_rows.inc, whose fragments, reduction kernel and padding rules it shares.
+// Included by ltr_mlp.hip behind ltr_mlp_stream.inc, whose fragments, row test, owner waves, f32 backward chains and
+// epilogue it calls, and whose host glue it shares.
 //
 // The row kernels (ltr_mlp_rows.inc) keep a wave's W1 fragments, and the gradient kernel its dW1 tile, in registers for
 // the workgroup's whole life: 56 + 56 registers at 224 features, 176 + 176 at 704, where W1 itself (176 KiB) is more
 // than the LDS.  Here the feature dimension is walked in CHUNKS of 128 features instead.  The unit of work, the mask
 // (`row % L < n[row / L]`), the persistent grid and the tile order (workgroup w takes the tiles w, w + G, w + 2G, ...)
-// are those of ltr_mlp_rows.inc; so is the wave layout (four waves, wave w owns hidden-1 rows 16w .. 16w + 15).
+// are those of ltr_mlp_stream.inc; so is the wave layout (four waves, wave w owns hidden-1 rows 16w .. 16w + 15).
 //
 // Forward (mlp_wide_fwd_kernel): a workgroup takes its tiles in GROUPS of eight (scores; four in front of the backward
 // half, mlp_wide_group) and keeps the layer-1 accumulators of the whole group in registers (8 per tile).  Chunk loop
@@ -16,13 +17,13 @@
 //         for tile of the group:  image[parity] <- the tile's 32 x 128 piece of X (requested one step ahead; the address
 //                 select of the row kernels keeps padded rows unread)                                 one barrier
 //                 64 MFMAs per wave into the tile's accumulators
-//     for tile of the group:  layers 2 and 3 and the score store as in mlp_rows_kernel; GRAD: dH2 rows, the dW2 tile,
+//     for tile of the group:  layers 2 and 3 and the score store as in mlp_stream_body; GRAD: dH2 rows, the dW2 tile,
 //                 the small sums, and the tile's d loss / d hidden-1 (zeros on padded rows) -> workspace, 256 B a row
 // The image and the layer-2 partials are double buffered by step / tile parity, which is what lets one barrier a step do.
 // Which rows of a group are real is worked out once per group: 256 threads, one row each, two tiles per ballot.
 //
 // Gradient, second kernel (mlp_wide_dw1_kernel): dW1 = dH1^T . X over (column slice of 128 or 176 features) x (row
-// range): exactly the dW1 chain of mlp_rows_kernel with the A operand read from the workspace and a dW1 slice of 32 / 44
+// range): the f32 dW1 chain of the row kernel (mlp_dw1_chain_f32) with the A operand read from the workspace and a dW1 slice of 32 / 44
 // registers per lane; X is read a second time.  One partial dW1 per row range, one partial vector of the small sums per
 // workgroup of the first kernel, two launches of mlp_reduce_launch(loss = NULL) add them in a fixed order.  No atomics.
 // DESIGN.md section 19 has the choice between this and a one-kernel gradient, the register / LDS table and the bytes.
@@ -30,98 +31,53 @@
 
 #include "ltr_mlp_wide.h"
 
-constexpr int kMwThreads = 256;
-constexpr int kMwWaves = 4;
-constexpr int kMwRows = 32;           // flat rows per tile (two 16-row subtiles)
-constexpr int kMwWgs = 2;             // workgroups per CU the launch bounds and the grids are sized for
 constexpr int kMwMaxF = 704;
 constexpr int kMwNTC = 8;             // 16-feature steps per chunk
 constexpr int kMwKC = 16 * kMwNTC;    // features per chunk
 constexpr int kMwIP = kMwKC + 4;      // image pitch (floats): odd number of 16-byte units
-constexpr int kMwTG = kMwThreads / kMwRows;      // most tiles per group: one thread per row works out the masks
+constexpr int kMwTG = kMsThreads / kMsRows;      // most tiles per group: one thread per row works out the masks
 // tiles per group: eight for the scores; four for the gradient's forward kernel, whose backward fragments and sums
 // (37 registers) next to eight tiles' accumulators spilled 30 registers under the 256 of two workgroups per CU
 constexpr int mlp_wide_group(bool grad) { return grad ? 4 : kMwTG; }
-constexpr int kMwPS = 20;             // row pitch (floats) of the partial / scratch / dH2 images
-constexpr int kMwRing = 3;            // dW1 kernel: tiles whose row mask is kept in LDS
 constexpr int kMwDH = 64;             // floats per flat row of the d loss / d hidden-1 tile in the workspace
-
-struct MlpWideParams {
-    const float *X, *W1, *b1, *W2, *b2, *W3, *b3, *g;
-    const int64_t *n;
-    float *scores_out;
-    float *part;                     // fwd: partial vectors of the small sums; dw1: partial dW1 matrices
-    float *dH1;                      // [tiles * 32][64]
-    int B, L, F, H1, H2;
-    int rows;                        // B * L
-    int tiles;                       // ceil(rows / 32)
-    int pitch;                       // floats between consecutive partial vectors of `part`
-};
 
 constexpr size_t mlp_wide_fwd_lds_bytes()
 {
-    return ((size_t)2 * kMwRows * kMwIP + (size_t)2 * kMwWaves * kMwRows * kMwPS + (size_t)kMwRows * kMwPS +
-            (size_t)kMwTG * kMwRows + kMwTG + 8) * sizeof(float);
+    return ((size_t)2 * kMsRows * kMwIP + (size_t)2 * kMsWaves * kMsRows * kMsPS + (size_t)kMsRows * kMsPS +
+            (size_t)kMwTG * kMsRows + kMwTG + 8) * sizeof(float);
 }
 constexpr size_t mlp_wide_dw1_lds_bytes(int NTS)
 {
     // two images [32][16 NTS + 4]; the four dW1 tiles (64 image rows) are staged in the same floats at the end
-    return ((size_t)2 * kMwRows * (16 * NTS + 4) + 8) * sizeof(float);
+    return ((size_t)2 * kMsRows * (16 * NTS + 4) + 8) * sizeof(float);
 }
-static_assert(mlp_wide_fwd_lds_bytes() <= kLdsBudget / kMwWgs && mlp_wide_dw1_lds_bytes(11) <= kLdsBudget / kMwWgs,
+static_assert(mlp_wide_fwd_lds_bytes() <= kLdsBudget / kMsWgs && mlp_wide_dw1_lds_bytes(11) <= kLdsBudget / kMsWgs,
               "two workgroups per CU");
 
 template <bool GRAD>
-__global__ void __launch_bounds__(kMwThreads, kMwWgs)
-mlp_wide_fwd_kernel(MlpWideParams p)
+__global__ void __launch_bounds__(kMsThreads, kMsWgs)
+mlp_wide_fwd_kernel(MlpStreamParams p)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int c16 = lane & 15;
-    const int g = lane >> 4;
-    const int L = p.L, F = p.F, H1 = p.H1, H2 = p.H2;
+    const MlpLane ln = mlp_lane();
+    const int tid = ln.tid, lane = ln.lane, w = ln.w, c16 = ln.c16, g = ln.g;
+    const int F = p.F;
+    const float *X = static_cast<const float *>(p.X);
     const int NC = (F + kMwKC - 1) / kMwKC;         // feature chunks
     constexpr int IP = kMwIP;
     constexpr int TG = mlp_wide_group(GRAD);        // tiles per group
     static_assert(TG % 2 == 0 && TG <= kMwTG, "buffers alternate by tile parity across the chunks");
 
     float *img = reinterpret_cast<float *>(smem);                  // [2][32][IP]    the piece of X of a step
-    float *part = img + (size_t)2 * kMwRows * IP;                  // [2][4][32][20] layer-2 partials / wave scratch
-    float *dH2s = part + (size_t)2 * kMwWaves * kMwRows * kMwPS;   // [32][20]
-    float *gs = dH2s + (size_t)kMwRows * kMwPS;                    // [8][32]        d loss / d score of the group's rows
-    unsigned *vmask = reinterpret_cast<unsigned *>(gs + kMwTG * kMwRows);      // [8] bit r: row r of tile j is real
+    float *part = img + (size_t)2 * kMsRows * IP;                  // [2][4][32][20] layer-2 partials / wave scratch
+    float *dH2s = part + (size_t)2 * kMsWaves * kMsRows * kMsPS;   // [32][20]
+    float *gs = dH2s + (size_t)kMsRows * kMsPS;                    // [8][32]        d loss / d score of the group's rows
+    unsigned *vmask = reinterpret_cast<unsigned *>(gs + kMwTG * kMsRows);      // [8] bit r: row r of tile j is real
 
     const mlp_f4 zero4 = {0.f, 0.f, 0.f, 0.f};
 
-    // ---- the small weight fragments (ltr_mlp_rows.inc); the W1 fragments exist per chunk ----
-    const int j1A = 16 * w + c16;                   // hidden-1 row as an A-operand row (lane & 15)
-    mlp_f4 b1v, w2a, w2t, b2v, w3v;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int j1D = 16 * w + 4 * g + i;         // hidden-1 row as a D-fragment row
-        const int j2D = 4 * g + i;                  // hidden-2 row as a D-fragment row
-        const bool ok1 = j1D < H1, ok2 = j2D < H2;
-        const float vb1 = p.b1[ok1 ? j1D : 0];
-        b1v[i] = ok1 ? vb1 : 0.f;
-        const bool oka = c16 < H2 && ok1;           // layer 2:  A[row j2 = c16][k <-> j1D]
-        const float va = p.W2[oka ? (size_t)c16 * H1 + j1D : 0];
-        w2a[i] = oka ? va : 0.f;
-        const bool okt = ok2 && j1A < H1;           // dH1:      A[row j1A][k <-> j2D]
-        const float vt = p.W2[okt ? (size_t)j2D * H1 + j1A : 0];
-        w2t[i] = okt ? vt : 0.f;
-        const float vb2 = p.b2[ok2 ? j2D : 0], v3 = p.W3[ok2 ? j2D : 0];
-        b2v[i] = ok2 ? vb2 : 0.f;
-        w3v[i] = ok2 ? v3 : 0.f;
-    }
-    const float b3 = p.b3[0];
-
-    // ---- accumulators that live across the tiles (disjoint between the waves) ----
-    mlp_f4 accW2 = zero4;            // dW2[j2 = 4g+i][j1 = 16w + c16]
-    mlp_f4 accB1 = zero4;            // db1[j1 = 16w+4g+i], partial over this lane's documents
-    mlp_f4 accB2 = zero4, accW3 = zero4;     // db2 / dW3 [j2 = 4g+i], documents this wave finished
-    float accB3 = 0.f;
+    const MlpSmallFrags sf = mlp_small_frags(p, ln);            // (the W1 fragments exist per chunk)
+    MlpSmallSums sums = mlp_small_sums_zero();
 
     // A step moves a 32 x 128 piece of X: 1024 float4 units, four per thread -- rows fr, fr + 8, fr + 16, fr + 24 of
     // the tile, 16 bytes at float 4 fc of the chunk
@@ -129,7 +85,7 @@ mlp_wide_fwd_kernel(MlpWideParams p)
     mlp_f4 P[4];                                    // the piece in flight
     auto issue_fill = [&](int tile, int ch, unsigned m) {
         const int f = ch * kMwKC + 4 * fc;
-        const float *Xt = p.X + ((size_t)tile * kMwRows + fr) * (size_t)F + f;
+        const float *Xt = X + ((size_t)tile * kMsRows + fr) * (size_t)F + f;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const bool ok = ((m >> (fr + 8 * k)) & 1u) && f < F;
@@ -156,14 +112,9 @@ mlp_wide_fwd_kernel(MlpWideParams p)
         __syncthreads();                           // (the masks and g of the group before are behind every wave)
         if (fr < TG) {                             // (wave-uniform: a wave holds the rows of two tiles)
             const int tile = t0 + fr * G;
-            const long long row = (long long)tile * kMwRows + fc;
-            bool ok = tile < p.tiles && row < (long long)p.rows;
-            float gv = 0.f;
-            if (ok) {
-                const int q = (int)row / L, j = (int)row - q * L;
-                ok = p.n ? j < clamp_n(p.n[q], L) : true;
-                if (GRAD && ok) gv = p.g[row];
-            }
+            const long long row = (long long)tile * kMsRows + fc;
+            float gv;
+            const bool ok = mlp_row_real<GRAD>(p, tile < p.tiles && row < (long long)p.rows, row, gv);
             const unsigned long long m = __ballot(ok);          // lanes 0 .. 31: tile 2w, lanes 32 .. 63: tile 2w + 1
             if (GRAD) gs[tid] = gv;
             if (lane == 0) {
@@ -175,25 +126,18 @@ mlp_wide_fwd_kernel(MlpWideParams p)
 
         mlp_f4 h1a[TG][2];                      // layer-1 pre-activations of the group: [j1 = 16w+4g+i][doc c16]
 #pragma unroll
-        for (int j = 0; j < TG; ++j) { h1a[j][0] = b1v; h1a[j][1] = b1v; }
+        for (int j = 0; j < TG; ++j) { h1a[j][0] = sf.b1v; h1a[j][1] = sf.b1v; }
 
         // ---- layer 1: chunk loop outside, tile loop inside ----
         unsigned mcur = __builtin_amdgcn_readfirstlane(vmask[0]);
         if (mcur) issue_fill(t0, 0, mcur);
         for (int ch = 0; ch < NC; ++ch) {
             mlp_f4 w1r[kMwNTC];                     // W1[j1A][128 ch + 16c + 4g .. +3]
-#pragma unroll
-            for (int c = 0; c < kMwNTC; ++c) {
-                const int f0 = ch * kMwKC + 16 * c + 4 * g;
-                const bool ok = j1A < H1 && f0 < F;
-                const mlp_f4 v = *reinterpret_cast<const mlp_f4 *>(p.W1 + (ok ? (size_t)j1A * F + f0 : 0));
-#pragma unroll
-                for (int i = 0; i < 4; ++i) w1r[c][i] = ok ? v[i] : 0.f;
-            }
+            mlp_load_w1_f32<kMwNTC>(w1r, p, ln, ch * kMwKC);
             const bool hi = F - ch * kMwKC > kMwKC / 2;         // the chunk's upper 64 features exist (uniform)
 #pragma unroll
             for (int j = 0; j < TG; ++j) {
-                float *im = img + (size_t)(j & 1) * kMwRows * IP;
+                float *im = img + (size_t)(j & 1) * kMsRows * IP;
                 if (mcur) fill_image(im, ch, mcur);             // (waits for the piece in P)
                 const int jn = j + 1 < TG ? j + 1 : 0;
                 const int chn = j + 1 < TG ? ch : ch + 1;
@@ -226,163 +170,73 @@ mlp_wide_fwd_kernel(MlpWideParams p)
             }
         }
 
-        // ---- layers 2 and 3 of every tile of the group (mlp_rows_kernel), GRAD: and back down to dH1 ----
+        // ---- layers 2 and 3 of every tile of the group (as in mlp_stream_body), GRAD: and back down to dH1 ----
 #pragma unroll
         for (int j = 0; j < TG; ++j) {
             const unsigned m = __builtin_amdgcn_readfirstlane(vmask[j]);
             const int tile = t0 + j * G;
             const int doc = 16 * w + c16;          // owner waves 0, 1: the row of the tile this lane finishes
-            const long long orow = (long long)tile * kMwRows + doc;
+            const long long orow = (long long)tile * kMsRows + doc;
             if (m == 0) {                          // padding only, or past the last tile
                 if (!GRAD && w < 2 && g == 0 && orow < (long long)p.rows) p.scores_out[orow] = 0.f;
                 lds_barrier();                     // (keeps the tiles on either side, of one parity, a barrier apart)
                 continue;
             }
-            float *pj = part + (size_t)(j & 1) * kMwWaves * kMwRows * kMwPS;
-            float *scr = pj + (size_t)w * kMwRows * kMwPS;
+            float *pj = part + (size_t)(j & 1) * kMsWaves * kMsRows * kMsPS;
+            float *scr = pj + (size_t)w * kMsRows * kMsPS;
             mlp_f4 h1[2];
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) h1[u][i] = fmaxf(h1a[j][u][i], 0.f);
-                mlp_f4 hp = zero4;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) hp = mfma16(w2a[i], h1[u][i], hp);
-                *reinterpret_cast<mlp_f4 *>(scr + (16 * u + c16) * kMwPS + 4 * g) = hp;
+                h1[u] = h1a[j][u];
+                mlp_layer2_partial(sf, h1[u], scr + (16 * u + c16) * kMsPS + 4 * g);
             }
             lds_barrier();                         // B: layer-2 partials (of parity j: rewritten two tiles on)
             const bool own = w < 2;
             mlp_f4 h2 = zero4;
             float s = 0.f;
-            if (own) {
-                h2 = b2v;
-#pragma unroll
-                for (int t = 0; t < kMwWaves; ++t) {
-                    const mlp_f4 v = *reinterpret_cast<const mlp_f4 *>(pj + ((size_t)t * kMwRows + doc) * kMwPS + 4 * g);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) h2[i] += v[i];
-                }
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    h2[i] = fmaxf(h2[i], 0.f);
-                    s = __builtin_fmaf(w3v[i], h2[i], s);
-                }
-                s += __shfl_xor(s, 16);
-                s += __shfl_xor(s, 32);
-                s += b3;
-            }
+            if (own) s = mlp_owner_fwd(sf, pj, doc, g, h2);
             if (!GRAD) {
                 if (own && g == 0 && orow < (long long)p.rows) p.scores_out[orow] = ((m >> doc) & 1u) ? s : 0.f;
                 continue;
             }
-            // ---- owner wave, backward through layers 3 and 2: dH2 rows -> LDS (g is 0 on padded rows) ----
-            if (own) {
-                const float ds = gs[j * kMwRows + doc];
-                mlp_f4 dh2;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    accW3[i] = __builtin_fmaf(ds, h2[i], accW3[i]);
-                    dh2[i] = (h2[i] > 0.f) ? ds * w3v[i] : 0.f;
-                    accB2[i] += dh2[i];
-                }
-                if (g == 0) accB3 += ds;
-                *reinterpret_cast<mlp_f4 *>(dH2s + doc * kMwPS + 4 * g) = dh2;
-            }
+            if (own) mlp_owner_bwd(sf, sums, h2, gs[j * kMsRows + doc], dH2s, doc, g);
             lds_barrier();                         // C: dH2 rows (rewritten behind barrier B of the next tile)
-            // ---- dW2[:, tile] += dH2^T . H1: H1 through the scratch (document-major -> k-major) ----
-            {
-                const float *tsrc = scr + g * kMwPS + c16;      // transposed reads: [4s + g][c16]
-                const float *dsrc = dH2s + g * kMwPS + c16;
-#pragma unroll
-                for (int u = 0; u < 2; ++u)
-                    *reinterpret_cast<mlp_f4 *>(scr + (16 * u + c16) * kMwPS + 4 * g) = h1[u];
-                mlp_f4 o = zero4;
-#pragma unroll
-                for (int sx = 0; sx < 8; ++sx) {
-                    const float a = dsrc[4 * sx * kMwPS], bb = tsrc[4 * sx * kMwPS];
-                    if (sx & 1) o = mfma16(a, bb, o); else accW2 = mfma16(a, bb, accW2);
-                }
-#pragma unroll
-                for (int i = 0; i < 4; ++i) accW2[i] += o[i];
-            }
-            // ---- dH1^T tile = (W2^T . dH2^T) . [H1 > 0] -> workspace: row (tile, 16u + c16), floats 16w + 4g .. +3 ----
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const mlp_f4 d2 = *reinterpret_cast<const mlp_f4 *>(dH2s + (16 * u + c16) * kMwPS + 4 * g);
-                mlp_f4 d1 = zero4;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) d1 = mfma16(w2t[i], d2[i], d1);
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    d1[i] = (h1[u][i] > 0.f) ? d1[i] : 0.f;
-                    accB1[i] += d1[i];
-                }
-                *reinterpret_cast<mlp_f4 *>(p.dH1 + ((size_t)tile * kMwRows + 16 * u + c16) * kMwDH + 16 * w + 4 * g) = d1;
-            }
+            mlp_dw2_tile<2>(sums, h1, scr, dH2s, 0, ln);
+            // the dH1^T tile -> workspace: row (tile, 16u + c16), floats 16w + 4g .. +3
+            mlp_dh1_tile<2>(sf, sums, h1, dH2s, 0, ln, [&](int u, const mlp_f4 &d1) {
+                *reinterpret_cast<mlp_f4 *>(p.dH1 + ((size_t)tile * kMsRows + 16 * u + c16) * kMwDH + 16 * w + 4 * g) = d1;
+            });
         }
     }
     if (!GRAD) return;
 
     // ---- this workgroup's partial vector of the small sums [db1 | dW2 | db2 | dW3 | db3] ----
     float *dst = p.part + (size_t)blockIdx.x * p.pitch;
-    const int oW2 = H1, oB2 = oW2 + H2 * H1, oW3 = oB2 + H2, oB3 = oW3 + H2;
     __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int j2 = 4 * g + i;
-        if (j2 < H2 && j1A < H1) dst[oW2 + j2 * H1 + j1A] = accW2[i];
-        const float s1 = row16_sum(accB1[i]);
-        const int j1 = 16 * w + 4 * g + i;
-        if (c16 == 0 && j1 < H1) dst[j1] = s1;
-        accB2[i] = row16_sum(accB2[i]);
-        accW3[i] = row16_sum(accW3[i]);
-    }
-    accB3 = wave_sum(accB3);
-    // the per-document-owner sums (db2, dW3, db3) fold over the waves in a fixed order
-    float *fold = reinterpret_cast<float *>(smem);
-    float *slv = fold + (size_t)w * 40;            // [16] db2 | [16] dW3 | [1] db3
-    if (c16 == 0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            slv[4 * g + i] = accB2[i];
-            slv[16 + 4 * g + i] = accW3[i];
-        }
-    }
-    if (lane == 0) slv[32] = accB3;
-    __syncthreads();
-    if (tid < 33) {
-        float t = 0.f;
-#pragma unroll
-        for (int k = 0; k < kMwWaves; ++k) t += fold[k * 40 + tid];
-        if (tid < 16) { if (tid < H2) dst[oB2 + tid] = t; }
-        else if (tid < 32) { if (tid - 16 < H2) dst[oW3 + tid - 16] = t; }
-        else dst[oB3] = t;
-    }
+    mlp_store_small_sums(sums, dst, 0, reinterpret_cast<float *>(smem), p, ln);
 }
 
 // dW1[:, slice] of the row range: workgroup blockIdx = range * nsl + slice (the workgroups that read the same dH1 rows
 // start next to each other), features 16 NTS * slice .. + 16 NTS - 1, tiles range, range + GR, range + 2 GR, ...
 template <int NTS>
-__global__ void __launch_bounds__(kMwThreads, kMwWgs)
-mlp_wide_dw1_kernel(MlpWideParams p, int nsl)
+__global__ void __launch_bounds__(kMsThreads, kMsWgs)
+mlp_wide_dw1_kernel(MlpStreamParams p, int nsl)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x;
-    constexpr int T = kMwThreads;
-    const int lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int c16 = lane & 15;
-    const int g = lane >> 4;
-    const int L = p.L, F = p.F, H1 = p.H1;
+    const MlpLane ln = mlp_lane();
+    const int tid = ln.tid, w = ln.w, c16 = ln.c16, g = ln.g;
+    constexpr int T = kMsThreads;
+    const int F = p.F;
+    const float *X = static_cast<const float *>(p.X);
     constexpr int IP = 16 * NTS + 4;                // image pitch (floats): odd number of 16-byte units
     constexpr int C4 = 4 * NTS;                     // float4 units per image row
-    constexpr int KP = (kMwRows * C4 + T - 1) / T;  // float4 units of a fill per thread
+    constexpr int KP = (kMsRows * C4 + T - 1) / T;  // float4 units of a fill per thread
     const int slice = (int)blockIdx.x % nsl, range = (int)blockIdx.x / nsl;
     const int GR = (int)gridDim.x / nsl;
     const int f0s = slice * 16 * NTS;
 
     float *img = reinterpret_cast<float *>(smem);                  // [2][32][IP]
-    unsigned *vmask = reinterpret_cast<unsigned *>(img + (size_t)2 * kMwRows * IP);        // [3]
+    unsigned *vmask = reinterpret_cast<unsigned *>(img + (size_t)2 * kMsRows * IP);        // [3]
     const mlp_f4 zero4 = {0.f, 0.f, 0.f, 0.f};
 
     mlp_f4 acc[NTS];                                // dW1[j1 = 16w+4g+i][f = f0s + 16c + c16]
@@ -395,30 +249,18 @@ mlp_wide_dw1_kernel(MlpWideParams p, int nsl)
         ur[k] = (tid + k * T) / C4;
         uc[k] = (tid + k * T) - ur[k] * C4;
     }
-    auto tile_meta = [&](int tile, int slot) {
-        if (tid < kMwRows) {
-            const long long row = (long long)tile * kMwRows + tid;
-            bool ok = row < (long long)p.rows;
-            if (ok) {
-                const int q = (int)row / L, j = (int)row - q * L;
-                ok = p.n ? j < clamp_n(p.n[q], L) : true;
-            }
-            const unsigned long long m = __ballot(ok);
-            if (tid == 0) vmask[slot] = (unsigned)m;
-        }
-    };
     mlp_f4 P[KP];                                   // the fill in flight ...
     float A[8];                                     // ... and its dH1^T operand: [j1 = 16w + c16][doc 4s + g]
     auto issue_fill = [&](int tile, unsigned m) {
-        const float *Xt = p.X + (size_t)tile * kMwRows * (size_t)F + f0s;
+        const float *Xt = X + (size_t)tile * kMsRows * (size_t)F + f0s;
 #pragma unroll
         for (int k = 0; k < KP; ++k) {
-            const bool ok = ur[k] < kMwRows && ((m >> (ur[k] & 31)) & 1u) && f0s + 4 * uc[k] < F;
+            const bool ok = ur[k] < kMsRows && ((m >> (ur[k] & 31)) & 1u) && f0s + 4 * uc[k] < F;
             const float *src = ok ? Xt + (size_t)ur[k] * F + 4 * uc[k] : p.W1;
             P[k] = *reinterpret_cast<const mlp_f4 *>(src);
         }
         // (every row of a tile with a real row was written by the forward kernel: zeros on its padded rows)
-        const float *Dt = p.dH1 + ((size_t)tile * kMwRows + g) * kMwDH + 16 * w + c16;
+        const float *Dt = p.dH1 + ((size_t)tile * kMsRows + g) * kMwDH + 16 * w + c16;
 #pragma unroll
         for (int s = 0; s < 8; ++s) A[s] = Dt[(size_t)4 * s * kMwDH];
     };
@@ -429,13 +271,13 @@ mlp_wide_dw1_kernel(MlpWideParams p, int nsl)
             mlp_f4 v;
 #pragma unroll
             for (int i = 0; i < 4; ++i) v[i] = ok ? P[k][i] : 0.f;
-            if (ur[k] < kMwRows) *reinterpret_cast<mlp_f4 *>(im + ur[k] * IP + 4 * uc[k]) = v;
+            if (ur[k] < kMsRows) *reinterpret_cast<mlp_f4 *>(im + ur[k] * IP + 4 * uc[k]) = v;
         }
     };
 
     int tile = range;
-    tile_meta(tile, 0);
-    tile_meta(tile + GR, 1);
+    mlp_ring_write<false>(p, tid, tile, 0, vmask, nullptr);
+    mlp_ring_write<false>(p, tid, tile + GR, 1, vmask, nullptr);
     __syncthreads();
     {
         const unsigned m0 = __builtin_amdgcn_readfirstlane(vmask[0]);
@@ -443,13 +285,12 @@ mlp_wide_dw1_kernel(MlpWideParams p, int nsl)
     }
     int slot = 0, par = 0;
     for (; tile < p.tiles; tile += GR, par ^= 1) {
-        const int slot1 = slot == kMwRing - 1 ? 0 : slot + 1;
-        const int slot2 = slot1 == kMwRing - 1 ? 0 : slot1 + 1;
+        const int slot1 = mlp_ring_next(slot), slot2 = mlp_ring_next(slot1);
         // (both masks were written in front of a barrier every wave has passed; the slot rewritten below was last
         // read in front of the barrier of the iteration before)
         const unsigned m = __builtin_amdgcn_readfirstlane(vmask[slot]);
         const unsigned mnext = __builtin_amdgcn_readfirstlane(vmask[slot1]);
-        float *im = img + (size_t)par * kMwRows * IP;
+        float *im = img + (size_t)par * kMsRows * IP;
         float a1[8];
 #pragma unroll
         for (int s = 0; s < 8; ++s) a1[s] = 0.f;
@@ -459,50 +300,19 @@ mlp_wide_dw1_kernel(MlpWideParams p, int nsl)
             for (int s = 0; s < 8; ++s) a1[s] = A[s];
         }
         if (mnext) issue_fill(tile + GR, mnext);   // (past the last tile: mask 0)
-        tile_meta(tile + 2 * GR, slot2);
+        mlp_ring_write<false>(p, tid, tile + 2 * GR, slot2, vmask, nullptr);
         lds_barrier();                             // image filled (one barrier a tile: the images alternate)
         slot = slot1;
         if (m == 0) continue;
-        // ---- dW1[slice] += dH1^T . X: B = image columns; three feature steps in flight (mlp_rows_kernel) ----
-        const float *xsrc = im + g * IP + c16;
-        constexpr int CG = 3;
-#pragma unroll
-        for (int c0 = 0; c0 < NTS; c0 += CG) {
-#pragma unroll
-            for (int s = 0; s < 8; ++s) {
-#pragma unroll
-                for (int cc = 0; cc < CG; ++cc) {
-                    if (c0 + cc < NTS) acc[c0 + cc] = mfma16(a1[s], xsrc[4 * s * IP + 16 * (c0 + cc)], acc[c0 + cc]);
-                }
-            }
-        }
+        mlp_dw1_chain_f32<NTS, IP>(acc, a1, im + g * IP + c16);     // dW1[slice] += dH1^T . X: B = image columns
     }
 
-    // ---- this row range's partial dW1, columns of the slice: the D fragments go through a wave-private LDS tile and
-    // leave as 16-byte stores of consecutive addresses ----
+    // ---- this row range's partial dW1, columns of the slice ----
     __syncthreads();
-    float *dst = p.part + (size_t)range * p.pitch;
-    float *tile_s = reinterpret_cast<float *>(smem) + (size_t)w * 16 * IP;
-#pragma unroll
-    for (int c = 0; c < NTS; ++c)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) tile_s[(4 * g + i) * IP + 16 * c + c16] = acc[c][i];
-    for (int idx = lane; idx < 16 * C4; idx += 64) {
-        const int r = idx / C4, f = f0s + 4 * (idx - r * C4);
-        if (16 * w + r < H1 && f < F)
-            *reinterpret_cast<mlp_f4 *>(dst + (size_t)(16 * w + r) * F + f) =
-                *reinterpret_cast<const mlp_f4 *>(tile_s + r * IP + (f - f0s));
-    }
+    mlp_store_dw1<NTS, IP>(acc, reinterpret_cast<float *>(smem), p.part + (size_t)range * p.pitch, p, f0s, C4, ln);
 }
 
 // ---- host side ----
-inline bool mlp_wide_bad_shape(int B, int L, int F, int H1, int H2)
-{
-    if (B < 0 || L <= 0 || F <= 0 || H1 <= 0 || H2 <= 0) return true;
-    if ((F & 3) || F > kMwMaxF || H1 > kMlpH1 || H2 > kMlpH2) return true;
-    return (long long)B * L > 0x7fffffffLL;
-}
-
 struct MlpWidePlan {
     int tiles;
     int g1;                          // workgroups of the forward kernel = partial vectors of the small sums
@@ -515,8 +325,8 @@ struct MlpWidePlan {
 inline MlpWidePlan mlp_wide_plan(long long rows, int F, int H1, int H2)
 {
     MlpWidePlan s;
-    s.tiles = (int)((rows + kMwRows - 1) / kMwRows);
-    const long long wgs = (long long)kMwWgs * device_cu_count();
+    s.tiles = (int)((rows + kMsRows - 1) / kMsRows);
+    const long long wgs = (long long)kMsWgs * device_cu_count();
     s.g1 = (int)(s.tiles < wgs ? s.tiles : wgs);
     const int NT = (F + 15) >> 4;
     s.nsl = (NT + 10) / 11;
@@ -528,25 +338,25 @@ inline MlpWidePlan mlp_wide_plan(long long rows, int F, int H1, int H2)
     s.pitchB = mlp_pitch(s.psmall);
     s.offB = (size_t)s.gr * s.pitchA * sizeof(float);
     s.offH = s.offB + (size_t)s.g1 * s.pitchB * sizeof(float);
-    s.bytes = s.offH + (size_t)s.tiles * kMwRows * kMwDH * sizeof(float);
+    s.bytes = s.offH + (size_t)s.tiles * kMsRows * kMwDH * sizeof(float);
     return s;
 }
 
 template <bool GRAD>
-int launch_mlp_wide_fwd(const MlpWideParams &p, int grid, hipStream_t stream)
+int launch_mlp_wide_fwd(const MlpStreamParams &p, int grid, hipStream_t stream)
 {
     const size_t lds = mlp_wide_fwd_lds_bytes();
     LTR_ENSURE_LDS((mlp_wide_fwd_kernel<GRAD>), lds);
-    hipLaunchKernelGGL((mlp_wide_fwd_kernel<GRAD>), dim3((unsigned)grid), dim3(kMwThreads), lds, stream, p);
+    hipLaunchKernelGGL((mlp_wide_fwd_kernel<GRAD>), dim3((unsigned)grid), dim3(kMsThreads), lds, stream, p);
     return (int)hipGetLastError();
 }
 
 template <int NTS>
-int launch_mlp_wide_dw1(const MlpWideParams &p, const MlpWidePlan &s, hipStream_t stream)
+int launch_mlp_wide_dw1(const MlpStreamParams &p, const MlpWidePlan &s, hipStream_t stream)
 {
     const size_t lds = mlp_wide_dw1_lds_bytes(NTS);
     LTR_ENSURE_LDS((mlp_wide_dw1_kernel<NTS>), lds);
-    hipLaunchKernelGGL((mlp_wide_dw1_kernel<NTS>), dim3((unsigned)(s.gr * s.nsl)), dim3(kMwThreads), lds, stream, p, s.nsl);
+    hipLaunchKernelGGL((mlp_wide_dw1_kernel<NTS>), dim3((unsigned)(s.gr * s.nsl)), dim3(kMsThreads), lds, stream, p, s.nsl);
     return (int)hipGetLastError();
 }
 
@@ -557,22 +367,19 @@ int ltr_mlp_wide_scores_f32(const float *X, const float *W1, const float *b1, co
                             float *scores_out, void *stream)
 {
     LTR_CLEAR_STALE_ERROR();
-    if (mlp_wide_bad_shape(B, L, F, H1, H2)) return LTR_ERR_SHAPE;
+    if (mlp_stream_bad_shape(B, L, F, H1, H2, 4, kMwMaxF)) return LTR_ERR_SHAPE;
     if (!W1 || !b1 || !W2 || !b2 || !W3 || !b3) return LTR_ERR_NULL;
     if (B == 0) return LTR_OK;
     if (!X || !scores_out) return LTR_ERR_NULL;
     const MlpWidePlan s = mlp_wide_plan((long long)B * L, F, H1, H2);
-    MlpWideParams p;
-    p.X = X; p.W1 = W1; p.b1 = b1; p.W2 = W2; p.b2 = b2; p.W3 = W3; p.b3 = b3; p.g = nullptr;
-    p.n = n; p.scores_out = scores_out; p.part = nullptr; p.dH1 = nullptr;
-    p.B = B; p.L = L; p.F = F; p.H1 = H1; p.H2 = H2;
-    p.rows = B * L; p.tiles = s.tiles; p.pitch = 0;
+    MlpStreamParams p = mlp_stream_params(X, W1, b1, W2, b2, W3, b3, nullptr, n, B, L, F, H1, H2);
+    p.scores_out = scores_out;
     return launch_mlp_wide_fwd<false>(p, s.g1, (hipStream_t)stream);
 }
 
 size_t ltr_mlp_wide_grad_workspace_bytes(int B, int L, int F, int H1, int H2)
 {
-    if (B <= 0 || mlp_wide_bad_shape(B, L, F, H1, H2)) return 0;
+    if (B <= 0 || mlp_stream_bad_shape(B, L, F, H1, H2, 4, kMwMaxF)) return 0;
     return mlp_wide_plan((long long)B * L, F, H1, H2).bytes;
 }
 
@@ -581,7 +388,7 @@ int ltr_mlp_wide_grad_f32(const float *X, const float *W1, const float *b1, cons
                           int H1, int H2, float *grads, void *workspace, size_t workspace_bytes, void *stream)
 {
     LTR_CLEAR_STALE_ERROR();
-    if (mlp_wide_bad_shape(B, L, F, H1, H2)) return LTR_ERR_SHAPE;
+    if (mlp_stream_bad_shape(B, L, F, H1, H2, 4, kMwMaxF)) return LTR_ERR_SHAPE;
     if (!W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !grads) return LTR_ERR_NULL;
     const int P = mlp_param_count(F, H1, H2);
     hipStream_t st = (hipStream_t)stream;
@@ -590,12 +397,8 @@ int ltr_mlp_wide_grad_f32(const float *X, const float *W1, const float *b1, cons
     const MlpWidePlan s = mlp_wide_plan((long long)B * L, F, H1, H2);
     if (!workspace || workspace_bytes < s.bytes) return LTR_ERR_WORKSPACE;
     unsigned char *ws = static_cast<unsigned char *>(workspace);
-    MlpWideParams p;
-    p.X = X; p.W1 = W1; p.b1 = b1; p.W2 = W2; p.b2 = b2; p.W3 = W3; p.b3 = b3; p.g = g;
-    p.n = n; p.scores_out = nullptr;
+    MlpStreamParams p = mlp_stream_params(X, W1, b1, W2, b2, W3, b3, g, n, B, L, F, H1, H2);
     p.dH1 = reinterpret_cast<float *>(ws + s.offH);
-    p.B = B; p.L = L; p.F = F; p.H1 = H1; p.H2 = H2;
-    p.rows = B * L; p.tiles = s.tiles;
     // forward and back down to dH1; the small sums, one partial vector per workgroup
     p.part = reinterpret_cast<float *>(ws + s.offB); p.pitch = s.pitchB;
     int rc = launch_mlp_wide_fwd<true>(p, s.g1, st);

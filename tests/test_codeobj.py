@@ -112,3 +112,21 @@ def test_eight_wave_entry_points_stay_under_the_sgpr_cliff():
             # (the DCG-hinge generic-width tiles keep five VGPRs in scratch under the cap -- and are 16 % faster for it)
             assert r.get("vgpr_spill_count", 0) <= (5 if "linear_regtile2_kernel<1, " in n and ", 0, 512>" in n else 0), n
     assert seen >= 10, seen
+
+
+def test_standalone_mlp_scorer_kernels_keep_their_occupancy():
+    """the stand-alone MLP scorer kernels (one streaming body under mlp_rows_kernel / mlp_bf16_kernel, the
+    two wide kernels) are sized for two workgroups of four waves per CU -- 256 registers a lane -- and keep nothing in
+    scratch; only the f32 gradient kernel of the widest bucket runs alone on its CU, with 512."""
+    recs = _records()
+    seen = 0
+    for r in recs:
+        n = r.get("demangled", r["name"]).replace("(anonymous namespace)::", "")
+        if not any(k in n for k in ("mlp_rows_kernel<", "mlp_bf16_kernel<", "mlp_wide_fwd_kernel<", "mlp_wide_dw1_kernel<")):
+            continue
+        seen += 1
+        assert r.get("vgpr_spill_count", 0) == 0 and r.get("private_segment_fixed_size", 0) == 0, \
+            "%s spills %d VGPRs (%d B scratch)" % (n, r.get("vgpr_spill_count", -1), r.get("private_segment_fixed_size", -1))
+        cap = 512 if "mlp_rows_kernel<14, true>" in n else 256
+        assert r["vgpr_count"] + r.get("agpr_count", 0) <= cap, (n, r["vgpr_count"], r.get("agpr_count", 0))
+    assert seen >= 4 + 4 + 14 + 2 + 2, seen
