@@ -1033,6 +1033,25 @@ inline bool mlp_listwise_fits(int loss, int L, int F)
     return true;
 }
 
+// B, L, the network and its limits as every launching entry point of this file checks them
+inline bool mlp_step_bad_network(int B, int L, int F, int H1, int H2)
+{
+    return B < 0 || L <= 0 || F <= 0 || H1 <= 0 || H2 <= 0 || (F & 3) || F > 16 * 14 || H1 > kMlpH1 || H2 > kMlpH2;
+}
+
+// the params of a launch without a loss: float labels at X (not used; any readable address for the prefetch); the rest is the caller's
+inline MlpParams mlp_step_params(const float *X, const float *W1, const float *b1, const float *W2, const float *b2,
+                                 const float *W3, const float *b3, const int64_t *n, int B, int L, int F, int H1, int H2)
+{
+    MlpParams p;
+    p.X = X; p.W1 = W1; p.b1 = b1; p.W2 = W2; p.b2 = b2; p.W3 = W3; p.b3 = b3;
+    p.rel = X; p.n = n; p.grad_out = nullptr;
+    p.loss = nullptr; p.scores_out = nullptr; p.part = nullptr;
+    p.B = B; p.L = L; p.F = F; p.H1 = H1; p.H2 = H2;
+    p.sigma = 1.0f; p.rel_dtype = LTR_LABEL_F32; p.P = mlp_param_count(F, H1, H2); p.pitch = mlp_pitch(p.P); p.fwd_only = 0;
+    return p;
+}
+
 extern "C" {
 
 LTR_DEBUG_HOOK void ltr_debug_mlp_layout(int layout) { mlp_layout_choice() = layout; }
@@ -1064,8 +1083,7 @@ int ltr_mlp_pairwise_f32(int kind, float sigma, const float *X, const float *W1,
                          void *stream)
 {
     LTR_CLEAR_STALE_ERROR();
-    if (B < 0 || L <= 0 || F <= 0 || H1 <= 0 || H2 <= 0) return LTR_ERR_SHAPE;
-    if ((F & 3) || F > 16 * 14 || H1 > kMlpH1 || H2 > kMlpH2) return LTR_ERR_SHAPE;
+    if (mlp_step_bad_network(B, L, F, H1, H2)) return LTR_ERR_SHAPE;
     if (L > (mlp2_takes(F) ? kM2MaxLen : kMlpMaxLen)) return LTR_ERR_LIST_TOO_LONG;
     if (kind < LTR_HINGE || kind > LTR_NDCG2) return LTR_ERR_KIND;
     if (rel_dtype < LTR_LABEL_I64 || rel_dtype > LTR_LABEL_I32) return LTR_ERR_KIND;
@@ -1078,12 +1096,9 @@ int ltr_mlp_pairwise_f32(int kind, float sigma, const float *X, const float *W1,
         return LTR_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     if (B > 0) {
-        MlpParams p;
-        p.X = X; p.W1 = W1; p.b1 = b1; p.W2 = W2; p.b2 = b2; p.W3 = W3; p.b3 = b3;
-        p.rel = rel; p.n = n; p.grad_out = grad_out;
+        MlpParams p = mlp_step_params(X, W1, b1, W2, b2, W3, b3, n, B, L, F, H1, H2);
+        p.rel = rel; p.rel_dtype = rel_dtype; p.grad_out = grad_out; p.sigma = sigma;
         p.loss = loss; p.scores_out = scores_out; p.part = (float *)workspace;
-        p.B = B; p.L = L; p.F = F; p.H1 = H1; p.H2 = H2;
-        p.sigma = sigma; p.rel_dtype = rel_dtype; p.P = P; p.pitch = mlp_pitch(P); p.fwd_only = 0;
         const int rc = tile ? with_kind(kind, [&](auto K) { return launch_mlp2_kind<K>(p, grid, s); })
                             : with_kind(kind, [&](auto K) { return launch_mlp_kind<K>(p, grid, s); });
         if (rc != 0) return rc;
@@ -1106,8 +1121,7 @@ int ltr_mlp_listwise_f32(int loss, int k, const float *X, const float *W1, const
 {
     LTR_CLEAR_STALE_ERROR();
     if (bad_mlp_listwise_loss(loss) || bad_label_dtype(rel_dtype)) return LTR_ERR_KIND;
-    if (B < 0 || L <= 0 || F <= 0 || H1 <= 0 || H2 <= 0) return LTR_ERR_SHAPE;
-    if ((F & 3) || F > 16 * 14 || H1 > kMlpH1 || H2 > kMlpH2) return LTR_ERR_SHAPE;
+    if (mlp_step_bad_network(B, L, F, H1, H2)) return LTR_ERR_SHAPE;
     if (L > (mlp2_takes(F) ? kM2MaxLen : kMlpMaxLen)) return LTR_ERR_LIST_TOO_LONG;
     if (B == 0) return LTR_OK;
     if (!X || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !rel || !n || !loss_out || !grads) return LTR_ERR_NULL;
@@ -1117,12 +1131,9 @@ int ltr_mlp_listwise_f32(int loss, int k, const float *X, const float *W1, const
     if (!workspace || workspace_bytes < (size_t)grid * mlp_pitch(P) * sizeof(float)) return LTR_ERR_WORKSPACE;
     if (!mlp_listwise_fits(loss, L, F)) return LTR_ERR_CONFIG;
     hipStream_t s = (hipStream_t)stream;
-    MlpParams p;
-    p.X = X; p.W1 = W1; p.b1 = b1; p.W2 = W2; p.b2 = b2; p.W3 = W3; p.b3 = b3;
-    p.rel = rel; p.n = n; p.grad_out = grad_out;
+    MlpParams p = mlp_step_params(X, W1, b1, W2, b2, W3, b3, n, B, L, F, H1, H2);
+    p.rel = rel; p.rel_dtype = rel_dtype; p.grad_out = grad_out;
     p.loss = loss_out; p.scores_out = scores_out; p.part = (float *)workspace;
-    p.B = B; p.L = L; p.F = F; p.H1 = H1; p.H2 = H2;
-    p.sigma = 1.0f; p.rel_dtype = rel_dtype; p.P = P; p.pitch = mlp_pitch(P); p.fwd_only = 0;
     p.lw.k = k;
     if (loss == LTR_LISTWISE_LISTMLE) {           // (ListNet ranks nothing: the tie arguments are ignored)
         if (use_seed) { p.lw.use_seed = 1; p.lw.tie_seed = seed; p.lw.tie_seed_dev = seed_dev; }
@@ -1146,12 +1157,8 @@ LTR_DEBUG_HOOK int ltr_debug_mlp_probe_f32(const float *X, const float *W1, cons
     LTR_CLEAR_STALE_ERROR();
     if (B <= 0 || L <= 0 || L > kM2ParkLen || F != 136 || H1 <= 0 || H2 <= 0 || H1 > kMlpH1 || H2 > kMlpH2) return LTR_ERR_SHAPE;
     if (!X || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !n || !out) return LTR_ERR_NULL;
-    MlpParams p;
-    p.X = X; p.W1 = W1; p.b1 = b1; p.W2 = W2; p.b2 = b2; p.W3 = W3; p.b3 = b3;
-    p.rel = X; p.n = n; p.grad_out = nullptr;
-    p.loss = out; p.scores_out = nullptr; p.part = nullptr;
-    p.B = B; p.L = L; p.F = F; p.H1 = H1; p.H2 = H2;
-    p.sigma = 1.0f; p.rel_dtype = LTR_LABEL_F32; p.P = mlp_param_count(F, H1, H2); p.pitch = mlp_pitch(p.P); p.fwd_only = 0;
+    MlpParams p = mlp_step_params(X, W1, b1, W2, b2, W3, b3, n, B, L, F, H1, H2);
+    p.loss = out;
     const size_t lds = mlp2_lds_bytes(LTR_HINGE, 9, kM2ParkLen);
     LTR_ENSURE_LDS((mlp_tile_kernel<LTR_HINGE, 9, 34, kM2ParkLen, false, true>), lds);
     hipLaunchKernelGGL((mlp_tile_kernel<LTR_HINGE, 9, 34, kM2ParkLen, false, true>), dim3((unsigned)mlp2_grid(B)), dim3(kM2Threads), lds,
@@ -1164,20 +1171,14 @@ int ltr_mlp_scores_f32(const float *X, const float *W1, const float *b1, const f
                        int L, int F, int H1, int H2, float *scores_out, void *stream)
 {
     LTR_CLEAR_STALE_ERROR();
-    if (B < 0 || L <= 0 || F <= 0 || H1 <= 0 || H2 <= 0) return LTR_ERR_SHAPE;
-    if ((F & 3) || F > 16 * 14 || H1 > kMlpH1 || H2 > kMlpH2) return LTR_ERR_SHAPE;
+    if (mlp_step_bad_network(B, L, F, H1, H2)) return LTR_ERR_SHAPE;
     const bool tile_scores = L > kMlpMaxLen && mlp2_takes(F);       // 129 .. 256 documents: the tile kernel
     if (L > (tile_scores ? kM2MaxLen : kMlpMaxLen)) return LTR_ERR_LIST_TOO_LONG;
     if (!W1 || !b1 || !W2 || !b2 || !W3 || !b3) return LTR_ERR_NULL;
     if (B == 0) return LTR_OK;
     if (!X || !n || !scores_out) return LTR_ERR_NULL;
-    MlpParams p;
-    p.X = X; p.W1 = W1; p.b1 = b1; p.W2 = W2; p.b2 = b2; p.W3 = W3; p.b3 = b3;
-    p.rel = X;                       // labels are not used; any readable address for the prefetch
-    p.n = n; p.grad_out = nullptr;
-    p.loss = nullptr; p.scores_out = scores_out; p.part = nullptr;
-    p.B = B; p.L = L; p.F = F; p.H1 = H1; p.H2 = H2;
-    p.sigma = 1.0f; p.rel_dtype = LTR_LABEL_F32; p.P = mlp_param_count(F, H1, H2); p.pitch = mlp_pitch(p.P); p.fwd_only = 1;
+    MlpParams p = mlp_step_params(X, W1, b1, W2, b2, W3, b3, n, B, L, F, H1, H2);
+    p.scores_out = scores_out; p.fwd_only = 1;
     if (tile_scores) return launch_mlp2_scores(p, mlp2_grid(B), (hipStream_t)stream);
     return launch_mlp_scores(p, mlp_grid(B), (hipStream_t)stream);
 }

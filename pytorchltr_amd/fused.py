@@ -816,14 +816,34 @@ def mlp_supported(L, F, H1, H2):
             and 0 < H1 <= MLP_MAX_HIDDEN[0] and 0 < H2 <= MLP_MAX_HIDDEN[1])
 
 
-def _pad_features(xs, w1):
-    """Feature counts that are not a multiple of 4 (MQ2007: 46, Yahoo: 699): zero columns are
-    appended to the features and to W1 -- same scores, and the extra dW1 columns are dropped.  Costs
-    one copy of the batch; pad the stored split once to avoid it."""
-    extra = (-xs.shape[-1]) % 4
-    if extra == 0:
-        return xs, w1, 0
-    return (torch.nn.functional.pad(xs, (0, extra)), torch.nn.functional.pad(w1, (0, extra)), extra)
+class _MLPFamily(collections.namedtuple("_MLPFamily", "name dtype align f_min f_max scores grad grad_ws limits")):
+    """One family of stand-alone MLP scorer kernels: the element type of its batch, the alignment and the range
+    (f_min, f_max] of its feature counts, the names of its three entry points, the limits as its ValueError states them."""
+    __slots__ = ()
+
+    def takes(self, F, H1, H2):
+        """Networks the family's kernels take, at any list length."""
+        return (self.f_min < F <= self.f_max and F % self.align == 0
+                and 0 < H1 <= MLP_MAX_HIDDEN[0] and 0 < H2 <= MLP_MAX_HIDDEN[1])
+
+
+_MLP_ROWS = _MLPFamily("rows", torch.float32, 4, 0, MLP_MAX_FEATURES,                               # include/ltr_mlp_rows.h
+                       "ltr_mlp_rows_scores_f32", "ltr_mlp_rows_grad_f32", "ltr_mlp_rows_grad_workspace_bytes",
+                       "the MLP row kernels take F <= %d with F %% 4 == 0" % MLP_MAX_FEATURES)
+_MLP_WIDE = _MLPFamily("wide", torch.float32, 4, MLP_MAX_FEATURES, MLP_WIDE_MAX_FEATURES,           # include/ltr_mlp_wide.h
+                       "ltr_mlp_wide_scores_f32", "ltr_mlp_wide_grad_f32", "ltr_mlp_wide_grad_workspace_bytes",
+                       "the wide-row MLP kernels take %d < F <= %d with F %% 4 == 0" % (MLP_MAX_FEATURES, MLP_WIDE_MAX_FEATURES))
+_MLP_BF16 = _MLPFamily("bf16", torch.bfloat16, 8, 0, MLP_MAX_FEATURES,    # include/ltr_mlp_bf16.h: rows of whole 16-byte pieces
+                       "ltr_mlp_bf16_scores", "ltr_mlp_bf16_grad", "ltr_mlp_bf16_grad_workspace_bytes",
+                       "the bf16 MLP kernels take F <= %d (after zero-padding to a multiple of 8)" % MLP_MAX_FEATURES)
+_mlp_rows_network, _mlp_wide_network, _mlp_bf16_network = _MLP_ROWS.takes, _MLP_WIDE.takes, _MLP_BF16.takes
+
+
+def _mlp_family_of(dtype, F, wide=False):
+    """The family of a prepared batch: bf16 -> bf16, more than 224 features -> wide, otherwise rows.  `wide` is the
+    launchers' earlier flag, which tests/test_gpu_mlp_wide.py still passes: the wide family on rows of any width.
+    (Plain values, not the batch: the launchers have F at hand, and a second `X.shape` costs more than this call.)"""
+    return _MLP_BF16 if dtype is torch.bfloat16 else _MLP_WIDE if wide or F > MLP_MAX_FEATURES else _MLP_ROWS
 
 
 def _flat_params(params, F):
@@ -880,35 +900,114 @@ def mlp_listwise_supported(kind, B, L, F, H1, H2):
     return B == 0 or bool(_C.lib().ltr_mlp_listwise_plan(kind.loss, B, L, F, H1, H2))
 
 
-_mlp_rows_ws = {}        # (device index, B, L, F, H1, H2) -> ltr_mlp_rows_grad_workspace_bytes (grows with the CU count)
+_mlp_rows_ws = {}        # (device index, B, L, F, H1, H2, family) -> *_grad_workspace_bytes (grows with the CU count)
 
 
-def _mlp_rows_network(F, H1, H2):
-    """Networks the stand-alone MLP kernels take (include/ltr_mlp_rows.h), at any list length."""
-    return (0 < F <= MLP_MAX_FEATURES and F % 4 == 0 and 0 < H1 <= MLP_MAX_HIDDEN[0] and 0 < H2 <= MLP_MAX_HIDDEN[1])
+def _zero_pad(xs, w1, align):
+    """Feature counts that are not a multiple of `align` (MQ2007: 46, Yahoo: 699; bf16 rows, whole 16-byte pieces of 8
+    values: Istella's 220): zero columns are appended to the features and to W1 -- same scores, and the extra dW1
+    columns are dropped (`_crop_grads`).  Costs one copy of the batch; pad the stored split once to avoid it."""
+    extra = (-xs.shape[-1]) % align
+    if extra == 0:
+        return xs, w1, 0
+    return torch.nn.functional.pad(xs, (0, extra)), torch.nn.functional.pad(w1.detach(), (0, extra)), extra
 
 
-def _mlp_wide_network(F, H1, H2):
-    """Networks the wide-row MLP kernels are routed (include/ltr_mlp_wide.h): more features than the row kernels take,
-    up to 704, at any list length."""
-    return (MLP_MAX_FEATURES < F <= MLP_WIDE_MAX_FEATURES and F % 4 == 0
-            and 0 < H1 <= MLP_MAX_HIDDEN[0] and 0 < H2 <= MLP_MAX_HIDDEN[1])
+def _mlp_prepare(xs, params, family=None, pad=True):
+    """The arguments of a family's kernels: ``(X, flat_params, H1, H2, extra, family)`` -- the contiguous batch on the
+    device, the fp32 parameters, the hidden sizes, the number of zero columns appended (`pad`; W1 is padded to match)
+    and the family, chosen from the batch where None is given (`_mlp_family_of`).  ValueError for a network the family
+    does not take.  The f32 families go through `_prepare_features` (any dtype is cast, `_padded_rows` views are
+    honoured, the device is checked first); the bf16 family takes bf16 batches only and checks the device last."""
+    if family is None and torch.is_tensor(xs) and xs.dtype is torch.bfloat16:
+        family = _MLP_BF16
+    bf16 = family is _MLP_BF16
+    if bf16:
+        if not torch.is_tensor(xs) or xs.dtype is not torch.bfloat16:
+            raise ValueError("the bf16 MLP kernels take torch.bfloat16 features (fp32 features: mlp_scores / mlp_grad)")
+        if xs.dim() != 3:
+            raise ValueError("features must have shape (batch, list_size, features)")
+    params, extra = list(params), 0
+    if pad:
+        xs, params[0], extra = _zero_pad(xs, params[0], family.align if family else 4)
+    X = xs if bf16 else _prepare_features(xs)
+    B, L, F = X.shape
+    flat_params, H1, H2 = _flat_params(params, F)
+    if family is None:
+        family = _mlp_family_of(X.dtype, F)
+    if not family.takes(F, H1, H2) or L == 0:
+        raise ValueError("%s, hidden <= %s and L >= 1; got L=%d F=%d hidden=(%d, %d)"
+                         % (family.limits, MLP_MAX_HIDDEN, L, F - extra, H1, H2))
+    if bf16:
+        _C.require_device(X, "xs")
+        X = X.contiguous()
+    return X, flat_params, H1, H2, extra, family
 
 
-def _mlp_rows_scores(X, flat_params, H1, H2, nn, wide=False):
-    """ltr_mlp_rows_scores_f32 (`wide`: ltr_mlp_wide_scores_f32; a bf16 `X`: ltr_mlp_bf16_scores) on prepared
-    arguments: (B, L) scores, 0 on the padded documents."""
+def _mlp_grad_buffer(out, P, dev):
+    """The flat gradient buffer of P floats: `out` where the caller preallocated one."""
+    flat = out if out is not None else torch.empty(P, dtype=torch.float32, device=dev)
+    if flat.numel() != P or flat.dtype != torch.float32 or not flat.is_contiguous():
+        raise ValueError("out must be a contiguous float32 tensor of %d elements" % P)
+    return flat
+
+
+def _crop_grads(parts, extra, shapes=None):
+    """The six gradients without the dW1 columns of `extra` zero-padded features, in the parameters' `shapes`."""
+    parts = list(parts)
+    if extra:
+        parts[0] = parts[0][:, :parts[0].shape[1] - extra]
+    return tuple(g if shapes is None or g.shape == s else g.reshape(s) for g, s in zip(parts, shapes or parts))
+
+
+def _mlp_rows_scores(X, flat_params, H1, H2, nn, wide=False, family=None):
+    """The family's score entry point (ltr_mlp_rows_scores_f32, ltr_mlp_wide_scores_f32, ltr_mlp_bf16_scores; None: the
+    family of `X`, `_mlp_family_of`) on prepared arguments: (B, L) scores, 0 on the padded documents."""
     B, L, F = X.shape
     scores = torch.empty(B, L, dtype=torch.float32, device=X.device)
     if B > 0:
-        if X.dtype is torch.bfloat16:
-            fn = _C.lib().ltr_mlp_bf16_scores
-        else:
-            fn = _C.lib().ltr_mlp_wide_scores_f32 if wide else _C.lib().ltr_mlp_rows_scores_f32
+        fn = getattr(_C.lib(), (family or _mlp_family_of(X.dtype, F, wide)).scores)
         with _C.device_ctx(X):
             _C.check(fn(_C.ptr(X), *[_C.ptr(t) for t in flat_params], _C.ptr(nn), B, L, F, H1, H2, _C.ptr(scores),
                         _C.stream_of(X)))
     return scores
+
+
+def _mlp_grad_call(X, flat_params, H1, H2, grad_scores, n, out, wide=False, family=None):
+    """The family's gradient entry point (ltr_mlp_rows_grad_f32, ltr_mlp_wide_grad_f32, ltr_mlp_bf16_grad; None: the
+    family of `X`) behind the shape checks of its caller."""
+    B, L, F = X.shape
+    dev = X.device
+    if grad_scores.numel() != B * L or grad_scores.device != dev:
+        raise ValueError("grad_scores must hold one value per document of xs, on its device")
+    g = grad_scores.detach().reshape(B, L)
+    if g.dtype is not torch.float32 or not g.is_contiguous():
+        g = g.float().contiguous()
+    nn = None if n is None else prepare_n(n, B)
+    lib = _C.lib()
+    flat = _mlp_grad_buffer(out, _mlp_sizes_for(max(B, 1), F, H1, H2)[0], dev)
+    family = family or _mlp_family_of(X.dtype, F, wide)
+    key = (dev.index, B, L, F, H1, H2, family.name)
+    with _C.device_ctx(X):
+        ws_bytes = _mlp_rows_ws.get(key)
+        if ws_bytes is None:                # (asked with X's device current: the grid follows its CU count)
+            ws_bytes = _mlp_rows_ws[key] = int(getattr(lib, family.grad_ws)(B, L, F, H1, H2))
+        st = _C.stream_of(X)
+        ws = _mlp_workspace(dev, st, ws_bytes)
+        _C.check(getattr(lib, family.grad)(
+            _C.ptr(X), *[_C.ptr(t) for t in flat_params], _C.ptr(g), _C.ptr(nn), B, L, F, H1, H2, _C.ptr(flat),
+            _C.ptr(ws), ws_bytes, st))
+    return _split_grads(flat, F, H1, H2)
+
+
+def _mlp_family_scores(xs, params, n, family):
+    X, flat_params, H1, H2, _, family = _mlp_prepare(xs, params, family, pad=family is _MLP_BF16)
+    return _mlp_rows_scores(X, flat_params, H1, H2, None if n is None else prepare_n(n, X.shape[0]), family=family)
+
+
+def _mlp_family_grad(xs, params, grad_scores, n, out, family):
+    X, flat_params, H1, H2, extra, family = _mlp_prepare(xs, params, family, pad=family is _MLP_BF16)
+    return _crop_grads(_mlp_grad_call(X, flat_params, H1, H2, grad_scores, n, out, family=family), extra)
 
 
 def mlp_grad(xs, params, grad_scores, n=None, out=None):
@@ -926,139 +1025,20 @@ def mlp_grad(xs, params, grad_scores, n=None, out=None):
     Returns:
         ``(dW1, db1, dW2, db2, dW3, db3)``, views of one flat buffer as :func:`mlp_loss_step` returns them.
     """
-    X = _prepare_features(xs)
-    B, L, F = X.shape
-    flat_params, H1, H2 = _flat_params(params, F)
-    if not _mlp_rows_network(F, H1, H2) or L == 0:
-        raise ValueError("the MLP row kernels take F <= %d with F %% 4 == 0, hidden <= %s and L >= 1; got L=%d F=%d "
-                         "hidden=(%d, %d)" % (MLP_MAX_FEATURES, MLP_MAX_HIDDEN, L, F, H1, H2))
-    return _mlp_grad_call(X, flat_params, H1, H2, grad_scores, n, out, False)
-
-
-def _mlp_grad_call(X, flat_params, H1, H2, grad_scores, n, out, wide):
-    """ltr_mlp_rows_grad_f32 (`wide`: ltr_mlp_wide_grad_f32; a bf16 `X`: ltr_mlp_bf16_grad) behind the shape checks of
-    its caller."""
-    B, L, F = X.shape
-    dev = X.device
-    if grad_scores.numel() != B * L or grad_scores.device != dev:
-        raise ValueError("grad_scores must hold one value per document of xs, on its device")
-    g = grad_scores.detach().reshape(B, L)
-    if g.dtype is not torch.float32 or not g.is_contiguous():
-        g = g.float().contiguous()
-    nn = None if n is None else prepare_n(n, B)
-    lib = _C.lib()
-    P = _mlp_sizes_for(max(B, 1), F, H1, H2)[0]
-    flat = out if out is not None else torch.empty(P, dtype=torch.float32, device=dev)
-    if flat.numel() != P or flat.dtype != torch.float32 or not flat.is_contiguous():
-        raise ValueError("out must be a contiguous float32 tensor of %d elements" % P)
-    bf16 = X.dtype is torch.bfloat16
-    key = (dev.index, B, L, F, H1, H2, "bf16" if bf16 else wide)
-    if bf16:
-        ws_fn, grad_fn = lib.ltr_mlp_bf16_grad_workspace_bytes, lib.ltr_mlp_bf16_grad
-    else:
-        ws_fn, grad_fn = ((lib.ltr_mlp_wide_grad_workspace_bytes, lib.ltr_mlp_wide_grad_f32) if wide
-                          else (lib.ltr_mlp_rows_grad_workspace_bytes, lib.ltr_mlp_rows_grad_f32))
-    with _C.device_ctx(X):
-        ws_bytes = _mlp_rows_ws.get(key)
-        if ws_bytes is None:                # (asked with X's device current: the grid follows its CU count)
-            ws_bytes = _mlp_rows_ws[key] = int(ws_fn(B, L, F, H1, H2))
-        st = _C.stream_of(X)
-        ws = _mlp_workspace(dev, st, ws_bytes)
-        _C.check(grad_fn(
-            _C.ptr(X), *[_C.ptr(t) for t in flat_params], _C.ptr(g), _C.ptr(nn), B, L, F, H1, H2, _C.ptr(flat),
-            _C.ptr(ws), ws_bytes, st))
-    return _split_grads(flat, F, H1, H2)
-
-
-def _mlp_wide_checked(xs, params):
-    X = _prepare_features(xs)
-    B, L, F = X.shape
-    flat_params, H1, H2 = _flat_params(params, F)
-    if not _mlp_wide_network(F, H1, H2) or L == 0:
-        raise ValueError("the wide-row MLP kernels take %d < F <= %d with F %% 4 == 0, hidden <= %s and L >= 1; got L=%d "
-                         "F=%d hidden=(%d, %d)" % (MLP_MAX_FEATURES, MLP_WIDE_MAX_FEATURES, MLP_MAX_HIDDEN, L, F, H1, H2))
-    return X, flat_params, H1, H2
+    return _mlp_family_grad(xs, params, grad_scores, n, out, _MLP_ROWS)
 
 
 def mlp_wide_scores(xs, params, n=None):
     """:func:`mlp_scores` for feature rows wider than 224 floats, up to 704 (ltr_mlp_wide_scores_f32: the feature
     dimension is streamed in chunks; any list length; no autograd): (B, L) float32 scores for documents < n[b] and 0 for
     the padded ones, whose features are not read; n=None scores every document.  Other networks raise ValueError."""
-    X, flat_params, H1, H2 = _mlp_wide_checked(xs, params)
-    return _mlp_rows_scores(X, flat_params, H1, H2, None if n is None else prepare_n(n, X.shape[0]), wide=True)
+    return _mlp_family_scores(xs, params, n, _MLP_WIDE)
 
 
 def mlp_wide_grad(xs, params, grad_scores, n=None, out=None):
     """:func:`mlp_grad` for feature rows wider than 224 floats, up to 704 (ltr_mlp_wide_grad_f32): same arguments, same
     ``(dW1, db1, dW2, db2, dW3, db3)`` views of one flat buffer.  Other networks raise ValueError."""
-    X, flat_params, H1, H2 = _mlp_wide_checked(xs, params)
-    return _mlp_grad_call(X, flat_params, H1, H2, grad_scores, n, out, True)
-
-
-class _MLPScoreFunction(torch.autograd.Function):
-    """``mlp(xs)`` with parameter gradients: forward is the row score kernel, backward the row gradient kernel on
-    ``grad_scores`` (the activations are recomputed; nothing but the features and the parameters is kept); rows wider
-    than 224 features run the wide-row pair of kernels (ltr_mlp_wide_*_f32).  The features get no gradient (they are data; callers route an input that requires one to the torch layers)."""
-
-    @staticmethod
-    def forward(ctx, xs, n, *params):
-        xp, w1, extra = _pad_features(xs, params[0].detach())
-        X = _prepare_features(xp)
-        B, L, F = X.shape
-        flat_params, H1, H2 = _flat_params((w1,) + tuple(t.detach() for t in params[1:]), F)
-        nn = None if n is None else prepare_n(n, B)
-        scores = _mlp_rows_scores(X, flat_params, H1, H2, nn, wide=_mlp_wide_network(F, H1, H2))
-        ctx.save_for_backward(X, nn if nn is not None else torch.empty(0, device=X.device), *flat_params)
-        ctx.has_n = nn is not None
-        ctx.extra = extra
-        ctx.shapes = [t.shape for t in params]
-        return scores.unsqueeze(-1)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_scores):
-        X, nn, *flat_params = ctx.saved_tensors
-        H1, H2 = flat_params[0].shape[0], flat_params[2].shape[0]
-        parts = list(_mlp_grad_call(X, flat_params, H1, H2, grad_scores, nn if ctx.has_n else None, None,
-                                    _mlp_wide_network(X.shape[2], H1, H2)))
-        if ctx.extra:
-            parts[0] = parts[0][:, :X.shape[2] - ctx.extra]
-        return (None, None) + tuple(g if g.shape == s else g.reshape(s) for g, s in zip(parts, ctx.shapes))
-
-
-def _mlp_bf16_network(F, H1, H2):
-    """Networks the bf16-feature MLP kernels take (include/ltr_mlp_bf16.h), at any list length."""
-    return (0 < F <= MLP_MAX_FEATURES and F % 8 == 0 and 0 < H1 <= MLP_MAX_HIDDEN[0] and 0 < H2 <= MLP_MAX_HIDDEN[1])
-
-
-def _pad_features_bf16(xs, w1):
-    """:func:`_pad_features` for the bf16 kernels, whose rows are whole 16-byte pieces of 8 values (Istella: 220 ->
-    224): zero columns are appended to the features and to W1, the extra dW1 columns are dropped.  One copy of the
-    batch; pad the stored split once to avoid it."""
-    extra = (-xs.shape[-1]) % 8
-    if extra == 0:
-        return xs, w1, 0
-    return (torch.nn.functional.pad(xs, (0, extra)), torch.nn.functional.pad(w1, (0, extra)), extra)
-
-
-def _mlp_bf16_checked(xs, params):
-    """The arguments of the bf16 kernels: the contiguous bf16 batch (zero-padded to F % 8 == 0), the fp32 parameters
-    (W1 padded to match), the hidden sizes and the number of padding columns; ValueError for anything else."""
-    if not torch.is_tensor(xs) or xs.dtype is not torch.bfloat16:
-        raise ValueError("the bf16 MLP kernels take torch.bfloat16 features (fp32 features: mlp_scores / mlp_grad)")
-    if xs.dim() != 3:
-        raise ValueError("features must have shape (batch, list_size, features)")
-    B, L, F = xs.shape
-    flat_params, H1, H2 = _flat_params([t.detach() for t in params], F)
-    F8 = (F + 7) & ~7
-    if not _mlp_bf16_network(F8, H1, H2) or L == 0:
-        raise ValueError("the bf16 MLP kernels take F <= %d (after zero-padding to a multiple of 8), hidden <= %s and "
-                         "L >= 1; got L=%d F=%d hidden=(%d, %d)" % (MLP_MAX_FEATURES, MLP_MAX_HIDDEN, L, F, H1, H2))
-    _C.require_device(xs, "xs")
-    xp, w1, extra = _pad_features_bf16(xs, flat_params[0])
-    X = xp if xp.is_contiguous() else xp.contiguous()
-    flat_params = (w1 if w1.is_contiguous() else w1.contiguous(),) + tuple(flat_params[1:])
-    return X, flat_params, H1, H2, extra
+    return _mlp_family_grad(xs, params, grad_scores, n, out, _MLP_WIDE)
 
 
 def mlp_scores_bf16(xs, params, n=None):
@@ -1068,8 +1048,7 @@ def mlp_scores_bf16(xs, params, n=None):
     kernel rounds W1 to bf16 (nearest even) for the first layer -- the scores are those of the network with
     ``W1.bfloat16()``, accumulated in fp32 -- everything behind the first layer is fp32.  Feature counts that are not a
     multiple of 8 are zero-padded with one copy.  Other networks raise ValueError."""
-    X, flat_params, H1, H2, _ = _mlp_bf16_checked(xs, params)
-    return _mlp_rows_scores(X, flat_params, H1, H2, None if n is None else prepare_n(n, X.shape[0]))
+    return _mlp_family_scores(xs, params, n, _MLP_BF16)
 
 
 def mlp_grad_bf16(xs, params, grad_scores, n=None, out=None):
@@ -1078,25 +1057,24 @@ def mlp_grad_bf16(xs, params, grad_scores, n=None, out=None):
     forward uses (a straight-through update of the fp32 master weights).  Same arguments and the same
     ``(dW1, db1, dW2, db2, dW3, db3)`` views of one flat buffer; with a feature count that is not a multiple of 8, `out`
     holds the padded network's parameters and ``dW1`` is the view of its first F columns."""
-    X, flat_params, H1, H2, extra = _mlp_bf16_checked(xs, params)
-    parts = _mlp_grad_call(X, flat_params, H1, H2, grad_scores, n, out, False)
-    if extra:
-        parts = (parts[0][:, :X.shape[2] - extra],) + tuple(parts[1:])
-    return parts
+    return _mlp_family_grad(xs, params, grad_scores, n, out, _MLP_BF16)
 
 
-class _MLPScoreBf16Function(torch.autograd.Function):
-    """:class:`_MLPScoreFunction` on a bf16 batch: forward is the bf16 score kernel, backward the bf16 gradient kernel;
-    the bf16 batch itself is what is saved (a copy only where the feature count had to be padded to 8)."""
+class _MLPScoreFunction(torch.autograd.Function):
+    """``mlp(xs)`` with parameter gradients: forward is the score kernel of the batch's family (`_mlp_family_of`: the
+    row kernels, the wide-row pair past 224 features, the bf16 pair on a bf16 batch), backward its gradient kernel on
+    ``grad_scores`` (the activations are recomputed; nothing but the prepared batch -- a copy only where the feature
+    count had to be padded -- and the parameters is kept).  The features get no gradient (they are data; callers route
+    an input that requires one to the torch layers)."""
 
     @staticmethod
     def forward(ctx, xs, n, *params):
-        X, flat_params, H1, H2, extra = _mlp_bf16_checked(xs, params)
+        X, flat_params, H1, H2, extra, family = _mlp_prepare(xs, [t.detach() for t in params])
         nn = None if n is None else prepare_n(n, X.shape[0])
-        scores = _mlp_rows_scores(X, flat_params, H1, H2, nn)
+        scores = _mlp_rows_scores(X, flat_params, H1, H2, nn, family=family)
         ctx.save_for_backward(X, nn if nn is not None else torch.empty(0, device=X.device), *flat_params)
         ctx.has_n = nn is not None
-        ctx.extra = extra
+        ctx.extra, ctx.family = extra, family
         ctx.shapes = [t.shape for t in params]
         return scores.unsqueeze(-1)
 
@@ -1105,35 +1083,61 @@ class _MLPScoreBf16Function(torch.autograd.Function):
     def backward(ctx, grad_scores):
         X, nn, *flat_params = ctx.saved_tensors
         H1, H2 = flat_params[0].shape[0], flat_params[2].shape[0]
-        parts = list(_mlp_grad_call(X, flat_params, H1, H2, grad_scores, nn if ctx.has_n else None, None, False))
-        if ctx.extra:
-            parts[0] = parts[0][:, :X.shape[2] - ctx.extra]
-        return (None, None) + tuple(g if g.shape == s else g.reshape(s) for g, s in zip(parts, ctx.shapes))
+        parts = _mlp_grad_call(X, flat_params, H1, H2, grad_scores, nn if ctx.has_n else None, None, family=ctx.family)
+        return (None, None) + _crop_grads(parts, ctx.extra, ctx.shapes)
 
 
-def _mlp_bf16_batch(xs):
-    """True for the batches the modules hand to the bf16 kernels: a bf16 (B, L, F) batch on the device that needs no
-    gradient itself, outside autocast.  (The torch layers cannot take it: their weights are fp32.  A network outside
-    the kernels' limits raises ValueError there.)"""
-    return (torch.is_tensor(xs) and xs.dim() == 3 and xs.is_cuda and xs.dtype is torch.bfloat16 and not xs.requires_grad
-            and xs.shape[1] > 0 and not torch.is_autocast_enabled())
+# ---- the route table: which kernels a batch reaches from each caller ----
+_FUSED, _PER_QUERY, _ROWS, _WIDE, _BF16, _TORCH = "fused step", "per-query scores", "rows", "wide", "bf16", "torch layers"
+_ROUTE_FAMILY = {_FUSED: _MLP_ROWS, _PER_QUERY: _MLP_ROWS, _ROWS: _MLP_ROWS, _WIDE: _MLP_WIDE, _BF16: _MLP_BF16}
 
 
-def _mlp_rows_usable(xs, H1, H2):
-    """True where ``_MLPScoreFunction`` computes ``mlp(xs)``: an fp32 (B, L, F) batch on the device that needs no
-    gradient itself, a network within the kernels' limits (F counted after the padding to a multiple of 4)."""
-    return (torch.is_tensor(xs) and xs.dim() == 3 and xs.is_cuda and xs.dtype is torch.float32 and not xs.requires_grad
-            and xs.shape[1] > 0 and not torch.is_autocast_enabled()
-            and (_mlp_rows_network((xs.shape[2] + 3) & ~3, H1, H2)
-                 or (_MLP_WIDE_ENABLED and _mlp_wide_network((xs.shape[2] + 3) & ~3, H1, H2))))
+def _f4(F):
+    """The row width of F features after the modules' zero-padding to whole float4."""
+    return (F + 3) & ~3
 
 
-# Set to False by scripts/bench_mlp_rows.py alone: the routes past the fused limits as they were before the row kernels
-# (torch layers + autograd), timed in the same process as the new ones.
-_MLP_ROWS_ENABLED = True
-# Set to False by scripts/bench_mlp_wide.py alone: rows wider than 224 features on the torch layers, as before the
-# wide-row kernels, timed in the same process as the new route.
-_MLP_WIDE_ENABLED = True
+def _mlp_route(caller, dtype, dim, is_cuda, requires_grad, grad_enabled, autocast, L, F, H1, H2, kind=None, plan=True):
+    """Which kernels compute ``mlp(xs)`` (and, for a caller with a loss `kind`, the step): plain values in, one of
+    _FUSED (the one-launch step, ltr_mlp_pairwise_f32 / ltr_mlp_listwise_f32), _PER_QUERY (ltr_mlp_scores_f32), _ROWS,
+    _WIDE, _BF16 (the three families) or _TORCH out -- the three ``nn.Linear`` layers in a module, ValueError in a
+    function, which has none.  A family's ValueError (bf16: a network it does not take) is raised by `_mlp_prepare`.
+
+    `caller`: "scorer" (MLPScorer.forward), "score" (the loss modules' score()), "loss" (their forward()), "step"
+    (mlp_loss_step), "scores" (mlp_scores).  `plan`: False where a listwise `kind` is off the plan of the fused
+    step (:func:`mlp_listwise_supported`, asked by the caller: this function calls nothing).
+    The modules zero-pad the feature count to a multiple of 4 (bf16: 8), the functions take it as it is.
+    """
+    if dim != 3 or not is_cuda or L <= 0:
+        return _TORCH
+    module = caller in ("scorer", "score", "loss")
+    data = not requires_grad and not autocast           # a batch that needs no gradient itself, outside autocast
+    if dtype is torch.bfloat16 and data and (module or (caller == "step" and F % 8 == 0)):
+        return _BF16                                     # at every list length: the fused kernels are fp32-only
+    if module:
+        F = _f4(F)                                       # (everything below computes in fp32)
+    if kind is not None and plan and mlp_supported(L, F, H1, H2):
+        return _FUSED                                    # any dtype (cast to fp32), also a batch that is no `data`
+    rows, wide = _MLP_ROWS.takes(F, H1, H2), _MLP_WIDE.takes(F, H1, H2)
+    if not module:                                       # any dtype is cast to fp32; no wide route, no torch layers
+        if caller == "scores" and rows and L <= mlp_max_list_len(F):
+            return _PER_QUERY
+        return _ROWS if rows else _TORCH
+    if caller != "scorer" and not grad_enabled:          # evaluation through score(): any dtype on the f32 kernels
+        if rows:
+            return _PER_QUERY if L <= mlp_max_list_len(F) else _ROWS
+        return _WIDE if wide and dtype is torch.float32 and not autocast else _TORCH
+    f32_data = dtype is torch.float32 and data
+    return _ROWS if rows and f32_data else _WIDE if wide and f32_data else _TORCH
+
+
+def _mlp_route_of(caller, xs, F, H1, H2, kind=None, plan=True):
+    """`_mlp_route` on a batch: its dtype, shape and flags, the grad mode and the autocast state (F None: the batch's)."""
+    if not torch.is_tensor(xs) or xs.dim() != 3:
+        return _TORCH
+    _, L, Fx = xs.shape
+    return _mlp_route(caller, xs.dtype, 3, xs.is_cuda, xs.requires_grad, torch.is_grad_enabled(),
+                      torch.is_autocast_enabled(), L, Fx if F is None else F, H1, H2, kind, plan)
 
 
 def _mlp_step_pieces(X, flat_params, H1, H2, relevance, n, kind, sigma, grad_out, return_scores, return_loss_sum, out):
@@ -1151,7 +1155,7 @@ def _mlp_step_pieces(X, flat_params, H1, H2, relevance, n, kind, sigma, grad_out
               else grad_out.reshape(B).float())
         (ds,) = torch.autograd.grad((lossv * go).sum(), s)
     lossv = lossv.detach()
-    res = (lossv, _mlp_grad_call(X, flat_params, H1, H2, ds, nn, out, False))
+    res = (lossv, _mlp_grad_call(X, flat_params, H1, H2, ds, nn, out))
     if return_scores:
         res = res + (scores,)
     if return_loss_sum:
@@ -1186,31 +1190,23 @@ def mlp_loss_step(xs, params, relevance, n, loss="hinge", grad_out=None, return_
     """
     kind, sigma = _resolve_loss(loss)
     listwise = isinstance(kind, _ListwiseKind)
-    if _mlp_bf16_batch(xs) and xs.shape[2] % 8 == 0:
-        # a bf16 batch: the three pieces on the bf16 kernels at every list length (the fused kernels are fp32-only)
-        X, flat_params, H1, H2, _ = _mlp_bf16_checked(xs, params)
+    F, H1, H2 = params[0].shape[-1], params[0].shape[0], params[2].shape[0]    # (the network's: W1 is (H1, F))
+    plan = not listwise or (xs.dim() == 3 and mlp_listwise_supported(kind, xs.shape[0], xs.shape[1], F, H1, H2))
+    route = _mlp_route_of("step", xs, F, H1, H2, kind, plan)
+    if route is _TORCH:
+        _mlp_not_taken(xs, params, True)
+    X, flat_params, H1, H2, _, _ = _mlp_prepare(xs, params, _ROUTE_FAMILY[route], pad=False)
+    if route is not _FUSED:
+        # past the fused kernels' list lengths or listwise plan, or a bf16 batch (they are fp32-only): three pieces
         return _mlp_step_pieces(X, flat_params, H1, H2, relevance, n, kind, sigma, grad_out, return_scores,
                                 return_loss_sum, out)
-    X = _prepare_features(xs)
     B, L, F = X.shape
-    flat_params, H1, H2 = _flat_params(params, F)
-    if not mlp_supported(L, F, H1, H2) or (listwise and not mlp_listwise_supported(kind, B, L, F, H1, H2)):
-        if _mlp_rows_network(F, H1, H2) and L > 0:
-            # past the list lengths the fused kernels hold (or their listwise plan): the same step from three pieces
-            return _mlp_step_pieces(X, flat_params, H1, H2, relevance, n, kind, sigma, grad_out, return_scores,
-                                    return_loss_sum, out)
-        raise ValueError("fused MLP kernel takes L <= %d (F <= 144: %d), F <= %d with F %% 4 == 0, "
-                         "hidden <= %s; got L=%d F=%d hidden=(%d, %d)"
-                         % (MLP_MAX_LIST_LEN, MLP_MAX_LIST_LEN_NARROW, MLP_MAX_FEATURES,
-                            MLP_MAX_HIDDEN, L, F, H1, H2))
     dev = X.device
     r, nn = _labels_and_n(relevance, n, B, L, dev)
     lib = _C.lib()
     P, ws_bytes = _mlp_sizes_for(B, F, H1, H2)
     lossv = torch.empty(B, dtype=torch.float32, device=dev)
-    flat = out if out is not None else torch.empty(P, dtype=torch.float32, device=dev)
-    if flat.numel() != P or flat.dtype != torch.float32 or not flat.is_contiguous():
-        raise ValueError("out must be a contiguous float32 tensor of %d elements" % P)
+    flat = _mlp_grad_buffer(out, P, dev)
     # (loss_sum is written, not accumulated, by the reduction launch; B == 0 launches nothing)
     lsum = None
     if return_loss_sum:
@@ -1255,16 +1251,19 @@ def mlp_scores(xs, params, n=None):
     Lists up to :func:`mlp_max_list_len` run the per-query kernel (ltr_mlp_scores_f32), longer ones the row kernel
     (ltr_mlp_rows_scores_f32: any length).  Feature counts and hidden sizes outside the kernels' limits raise
     ValueError (see :func:`mlp_supported`)."""
-    X = _prepare_features(xs)
+    route = _mlp_route_of("scores", xs, params[0].shape[-1], params[0].shape[0], params[2].shape[0])
+    if route is _TORCH:
+        _mlp_not_taken(xs, params, False)
+    X, flat_params, H1, H2, _, _ = _mlp_prepare(xs, params, _MLP_ROWS, pad=False)
+    fn = _mlp_query_scores if route is _PER_QUERY else _mlp_rows_scores
+    return fn(X, flat_params, H1, H2, None if n is None else prepare_n(n, X.shape[0]))
+
+
+def _mlp_query_scores(X, flat_params, H1, H2, nn):
+    """ltr_mlp_scores_f32, the per-query score kernel, on prepared arguments: (B, L) scores, 0 on the padded documents."""
     B, L, F = X.shape
-    flat_params, H1, H2 = _flat_params(params, F)
-    if L > mlp_max_list_len(F) and _mlp_rows_network(F, H1, H2):
-        return _mlp_rows_scores(X, flat_params, H1, H2, None if n is None else prepare_n(n, B))
-    if not mlp_supported(L, F, H1, H2):
-        raise ValueError("fused MLP kernel takes L <= %d (F <= 144: %d), F <= %d with F %% 4 == 0, "
-                         "hidden <= %s" % (MLP_MAX_LIST_LEN, MLP_MAX_LIST_LEN_NARROW, MLP_MAX_FEATURES,
-                                           MLP_MAX_HIDDEN))
-    nn = (torch.full((B,), L, dtype=torch.int64, device=X.device) if n is None else prepare_n(n, B))
+    if nn is None:
+        nn = torch.full((B,), L, dtype=torch.int64, device=X.device)
     scores = torch.empty(B, L, dtype=torch.float32, device=X.device)
     if B > 0:
         with _C.device_ctx(X):
@@ -1272,6 +1271,15 @@ def mlp_scores(xs, params, n=None):
                 _C.ptr(X), *[_C.ptr(t) for t in flat_params], _C.ptr(nn), B, L, F, H1, H2,
                 _C.ptr(scores), _C.stream_of(X)))
     return scores
+
+
+def _mlp_not_taken(xs, params, got):
+    """What mlp_loss_step / mlp_scores raise where `_mlp_route` finds no kernel: the prepare step's errors come first."""
+    X = _prepare_features(xs)
+    _, H1, H2 = _flat_params(params, X.shape[2])
+    raise ValueError("fused MLP kernel takes L <= %d (F <= 144: %d), F <= %d with F %% 4 == 0, hidden <= %s"
+                     % (MLP_MAX_LIST_LEN, MLP_MAX_LIST_LEN_NARROW, MLP_MAX_FEATURES, MLP_MAX_HIDDEN)
+                     + ("; got L=%d F=%d hidden=(%d, %d)" % (X.shape[1], X.shape[2], H1, H2) if got else ""))
 
 
 class _MLPLossFunction(torch.autograd.Function):
@@ -1283,7 +1291,7 @@ class _MLPLossFunction(torch.autograd.Function):
         B = xs.shape[0]
         go = None if mean else torch.ones(B, dtype=torch.float32, device=xs.device)
         loss = _KindProxy(*kind_sigma)
-        xs, w1, extra = _pad_features(xs, params[0].detach())
+        xs, w1, extra = _zero_pad(xs, params[0], 4)
         lossv, grads, lsum = mlp_loss_step(xs, (w1,) + tuple(params[1:]), relevance, n, loss=loss,
                                            grad_out=go, return_loss_sum=True)
         ctx.save_for_backward(grads[0]._base)       # the flat buffer: one scale in backward
@@ -1300,10 +1308,7 @@ class _MLPLossFunction(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad_total, grad_unused):
         (flat,) = ctx.saved_tensors
-        parts = list(_split_grads(flat * grad_total, *ctx.dims))
-        if ctx.extra:
-            parts[0] = parts[0][:, :ctx.dims[0] - ctx.extra]
-        scaled = tuple(g if g.shape == s else g.reshape(s) for g, s in zip(parts, ctx.shapes))
+        scaled = _crop_grads(_split_grads(flat * grad_total, *ctx.dims), ctx.extra, ctx.shapes)
         return (None, None, None, None, None) + scaled
 
 
@@ -1313,20 +1318,45 @@ class _KindProxy:
         self.sigma = sigma
 
 
-class _FusedMLPBase(torch.nn.Module):
-    """What FusedMLPLoss and FusedMLPListwiseLoss share: the three ``nn.Linear`` layers, ``score()``, the fused step
-    where ``_fused_shape`` takes the batch and the unfused composition (``_pieces``) where it does not."""
+class _MLPLayers(torch.nn.Module):
+    """What the MLP modules share: the three ``nn.Linear`` layers (``l1`` / ``l2`` / ``l3``, the state_dict of the
+    guide's ``Model``) and ``mlp(xs)`` by the route `_mlp_route` names."""
 
-    def __init__(self, in_features, loss, hidden, reduction):
+    def __init__(self, in_features, hidden=(50, 10)):
         super().__init__()
-        if reduction not in ("mean", "sum"):
-            raise ValueError("reduction must be 'mean' or 'sum'")
         self.in_features = in_features
-        self.reduction = reduction
-        self.kind, self.sigma = self._resolve(loss)
         self.l1 = torch.nn.Linear(in_features, hidden[0])
         self.l2 = torch.nn.Linear(hidden[0], hidden[1])
         self.l3 = torch.nn.Linear(hidden[1], 1)
+
+    def _params(self):
+        return (self.l1.weight, self.l1.bias, self.l2.weight, self.l2.bias, self.l3.weight, self.l3.bias)
+
+    def _hidden(self):
+        layers = self._modules      # (not self.l1: nn.Module.__getattr__ costs 2 us a look, and forward() is a timed path)
+        return layers["l1"].out_features, layers["l2"].out_features
+
+    def _score(self, xs, n, route):
+        if route is _TORCH:
+            return self.l3(torch.nn.functional.relu(self.l2(torch.nn.functional.relu(self.l1(xs)))))
+        if torch.is_grad_enabled():
+            return _MLPScoreFunction.apply(xs, n, *self._params())     # (backward: the family's gradient kernel)
+        # evaluation: one launch (the per-query kernel up to mlp_max_list_len documents)
+        X, flat_params, H1, H2, _, _ = _mlp_prepare(xs, self._params(), _ROUTE_FAMILY[route])
+        fn = _mlp_query_scores if route is _PER_QUERY else _mlp_rows_scores
+        return fn(X, flat_params, H1, H2, None if n is None else prepare_n(n, X.shape[0])).unsqueeze(-1)
+
+
+class _FusedMLPBase(_MLPLayers):
+    """What FusedMLPLoss and FusedMLPListwiseLoss share: ``score()``, the fused step where the route is `_FUSED` and the
+    unfused composition (``_pieces``) where it is not."""
+
+    def __init__(self, in_features, loss, hidden, reduction):
+        if reduction not in ("mean", "sum"):
+            raise ValueError("reduction must be 'mean' or 'sum'")
+        super().__init__(in_features, hidden)
+        self.reduction = reduction
+        self.kind, self.sigma = self._resolve(loss)
         self.last_losses = None
 
     def score(self, xs, n=None):
@@ -1340,45 +1370,26 @@ class _FusedMLPBase(torch.nn.Module):
         kernels (ltr_mlp_bf16_*: W1 rounded to bf16 for the first layer, fp32 behind it) at every list length, with
         and without gradients; more than 224 features (after padding to 8) or hidden sizes past (64, 16) raise
         ValueError there."""
-        H1, H2 = self.l1.out_features, self.l2.out_features
-        if _mlp_bf16_batch(xs):
-            # a bf16 batch: the bf16 score kernel (its backward: the bf16 gradient kernel), at every list length
-            return _MLPScoreBf16Function.apply(xs, n, *self._params())
-        if torch.is_tensor(xs) and xs.dim() == 3 and xs.is_cuda:
-            if not torch.is_grad_enabled():
-                # evaluation: mlp_scores (the per-query kernel up to mlp_max_list_len documents, the row kernel past it)
-                F4, L = (xs.shape[2] + 3) & ~3, xs.shape[1]
-                if mlp_supported(L, F4, H1, H2) or (_MLP_ROWS_ENABLED and L > 0 and _mlp_rows_network(F4, H1, H2)):
-                    xp, w1, _ = _pad_features(xs, self.l1.weight.detach())
-                    return mlp_scores(xp, (w1,) + self._params()[1:], n).unsqueeze(-1)
-                if (_MLP_WIDE_ENABLED and L > 0 and _mlp_wide_network(F4, H1, H2) and xs.dtype is torch.float32
-                        and not torch.is_autocast_enabled()):
-                    xp, w1, _ = _pad_features(xs, self.l1.weight.detach())
-                    return mlp_wide_scores(xp, (w1,) + self._params()[1:], n).unsqueeze(-1)
-            elif _mlp_rows_usable(xs, H1, H2) and (_MLP_ROWS_ENABLED or _mlp_wide_network((xs.shape[2] + 3) & ~3, H1, H2)):
-                return _MLPScoreFunction.apply(xs, n, *self._params())
-        # everything else: the torch layers
-        o1 = torch.nn.functional.relu(self.l1(xs))
-        o2 = torch.nn.functional.relu(self.l2(o1))
-        return self.l3(o2)
+        return self._score(xs, n, _mlp_route_of("score", xs, None, *self._hidden()))
 
-    def _params(self):
-        return (self.l1.weight, self.l1.bias, self.l2.weight, self.l2.bias, self.l3.weight,
-                self.l3.bias)
+    def _plan(self, B, L, F4, H1, H2):
+        """The `plan` of `_mlp_route`: the pairwise fused step has none beyond :func:`mlp_supported`."""
+        return True
 
     def _fused_shape(self, B, L, F4):
-        return mlp_supported(L, F4, self.l1.out_features, self.l2.out_features)
+        return mlp_supported(L, F4, *self._hidden()) and self._plan(B, L, F4, *self._hidden())
 
     def forward(self, xs, relevance, n):
         _C.require_device(xs, "xs")
         B, L, F = xs.shape
-        # (a bf16 batch: score() on the bf16 kernels + the loss kernel, the fused per-query kernels are fp32-only)
-        if not _mlp_bf16_batch(xs) and self._fused_shape(B, L, (F + 3) & ~3):
+        H1, H2 = self._hidden()
+        route = _mlp_route_of("loss", xs, F, H1, H2, self.kind, self._plan(B, L, _f4(F), H1, H2))
+        if route is _FUSED:
             total, per_query = _MLPLossFunction.apply(
                 xs, relevance, n, (self.kind, self.sigma), self.reduction == "mean", *self._params())
             self.last_losses = per_query
             return total
-        per_query = self._pieces(self.score(xs, n), relevance, n)
+        per_query = self._pieces(self._score(xs, n, route), relevance, n)
         self.last_losses = per_query.detach()
         return per_query.mean() if self.reduction == "mean" else per_query.sum()
 
@@ -1432,14 +1443,14 @@ class FusedMLPListwiseLoss(_FusedMLPBase):
 
     _resolve = staticmethod(_resolve_listwise_loss)
 
-    def _fused_shape(self, B, L, F4):
-        return mlp_listwise_supported(self.kind, B, L, F4, self.l1.out_features, self.l2.out_features)
+    def _plan(self, B, L, F4, H1, H2):
+        return mlp_listwise_supported(self.kind, B, L, F4, H1, H2)
 
     def _pieces(self, scores, relevance, n):
         return _listwise_pieces(scores, relevance, n, self.kind)
 
 
-class MLPScorer(torch.nn.Module):
+class MLPScorer(_MLPLayers):
     """The guide's scorer ``Linear(F, H1) / ReLU / Linear(H1, H2) / ReLU / Linear(H2, 1)`` on its own -- what
     :class:`LinearScorer` is to ``nn.Linear(F, 1)``: ``loss_fn(scorer(xs), ys, n)`` with any loss, at any list length.
     ``l1`` / ``l2`` / ``l3`` are ordinary ``torch.nn.Linear`` layers (the state_dict of :class:`FusedMLPLoss` and of
@@ -1452,22 +1463,6 @@ class MLPScorer(torch.nn.Module):
     half the bytes, W1 rounded to bf16 for the first layer; up to 224 features, ValueError past that); 228 to 704 features (Yahoo: 699, padded to 700) run the wide-row kernels (ltr_mlp_wide_*_f32), which
     stream the feature dimension in chunks.  CPU tensors are refused: there is no CPU fallback."""
 
-    def __init__(self, in_features, hidden=(50, 10)):
-        super().__init__()
-        self.in_features = in_features
-        self.l1 = torch.nn.Linear(in_features, hidden[0])
-        self.l2 = torch.nn.Linear(hidden[0], hidden[1])
-        self.l3 = torch.nn.Linear(hidden[1], 1)
-
-    def _params(self):
-        return (self.l1.weight, self.l1.bias, self.l2.weight, self.l2.bias, self.l3.weight, self.l3.bias)
-
     def forward(self, xs, n=None):
         _C.require_device(xs, "xs")
-        if _mlp_bf16_batch(xs):
-            return _MLPScoreBf16Function.apply(xs, n, *self._params())
-        if _mlp_rows_usable(xs, self.l1.out_features, self.l2.out_features):
-            return _MLPScoreFunction.apply(xs, n, *self._params())
-        o1 = torch.nn.functional.relu(self.l1(xs))
-        o2 = torch.nn.functional.relu(self.l2(o1))
-        return self.l3(o2)
+        return self._score(xs, n, _mlp_route_of("scorer", xs, None, *self._hidden()))

@@ -7,8 +7,8 @@ network Linear(F, 50) / ReLU / Linear(50, 10) / ReLU / Linear(10, 1), median tim
                  kernels; `fused` = ltr_mlp_scores_f32 where that kernel takes the shape;
   hinge_step  -- (b) FusedMLPLoss(F, "hinge") forward + backward of the mean loss: `rows` = row scores, the stand-alone
                  loss kernel, the row gradient kernel; `torch` = the torch layers, the same loss kernel and torch's
-                 autograd (the route before; the private switch fused._MLP_ROWS_ENABLED selects it in this process);
-                 `fused_path` says whether the one-launch fused step takes the shape (then both columns are that step);
+                 autograd (the route before, written out here: `torch_step` below, at
+                 every shape); `fused_path` says whether the one-launch fused step takes the shape (then `rows` is it);
   kernels     -- (c) the two row kernels on their own (fused._mlp_rows_scores; fused.mlp_grad = gradient kernel + the
                  reduction of the partial vectors) and their share of the 155 TFLOP/s f32 MFMA peak, counting the
                  FLOPs of the real rows at the padded tile sizes (16-feature chunks x 64 x 16).
@@ -39,6 +39,17 @@ def row_flops(F):
     return fwd, fwd + 2 * (Fp * 64 + 64 * 16 + 64 * 16 + 16)
 
 
+def torch_scores(module, xs):
+    """The route before the kernels: the module's three nn.Linear layers."""
+    return module.l3(torch.relu(module.l2(torch.relu(module.l1(xs)))))
+
+
+def torch_step(module, xs, y, n):
+    module._pieces(torch_scores(module, xs), y, n).mean().backward()
+    for p in module.parameters():
+        p.grad = None
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--regions", type=int, default=7)
@@ -66,19 +77,12 @@ def main():
 
         def score_torch(xs, y, n):
             with torch.no_grad():
-                module.l3(torch.relu(module.l2(torch.relu(module.l1(xs)))))
+                torch_scores(module, xs)
 
         def step(xs, y, n):
             module(xs, y, n).backward()
             for p in module.parameters():
                 p.grad = None
-
-        def with_rows(on, fn):
-            fused._MLP_ROWS_ENABLED = on
-            try:
-                return timed(fn)
-            finally:
-                fused._MLP_ROWS_ENABLED = True
 
         row = {"batches": len(data), "real_rows": round(real), "fused_path": fused_path}
         # (a) scores.  Where the per-query kernel takes the shape, score() is that kernel: the row kernel is called directly
@@ -87,7 +91,7 @@ def main():
         if fused.mlp_supported(L, F, *HIDDEN):
             row["scores"]["fused"] = timed(score)
         # (b) the training step of FusedMLPLoss("hinge")
-        row["hinge_step"] = {"rows": with_rows(True, step), "torch": with_rows(False, step)}
+        row["hinge_step"] = {"rows": timed(step), "torch": timed(lambda xs, y, n: torch_step(module, xs, y, n))}
         # (c) the kernels and their share of the MFMA peak
         it = iter(range(1 << 30))
         k_grad = timed(lambda xs, y, n: fused.mlp_grad(xs, params, gs[next(it) % len(gs)], n))

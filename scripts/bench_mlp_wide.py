@@ -6,7 +6,7 @@ guide's network Linear(F, 50) / ReLU / Linear(50, 10) / ReLU / Linear(10, 1), me
                  nn.Linear layers (rocBLAS), the route before the wide kernels;
   hinge_step  -- (b) FusedMLPLoss(F, "hinge") forward + backward of the mean loss: `wide` = wide scores, the stand-alone
                  loss kernel, the wide gradient (two kernels + two reductions); `torch` = the torch layers, the same
-                 loss kernel and torch's autograd (the private switch fused._MLP_WIDE_ENABLED selects it in this process);
+                 loss kernel and torch's autograd, written out: `bench_mlp_rows.torch_step`;
   kernels     -- (c) the entry points on their own (fused.mlp_wide_scores; fused.mlp_wide_grad) and their share of the
                  155 TFLOP/s f32 MFMA peak, counting the FLOPs of the real rows at the padded tile sizes
                  (16-feature steps x 64 x 16), and the score kernel's feature bytes per second.
@@ -24,7 +24,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench_listwise_fused import batches, time_region  # noqa: E402
-from bench_mlp_rows import HIDDEN, PEAK_F32_MFMA, row_flops  # noqa: E402
+from bench_mlp_rows import HIDDEN, PEAK_F32_MFMA, row_flops, torch_scores, torch_step  # noqa: E402
 from pytorchltr_amd import fused  # noqa: E402
 
 
@@ -54,22 +54,19 @@ def main():
             with torch.no_grad():
                 module.score(xs, n)
 
+        def score_torch(xs, y, n):
+            with torch.no_grad():
+                torch_scores(module, xs)
+
         def step(xs, y, n):
             module(xs, y, n).backward()
             for p in module.parameters():
                 p.grad = None
 
-        def with_wide(on, fn):
-            fused._MLP_WIDE_ENABLED = on
-            try:
-                return timed(fn)
-            finally:
-                fused._MLP_WIDE_ENABLED = True
-
         row = {"batches": len(data), "real_rows": round(real)}
-        # (a) scores under no_grad, (b) the training step of FusedMLPLoss("hinge"): both routes through the switch
-        row["scores"] = {"wide": with_wide(True, score), "torch": with_wide(False, score)}
-        row["hinge_step"] = {"wide": with_wide(True, step), "torch": with_wide(False, step)}
+        # (a) scores under no_grad, (b) the training step of FusedMLPLoss("hinge"): the module's route, the torch route
+        row["scores"] = {"wide": timed(score), "torch": timed(score_torch)}
+        row["hinge_step"] = {"wide": timed(step), "torch": timed(lambda xs, y, n: torch_step(module, xs, y, n))}
         # (c) the entry points and their share of the MFMA peak
         it = iter(range(1 << 30))
         k_scores = timed(lambda xs, y, n: fused.mlp_wide_scores(xs, params, n))

@@ -145,7 +145,6 @@ def test_python_surface():
     assert MLPScorer(8).l1.out_features == 50 and MLPScorer(8).l2.out_features == 10
     assert fused._mlp_rows_network(224, 64, 16) and not fused._mlp_rows_network(228, 64, 16)
     assert not fused._mlp_rows_network(6, 4, 4) and not fused._mlp_rows_network(8, 65, 4)
-    assert fused._MLP_ROWS_ENABLED is True
 
 
 def test_cpu_tensors_are_refused():
