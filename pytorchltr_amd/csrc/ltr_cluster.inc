@@ -1,5 +1,5 @@
 // ltr_cluster.inc -- Linear(F,1) scorer fused with the pairwise loss for LONG lists, features read
-// ONCE (included by ltr_kernels.hip after ltr_linear.inc).
+// ONCE (included by ltr_linear.hip after ltr_linear.inc and ltr_areas.inc).
 //
 // The general fused kernel (linear_pairwise_kernel) gives a query to one workgroup: its rows do
 // not fit the workgroup's registers, so the features are read twice (scores, then dW), and the
@@ -435,7 +435,7 @@ __device__ __forceinline__ float cluster_hinge_from_runs(const QueryLds &q, cons
 
 // The counters reset themselves: the last workgroup of a cluster (the one that adds the shares) zeroes the
 // cluster's three counters, so a launch finds them as it needs them -- round 2 zeroed them with a launch of their
-// own in front of every step (4.7 us).  They live in the exchange area the library owns (ltr_linear.inc:
+// own in front of every step (4.7 us).  They live in the exchange area the library owns (ltr_areas.inc:
 // exchange_area_get), zeroed when it is allocated and never handed to anybody else: round 3 kept them in the
 // caller's workspace behind a magic word, which a recycled allocation could leave intact over dirty counters
 // (ADVICE r3).  A launch that gave up leaves them dirty: the host zeroes the area once the status has been cleared.

@@ -16,7 +16,7 @@
 // defined in ltr_kernels.hip (hidden visibility: internal to the shared library)
 extern "C" __attribute__((visibility("hidden"))) int *ltr_internal_status_device_ptr(void *stream);
 extern "C" __attribute__((visibility("hidden"))) int ltr_internal_status_peek(void);
-// defined in ltr_linear.inc: every exchange area is zeroed before its next use (a launch gave up)
+// defined in ltr_areas.inc: every exchange area is zeroed before its next use (a launch gave up)
 extern "C" __attribute__((visibility("hidden"))) void ltr_internal_exchange_mark_dirty(void);
 
 namespace {

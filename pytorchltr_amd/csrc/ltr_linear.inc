@@ -1,5 +1,6 @@
-// ltr_linear.inc -- Linear(F,1) scorer fused with the pairwise loss (included by
-// ltr_kernels.hip).  One workgroup per query runs the whole training-step slice
+// ltr_linear.inc -- Linear(F,1) scorer fused with the pairwise loss: LinearParams, the kernels, their shape choosers and
+// launchers (included by ltr_linear.hip; the host side of the step is in ltr_linear_step.inc and the files listed there).
+// One workgroup per query runs the whole training-step slice
 //     scores = X[b] . W + bias  ->  loss[b], d loss/d scores  ->  dW_b = (go_b * g)^T X[b]
 // (examples/01-basic-usage.py:70-75 in the reference: loss_fn(model(xs), ys, n).mean().backward()
 // with model = torch.nn.Linear(F, 1)).
@@ -29,7 +30,7 @@ constexpr int kLinearThreads = 512;
 
 // (the per-query partial rows: partial_pitch, ltr_common.inc)
 
-// The mailbox of a data-parallel lazy step as the device sees it (ltr_mailbox_*, further down): a small struct in this rank's
+// The mailbox of a data-parallel lazy step as the device sees it (ltr_mailbox_*, ltr_mailbox.inc; here because LinearParams carries it): a small struct in this rank's
 // own device memory -- every rank's mailbox mapped into THIS address space, who I am, the granules per (parity, rank) slot.
 constexpr int kMbMaxRanks = 16;
 struct MailboxDev {
@@ -1258,1151 +1259,3 @@ int launch_regtile(int kind, const LinearParams &p, const RegtileShape &s, hipSt
 }
 
 }  // namespace
-
-// ---------------------------------------------------------------------------------------------
-// Exchange areas.  The kernels whose workgroups hand data to each other inside a launch
-// (ltr_parts.inc) keep their control words and tagged granules in device memory that the LIBRARY owns:
-// zeroed when it is allocated and never handed to anybody else, so no kernel ever trusts
-// uninitialised memory (round 3 kept them in the caller's workspace behind a magic word; a recycled
-// allocation could leave the magic intact over dirty counters -- ADVICE r3).  One area per (device,
-// stream) for eager launches -- launches on a stream are ordered, so they can share it; a PRIVATE
-// area for every call made under stream capture -- a captured launch may be replayed on any stream,
-// next to anything.  An area is two allocations: `gran` holds nothing but granules ({tag, value}
-// words and zeros: memory that has carried other data can never look like a granule of the current
-// tag), `misc` the control block (fixed size, in front) and the parked shares.  Areas grow, they are
-// never freed while the process lives (a graph may still refer to them); ltr_exchange_release()
-// frees them all when the caller knows nothing is in flight.
-// ---------------------------------------------------------------------------------------------
-namespace {
-// control region in front of `misc`: the parts kernel's control block (tag, tickets, arrival counters of up to 8192
-// queries), then the cluster kernel's counters (256 bytes per query); both zero between launches
-constexpr size_t kExPartsCtrlBytes = 64 * 1024;
-constexpr size_t kExClusterCtrlBytes = 128 * 1024;
-constexpr size_t kExCtrlBytes = kExPartsCtrlBytes + kExClusterCtrlBytes;
-struct ExchangeArea {
-    int device;
-    hipStream_t stream;
-    bool captured;                  // belongs to one stream capture (capture_id): shared by the calls of that capture, never
-                                    // looked up by anybody else
-    unsigned long long capture_id;
-    bool dirty;                     // a launch gave up: zero before the next use
-    unsigned char *gran, *misc;
-    size_t gran_bytes, misc_bytes;
-};
-struct ExchangeAreas { std::mutex m; std::deque<ExchangeArea> v; std::deque<void *> retired; };
-inline ExchangeAreas &exchange_areas() { static ExchangeAreas *a = new ExchangeAreas(); return *a; }
-
-// device memory, zeroed; legal under stream capture (the allocation is not part of the captured work:
-// the thread's capture mode is relaxed around it, the zeroing runs on a stream of its own)
-inline hipError_t exchange_alloc_zeroed(void **out, size_t bytes)
-{
-    hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
-    (void)hipThreadExchangeStreamCaptureMode(&mode);
-    void *ptr = nullptr;
-    hipError_t e = hipMalloc(&ptr, bytes);
-    if (e == hipSuccess) {
-        hipStream_t zs = nullptr;
-        e = hipStreamCreateWithFlags(&zs, hipStreamNonBlocking);
-        if (e == hipSuccess) {
-            e = hipMemsetAsync(ptr, 0, bytes, zs);
-            const hipError_t e2 = hipStreamSynchronize(zs);
-            if (e == hipSuccess) e = e2;
-            (void)hipStreamDestroy(zs);
-        }
-        if (e != hipSuccess) { (void)hipFree(ptr); ptr = nullptr; }
-    }
-    (void)hipThreadExchangeStreamCaptureMode(&mode);
-    *out = ptr;
-    return e;
-}
-
-int exchange_area_get(hipStream_t stream, size_t gran_bytes, size_t misc_bytes, unsigned char **gran, unsigned char **misc,
-                      size_t *gran_have = nullptr)
-{
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    // Under stream capture the area belongs to the CAPTURE (its id): every call captured into one graph shares it -- the
-    // graph's kernel nodes run one after the other like the launches of a stream -- and a later capture gets its own (round 4
-    // gave every captured CALL an area: a graph of K steps held K of them; ADVICE r4).
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    unsigned long long cid = 0;
-    if (hipStreamGetCaptureInfo(stream, &cs, &cid) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; cid = 0; }
-    const bool capturing = cs != hipStreamCaptureStatusNone;
-    ExchangeAreas &A = exchange_areas();
-    std::lock_guard<std::mutex> lock(A.m);
-    ExchangeArea *a = nullptr;
-    for (auto &x : A.v)
-        if (x.device == dev && x.stream == stream && x.captured == capturing && (!capturing || x.capture_id == cid)) { a = &x; break; }
-    if (!a) {
-        A.v.push_back(ExchangeArea{dev, stream, capturing, capturing ? cid : 0ull, false, nullptr, nullptr, 0, 0});
-        a = &A.v.back();
-    }
-    auto grow = [&](unsigned char *&ptr, size_t &have, size_t need) -> hipError_t {
-        if (have >= need) return hipSuccess;
-        size_t bytes = (need + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
-        if (!capturing && have > 0 && bytes < have + have / 2) bytes = have + have / 2;      // (geometric: few retired blocks)
-        void *np = nullptr;
-        const hipError_t e = exchange_alloc_zeroed(&np, bytes);
-        if (e != hipSuccess) return e;
-        if (ptr) A.retired.push_back(ptr);              // (work queued on the stream may still use it)
-        ptr = reinterpret_cast<unsigned char *>(np);
-        have = bytes;
-        return hipSuccess;
-    };
-    // (a new control block behind a grown `misc` starts at tag 1 again: `gran` must not keep granules of
-    // the old block's tags -- the two grow together)
-    const bool regrow = (a->gran_bytes < gran_bytes) || (a->misc_bytes < misc_bytes);
-    if (regrow && (a->gran || a->misc)) {
-        if (a->gran) A.retired.push_back(a->gran);
-        if (a->misc) A.retired.push_back(a->misc);
-        const size_t g = a->gran_bytes + a->gran_bytes / 2, m = a->misc_bytes + a->misc_bytes / 2;
-        gran_bytes = gran_bytes > g ? gran_bytes : g;
-        misc_bytes = misc_bytes > m ? misc_bytes : m;
-        a->gran = a->misc = nullptr;
-        a->gran_bytes = a->misc_bytes = 0;
-    }
-    hipError_t e = grow(a->gran, a->gran_bytes, gran_bytes);
-    if (e == hipSuccess) e = grow(a->misc, a->misc_bytes, misc_bytes);
-    if (e != hipSuccess) { (void)hipGetLastError(); return (int)e; }
-    if (a->dirty) {
-        // a launch on this area gave up and the caller has cleared the status: start from zero
-        e = hipMemsetAsync(a->gran, 0, a->gran_bytes, stream);
-        if (e == hipSuccess) e = hipMemsetAsync(a->misc, 0, a->misc_bytes, stream);
-        if (e != hipSuccess) return (int)e;
-        a->dirty = false;
-    }
-    *gran = a->gran;
-    *misc = a->misc;
-    if (gran_have) *gran_have = a->gran_bytes;          // (the whole area: what a tag wrap has to zero)
-    return LTR_OK;
-}
-}  // namespace
-
-// (called by ltr_device_status(clear) in ltr_kernels.hip once a timeout has been acknowledged)
-extern "C" __attribute__((visibility("hidden"))) void ltr_internal_exchange_mark_dirty(void)
-{
-    ExchangeAreas &A = exchange_areas();
-    std::lock_guard<std::mutex> lock(A.m);
-    for (auto &x : A.v) x.dirty = true;
-}
-
-#include "ltr_cluster.inc"
-#include "ltr_parts.inc"
-
-namespace {
-inline size_t linear_partials_bytes(int B, int F)
-{
-    // (B, partial_pitch(F)) partials, rounded up, plus -- batches the split reduction takes: launch_linear_reduce -- its scratch
-    // rows, plus a reserved 256-byte tail
-    const size_t PF = (size_t)partial_pitch(F);
-    const size_t split = (B >= kReduceSplitMin && PF / 4 <= 256) ? (size_t)kReduceMaxSplit * (size_t)reduce_scratch_pitch((int)PF) * sizeof(float) : 0;
-    return ((((size_t)B * PF * sizeof(float)) + 255) & ~(size_t)255) + split + 256;
-}
-}  // namespace
-
-namespace {
-// The cluster kernel takes the shapes it covers first (small batches of lists the symmetric pass takes: measured
-// faster than the parts kernel there, round 4)
-inline bool prefer_cluster()
-{
-    return !parts_debug_all();          // (tests of the parts kernel: ltr_debug_parts_all puts it first)
-}
-
-// Which kernel family runs a fused Linear step of (kind, B, L, F), and its shape: the ONE copy of the fallback chain register
-// tile -> cluster (when prefer_cluster()) -> parts -> cluster -> general.  What the launch knows and the plan ABI does not is
-// an argument: vec = 4 when X's rows are whole, 16-byte aligned float4; fast = LTR_TRACE_ALLOW_FAST (no score matrix asked
-// for); labels = the cluster kernel's label kind (1 integer, 0 float, -1 unknown).  The general kernel's shape stays with its
-// launch (choose_linear_shape).
-struct LinearPlan { int family; RegtileShape rs; ClusterShape cs; PartsShape ps; };
-
-LinearPlan plan_linear(int kind, int B, int L, int F, int vec, bool fast, int labels)
-{
-    LinearPlan pl;
-    pl.family = LTR_PLAN_GENERAL;
-    if (vec != 4 || !fast) return pl;
-    const bool cluster_first = prefer_cluster();
-    if (choose_regtile_shape(kind, L, F, pl.rs)) pl.family = LTR_PLAN_REGISTER_TILE;
-    else if (cluster_first && choose_cluster_shape(kind, B, L, F, pl.cs, labels)) pl.family = LTR_PLAN_CLUSTER;
-    else if (choose_parts_shape(kind, B, L, F, pl.ps)) pl.family = LTR_PLAN_PARTS;
-    else if (!cluster_first && choose_cluster_shape(kind, B, L, F, pl.cs, labels)) pl.family = LTR_PLAN_CLUSTER;
-    return pl;
-}
-
-// hold-backs of a lazy launch's query workgroups in units of 512 cycles (LinearParams::pend_sleep): without quiet workgroups,
-// and with them -- everybody else's and the quiet ones' own (profiles/r07_lazy_quiet.txt)
-constexpr int kLazyHoldPlain = 2, kLazyHold = 0, kLazyHoldQuiet = 8;
-inline int &lazy_holdback() { static int v = -1; return v; }       // ltr_debug_lazy_holdback: >= 0 replaces the packed word
-// Where the quiet rule was measured to pay (profiles/r07_lazy_quiet.txt): the hinge kinds -- their launch is bound by the memory
-// system all CUs share, the others by their most loaded CU, which the reducers' CUs taking the shortest lists unbalances (C3,
-// LambdaNDCG2: 17.3 -> 18.2 us; logistic 14.4 -> 15.2) --, a grid that fills the CUs (a fourth workgroup on some: at 600 queries
-// the quiet ones' wait is the launch's tail, 10.4 -> 11.0) and rows of at least 64 features (8 features: 19.8 -> 20.1)
-inline bool lazy_quiet_pays(int kind, int B, int F)
-{
-    return (kind == LTR_HINGE || kind == LTR_DCG_HINGE) && B > 3 * device_cu_count() && F >= 64;
-}
-}  // namespace
-
-extern "C" {
-
-LTR_DEBUG_HOOK void ltr_debug_force_timeout(int on) { cluster_force_timeout() = on ? 1 : 0; }
-LTR_DEBUG_HOOK void ltr_debug_cluster_mode(int bits) { cluster_debug_mode() = bits; }
-LTR_DEBUG_HOOK int ltr_debug_parts_all(int on) { const int old = parts_debug_all(); parts_debug_all() = on ? 1 : 0; return old; }
-
-// Frees every exchange area of the process (ltr_hip.h): only when no launch that used one is in flight and no
-// captured graph that contains one will be replayed again.
-namespace { int lazy_areas_release(); }
-
-int ltr_exchange_release(void)
-{
-    const int lz = lazy_areas_release();            // (the lazy steps' weight granules: same rule -- nothing in flight)
-    ExchangeAreas &A = exchange_areas();
-    std::lock_guard<std::mutex> lock(A.m);
-    hipError_t e = (hipError_t)lz;
-    for (auto &x : A.v) {
-        if (x.gran) { const hipError_t r = hipFree(x.gran); if (r != hipSuccess) e = r; }
-        if (x.misc) { const hipError_t r = hipFree(x.misc); if (r != hipSuccess) e = r; }
-    }
-    for (void *r : A.retired) { const hipError_t q = hipFree(r); if (q != hipSuccess) e = q; }
-    A.v.clear();
-    A.retired.clear();
-    return (int)e;
-}
-
-// The tag the NEXT launch on `stream`'s exchange area will use (tests: the wrap from 2^32 - 1 to 1).
-LTR_DEBUG_HOOK int ltr_debug_set_exchange_tag(void *stream, unsigned tag)
-{
-    unsigned char *gran = nullptr, *misc = nullptr;
-    if (const int rc = exchange_area_get((hipStream_t)stream, 16, kExCtrlBytes, &gran, &misc)) return rc;
-    static unsigned staged[8];
-    static int slot = 0;
-    unsigned *src = &staged[slot++ & 7];
-    *src = tag;
-    return (int)hipMemcpyAsync(misc, src, sizeof(unsigned), hipMemcpyHostToDevice, (hipStream_t)stream);
-}
-
-size_t ltr_linear_workspace_bytes(int B, int L, int F)
-{
-    if (B <= 0 || F <= 0) return 0;
-    size_t bytes = linear_partials_bytes(B, F);
-    // long lists on small batches, NDCG kinds: scratch of the cluster kernel behind the partials (the parts
-    // kernel keeps its exchange buffers in memory the library owns: exchange_area_get)
-    size_t scratch = 0;
-    ClusterShape cs;
-    // (the largest over the kinds: their batch limits differ, and the NDCG kinds carry the rank exchange -- round 4's
-    // fuzz found LambdaNDCG1 at a batch size LambdaNDCG2 and the logistic loss both decline, sized from those two)
-    // (and over the label dtypes: the hinge kinds' members are lighter -- more of them per query -- on integer labels)
-    for (int kind = LTR_HINGE; kind <= LTR_NDCG2 && L > 0; ++kind)
-        for (int labels = 0; labels <= 1; ++labels)
-            if (choose_cluster_shape(kind, B, L, F, cs, labels) && cs.scratch_floats * sizeof(float) > scratch)
-                scratch = cs.scratch_floats * sizeof(float);
-    return bytes + scratch;
-}
-
-int ltr_linear_fused_plan(int kind, int B, int L, int F)
-{
-    LTR_CLEAR_STALE_ERROR();
-    if (kind < LTR_HINGE || kind > LTR_NDCG2 || B <= 0 || L <= 0 || F <= 0) return LTR_PLAN_NONE;
-    if (L > kMaxListLen) return LTR_PLAN_NONE;
-    // (the plan of a launch on 16-byte aligned rows, no score matrix asked for, the label dtype not known)
-    return plan_linear(kind, B, L, F, 4, true, -1).family;
-}
-
-namespace {
-// the pending update a lazy step hands to the register-tile launch (ltr_linear_sgd_lazy_step_f32), or the flush to its reducers
-struct LazyRequest {
-    int pend_B; float lr; float *W, *bias, *out; unsigned long long *gran; unsigned tag; int part_g, pend_g;
-    float scale;                        // weight of a pending query's gradient row (<= 0: 1 / pend_B)
-    const float *scale_dev;             // ... or the weights on the device (or null): query b's is scale_dev[b * scale_stride]
-    int scale_stride;
-    const MailboxDev *mb;               // data parallel: the mailbox (gran / tag are then ITS granules and the tag of its lazy half)
-};
-
-// the uniform weight of a pending query's gradient row
-inline float pending_weight(float scale, int pend_B) { return scale > 0.f ? scale : 1.0f / (float)pend_B; }
-
-// The pending update's fields of a launch that carries reducers (linear_lazy_reduce): the ONE copy of the layout they read the
-// rows in, for the lazy step's launch and for the flush alike.  queries: the lazy step -- its queries' workgroups hold their
-// bursts back and poll the reducers' granules, so the status word and the spin limit are always set; false: the flush, the
-// reducers alone, which only wait on the all-reduce of a mailbox.
-void set_pending_update(LinearParams &p, const LazyRequest &r, int F, bool queries, hipStream_t stream, bool quiet_pays = false)
-{
-    p.pend_B = r.pend_B; p.pend_g = r.pend_g; p.pend_lr = r.lr; p.pend_w = pending_weight(r.scale, r.pend_B);
-    p.pend_mb = r.mb; p.pend_wptr = r.scale_dev; p.pend_wstride = r.scale_stride;
-    p.pend_W = r.W; p.pend_bias = r.bias; p.pend_out = r.out;
-    p.pend_gran = r.gran; p.pend_tag = r.tag; p.pend_gstride = (F + 2 + 15) & ~15;
-    // four columns per reducer + the losses' one
-    p.pend_nred = (F + 1 + 3) / 4 + 1;
-    p.pend_general = (p.pend_mb || p.pend_wptr || !p.pend_W) ? 1 : 0;
-    // (a reducer sums ~1024 rows at most, whatever the batch size.  Low byte: every query workgroup's hold-back; next byte: the
-    // quiet ones' -- under the list-length order with fewer reducers than CUs, sched_quiet, on the kinds where it pays; 0: nobody
-    // is quiet)
-    const bool quiet = quiet_pays && p.sched != 0 && p.pend_nred < (p.sched >> 16);
-    p.pend_sleep = !queries ? 0 : lazy_holdback() >= 0 ? lazy_holdback() : quiet ? kLazyHoldQuiet << 8 | kLazyHold : kLazyHoldPlain;
-    if (queries || r.mb) {
-        p.status = status_device_ptr(stream);
-        p.spin_limit = cluster_force_timeout() ? -1 : (r.mb ? 0x7fffffff : (1 << 22));
-    }
-}
-
-int linear_partials_launch(int kind, float sigma, const float *X, const float *W, const float *bias, const void *rel, int rel_dtype,
-                           const int64_t *n, int B, int L, int F, float *loss, float *scores_out, float *partials, void *stream,
-                           const LazyRequest *lazy);
-}  // namespace
-
-int ltr_linear_partials_f32(int kind, float sigma, const float *X, const float *W,
-                            const float *bias, const void *rel, int rel_dtype,
-                            const int64_t *n, int B, int L, int F, float *loss,
-                            float *scores_out, float *partials, void *stream)
-{
-    return linear_partials_launch(kind, sigma, X, W, bias, rel, rel_dtype, n, B, L, F, loss, scores_out, partials, stream, nullptr);
-}
-
-namespace {
-int linear_partials_launch(int kind, float sigma, const float *X, const float *W, const float *bias, const void *rel, int rel_dtype,
-                           const int64_t *n, int B, int L, int F, float *loss, float *scores_out, float *partials, void *stream,
-                           const LazyRequest *lazy)
-{
-    LTR_CLEAR_STALE_ERROR();
-    if (const int rc = check_kind(kind, rel_dtype)) return rc;
-    if (B < 0 || L <= 0 || F <= 0) return LTR_ERR_SHAPE;
-    if (L > kMaxListLen) return LTR_ERR_LIST_TOO_LONG;
-    if (B == 0) return LTR_OK;
-    if (!X || !W || !rel || !n || !loss || !partials) return LTR_ERR_NULL;
-    if (const int st = status_peek()) return st;           // a kernel of an earlier call gave up
-    const int vec = (F % 4 == 0 && ((uintptr_t)X % 16 == 0)) ? 4 : 1;
-    LinearParams p;
-    p.X = X; p.W = W; p.bias = bias; p.rel = rel; p.n = n;
-    p.loss = loss; p.scores_out = scores_out; p.part = partials;
-    p.B = B; p.L = L; p.F = F; p.sigma = sigma; p.rel_dtype = rel_dtype;
-    p.sched = 0; p.rows_r = 0;
-    const LinearPlan pl = plan_linear(kind, B, L, F, vec, LTR_TRACE_ALLOW_FAST(scores_out), rel_dtype != LTR_LABEL_F32 ? 1 : 0);
-    if (lazy && pl.family != LTR_PLAN_REGISTER_TILE) return LTR_ERR_CONFIG;        // (the caller checked: lazy_layout_g)
-    switch (pl.family) {
-    case LTR_PLAN_REGISTER_TILE:
-        p.msplit = kRegtileThreads / 64;         // (the body takes its slices from TT; the argument is eight on every tile)
-        // (lists of 64 and fewer do not win the pass back: 512 x 64 x 136 6.7 -> 7.0 us; 1024 x 96: 11.3 -> 10.4)
-        p.sched = (L > 64) ? sched_groups(B, kSchedMaxPerCu) : 0;
-        // (snake dealing of the rounds, sched_query_sampled: measured round 6 on 1024 x 128 x 136 with four workgroups per CU resident --
-        // LambdaNDCG2 16.6 -> 16.1 us, logistic 14.0 -> 13.5, hinge 11.84 -> 11.82: the kinds with compute behind their loads are
-        // bound by their most loaded CU.  EXPERIMENTS.md round 6)
-        if (p.sched) p.sched |= device_cu_count() << 16;
-        if (lazy) p.part_g = lazy->part_g;
-        p.scores_out = LTR_TRACE_BUFFER(p.scores_out);      // (trace builds: the lazy step's launches have no score matrix to stamp)
-        if (lazy && lazy->pend_B > 0) set_pending_update(p, *lazy, F, true, (hipStream_t)stream, lazy_quiet_pays(kind, B, F));
-        return launch_regtile(kind, p, pl.rs, (hipStream_t)stream);
-    case LTR_PLAN_PARTS:
-        p.msplit = 0;
-        return launch_parts(kind, p, pl.ps, (hipStream_t)stream);
-    case LTR_PLAN_CLUSTER: {
-        p.msplit = pl.cs.threads / 64;
-        p.sched = (B >= 16) ? (B + 63) / 64 : 0;
-        float *scratch = partials + linear_partials_bytes(B, F) / sizeof(float);
-        return launch_cluster(kind, p, pl.cs, scratch, (hipStream_t)stream);
-    }
-    default: break;
-    }
-    LinearShape s;
-    if (!choose_linear_shape(kind, B, L, F, vec, s)) return LTR_ERR_SHAPE;
-    p.msplit = s.msplit; p.rows_r = s.R;
-    p.sched = sched_groups_for_lists(B, L);
-    return (vec == 4) ? launch_linear<4>(kind, p, s, (hipStream_t)stream)
-                      : launch_linear<1>(kind, p, s, (hipStream_t)stream);
-}
-}  // namespace
-
-LTR_DEBUG_HOOK int ltr_debug_sched_slots(int B, int G, int cus, int nred, int *group, int *rank)
-{
-    if (B <= 0 || G <= 0 || cus < 0 || nred < 0) return LTR_ERR_SHAPE;
-    if (nred > 0 && nred < cus && (long long)B + nred >= 8ll * cus) return LTR_ERR_SHAPE;        // (sched_round)
-    if (!group || !rank) return LTR_ERR_NULL;
-    for (int i = 0; i < B; ++i) {
-        const SchedSlot s = sched_slot(nred + i, B, G, cus, nred);
-        group[i] = s.group;
-        rank[i] = s.rank;
-    }
-    return LTR_OK;
-}
-
-#ifdef LTR_TRACE
-// Trace builds only: the stamp buffer of the launches that are given no score matrix (the lazy step's), or null.
-int ltr_debug_trace_buffer(void *buf) { trace_buffer() = (float *)buf; return LTR_OK; }
-#endif
-
-LTR_DEBUG_HOOK int ltr_debug_lazy_holdback(int packed)
-{
-    const int old = lazy_holdback();
-    lazy_holdback() = packed < 0 ? -1 : (packed & 0xffff);
-    return old;
-}
-
-// Measurement aid (bench.py `roofline`): the next launch of the 512-thread register tile on this thread records `start` right
-// before and `stop` right behind the kernel (hipExtLaunchKernelGGL) -- the kernel's own duration, as a profiler sees it.
-LTR_DEBUG_HOOK int ltr_debug_kernel_events(void *start, void *stop)
-{
-    KernelEvents &ke = kernel_events();
-    ke.start = (hipEvent_t)start; ke.stop = (hipEvent_t)stop;
-    ke.armed = start != nullptr && stop != nullptr;
-    return LTR_OK;
-}
-
-LTR_DEBUG_HOOK int ltr_debug_stream_probe_f32(const float *X, const int64_t *n, int B, int L, int F, float *out, void *stream)
-{
-    LTR_CLEAR_STALE_ERROR();
-    if (B <= 0 || L <= 0 || F <= 0 || F % 4 != 0) return LTR_ERR_SHAPE;
-    if (!X || !n || !out) return LTR_ERR_NULL;
-    const long long vecs = (long long)L * (F / 4);
-    const dim3 grid((unsigned)B);
-    hipStream_t st = (hipStream_t)stream;
-#define LTR_PROBE(NI_, TT_) hipLaunchKernelGGL((stream_probe_kernel<NI_, TT_>), grid, dim3(TT_), 0, st, X, n, L, F, out)
-    if (vecs <= 3 * 512) LTR_PROBE(3, 512);
-    else if (vecs <= 5 * 512) LTR_PROBE(5, 512);
-    else if (vecs <= 9 * 512) LTR_PROBE(9, 512);
-    else if (vecs <= 12 * 512) LTR_PROBE(12, 512);
-    else if (vecs <= 19 * 512) LTR_PROBE(19, 512);
-    else return LTR_ERR_SHAPE;
-#undef LTR_PROBE
-    return (int)hipGetLastError();
-}
-
-int ltr_linear_reduce_accum_f32(const float *partials, const float *grad_out, const float *loss,
-                                int B, int F, float *dW, float *db, float *loss_sum, int accumulate,
-                                void *stream)
-{
-    LTR_CLEAR_STALE_ERROR();
-    if (B < 0 || F <= 0) return LTR_ERR_SHAPE;
-    if (!dW || !db) return LTR_ERR_NULL;
-    if (B > 0 && !partials) return LTR_ERR_NULL;
-    if ((loss_sum != nullptr) && B > 0 && !loss) return LTR_ERR_NULL;
-    if (const int st = status_peek()) return st;           // a kernel of an earlier call gave up
-    return launch_linear_reduce((hipStream_t)stream, partials, grad_out, B > 0 ? 1.0f / (float)B : 0.f, 1, B, F, dW, db, loss, loss_sum,
-                                accumulate ? 1 : 0, nullptr, nullptr, 0.f);
-}
-
-// include/ltr_hip.h: dW = scale[0] * sum_b partials[b, :], the upstream gradient a DEVICE scalar (what autograd hands a
-// `.mean().backward()` / `.sum().backward()`: an expanded scalar of stride 0 -- no (B,) copy of it is made)
-int ltr_linear_reduce_bcast_f32(const float *partials, const float *scale, int B, int F, float *dW, float *db, void *stream)
-{
-    LTR_CLEAR_STALE_ERROR();
-    if (B < 0 || F <= 0) return LTR_ERR_SHAPE;
-    if (!dW || !db || !scale) return LTR_ERR_NULL;
-    if (B > 0 && !partials) return LTR_ERR_NULL;
-    if (const int st = status_peek()) return st;
-    return launch_linear_reduce((hipStream_t)stream, partials, scale, 0.f, 0, B, F, dW, db, nullptr, nullptr, 0, nullptr, nullptr, 0.f);
-}
-
-int ltr_linear_reduce_loss_f32(const float *partials, const float *grad_out, const float *loss,
-                               int B, int F, float *dW, float *db, float *loss_sum, void *stream)
-{
-    LTR_CLEAR_STALE_ERROR();
-    return ltr_linear_reduce_accum_f32(partials, grad_out, loss, B, F, dW, db, loss_sum, 0, stream);
-}
-
-int ltr_linear_reduce_f32(const float *partials, const float *grad_out, int B, int F, float *dW,
-                          float *db, void *stream)
-{
-    LTR_CLEAR_STALE_ERROR();
-    return ltr_linear_reduce_loss_f32(partials, grad_out, nullptr, B, F, dW, db, nullptr, stream);
-}
-
-// ---- the step in one call, with its gradient all-reduce overlapped (include/ltr_hip.h) ----
-// Measured on MI355X / ROCm 7.2 (scripts/dev/hostcost.py): hipEventRecord 0.9 us and hipStreamWaitEvent on
-// a COMPLETED event 0.4 us of host time, but a wait on an event that has just been recorded (a real
-// cross-stream dependency) 6.5 us -- two of those per step make the thread that launches the 15 us step
-// host-bound at 33 us.  So the dependency-creating calls live on a helper thread of the handle: the
-// launching thread only records `ready` behind its kernels and hands the slot over; the helper makes the
-// side stream wait for it, enqueues the all-reduce and records `done`.  When the launching thread comes
-// back to the slot (depth steps later) `done` has long completed and its wait costs 0.4 us.
-namespace {
-constexpr int kOverlapMaxDepth = 8;
-struct LtrOverlap {
-    ltr_allreduce_fn fn;
-    void *comm;
-    int depth, device;
-    hipStream_t side;
-    hipEvent_t ready[kOverlapMaxDepth], done[kOverlapMaxDepth];
-    float *bucket[kOverlapMaxDepth];
-    size_t count[kOverlapMaxDepth];
-    std::atomic<unsigned> submitted[kOverlapMaxDepth], completed[kOverlapMaxDepth];
-    bool pending[kOverlapMaxDepth];
-    std::atomic<int> error;
-    std::thread worker;
-    std::mutex m;
-    std::condition_variable cv;
-    std::deque<int> jobs;
-    bool stop;
-};
-
-void overlap_worker(LtrOverlap *o)
-{
-    (void)hipSetDevice(o->device);
-    for (;;) {
-        int slot;
-        {
-            std::unique_lock<std::mutex> lock(o->m);
-            o->cv.wait(lock, [o] { return o->stop || !o->jobs.empty(); });
-            if (o->jobs.empty()) return;                   // stop requested and nothing left to do
-            slot = o->jobs.front();
-            o->jobs.pop_front();
-        }
-        hipError_t e = hipStreamWaitEvent(o->side, o->ready[slot], 0);
-        int rc = (e == hipSuccess) ? 0 : (int)e;
-        if (rc == 0) {
-            const int nrc = o->fn(o->bucket[slot], o->bucket[slot], o->count[slot], 7 /* ncclFloat32 */, 0 /* ncclSum */,
-                                  o->comm, o->side);
-            if (nrc != 0) rc = 1000 + nrc;                 // an ncclResult_t of the caller's collective
-        }
-        if (rc == 0) { e = hipEventRecord(o->done[slot], o->side); if (e != hipSuccess) rc = (int)e; }
-        if (rc != 0) { int zero = 0; o->error.compare_exchange_strong(zero, rc); }
-        o->completed[slot].fetch_add(1, std::memory_order_release);
-    }
-}
-
-// the helper has taken every job handed to this slot (its `done` event is recorded)
-inline void overlap_settle(LtrOverlap *o, int slot)
-{
-    const unsigned want = o->submitted[slot].load(std::memory_order_relaxed);
-    while (o->completed[slot].load(std::memory_order_acquire) != want) std::this_thread::yield();
-}
-}  // namespace
-
-int ltr_overlap_create(ltr_allreduce_fn allreduce_fn, void *comm, int depth, void **handle)
-{
-    LTR_CLEAR_STALE_ERROR();
-    if (!allreduce_fn || !handle) return LTR_ERR_NULL;
-    if (depth < 0 || depth > kOverlapMaxDepth) return LTR_ERR_CONFIG;
-    LtrOverlap *o = new LtrOverlap();
-    o->fn = allreduce_fn; o->comm = comm; o->depth = depth; o->side = nullptr; o->stop = false;
-    o->error.store(0);
-    o->device = 0;
-    (void)hipGetDevice(&o->device);
-    for (int i = 0; i < kOverlapMaxDepth; ++i) {
-        o->ready[i] = nullptr; o->done[i] = nullptr; o->pending[i] = false; o->bucket[i] = nullptr; o->count[i] = 0;
-        o->submitted[i].store(0); o->completed[i].store(0);
-    }
-    if (depth == 0) {            // in-stream mode: the all-reduce is enqueued on the step's own stream, no helper
-        *handle = o;
-        return LTR_OK;
-    }
-    hipError_t e = hipStreamCreateWithFlags(&o->side, hipStreamNonBlocking);
-    for (int i = 0; i < depth && e == hipSuccess; ++i) {
-        e = hipEventCreateWithFlags(&o->ready[i], hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&o->done[i], hipEventDisableTiming);
-    }
-    if (e != hipSuccess) { (void)ltr_overlap_destroy(o); return (int)e; }
-    o->worker = std::thread(overlap_worker, o);
-    *handle = o;
-    return LTR_OK;
-}
-
-int ltr_overlap_destroy(void *handle)
-{
-    LtrOverlap *o = reinterpret_cast<LtrOverlap *>(handle);
-    if (!o) return LTR_OK;
-    if (o->worker.joinable()) {
-        { std::lock_guard<std::mutex> lock(o->m); o->stop = true; }
-        o->cv.notify_all();
-        o->worker.join();
-    }
-    if (o->side) { (void)hipStreamSynchronize(o->side); (void)hipStreamDestroy(o->side); }
-    for (int i = 0; i < kOverlapMaxDepth; ++i) {
-        if (o->ready[i]) (void)hipEventDestroy(o->ready[i]);
-        if (o->done[i]) (void)hipEventDestroy(o->done[i]);
-    }
-    delete o;
-    return LTR_OK;
-}
-
-int ltr_overlap_wait(void *handle, int slot, void *stream)
-{
-    LtrOverlap *o = reinterpret_cast<LtrOverlap *>(handle);
-    if (!o) return LTR_ERR_NULL;
-    if (o->depth == 0) return LTR_OK;
-    if (slot < 0 || slot >= o->depth) return LTR_ERR_CONFIG;
-    if (!o->pending[slot]) return o->error.load();
-    overlap_settle(o, slot);
-    o->pending[slot] = false;
-    if (const int err = o->error.load()) return err;
-    return (int)hipStreamWaitEvent((hipStream_t)stream, o->done[slot], 0);
-}
-
-int ltr_overlap_flush(void *handle)
-{
-    LtrOverlap *o = reinterpret_cast<LtrOverlap *>(handle);
-    if (!o) return LTR_ERR_NULL;
-    if (o->depth == 0) return LTR_OK;
-    for (int i = 0; i < o->depth; ++i) { overlap_settle(o, i); o->pending[i] = false; }
-    const hipError_t e = hipStreamSynchronize(o->side);
-    if (const int err = o->error.load()) return err;
-    return (int)e;
-}
-
-int ltr_linear_step_f32(int kind, float sigma, const float *X, const float *W, const float *bias,
-                        const void *rel, int rel_dtype, const int64_t *n, const float *grad_out,
-                        int B, int L, int F, float *loss, float *bucket, int accumulate,
-                        void *workspace, size_t workspace_bytes, void *overlap, int slot, void *stream)
-{
-    LTR_CLEAR_STALE_ERROR();
-    if (B < 0 || L <= 0 || F <= 0) return LTR_ERR_SHAPE;
-    if (!bucket) return LTR_ERR_NULL;
-    if (B > 0 && (!workspace || workspace_bytes < ltr_linear_workspace_bytes(B, L, F))) return LTR_ERR_WORKSPACE;
-    LtrOverlap *o = reinterpret_cast<LtrOverlap *>(overlap);
-    if (o && o->depth > 0 && (slot < 0 || slot >= o->depth)) return LTR_ERR_CONFIG;
-    // the bucket of this slot may still be in its last all-reduce: the kernels queue up behind it
-    if (o) { const int rc = ltr_overlap_wait(o, slot, stream); if (rc != 0) return rc; }
-    int rc = ltr_linear_partials_f32(kind, sigma, X, W, bias, rel, rel_dtype, n, B, L, F, loss, nullptr,
-                                     (float *)workspace, stream);
-    if (rc != 0) return rc;
-    rc = ltr_linear_reduce_accum_f32((const float *)workspace, grad_out, loss, B, F, bucket, bucket + F,
-                                     bucket + F + 1, accumulate, stream);
-    if (rc != 0 || !o) return rc;
-    if (o->depth == 0) {         // in-stream: one ncclAllReduce behind the kernels, nothing else
-        const int nrc = o->fn(bucket, bucket, (size_t)F + 2, 7 /* ncclFloat32 */, 0 /* ncclSum */, o->comm, stream);
-        return nrc != 0 ? 1000 + nrc : LTR_OK;
-    }
-    const hipError_t e = hipEventRecord(o->ready[slot], (hipStream_t)stream);
-    if (e != hipSuccess) return (int)e;
-    o->bucket[slot] = bucket;
-    o->count[slot] = (size_t)F + 2;
-    o->pending[slot] = true;
-    o->submitted[slot].fetch_add(1, std::memory_order_relaxed);
-    { std::lock_guard<std::mutex> lock(o->m); o->jobs.push_back(slot); }
-    o->cv.notify_one();
-    return LTR_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Mailbox all-reduce: the step's gradient bucket (F + 2 floats, < 3 KB) summed over the ranks of one node
-// WITHOUT a collective library in the step -- the parts kernel's exchange, across GPUs.  Every rank owns a
-// MAILBOX in fine-grained device memory, [2 parities][world][count_max] 8-byte granules, mapped into every other
-// rank's address space with hipIpcGetMemHandle / hipIpcOpenMemHandle (one process per GPU).  One small kernel
-// per all-reduce (one 256-thread workgroup):
-//   1. thread i stores {tag, send[i]} into slot [parity][my rank][i] of EVERY peer's mailbox (system-scope 8-byte
-//      stores: over xGMI for the other GPUs) -- the data is the flag;
-//   2. it then takes the ranks 0 .. world-1 IN RANK ORDER, its own value from the register, the others' from its
-//      own mailbox (system-scope loads until the tag is this all-reduce's), and adds them: every rank adds the
-//      same numbers in the same order, so all ranks end with bit-identical sums, run after run;
-//   3. recv[i] = sum; with an update target, W[i] -= lr * sum too (the optimiser step of a synchronous-SGD step:
-//      ltr_linear_sgd_step_f32 saves a launch).
-// The tag counts the all-reduces of this mailbox (device state: a captured launch replays with fresh tags).  Two
-// parities because a peer may run ONE all-reduce ahead: it cannot finish all-reduce k + 1 before it has my k + 1
-// granule, which I send only after I have read its granule of all-reduce k -- so while I still poll for k, a fast
-// peer's k + 1 lands in the other half and nothing I have not read is overwritten.  Latency-bound by design: no
-// rings, no protocol negotiation, one hop.  RCCL stays the fallback (and the cross-check at set-up).
-// ---------------------------------------------------------------------------------------------
-namespace {
-// how long one all-reduce waits for its peers before it gives up (a collective library's watchdog waits minutes: a
-// rank may be late by a checkpoint, an evaluation pass, a stalled data loader).  LTR_MAILBOX_TIMEOUT_MS in the
-// environment (read once) or ltr_mailbox_set_timeout_ms() override the default of 120 s.
-inline long long *mailbox_timeout_ms()
-{
-    static long long v = [] { const char *e = getenv("LTR_MAILBOX_TIMEOUT_MS"); const long long x = e ? atoll(e) : 0; return x > 0 ? x : 120000ll; }();
-    return &v;
-}
-struct LtrMailbox {
-    int rank, world, count_max, device;
-    unsigned long long *mine;                       // [2][world][count_max]
-    unsigned long long *peer[kMbMaxRanks];          // peer[r]: rank r's mailbox in MY address space (peer[rank] == mine)
-    bool opened[kMbMaxRanks];
-    unsigned *tag;                                  // device word: all-reduces done on this mailbox
-    int *status;                                    // device status word (pinned host page) or null
-    // the data-parallel LAZY steps' half of the mailbox (halves 2 and 3 of `mine`: [2][world][count_max] more granules): its
-    // all-reduces happen inside the fused launch (linear_lazy_reduce), their tag is a host-side counter -- eager launches only
-    unsigned lazy_tag;
-    MailboxDev *dev;                                // the peers' addresses etc. in (ordinary) device memory, for those launches
-    unsigned long long *lazy_gran;                  // the weight granules of those launches (kLazyCopies copies of count_max, padded)
-    size_t lazy_gran_count;
-    long long dev_ticks;                            // what dev->ticks holds (in stream order)
-    long long stage[16];                            // host staging of ticks updates (a ring: an update is rare)
-    int stage_i;
-};
-struct MailboxArgs {
-    unsigned long long *peer[kMbMaxRanks];
-    unsigned long long *mine;
-    unsigned *tag;
-    int *status;
-    int rank, world, count_max;
-    long long timeout_ticks;                        // 100 MHz ticks one all-reduce may wait for its peers; <= 0: give up at once (tests)
-};
-
-// (tag sequence 1, 2, ..., 0xFFFFFFFF, 2, 3, ...: the wrap skips 0 -- "never written" -- AND 1, so that consecutive
-// all-reduces always alternate between the two halves; round 4 wrapped to 1 and used one half twice in a row)
-__host__ __device__ inline unsigned mailbox_next_tag(unsigned prev) { const unsigned t = prev + 1u; return t ? t : 2u; }
-
-__global__ void __launch_bounds__(256)
-mailbox_allreduce_kernel(MailboxArgs a, const float *__restrict__ send, float *__restrict__ recv, int count,
-                         float *__restrict__ w_upd, float *__restrict__ b_upd, float lr, int F)
-{
-    const int tid = threadIdx.x;
-    const unsigned t = mailbox_next_tag((unsigned)__builtin_amdgcn_readfirstlane((int)a.tag[0]));
-    const size_t half = (size_t)(t & 1u) * (size_t)a.world * (size_t)a.count_max;
-    // ONE time budget for the whole all-reduce (100 MHz wall clock), shared by every peer and element: a peer that
-    // never shows up costs timeout_ticks once, not once per peer and element; polls back off to ~1 us
-    const long long deadline = (long long)__builtin_amdgcn_s_memrealtime() + a.timeout_ticks;
-    __shared__ int s_failed;
-    if (tid == 0) s_failed = 0;
-    __syncthreads();
-    // 1. my granules to every peer (all of them before the first poll: nobody waits for a slow sender's later elements)
-    for (int i = tid; i < count; i += 256) {
-        const unsigned long long g = ((unsigned long long)t << 32) | (unsigned long long)__float_as_uint(send[i]);
-        for (int r = 0; r < a.world; ++r)
-            if (r != a.rank)
-                __hip_atomic_store(a.peer[r] + half + (size_t)a.rank * a.count_max + i, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    // 2. the sums, in rank order
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};                   // count <= 1024 in practice; more elements loop below
-    bool ok = a.timeout_ticks > 0;                         // (tests: a zero budget fails on every rank, arrived or not)
-    if (!ok) __hip_atomic_store(&s_failed, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    for (int i = tid, u = 0; i < count && ok; i += 256, ++u) {
-        const float v = send[i];
-        float sum = 0.f;
-        for (int r = 0; r < a.world && ok; ++r) {
-            float x = v;
-            if (r != a.rank) {
-                const unsigned long long *src = a.mine + half + (size_t)r * a.count_max + i;
-                unsigned long long gv = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                int spins = 0;
-                while ((unsigned)(gv >> 32) != t) {
-                    if ((++spins & 15) == 0 &&
-                        ((long long)__builtin_amdgcn_s_memrealtime() > deadline || __hip_atomic_load(&s_failed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))) {
-                        ok = false;
-                        break;
-                    }
-                    if (spins < 64) __builtin_amdgcn_s_sleep(2); else __builtin_amdgcn_s_sleep(32);
-                    gv = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                }
-                x = __uint_as_float((unsigned)gv);
-            }
-            sum += x;
-        }
-        if (!ok) { __hip_atomic_store(&s_failed, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); break; }
-        if (u < 4) acc[u] = sum; else recv[i] = sum;        // (elements beyond 1024: stored at once, see below)
-    }
-    __syncthreads();
-    const bool failed = s_failed != 0;
-    // 3. results.  A peer that never arrived: the bucket is poisoned, the WEIGHTS ARE LEFT ALONE (round 4 wrote NaN into
-    // them -- unrecoverable) and the sticky status says LTR_ERR_TIMEOUT: callers of ltr_linear_sgd_step_f32 must look
-    // at ltr_device_status before they trust W after a step that may have timed out.
-    for (int i = tid, u = 0; i < count; i += 256, ++u) {
-        const float sum = failed ? __builtin_nanf("") : (u < 4 ? acc[u] : recv[i]);
-        recv[i] = sum;
-        if (w_upd && !failed) {
-            if (i < F) w_upd[i] -= lr * sum;
-            else if (i == F && b_upd) b_upd[0] -= lr * sum;
-        }
-    }
-    if (failed && tid == 0 && a.status) __hip_atomic_store(a.status, (int)LTR_ERR_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    if (tid == 0) a.tag[0] = t;
-}
-
-int mailbox_launch(LtrMailbox *m, const float *send, float *recv, size_t count, float *w_upd, float *b_upd, float lr,
-                   int F, hipStream_t stream)
-{
-    if (!m) return LTR_ERR_NULL;
-    if (count > (size_t)m->count_max) return LTR_ERR_SHAPE;
-    MailboxArgs a;
-    for (int r = 0; r < kMbMaxRanks; ++r) a.peer[r] = (r < m->world) ? m->peer[r] : nullptr;
-    a.mine = m->mine; a.tag = m->tag; a.status = status_device_ptr(stream);
-    a.rank = m->rank; a.world = m->world; a.count_max = m->count_max;
-    a.timeout_ticks = cluster_force_timeout() ? 0 : *mailbox_timeout_ms() * 100000ll;
-    hipLaunchKernelGGL(mailbox_allreduce_kernel, dim3(1), dim3(256), 0, stream, a, send, recv, (int)count, w_upd, b_upd, lr, F);
-    return (int)hipGetLastError();
-}
-}  // namespace
-
-// include/ltr_hip.h: the mailbox all-reduce (no counterpart in the reference: it is single-process)
-int ltr_mailbox_create(int rank, int world, int count_max, void **handle, void *ipc_handle_out /* 64 bytes */)
-{
-    LTR_CLEAR_STALE_ERROR();
-    if (!handle || !ipc_handle_out) return LTR_ERR_NULL;
-    if (world < 1 || world > kMbMaxRanks || rank < 0 || rank >= world || count_max < 1) return LTR_ERR_CONFIG;
-    static_assert(sizeof(hipIpcMemHandle_t) == 64, "the IPC handle travels as 64 bytes");
-    LtrMailbox *m = new LtrMailbox();
-    m->rank = rank; m->world = world; m->count_max = count_max; m->device = 0;
-    (void)hipGetDevice(&m->device);
-    for (int r = 0; r < kMbMaxRanks; ++r) { m->peer[r] = nullptr; m->opened[r] = false; }
-    const size_t bytes = 4 * (size_t)world * (size_t)count_max * 8 + 256;      // (two halves per kind of all-reduce: plain, lazy)
-    m->lazy_tag = 0u; m->dev = nullptr; m->lazy_gran = nullptr; m->lazy_gran_count = 0; m->dev_ticks = -1; m->stage_i = 0;
-    void *p = nullptr;
-    // fine-grained: the peers' stores land without a kernel boundary, my polling loads see them
-    // (no silent fall-back to coarse-grained memory: a peer's stores would not be guaranteed visible before a kernel
-    // boundary -- the caller sees the error and takes the collective library instead; one rank needs no peers)
-    hipError_t e = hipExtMallocWithFlags(&p, bytes, hipDeviceMallocFinegrained);
-    if (e != hipSuccess && world == 1) { (void)hipGetLastError(); e = hipMalloc(&p, bytes); }
-    if (e != hipSuccess) { (void)hipGetLastError(); delete m; return LTR_ERR_CONFIG; }
-    if (e == hipSuccess) e = hipMemset(p, 0, bytes);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) { if (p) (void)hipFree(p); delete m; return (int)e; }
-    m->mine = reinterpret_cast<unsigned long long *>(p);
-    m->tag = reinterpret_cast<unsigned *>(reinterpret_cast<unsigned char *>(p) + 4 * (size_t)world * (size_t)count_max * 8);
-    m->peer[rank] = m->mine;
-    hipIpcMemHandle_t h;
-    memset(&h, 0, sizeof(h));
-    if (world > 1) {
-        e = hipIpcGetMemHandle(&h, p);
-        if (e != hipSuccess) { (void)hipFree(p); delete m; return (int)e; }
-    }
-    memcpy(ipc_handle_out, &h, 64);
-    *handle = m;
-    return LTR_OK;
-}
-
-int ltr_mailbox_connect(void *handle, const void *all_ipc_handles /* world x 64 bytes, rank order */)
-{
-    LTR_CLEAR_STALE_ERROR();
-    LtrMailbox *m = reinterpret_cast<LtrMailbox *>(handle);
-    if (!m || !all_ipc_handles) return LTR_ERR_NULL;
-    for (int r = 0; r < m->world; ++r) {
-        if (r == m->rank || m->opened[r]) continue;
-        hipIpcMemHandle_t h;
-        memcpy(&h, reinterpret_cast<const unsigned char *>(all_ipc_handles) + 64 * (size_t)r, 64);
-        void *p = nullptr;
-        const hipError_t e = hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess);
-        if (e != hipSuccess) { (void)hipGetLastError(); return (int)e; }
-        m->peer[r] = reinterpret_cast<unsigned long long *>(p);
-        m->opened[r] = true;
-    }
-    // what the lazy steps' launches read: the same addresses, in device memory
-    MailboxDev h;
-    memset(&h, 0, sizeof(h));
-    for (int r = 0; r < m->world; ++r) h.peer[r] = m->peer[r];
-    h.rank = m->rank; h.world = m->world; h.count_max = m->count_max;
-    h.ticks = *mailbox_timeout_ms() * 100000ll;
-    if (!m->dev) { void *d = nullptr; if (hipMalloc(&d, sizeof(MailboxDev)) != hipSuccess) { (void)hipGetLastError(); return LTR_ERR_CONFIG; } m->dev = reinterpret_cast<MailboxDev *>(d); }
-    if (!m->lazy_gran) {
-        m->lazy_gran_count = lazy_area_words(m->count_max - 2 > 0 ? m->count_max - 2 : 1);
-        void *d = nullptr;
-        if (hipMalloc(&d, m->lazy_gran_count * 8) != hipSuccess) { (void)hipGetLastError(); return LTR_ERR_CONFIG; }
-        if (hipMemset(d, 0, m->lazy_gran_count * 8) != hipSuccess) { (void)hipFree(d); return LTR_ERR_CONFIG; }
-        m->lazy_gran = reinterpret_cast<unsigned long long *>(d);
-    }
-    const hipError_t ec = hipMemcpy(m->dev, &h, sizeof(h), hipMemcpyHostToDevice);
-    m->dev_ticks = h.ticks;
-    return ec == hipSuccess ? LTR_OK : (int)ec;
-}
-
-int ltr_mailbox_destroy(void *handle)
-{
-    LtrMailbox *m = reinterpret_cast<LtrMailbox *>(handle);
-    if (!m) return LTR_OK;
-    (void)hipDeviceSynchronize();
-    for (int r = 0; r < m->world; ++r)
-        if (m->opened[r] && m->peer[r]) (void)hipIpcCloseMemHandle(m->peer[r]);
-    if (m->mine) (void)hipFree(m->mine);
-    if (m->dev) (void)hipFree(m->dev);
-    if (m->lazy_gran) (void)hipFree(m->lazy_gran);
-    delete m;
-    return LTR_OK;
-}
-
-long long ltr_mailbox_set_timeout_ms(long long timeout_ms)
-{
-    const long long old = *mailbox_timeout_ms();
-    if (timeout_ms > 0) *mailbox_timeout_ms() = timeout_ms;
-    return old;
-}
-
-// tests (include/ltr_hip.h)
-LTR_DEBUG_HOOK int ltr_debug_mailbox_state(void *handle, long long timeout_ms, long long tag)
-{
-    LtrMailbox *m = reinterpret_cast<LtrMailbox *>(handle);
-    if (timeout_ms > 0) *mailbox_timeout_ms() = timeout_ms;
-    if (tag >= 0) {
-        if (!m) return LTR_ERR_NULL;
-        const unsigned t = (unsigned)tag;
-        (void)hipDeviceSynchronize();
-        m->lazy_tag = t;                                 // (the lazy steps' half counts on the host)
-        return (int)hipMemcpy(m->tag, &t, sizeof(t), hipMemcpyHostToDevice);
-    }
-    return LTR_OK;
-}
-
-// an ltr_allreduce_fn (ncclFloat32 / ncclSum): comm = the mailbox handle
-int ltr_mailbox_allreduce(const void *sendbuf, void *recvbuf, size_t count, int dtype, int op, void *comm, void *stream)
-{
-    if (dtype != 7 || op != 0) return 1;
-    return mailbox_launch(reinterpret_cast<LtrMailbox *>(comm), (const float *)sendbuf, (float *)recvbuf, count, nullptr, nullptr,
-                          0.f, 0, (hipStream_t)stream) == 0 ? 0 : 1;
-}
-
-// One synchronous-SGD step of the reference's training loop (examples/01-basic-usage.py:66-75:
-// loss_fn(model(xs), ys, n).mean().backward(); optimizer.step() with torch.optim.SGD) in ONE call: partials +
-// reduction into the bucket [dW | db | loss_sum] with the upstream gradient grad_out (NULL = 1 / B), the
-// step's gradient all-reduce when an in-stream overlap handle is given (data parallel: grad_out = 1 / (B * N)
-// makes the summed bucket the gradient of the global mean), then W -= lr * dW, bias -= lr * db.  The next step's
-// scores depend on this step's all-reduced gradient: the collective sits on the critical path by construction.
-// At one rank the update rides in the reduction kernel (two launches in all); behind an all-reduce it is one
-// small launch more.
-int ltr_linear_sgd_step_f32(int kind, float sigma, const float *X, float *W, float *bias, const void *rel,
-                            int rel_dtype, const int64_t *n, const float *grad_out, int B, int L, int F,
-                            float lr, float *loss, float *bucket, void *workspace, size_t workspace_bytes,
-                            void *overlap, void *stream)
-{
-    LTR_CLEAR_STALE_ERROR();
-    if (B < 0 || L <= 0 || F <= 0) return LTR_ERR_SHAPE;
-    if (!bucket || !W) return LTR_ERR_NULL;
-    if (B > 0 && (!workspace || workspace_bytes < ltr_linear_workspace_bytes(B, L, F))) return LTR_ERR_WORKSPACE;
-    LtrOverlap *o = reinterpret_cast<LtrOverlap *>(overlap);
-    if (o && o->depth != 0) return LTR_ERR_CONFIG;              // (a deferred all-reduce cannot feed this step's update)
-    int rc = ltr_linear_partials_f32(kind, sigma, X, W, bias, rel, rel_dtype, n, B, L, F, loss, nullptr,
-                                     (float *)workspace, stream);
-    if (rc != 0) return rc;
-    if (const int st = status_peek()) return st;
-    rc = launch_linear_reduce((hipStream_t)stream, (const float *)workspace, grad_out, B > 0 ? 1.0f / (float)B : 0.f, 1, B, F, bucket,
-                              bucket + F, loss, bucket + F + 1, 0, o ? nullptr : W, o ? nullptr : bias, lr);
-    if (rc != 0 || !o) return rc;
-    if (o->fn == &ltr_mailbox_allreduce)          // (the mailbox kernel sums AND applies the update: one launch)
-        return mailbox_launch(reinterpret_cast<LtrMailbox *>(o->comm), bucket, bucket, (size_t)F + 2, W, bias, lr, F,
-                              (hipStream_t)stream);
-    const int nrc = o->fn(bucket, bucket, (size_t)F + 2, 7 /* ncclFloat32 */, 0 /* ncclSum */, o->comm, stream);
-    if (nrc != 0) return 1000 + nrc;
-    hipLaunchKernelGGL(sgd_update_kernel, dim3((unsigned)((F + 1 + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       W, bias, (const float *)bucket, lr, F);
-    return (int)hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------------
-// LAZY synchronous SGD (include/ltr_hip.h).  ltr_linear_sgd_step_f32 is two launches -- the fused kernel, then the reduction of
-// its (B, F + 1) partial rows with the update -- and two kernel boundaries per step (1.5-1.9 us each on this stack).  The update of
-// step k only has to be applied before step k + 1 takes its dot products, and those come BEHIND the tile burst: so step k + 1's
-// launch applies it itself (the first workgroups reduce a column each in front of their burst and publish the new weights as
-// tagged granules, every workgroup picks its weights up behind its burst: linear_regtile2_kernel), and the reduction launch and
-// one boundary are gone from every step but the last, whose update ltr_linear_sgd_flush_f32 applies.  The same arithmetic in
-// the same order as the two launches: W, bias, dW, db and the losses are bit-identical (tests/test_gpu_step.py).
-// Granules and their tags live in a lazy area per (device, stream): library-owned, zeroed when allocated, the tag a host-side
-// counter -- eager launches only (a captured launch would replay a frozen tag): under capture, and on shapes the register tile
-// does not take, the pending update is flushed first and the step runs as the plain launch.
-// ---------------------------------------------------------------------------------------------
-namespace {
-struct LazyArea { int device; hipStream_t stream; unsigned tag; unsigned long long *gran; size_t cap; };
-struct LazyAreas { std::mutex m; std::deque<LazyArea> v; };
-inline LazyAreas *lazy_areas() { static LazyAreas *a = new LazyAreas(); return a; }     // (a pointer: this sits inside extern "C")
-
-// the next tag of the stream's lazy area and its granules (at least `count` of them)
-int lazy_area_next(hipStream_t stream, size_t count, unsigned long long **gran, unsigned *tag)
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return LTR_ERR_CONFIG;
-    LazyAreas &A = *lazy_areas();
-    std::lock_guard<std::mutex> lock(A.m);
-    LazyArea *a = nullptr;
-    for (auto &x : A.v) if (x.device == dev && x.stream == stream) { a = &x; break; }
-    if (!a) { A.v.push_back(LazyArea{dev, stream, 0u, nullptr, 0}); a = &A.v.back(); }
-    if (a->cap < count) {
-        // (a larger buffer starts a new tag sequence on zeroed memory; the old one stays allocated until ltr_exchange_release:
-        // a launch in flight may still read it)
-        void *ptr = nullptr;
-        const size_t cap = count < 4096 ? 4096 : count;
-        if (exchange_alloc_zeroed(&ptr, cap * 8) != hipSuccess) return LTR_ERR_CONFIG;
-        if (a->gran) { ExchangeAreas &E = exchange_areas(); std::lock_guard<std::mutex> l2(E.m); E.retired.push_back(a->gran); }
-        a->gran = reinterpret_cast<unsigned long long *>(ptr);
-        a->cap = cap;
-        a->tag = 0u;
-    }
-    if (++a->tag == 0u) {
-        // 2^32 launches on this area: the granules go back to zero (in stream order) before the tags start over
-        if (hipMemsetAsync(a->gran, 0, a->cap * 8, stream) != hipSuccess) return LTR_ERR_CONFIG;
-        a->tag = 1u;
-    }
-    *gran = a->gran;
-    *tag = a->tag;
-    return LTR_OK;
-}
-
-int lazy_areas_release()
-{
-    LazyAreas &A = *lazy_areas();
-    std::lock_guard<std::mutex> lock(A.m);
-    hipError_t e = hipSuccess;
-    for (auto &x : A.v)
-        if (x.gran) { const hipError_t r = hipFree(x.gran); if (r != hipSuccess) e = r; }
-    A.v.clear();
-    return (int)e;
-}
-
-bool stream_is_capturing(hipStream_t stream)
-{
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &cs) != hipSuccess) return true;      // (cannot tell: the safe path)
-    return cs != hipStreamCaptureStatusNone;
-}
-}  // namespace
-
-// Does a lazy step write the partial rows of a (B, L, F) batch column-group major?  A matter of the SHAPE only -- the step that
-// wrote them, the step that reads them and the flush must agree: the register-tile kernel's shapes.  (X must be 16-byte aligned
-// for the lazy entry points when F % 4 == 0.)
-// ONE ROUND of workgroups at most (B <= 4 x CUs): a larger batch's update never rides in the next launch (see below), so
-// its step is the plain launch behind a reduction launch either way -- and row-major rows have the better of both: a query's row
-// is ONE contiguous store (the column-group layout scatters it in 16-byte pieces: 65 536 full lists 894 against 779 us per step)
-// and launch_linear_reduce's split kernels sum them at the chip's bandwidth whatever B (round 6; the first version of this
-// round split the lazy reducers instead -- several workgroups per column group, tagged scratch rows: dropped, EXPERIMENTS.md).
-static bool lazy_one_round(int B) { return B <= 4 * device_cu_count(); }
-static bool lazy_layout_g(int kind, int B, int L, int F)
-{
-    if (B <= 0 || F % 4 != 0 || !lazy_one_round(B)) return false;
-    RegtileShape rs;
-    return choose_regtile_shape(kind, L, F, rs);         // (plan_linear's first choice)
-}
-// (May a launch of MORE than one round take a pending update along?  No: every workgroup of every later round still pays the
-// hold-back and the hand-over in front of its dot products -- its poll sits behind its tile burst in the in-order return queue --
-// and the launch loses more than the reduction launch costs.  4096 x 128 x 136, round 5: 40.6 -> 44.4 us per step; round 6 with
-// split reducers: 36.8 -> 45.6, and with their combine stripped of its fences and load chain, hold-back 0 / 1 / 2:
-// 35.0 -> 36.3 .. 36.9 at 4096 queries, 68.1 -> 71.6 .. 74.4 at 8192.)
-
-// The next in-launch all-reduce of the mailbox's lazy half: ONE host-side tag (eager launches only; every rank makes the same
-// calls) for the peers' granules AND the launch's own weight granules, which belong to the mailbox for these launches; the time
-// budget travels in device memory (updated in stream order when it changed: ltr_mailbox_set_timeout_ms, the tests' forced give-up).
-static int lazy_mailbox_next(LtrMailbox *m, hipStream_t stream, int F, const MailboxDev **mb, unsigned long long **gran, unsigned *tag)
-{
-    if (lazy_area_words(F) > m->lazy_gran_count) return LTR_ERR_CONFIG;
-    const long long ticks = cluster_force_timeout() ? 0 : *mailbox_timeout_ms() * 100000ll;
-    if (ticks != m->dev_ticks) {
-        long long *src = &m->stage[m->stage_i++ & 15];
-        *src = ticks;
-        if (hipMemcpyAsync(&m->dev->ticks, src, sizeof(long long), hipMemcpyHostToDevice, stream) != hipSuccess) return LTR_ERR_CONFIG;
-        m->dev_ticks = ticks;
-    }
-    const unsigned next = mailbox_next_tag(m->lazy_tag);
-    if (next < m->lazy_tag) {
-        // the tags start over (2^32 all-reduces): the weight granules go back to zero first, in stream order
-        if (hipMemsetAsync(m->lazy_gran, 0, m->lazy_gran_count * 8, stream) != hipSuccess) return LTR_ERR_CONFIG;
-    }
-    m->lazy_tag = next;
-    *mb = m->dev; *gran = m->lazy_gran; *tag = next;
-    return LTR_OK;
-}
-
-namespace {
-int lazy_flush_impl(int kind, float *W, float *bias, int pending_B, int L, int F, float lr, float pending_scale,
-                    const float *pending_scale_dev, int pending_scale_stride, const float *loss, float *bucket, const void *workspace, void *mailbox,
-                    void *stream, bool weights)
-{
-    LTR_CLEAR_STALE_ERROR();
-    if (pending_B < 0 || F <= 0 || L <= 0) return LTR_ERR_SHAPE;
-    LtrMailbox *m = reinterpret_cast<LtrMailbox *>(mailbox);
-    if (m && m->world == 1) m = nullptr;                          // (one rank: nothing to exchange)
-    if (pending_B == 0) return m ? LTR_ERR_SHAPE : LTR_OK;       // (data parallel: every rank brings at least one query to every step)
-    if ((weights && !W) || !bucket || !workspace || !loss) return LTR_ERR_NULL;
-    if (!weights) { W = nullptr; if (m) return LTR_ERR_CONFIG; }
-    if (m && (!m->dev || m->count_max < F + 2 || !bias)) return LTR_ERR_CONFIG;
-    if (const int st = status_peek()) return st;
-    if (lazy_layout_g(kind, pending_B, L, F) && bias) {
-        // rows in the lazy step's layout: the reducers of the lazy launch, on their own (data parallel: with their all-reduce)
-        LazyRequest req{pending_B, lr, W, bias, bucket, nullptr, 0u, 0, 1, pending_scale, pending_scale_dev, pending_scale_stride, nullptr};
-        if (m) {
-            if (stream_is_capturing((hipStream_t)stream)) return LTR_ERR_CONFIG;      // (host-side tags: eager launches only)
-            if (const int rc = lazy_mailbox_next(m, (hipStream_t)stream, F, &req.mb, &req.gran, &req.tag)) return rc;
-        }
-        LinearParams p{};
-        p.part = const_cast<float *>(reinterpret_cast<const float *>(workspace));
-        p.loss = const_cast<float *>(loss);
-        p.F = F; p.B = pending_B;
-        set_pending_update(p, req, F, false, (hipStream_t)stream);
-        hipLaunchKernelGGL(linear_lazy_flush_kernel, dim3((unsigned)p.pend_nred), dim3(256), 0, (hipStream_t)stream, p);
-        return (int)hipGetLastError();
-    }
-    // (the upstream gradient: a device scalar read with stride 0, or the uniform weight)
-    const float *go = pending_scale_dev;
-    const float scale = pending_weight(pending_scale, pending_B);
-    if (!m)
-        return launch_linear_reduce((hipStream_t)stream, (const float *)workspace, go, scale, pending_scale_stride, pending_B, F, bucket,
-                                    bucket + F, loss, bucket + F + 1, 0, W, W ? bias : nullptr, lr);
-    // data parallel, rows by query (shapes off the register tile): the reduction launch, then the plain mailbox all-reduce with
-    // the update riding in it
-    if (const int rc = launch_linear_reduce((hipStream_t)stream, (const float *)workspace, go, scale, pending_scale_stride, pending_B, F,
-                                            bucket, bucket + F, loss, bucket + F + 1, 0, nullptr, nullptr, lr)) return rc;
-    return mailbox_launch(m, bucket, bucket, (size_t)F + 2, W, bias, lr, F, (hipStream_t)stream);
-}
-}  // namespace
-
-int ltr_linear_sgd_flush_dp_f32(int kind, float *W, float *bias, int pending_B, int L, int F, float lr, float pending_scale,
-                                const float *pending_scale_dev, int pending_scale_stride, const float *loss, float *bucket,
-                                const void *workspace, void *mailbox, void *stream)
-{
-    return lazy_flush_impl(kind, W, bias, pending_B, L, F, lr, pending_scale, pending_scale_dev, pending_scale_stride, loss, bucket,
-                           workspace, mailbox, stream, true);
-}
-
-int ltr_linear_lazy_rows_reduce_f32(int kind, int pending_B, int L, int F, float pending_scale, const float *pending_scale_dev,
-                                    int pending_scale_stride, const float *loss, float *bucket, const void *workspace, int has_bias, void *stream)
-{
-    // (the rows' layout follows from the shape and from whether the step had a bias -- lazy_layout_g(...) && bias)
-    static float dummy_bias_tag;
-    return lazy_flush_impl(kind, nullptr, has_bias ? &dummy_bias_tag : nullptr, pending_B, L, F, 0.f, pending_scale, pending_scale_dev,
-                           pending_scale_stride, loss, bucket, workspace, nullptr, stream, false);
-}
-
-int ltr_linear_sgd_flush_f32(int kind, float *W, float *bias, int pending_B, int L, int F, float lr, const float *loss,
-                             float *bucket, const void *workspace, void *stream)
-{
-    return ltr_linear_sgd_flush_dp_f32(kind, W, bias, pending_B, L, F, lr, 0.f, nullptr, 0, loss, bucket, workspace, nullptr, stream);
-}
-
-int ltr_linear_sgd_lazy_step_dp_f32(int kind, float sigma, const float *X, float *W, float *bias, const void *rel,
-                                    int rel_dtype, const int64_t *n, int B, int L, int F, float lr, float *loss, float *bucket,
-                                    void *workspace, size_t workspace_bytes, int pending_B, float pending_scale,
-                                    const float *pending_scale_dev, int pending_scale_stride, void *mailbox, void *stream)
-{
-    LTR_CLEAR_STALE_ERROR();
-    if (B < 0 || L <= 0 || F <= 0 || pending_B < 0) return LTR_ERR_SHAPE;
-    if (!bucket || !W || !loss) return LTR_ERR_NULL;
-    LtrMailbox *m = reinterpret_cast<LtrMailbox *>(mailbox);
-    if (m && m->world == 1) m = nullptr;
-    if (m && (!m->dev || m->count_max < F + 2 || !bias)) return LTR_ERR_CONFIG;
-    if (B > 0 && (!workspace || workspace_bytes < ltr_linear_workspace_bytes(B, L, F))) return LTR_ERR_WORKSPACE;
-    if (pending_B > 0 && (!workspace || workspace_bytes < ltr_linear_workspace_bytes(pending_B, L, F))) return LTR_ERR_WORKSPACE;
-    if (F % 4 == 0 && (uintptr_t)X % 16 != 0) return LTR_ERR_CONFIG;          // (the layout of the rows must follow from the shape alone)
-    if (B == 0) return ltr_linear_sgd_flush_dp_f32(kind, W, bias, pending_B, L, F, lr, pending_scale, pending_scale_dev, pending_scale_stride, loss, bucket, workspace, mailbox, stream);
-    const bool part_g = lazy_layout_g(kind, B, L, F) && bias != nullptr;
-    const bool pend_g = pending_B > 0 && lazy_layout_g(kind, pending_B, L, F) && bias != nullptr;
-    // does this launch take the pending update along?  (both batches on the register-tile kernel, an eager launch)
-    const bool along = pending_B > 0 && part_g && pend_g && lazy_one_round(B) && !stream_is_capturing((hipStream_t)stream);
-    if (pending_B > 0 && !along) {
-        const int rc = ltr_linear_sgd_flush_dp_f32(kind, W, bias, pending_B, L, F, lr, pending_scale, pending_scale_dev, pending_scale_stride, loss, bucket, workspace, mailbox, stream);
-        if (rc != 0) return rc;
-    }
-    LazyRequest req{along ? pending_B : 0, lr, W, bias, bucket, nullptr, 0u, part_g ? 1 : 0, pend_g ? 1 : 0, pending_scale, pending_scale_dev, pending_scale_stride, nullptr};
-    if (along) {
-        if (m) {
-            if (const int rc = lazy_mailbox_next(m, (hipStream_t)stream, F, &req.mb, &req.gran, &req.tag)) return rc;
-        } else if (const int rc = lazy_area_next((hipStream_t)stream, lazy_area_words(F), &req.gran, &req.tag)) return rc;
-    }
-    return linear_partials_launch(kind, sigma, X, W, bias, rel, rel_dtype, n, B, L, F, loss, nullptr, (float *)workspace, stream,
-                                  part_g ? &req : nullptr);
-}
-
-int ltr_linear_sgd_lazy_step_f32(int kind, float sigma, const float *X, float *W, float *bias, const void *rel,
-                                 int rel_dtype, const int64_t *n, int B, int L, int F, float lr, float *loss, float *bucket,
-                                 void *workspace, size_t workspace_bytes, int pending_B, void *stream)
-{
-    return ltr_linear_sgd_lazy_step_dp_f32(kind, sigma, X, W, bias, rel, rel_dtype, n, B, L, F, lr, loss, bucket, workspace,
-                                           workspace_bytes, pending_B, 0.f, nullptr, 0, nullptr, stream);
-}
-
-// Tests only: an `ltr_allreduce_fn` that adds a second, known bucket -- `comm` is a device pointer to `count`
-// floats, "the other rank's contribution" -- on the given stream.
-LTR_DEBUG_HOOK int ltr_debug_fake_allreduce(const void *sendbuf, void *recvbuf, size_t count, int dtype, int op, void *comm, void *stream)
-{
-    if (dtype != 7 || op != 0 || !comm) return 1;
-    hipLaunchKernelGGL(fake_allreduce_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const float *)sendbuf, (float *)recvbuf, (const float *)comm, count);
-    return hipGetLastError() == hipSuccess ? 0 : 1;
-}
-
-int ltr_linear_pairwise_f32(int kind, float sigma, const float *X, const float *W,
-                            const float *bias, const void *rel, int rel_dtype,
-                            const int64_t *n, const float *grad_out, int B, int L, int F,
-                            float *loss, float *scores_out, float *dW, float *db,
-                            void *workspace, size_t workspace_bytes, void *stream)
-{
-    LTR_CLEAR_STALE_ERROR();
-    if (B < 0 || L <= 0 || F <= 0) return LTR_ERR_SHAPE;
-    if (!dW || !db) return LTR_ERR_NULL;
-    if (B > 0 && (!workspace || workspace_bytes < ltr_linear_workspace_bytes(B, L, F)))
-        return LTR_ERR_WORKSPACE;
-    int rc = ltr_linear_partials_f32(kind, sigma, X, W, bias, rel, rel_dtype, n, B, L, F, loss,
-                                     scores_out, (float *)workspace, stream);
-    if (rc != 0) return rc;
-    return ltr_linear_reduce_f32((const float *)workspace, grad_out, B, F, dW, db, stream);
-}
-
-}  // extern "C"

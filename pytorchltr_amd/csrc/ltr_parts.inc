@@ -1,6 +1,6 @@
 // ltr_parts.inc -- Linear(F,1) scorer fused with the pairwise loss for lists that do not fit one
 // workgroup's registers: features read ONCE, one exchange per query, persistent workgroups
-// (included by ltr_linear.inc; the step it replaces is examples/01-basic-usage.py:66-75 of the
+// (included by ltr_linear.hip after ltr_areas.inc and ltr_cluster.inc; the step it replaces is examples/01-basic-usage.py:66-75 of the
 // reference, loss_fn(Linear(F,1)(xs), ys, n).mean().backward() with the losses of
 // loss/pairwise_additive.py:51-163 and loss/pairwise_lambda.py:114-140).
 //
@@ -35,7 +35,7 @@
 //     g is g itself; block 0, which the dispatcher starts first, also brings up the control block.)
 //   * queries are taken longest first (a counting sort on the part count, built by every workgroup
 //     in LDS from n[]), so the launch ends on the shortest parts.
-//   * control words and granule buffers live in an EXCHANGE AREA the library owns (ltr_linear.inc:
+//   * control words and granule buffers live in an EXCHANGE AREA the library owns (ltr_areas.inc:
 //     exchange_area_get -- one per (device, stream), a private one per captured call; zeroed when it is
 //     allocated, never handed to anybody else: nothing in it is ever uninitialised memory).  The control
 //     words are SELF-RESETTING: the last part of a query zeroes its arrival counter, the last workgroup
@@ -86,7 +86,7 @@ constexpr int kPtSpinLimit = 1 << 18;
 // control block (in the library's exchange area: zero when allocated), ints:
 // [0] tag of the NEXT launch (0 = 1) | [4] tickets drawn | [5] workgroups gone | [8 + b] arrivals of query b
 constexpr int kPtCtrlHeader = 8;
-constexpr size_t kPtCtrlBytes = kExCtrlBytes;   // the control region of the exchange area (ltr_linear.inc), fixed: the shares start behind it
+constexpr size_t kPtCtrlBytes = kExCtrlBytes;   // the control region of the exchange area (ltr_areas.inc), fixed: the shares start behind it
 constexpr int kPtSleep = 4;
 constexpr int kPtCombineInflight = 8;      // shares per thread in flight when a query's shares are added up
 

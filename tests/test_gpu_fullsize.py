@@ -229,6 +229,48 @@ def test_exchange_area_tag_wraps_around():
     _C.device_status()
 
 
+def test_exchange_area_release_frees_every_area_and_the_next_launches_start_over():
+    """ltr_exchange_release (include/ltr_hip.h) frees every library-owned area of the process -- the parts kernel's exchange
+    area and the lazy step's weight granules alike -- once nothing is in flight: it returns 0, and the same calls made
+    again from the same inputs allocate fresh, zeroed areas and give the same bits (losses, gradients, weights)."""
+    from pytorchltr_amd import _C
+    from pytorchltr_amd.fused import LazySGD, linear_loss_step
+    dev = _dev()
+    lib = _C.lib()
+    B, L, F = 70, 512, 700
+    assert lib.ltr_linear_fused_plan(_C.HINGE, B, L, F) == _C.PLAN_PARTS
+    s, y, n, X, W, b = synth(B, L, 77, F=F)
+    parts_in = [t.to(dev) for t in (X, W, b, y, n)]
+    # (the smallest register-tile shape of tests/test_gpu_step.py's lazy steps: the second step takes the first one's update along)
+    lB, lL, lF = 1, 128, 136
+    assert lib.ltr_linear_fused_plan(_C.NDCG1, lB, lL, lF) == _C.PLAN_REGISTER_TILE
+    lazy_in = []
+    for i in range(2):
+        s, y, n, X, W0, b0 = synth(lB, lL, 11 + i, F=lF)
+        lazy_in.append([t.to(dev) for t in (X, y, n)])
+
+    def run():
+        Xd, Wd, bd, yd, nd = parts_in
+        out = list(linear_loss_step(Xd, Wd, bd, yd, nd, loss="hinge"))
+        w, bias = W0.clone().to(dev), b0.clone().to(dev)
+        opt = LazySGD(w, bias, 0.05, loss="ndcg1")
+        for xs, ys, nn in lazy_in:
+            opt.step(xs, ys, nn)
+            out.append(opt.loss.clone())
+        mean_loss, grad = opt.flush()
+        out += [mean_loss, grad, w, bias]
+        torch.cuda.synchronize()
+        return [t.cpu().numpy() for t in out]
+
+    first = run()
+    assert lib.ltr_exchange_release() == 0
+    again = run()
+    for a, c in zip(first, again):
+        assert np.all(np.isfinite(a))
+        assert np.array_equal(a, c)
+    _C.device_status()
+
+
 def test_parts_kernel_captured_without_a_warm_up_launch():
     """A call made under stream capture gets an exchange area of its own (allocated with the thread's capture mode
     relaxed): a graph captured as the very first use of a shape replays correctly, next to eager launches of the same

@@ -35,7 +35,7 @@ def _dev():
 
 
 def _one_round():
-    """R: the largest batch whose update rides in the next launch (csrc/ltr_linear.inc: lazy_one_round) -- 1024 on an MI355X."""
+    """R: the largest batch whose update rides in the next launch (csrc/ltr_linear_lazy.inc: lazy_one_round) -- 1024 on an MI355X."""
     return 4 * torch.cuda.get_device_properties(_dev()).multi_processor_count
 
 
