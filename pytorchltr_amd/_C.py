@@ -1,5 +1,6 @@
 """ctypes binding of the C ABI in ``include/ltr_hip.h``, ``include/ltr_eval.h``, ``include/ltr_listwise.h``,
-``include/ltr_longpair.h``, ``include/ltr_mlp_rows.h``, ``include/ltr_mlp_bf16.h``, ``include/ltr_mlp_wide.h`` and ``include/ltr_sched.h`` (pytorchltr_amd/csrc/libltr_hip.so).
+``include/ltr_longpair.h``, ``include/ltr_mlp_rows.h``, ``include/ltr_mlp_bf16.h``, ``include/ltr_mlp_wide.h``,
+``include/ltr_linear_bf16.h`` and ``include/ltr_sched.h`` (pytorchltr_amd/csrc/libltr_hip.so).
 
 PyTorch supplies device memory and the current HIP stream; every call here hands raw device
 pointers to the library.  The library must exist -- there is deliberately no fallback.
@@ -150,6 +151,17 @@ MLP_BF16_SIGNATURES = {
     "ltr_mlp_bf16_grad": (_i, [_vp] * 9 + [_i] * 5 + [_vp, _vp, _sz, _vp]),
 }
 
+# name -> (restype, argtypes); mirrors include/ltr_linear_bf16.h (the Linear(F, 1) scorer on a bf16 feature batch: the
+# streaming score / gradient kernels, the fused register-tile step and its plan, the bf16 collate)
+LINEAR_BF16_SIGNATURES = {
+    "ltr_linear_scores_bf16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "ltr_linear_grad_workspace_bytes_bf16": (_sz, [_i, _i, _i]),
+    "ltr_linear_grad_bf16": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "ltr_linear_bf16_plan": (_i, [_i, _i, _i, _i]),
+    "ltr_linear_partials_bf16": (_i, [_i, _f, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "ltr_collate_pad_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+}
+
 # name -> (restype, argtypes); mirrors include/ltr_mlp_wide.h (the same scorer on rows of up to 704 features)
 MLP_WIDE_SIGNATURES = {
     "ltr_mlp_wide_scores_f32": (_i, [_vp] * 8 + [_i] * 5 + [_vp, _vp]),
@@ -207,7 +219,7 @@ def lib():
         for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(EVAL_SIGNATURES.items())
                                           + list(LISTWISE_SIGNATURES.items()) + list(LONGPAIR_SIGNATURES.items())
                                           + list(MLP_ROWS_SIGNATURES.items()) + list(MLP_WIDE_SIGNATURES.items())
-                                          + list(MLP_BF16_SIGNATURES.items())
+                                          + list(MLP_BF16_SIGNATURES.items()) + list(LINEAR_BF16_SIGNATURES.items())
                                           + list(SCHED_SIGNATURES.items())):
             if name.startswith("ltr_debug_") and not hasattr(handle, name):
                 continue                     # a production build (-DLTR_NO_DEBUG_HOOKS) leaves the test hooks out

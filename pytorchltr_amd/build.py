@@ -11,15 +11,17 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(CSRC, "libltr_hip.so")
-# three translation units, compiled side by side and linked into one library: the loss / metric /
-# helper kernels with the C ABI, the fused Linear scorer + loss kernels, the fused MLP + scorer layer
-SOURCES = [os.path.join(CSRC, f) for f in ("ltr_kernels.hip", "ltr_linear.hip", "ltr_mlp.hip")]
+# four translation units, compiled side by side and linked into one library: the loss / metric /
+# helper kernels with the C ABI, the fused Linear scorer + loss kernels, the fused MLP + scorer layer,
+# the Linear scorer on bf16 feature batches (include/ltr_linear_bf16.h)
+SOURCES = [os.path.join(CSRC, f) for f in ("ltr_kernels.hip", "ltr_linear.hip", "ltr_mlp.hip", "ltr_linear_bf16.hip")]
 SOURCE_FLAGS = {}          # per-source compiler flags (none at present)
 OBJ_DIR = os.path.join(_ROOT, "build", "obj")
 # every .inc the translation units include, and the public headers
 DEPENDS = SOURCES + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".inc")) + \
     [os.path.join(_ROOT, "include", h) for h in ("ltr_hip.h", "ltr_eval.h", "ltr_listwise.h", "ltr_longpair.h",
-                                                "ltr_mlp_bf16.h", "ltr_mlp_rows.h", "ltr_mlp_wide.h", "ltr_sched.h")]
+                                                "ltr_linear_bf16.h", "ltr_mlp_bf16.h", "ltr_mlp_rows.h", "ltr_mlp_wide.h",
+                                                "ltr_sched.h")]
 ARCH = "gfx950"
 IO_LIB_PATH = os.path.join(CSRC, "libltr_io.so")
 IO_SOURCES = [os.path.join(CSRC, "svmrank_parser.cpp")]

@@ -1,5 +1,5 @@
 // ltr_common.inc -- device helpers, the two pair passes and the host-side launch helpers shared by
-// every translation unit of libltr_hip.so (ltr_kernels.hip, ltr_linear.hip, ltr_mlp.hip).  Everything
+// every translation unit of libltr_hip.so (ltr_kernels.hip, ltr_linear.hip, ltr_mlp.hip, ltr_linear_bf16.hip).  Everything
 // here lives in an anonymous namespace: each translation unit gets its own copy, nothing is exported.
 // The one piece of process-wide state, the device status page, is owned by ltr_kernels.hip and
 // reached through two hidden (non-exported) functions.

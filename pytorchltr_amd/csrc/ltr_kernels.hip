@@ -1224,6 +1224,35 @@ int ltr_collate_pad_f32(const float *xs, const int64_t *ys, const int64_t *offse
     return (int)hipGetLastError();
 }
 
+// include/ltr_linear_bf16.h: the same copy on bf16 rows, in the widest pieces the row width and the pointers allow
+int ltr_collate_pad_bf16(const uint16_t *xs, const int64_t *ys, const int64_t *offsets,
+                         const int64_t *qidx, const int64_t *sel, int Q, int B, int L, int F,
+                         uint16_t *out_x, int64_t *out_y, int64_t *out_n, void *stream)
+{
+    LTR_CLEAR_STALE_ERROR();
+    if (B < 0 || L <= 0 || F <= 0 || Q <= 0) return LTR_ERR_SHAPE;
+    if (B == 0) return LTR_OK;
+    if (!xs || !ys || !offsets || !qidx || !out_x || !out_y || !out_n) return LTR_ERR_NULL;
+    const uintptr_t both = (uintptr_t)xs | (uintptr_t)out_x;
+    const int per = (F % 8 == 0 && both % 16 == 0) ? 8 : ((F % 2 == 0 && both % 4 == 0) ? 2 : 1);    // bf16 per piece
+    const int C = F / per;
+    const size_t per_query = (size_t)L * C;
+    unsigned gy = (unsigned)((per_query + 256 * 8 - 1) / (256 * 8));
+    if (gy < 1) gy = 1;
+    if (gy > 64) gy = 64;
+    const dim3 grid((unsigned)B, gy), block(256);
+    if (per == 8)
+        hipLaunchKernelGGL((collate_pad_kernel<uint4>), grid, block, 0, (hipStream_t)stream, (const uint4 *)xs, ys,
+                           offsets, qidx, sel, Q, L, C, (uint4 *)out_x, out_y, out_n);
+    else if (per == 2)
+        hipLaunchKernelGGL((collate_pad_kernel<uint32_t>), grid, block, 0, (hipStream_t)stream, (const uint32_t *)xs, ys,
+                           offsets, qidx, sel, Q, L, C, (uint32_t *)out_x, out_y, out_n);
+    else
+        hipLaunchKernelGGL((collate_pad_kernel<uint16_t>), grid, block, 0, (hipStream_t)stream, xs, ys,
+                           offsets, qidx, sel, Q, L, C, out_x, out_y, out_n);
+    return (int)hipGetLastError();
+}
+
 int ltr_collate_pad_csr_f32(const int64_t *indptr, const int32_t *indices, const float *values,
                             const int64_t *ys, const int64_t *offsets, const int64_t *qidx, const int64_t *sel,
                             int Q, int B, int L, int F, float *out_x, int64_t *out_y, int64_t *out_n, void *stream)

@@ -1,5 +1,5 @@
 // ltr_linear.hip -- translation unit of the fused Linear(F,1) scorer + pairwise loss step of libltr_hip.so; compiled next to
-// ltr_kernels.hip and ltr_mlp.hip (pytorchltr_amd/build.py), so the three build in parallel.  This file is the table of
+// ltr_kernels.hip, ltr_mlp.hip and ltr_linear_bf16.hip (pytorchltr_amd/build.py), so the four build in parallel.  This file is the table of
 // contents: the code is in the .inc files below, each of which needs only what stands above it.
 #include <atomic>
 #include <condition_variable>

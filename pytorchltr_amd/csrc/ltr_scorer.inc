@@ -156,6 +156,17 @@ linear_grad_kernel(ScorerParams p)
     }
 }
 
+// The fixed-order sum of a workspace of partial vectors for the translation units that do not have mlp_reduce_kernel
+// (ltr_linear_bf16.inc): out[i] = sum over the nPart vectors, `pitch` floats apart, i < P.  Not part of the C ABI.
+extern "C" __attribute__((visibility("hidden"))) int ltr_internal_reduce_partials(const float *part, int nPart, int P, int pitch,
+                                                                                  float *out, void *stream)
+{
+    hipLaunchKernelGGL(mlp_reduce_kernel, dim3((unsigned)((P + kMlpRedCols - 1) / kMlpRedCols)),
+                       dim3(kMlpRedCols * kMlpRedSlices), 0, (hipStream_t)stream, part, nPart, P, pitch, out,
+                       (const float *)nullptr, 0, (float *)nullptr);
+    return (int)hipGetLastError();
+}
+
 extern "C" {
 
 int ltr_linear_scores_f32(const float *X, const float *W, const float *bias, const int64_t *n, int B,

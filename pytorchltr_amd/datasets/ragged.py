@@ -5,7 +5,8 @@ The reference pads a batch with a Python loop over samples on the host
 ``features (B, L, F)`` zero-padded, ``relevance (B, L)`` int64 zero-padded, ``n = min(n_i, L)``,
 ``L = max_i min(max_list_size, n_i)``, over-long queries truncated by a ``ListSampler``.
 ``RaggedQueries`` keeps the whole split on the GPU as concatenated rows plus offsets and
-produces the same batch with ``ltr_collate_pad_f32`` (a gather/pad copy at HBM speed); only the
+produces the same batch with ``ltr_collate_pad_f32`` (a gather/pad copy at HBM speed; ``ltr_collate_pad_bf16`` for a
+split kept as ``torch.bfloat16``, include/ltr_linear_bf16.h); only the
 index vectors of truncated queries are drawn on the host, by the same sampler calls in the same
 order as the reference.
 """
@@ -45,13 +46,23 @@ class RaggedQueries(_torch.utils.data.Dataset):
             counts that are not a multiple of 4 (Example3: 5, the reference's test file: 45, MQ2007 / MQ2008: 46) then
             take the 16-byte-vector kernels of this package (register tile, streaming scorer) instead of the scalar
             ones; ``torch.nn.Linear`` takes the view like any other tensor.  Default 1: rows packed like the reference's.
+            A bf16 split takes 1 or 8: whole 16-byte pieces of eight bf16 (Istella: 220 -> 224, Yahoo: 699 -> 704).
+        feature_dtype: ``torch.float32`` (default) or ``torch.bfloat16`` -- the dense split is rounded ONCE, to nearest
+            even, and kept as bf16 (half the memory); every batch's ``features`` is then a bf16 tensor, which
+            ``LinearScorer`` / ``FusedLinearLoss`` / ``linear_loss_step`` and the MLP scorer take as it is stored.  Not
+            with `csr`.
     """
 
     def __init__(self, features, relevance, offsets, qids=None, device="cuda", csr=None, num_features=None,
-                 pad_features_to=1):
+                 pad_features_to=1, feature_dtype=_torch.float32):
         relevance = _torch.as_tensor(relevance, dtype=_torch.int64)
         offsets = _torch.as_tensor(offsets, dtype=_torch.int64).cpu()
         self.csr = None
+        if feature_dtype not in (_torch.float32, _torch.bfloat16):
+            raise ValueError("feature_dtype must be torch.float32 or torch.bfloat16")
+        if csr is not None and feature_dtype is not _torch.float32:
+            raise ValueError("a csr split is stored and collated as float32 (feature_dtype=torch.bfloat16: dense splits only)")
+        self.feature_dtype = feature_dtype
         if csr is not None:
             # the sparse branch (svmrank.py:162-176): the split as CSR, collated into DENSE padded batches
             indptr, indices, values = csr
@@ -76,8 +87,8 @@ class RaggedQueries(_torch.utils.data.Dataset):
         if offsets.dim() != 1 or offsets.numel() < 1 or int(offsets[0]) != 0 or \
                 int(offsets[-1]) != features.shape[0] or bool((offsets[1:] < offsets[:-1]).any()):
             raise ValueError("offsets must be non-decreasing, start at 0 and end at N")
-        if pad_features_to not in (1, 4):
-            raise ValueError("pad_features_to must be 1 or 4")
+        if pad_features_to not in ((1, 8) if feature_dtype is _torch.bfloat16 else (1, 4)):
+            raise ValueError("pad_features_to must be 1 or 4 (a bf16 split: 1 or 8)")
         if self.num_features is None:
             self.num_features = int(features.shape[1])
         self._row_width = (self.num_features + pad_features_to - 1) // pad_features_to * pad_features_to
@@ -92,7 +103,7 @@ class RaggedQueries(_torch.utils.data.Dataset):
         self._qids_host = (_torch.arange(self._q, dtype=_torch.int64) if qids is None
                            else _torch.as_tensor(qids, dtype=_torch.int64).cpu())
         dev = _torch.device(device)
-        self.features = features.to(dev).contiguous()
+        self.features = features.to(dev).to(feature_dtype).contiguous()     # (bf16: rounded once, to nearest even)
         self.relevance = relevance.to(dev).contiguous()
         self.offsets = offsets.to(dev)
         if csr is not None:
@@ -161,8 +172,8 @@ class RaggedQueries(_torch.utils.data.Dataset):
         B = idx.numel()
         list_size, select = self.plan(idx.tolist(), list_sampler)
         dev = self.relevance.device
-        F = self._row_width                         # (the row width in memory: num_features, or padded to a multiple of 4)
-        out_x = _torch.empty(B, list_size, F, dtype=_torch.float32, device=dev)
+        F = self._row_width                         # (the row width in memory: num_features, or padded to a multiple of 4 / 8)
+        out_x = _torch.empty(B, list_size, F, dtype=self.feature_dtype, device=dev)
         out_y = _torch.empty(B, list_size, dtype=_torch.int64, device=dev)
         out_n = _torch.empty(B, dtype=_torch.int64, device=dev)
         qidx = idx.to(dev)
@@ -175,7 +186,8 @@ class RaggedQueries(_torch.utils.data.Dataset):
                     _C.ptr(out_y), _C.ptr(out_n), _C.stream_of(out_x)))
         elif B > 0 and list_size > 0:
             with _C.device_ctx(out_x):
-                _C.check(_C.lib().ltr_collate_pad_f32(
+                entry = _C.lib().ltr_collate_pad_bf16 if self.feature_dtype is _torch.bfloat16 else _C.lib().ltr_collate_pad_f32
+                _C.check(entry(
                     _C.ptr(self.features), _C.ptr(self.relevance), _C.ptr(self.offsets),
                     _C.ptr(qidx), _C.ptr(sel), self._q, B, list_size, F, _C.ptr(out_x),
                     _C.ptr(out_y), _C.ptr(out_n), _C.stream_of(out_x)))
@@ -183,7 +195,7 @@ class RaggedQueries(_torch.utils.data.Dataset):
             out_n.zero_()
         qid = self._qids_host[idx].to(dev)
         if F != self.num_features:
-            out_x = out_x[:, :, :self.num_features]          # the reference's (B, L, F) batch, rows F4 floats apart
+            out_x = out_x[:, :, :self.num_features]          # the reference's (B, L, F) batch, rows F4 floats (F8 bf16) apart
             out_x._ltr_zero_padded_rows = True               # (the hidden columns ARE zeros: what fused._padded_rows asks for)
         return SVMRankBatch(out_x, out_y, out_n, qid, False)
 

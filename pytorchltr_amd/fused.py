@@ -80,28 +80,56 @@ def _padded_rows(xs):
     ``RaggedQueries(pad_features_to=4)`` collates (feature counts like Example3's 5, LETOR's 45 / 46: rows that are not
     whole float4 otherwise run the scalar kernels) -- as the (B, L, F4) tensor it lives in, or None.  The hidden
     columns meet zero weights, so any FINITE content is harmless (the collate writes zeros)."""
-    if xs.dim() != 3 or xs.dtype is not torch.float32 or not xs.is_cuda:
+    # (a bf16 batch -- RaggedQueries(feature_dtype=torch.bfloat16, pad_features_to=8): rows a multiple of EIGHT values
+    # apart, whole 16-byte pieces again; F4 below is then that width)
+    if xs.dim() != 3 or xs.dtype not in (torch.float32, torch.bfloat16) or not xs.is_cuda:
         return None
+    align = 8 if xs.dtype is torch.bfloat16 else 4
     # only batches the collate of this package made: there the hidden columns are zeros.  A user's own view with the same
     # strides (big[..., :5] of an 8-column tensor) may hide NaN / Inf / metadata columns, which nn.Linear ignores and a
     # zero weight does not (NaN * 0): those are copied to a contiguous batch like any other view (ADVICE r5)
     if not getattr(xs, "_ltr_zero_padded_rows", False):
         return None
     B, L, F = xs.shape
-    F4 = (F + 3) & ~3
+    F4 = (F + align - 1) // align * align
     if F4 == F or B == 0 or L == 0 or xs.stride(2) != 1 or xs.stride(1) != F4 or (B > 1 and xs.stride(0) != L * F4):
         return None
     off = xs.storage_offset()
-    if off % 4 != 0 or xs.untyped_storage().nbytes() < 4 * (off + B * L * F4):
+    if off % align != 0 or xs.untyped_storage().nbytes() < xs.element_size() * (off + B * L * F4):
         return None
     return xs.as_strided((B, L, F4), (L * F4, F4, 1), off)
 
 
-def _prepare_features(xs):
+def _bf16_batch(xs):
+    """True for a batch the bf16 Linear kernels (include/ltr_linear_bf16.h) take as it is stored: a torch.bfloat16
+    (B, L, F) device tensor that needs no gradient itself, outside autocast."""
+    return (torch.is_tensor(xs) and xs.dtype is torch.bfloat16 and xs.dim() == 3 and xs.is_cuda
+            and not xs.requires_grad and not torch.is_autocast_enabled())
+
+
+def _prepare_features_bf16(xs):
+    """`_prepare_features` for a `_bf16_batch`: contiguous bf16 (B, L, F') with F' % 8 == 0 -- the batch itself where
+    F % 8 == 0 and it is contiguous, the (B, L, F8) tensor a marked `_padded_rows` view lives in, else ONE copy that
+    appends zero columns up to a multiple of 8 (as `_zero_pad` does for the MLP; the callers zero-pad the weights to
+    match and crop the gradient).  No fp32 copy is ever made."""
+    extra = (-xs.shape[2]) % 8
+    if extra == 0:
+        if xs.is_contiguous() and xs.data_ptr() % 16 != 0:      # (a contiguous view at an odd offset: rows off 16 bytes)
+            return xs.clone()
+        return xs if xs.is_contiguous() else xs.contiguous()
+    padded = _padded_rows(xs)
+    return padded if padded is not None else torch.nn.functional.pad(xs, (0, extra))
+
+
+def _prepare_features(xs, bf16=False):
     """The feature batch as the kernels take it: contiguous fp32 (B, L, F') on the device -- F' = F, or the padded
-    row width of a `_padded_rows` view (the callers zero-pad the weights to match and crop the gradient)."""
+    row width of a `_padded_rows` view (the callers zero-pad the weights to match and crop the gradient).
+    `bf16`: the caller has the bf16 kernels -- a `_bf16_batch` stays bf16 (`_prepare_features_bf16`); every other
+    dtype, and every caller without them (the listwise steps, the lazy launch, the MLP's fp32 families), casts."""
     if xs.dtype is torch.float32 and xs.is_cuda and xs.dim() == 3 and xs.is_contiguous():
         return xs                                   # the common case: nothing to do
+    if bf16 and _bf16_batch(xs):
+        return _prepare_features_bf16(xs)
     _C.require_device(xs, "xs")
     if xs.dim() != 3:
         raise ValueError("features must have shape (batch, list_size, features)")
@@ -167,7 +195,8 @@ def _linear_ws_bytes(B, L, F):
 class _LinearLossFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xs, weight, bias, relevance, n, kind, sigma, want_scores):
-        X = _prepare_features(xs)
+        X = _prepare_features(xs, bf16=True)        # (a bf16 batch: the caller found it on the bf16 plan, _linear_route)
+        bf16 = X.dtype is torch.bfloat16
         B, L, F = X.shape                           # (F: the row width in memory, >= the logical feature count)
         Fw = xs.shape[2]
         if weight.numel() != Fw:
@@ -178,8 +207,9 @@ class _LinearLossFunction(torch.autograd.Function):
         # step's update in ONE launch); its backward and the optimizer step then launch nothing
         st = getattr(weight, "_ltr_lazy", None)
         if st is not None:
-            if (not want_scores and bias is not None and Fw == F and ctx.needs_input_grad[1] and ctx.needs_input_grad[2]
-                    and getattr(bias, "_ltr_lazy", None) is st):
+            # (there is no bf16 lazy launch: a bf16 batch settles the pending update and takes the ordinary path)
+            if (not bf16 and not want_scores and bias is not None and Fw == F and ctx.needs_input_grad[1]
+                    and ctx.needs_input_grad[2] and getattr(bias, "_ltr_lazy", None) is st):
                 loss = st.forward(ctx, X, r, _LABEL_CODE[r.dtype], nn, kind, sigma)
                 if loss is not None:
                     ctx.lazy_loss = loss.detach()            # (an alias without the autograd node: no reference cycle)
@@ -199,7 +229,8 @@ class _LinearLossFunction(torch.autograd.Function):
         scores = torch.empty((B, L), dtype=torch.float32, device=dev) if want_scores else None
         if B > 0:
             with _C.device_ctx(X):
-                rc = _C.lib().ltr_linear_partials_f32(
+                entry = _C.lib().ltr_linear_partials_bf16 if bf16 else _C.lib().ltr_linear_partials_f32
+                rc = entry(
                     kind, float(sigma), X.data_ptr(), W.data_ptr(),
                     None if bvec is None else bvec.data_ptr(), r.data_ptr(), _LABEL_CODE[r.dtype],
                     nn.data_ptr(), B, L, F, loss.data_ptr(),
@@ -254,6 +285,8 @@ def _reduce_rows(ctx, ws, grad_loss):
     db = torch.empty(1, dtype=torch.float32, device=ws.device)
     # `.mean().backward()` / `.sum().backward()`: autograd hands over an expanded scalar (stride 0) -- the reduction
     # reads it where it is instead of a (B,) copy being made first
+    if B == 0:                                  # (an empty batch: its upstream gradient has no storage to point the reduction at)
+        return dW.zero_()[:ctx.Fw].reshape(ctx.w_shape), (db.zero_() if ctx.has_bias else None)
     bcast = go.dtype is torch.float32 and go.dim() == 1 and go.stride(0) == 0
     if not bcast and (go.dtype is not torch.float32 or go.dim() != 1 or not go.is_contiguous()):
         go = go.reshape(B).float().contiguous()
@@ -379,6 +412,57 @@ def _prefer_pieces(kind, B, L, F):
     return v
 
 
+_LIN_BF16_FUSED, _LIN_BF16_PIECES, _LIN_F32 = "bf16 fused", "bf16 pieces", "f32"
+_bf16_plan_cache = {}
+
+
+def _linear_bf16_plan(kind, B, L, F8):
+    """True where ltr_linear_partials_bf16 takes the shape (ltr_linear_bf16_plan; F8: the row width in memory)."""
+    key = (int(kind), B, L, F8)
+    v = _bf16_plan_cache.get(key)
+    if v is None:
+        v = _bf16_plan_cache[key] = _C.lib().ltr_linear_bf16_plan(int(kind), B, L, F8) == _C.PLAN_REGISTER_TILE
+    return v
+
+
+def _prefer_pieces_bf16(kind, B, L, cus):
+    """`_prefer_pieces` for a bf16 batch on a device of `cus` CUs: the same rule -- a few lists cannot fill the GPU with
+    one workgroup per query -- without the cluster / parts exemptions, which have no bf16 kernel."""
+    if B <= 0 or _C.lib().ltr_pairwise_loss_workspace_bytes(int(kind), B, L) == 0:
+        return False
+    heavy_pairs = int(kind) not in (_C.HINGE, _C.DCG_HINGE)
+    return (2 * B <= cus) or (heavy_pairs and B <= cus and L > 768)
+
+
+def _linear_route(caller, dtype, dim, is_cuda, requires_grad, autocast, kind, B, L, F, cus=None):
+    """Which kernels run ``loss_fn(Linear(F, 1)(xs), ...)`` for a batch of these plain values: _LIN_BF16_FUSED
+    (ltr_linear_partials_bf16 and the existing reduce), _LIN_BF16_PIECES (the bf16 scorer, the stand-alone loss on the
+    fp32 scores, the bf16 weight-gradient kernel) or _LIN_F32 -- today's routes, which cast anything that is not fp32.
+
+    `caller`: "step" (linear_loss_step: fused wherever the plan takes the shape) or "module" (FusedLinearLoss, a loss
+    module on LazyScores: the pieces also where `_prefer_pieces_bf16` prefers them; `cus`: the device's CU count, read
+    from the current device when None).  `kind`: a pairwise kind (a LongKind with its flag); the listwise kinds have no
+    bf16 fused step and cast.  `F`: the logical feature count; the bf16 rows are zero-padded to a multiple of 8."""
+    if dtype is not torch.bfloat16 or dim != 3 or not is_cuda or requires_grad or autocast or isinstance(kind, _ListwiseKind):
+        return _LIN_F32
+    if _long_pair_shape(kind, L) or not _linear_bf16_plan(kind, max(B, 1), L, (F + 7) & ~7):
+        return _LIN_BF16_PIECES
+    if caller == "module":
+        if cus is None:
+            cus = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
+        if _prefer_pieces_bf16(kind, B, L, cus):
+            return _LIN_BF16_PIECES
+    return _LIN_BF16_FUSED
+
+
+def _linear_route_of(caller, xs, kind):
+    """`_linear_route` on a batch: its dtype, shape and flags and the autocast state."""
+    if not torch.is_tensor(xs) or xs.dim() != 3:
+        return _LIN_F32
+    B, L, F = xs.shape
+    return _linear_route(caller, xs.dtype, 3, xs.is_cuda, xs.requires_grad, torch.is_autocast_enabled(), kind, B, L, F)
+
+
 class FusedLinearLoss(torch.nn.Module):
     """``loss_fn(Linear(in_features, 1)(xs), relevance, n)`` as one fused op.
 
@@ -403,8 +487,9 @@ class FusedLinearLoss(torch.nn.Module):
     def forward(self, xs, relevance, n, return_scores=False):
         if isinstance(self.kind, _ListwiseKind):
             return _listwise_linear_loss(xs, self.weight, self.bias, relevance, n, self.kind, bool(return_scores))
-        if xs.dim() == 3 and xs.is_cuda and (_long_pair_shape(self.kind, xs.shape[1])
-                                             or self._pieces_cached(xs.shape[0], xs.shape[1])):
+        route = _linear_route_of("module", xs, self.kind)
+        if route == _LIN_BF16_PIECES or route == _LIN_F32 and xs.dim() == 3 and xs.is_cuda and (
+                _long_pair_shape(self.kind, xs.shape[1]) or self._pieces_cached(xs.shape[0], xs.shape[1])):
             # a few long lists: one workgroup per query cannot fill the GPU; the balanced pieces
             # (streaming scorer, split-query loss, streaming weight gradient) are faster -- and past
             # max_list_len() documents (long_lists=True) they are the only path
@@ -436,7 +521,11 @@ def linear_loss_step(xs, weight, bias, relevance, n, loss="hinge", grad_out=None
     ``.mean()`` of the reference's training loop (1/B each).  Two launches: the fused
     scorer+loss kernel and the cross-query reduction (which also totals the loss)."""
     kind, sigma = _resolve_loss(loss)
-    X = _prepare_features(xs)
+    route = _linear_route_of("step", xs, kind)
+    if route == _LIN_BF16_PIECES:                   # a bf16 batch off the plan of the bf16 fused step
+        return _step_pieces(xs, weight, bias, relevance, n, kind, sigma, grad_out, return_scores, return_loss_sum)
+    bf16 = route == _LIN_BF16_FUSED
+    X = _prepare_features(xs, bf16=bf16)
     listwise = isinstance(kind, _ListwiseKind)
     if listwise and not _listwise_fused(kind, X):
         return _step_pieces(xs, weight, bias, relevance, n, kind, sigma, grad_out, return_scores, return_loss_sum)
@@ -460,7 +549,8 @@ def linear_loss_step(xs, weight, bias, relevance, n, loss="hinge", grad_out=None
         if listwise:
             _listwise_launch(kind, X, W, bvec, r, nn, lossv, scores, ws)
         else:
-            _C.check(_C.lib().ltr_linear_partials_f32(
+            entry = _C.lib().ltr_linear_partials_bf16 if bf16 else _C.lib().ltr_linear_partials_f32
+            _C.check(entry(
                 kind, float(sigma), _C.ptr(X), _C.ptr(W), _C.ptr(bvec), _C.ptr(r), _C.label_dtype(r),
                 _C.ptr(nn), B, L, F, _C.ptr(lossv), _C.ptr(scores), _C.ptr(ws), st))
         _C.check(_C.lib().ltr_linear_reduce_loss_f32(
@@ -510,7 +600,9 @@ class LazySGD:
     update inside the same launch (its first workgroups sum that batch's rows and hand the new weights to every
     workgroup before the dot products), so the reduction launch and a kernel boundary per step are gone.  Weights,
     gradients and losses are bit-identical to the eager step's.  `weight` (F elements) / `bias` (one element) are
-    contiguous fp32 device tensors, updated in place; every batch must have the same (B, L, F).
+    contiguous fp32 device tensors, updated in place; every batch must have the same (B, L, F).  There is no bf16 lazy
+    launch: a ``torch.bfloat16`` batch is cast to fp32 in every ``step`` (train on it through ``linear_loss_step`` or the
+    modules instead, which take it as it is stored).
 
     Data parallel (one process per GPU, every rank steps through its shard of each global batch):
     ``LazySGD(weight, bias, lr, loss, mailbox=MailboxOverlap(F, count=B_shard, device=dev))`` -- the step stays ONE launch
@@ -535,7 +627,7 @@ class LazySGD:
         self.loss = self.bucket = self.ws = None
 
     def step(self, xs, relevance, n):
-        X = _prepare_features(xs)
+        X = _prepare_features(xs)                   # (no bf16 lazy launch: a bf16 batch is cast to fp32 here, every step)
         B, L, F = X.shape
         if self.shape is None:
             if self.weight.numel() != F:
@@ -580,7 +672,7 @@ class LazySGD:
 class _LinearScoreFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xs, weight, bias, n):
-        X = _prepare_features(xs)
+        X = _prepare_features(xs, bf16=True)        # (a bf16 batch stays bf16: ltr_linear_scores_bf16 / ltr_linear_grad_bf16)
         B, L, F = X.shape                           # (F: the row width in memory -- a padded view's F4)
         Fw = xs.shape[2]
         W = _pad_weight(weight.detach().reshape(Fw).float().contiguous(), F)
@@ -590,8 +682,8 @@ class _LinearScoreFunction(torch.autograd.Function):
         scores = torch.empty(B, L, dtype=torch.float32, device=X.device)
         if B > 0:
             with _C.device_ctx(X):
-                _C.check(_C.lib().ltr_linear_scores_f32(_C.ptr(X), _C.ptr(W), _C.ptr(bvec), _C.ptr(nn),
-                                                        B, L, F, _C.ptr(scores), _C.stream_of(X)))
+                entry = _C.lib().ltr_linear_scores_bf16 if X.dtype is torch.bfloat16 else _C.lib().ltr_linear_scores_f32
+                _C.check(entry(_C.ptr(X), _C.ptr(W), _C.ptr(bvec), _C.ptr(nn), B, L, F, _C.ptr(scores), _C.stream_of(X)))
         # (the layer's input needs a gradient only when it is not the feature batch itself -- a hidden
         # layer's output: the weight is kept for grad_xs = grad_scores (x) weight in that case)
         ctx.xs_grad = bool(ctx.needs_input_grad[0])
@@ -611,11 +703,13 @@ class _LinearScoreFunction(torch.autograd.Function):
         g = grad_scores.reshape(B, L).float().contiguous()
         lib = _C.lib()
         out = torch.empty(F + 1, dtype=torch.float32, device=X.device)
-        ws_bytes = lib.ltr_linear_grad_workspace_bytes(B, L, F)
+        bf16 = X.dtype is torch.bfloat16
+        ws_bytes = (lib.ltr_linear_grad_workspace_bytes_bf16 if bf16 else lib.ltr_linear_grad_workspace_bytes)(B, L, F)
         ws = torch.empty(max(ws_bytes, 4) // 4, dtype=torch.float32, device=X.device)
         with _C.device_ctx(X):
-            _C.check(lib.ltr_linear_grad_f32(_C.ptr(X), _C.ptr(g), _C.ptr(nn) if ctx.has_n else None,
-                                             B, L, F, _C.ptr(out), _C.ptr(ws), ws_bytes, _C.stream_of(X)))
+            _C.check((lib.ltr_linear_grad_bf16 if bf16 else lib.ltr_linear_grad_f32)(
+                _C.ptr(X), _C.ptr(g), _C.ptr(nn) if ctx.has_n else None,
+                B, L, F, _C.ptr(out), _C.ptr(ws), ws_bytes, _C.stream_of(X)))
         gx = None
         if ctx.xs_grad:
             gm = g
@@ -672,7 +766,11 @@ class LazyScores(torch.Tensor):
         if kind == _LISTWISE_SOFTMAX:
             return None
         B, L, F = xs.shape
-        if _long_pair_shape(kind, L) or _prefer_pieces(kind, B, L, (F + 3) & ~3 if not xs.is_contiguous() else F):
+        route = _linear_route_of("module", xs, kind)
+        if route == _LIN_BF16_PIECES:
+            return None
+        if route == _LIN_F32 and (_long_pair_shape(kind, L)
+                                  or _prefer_pieces(kind, B, L, (F + 3) & ~3 if not xs.is_contiguous() else F)):
             return None
         self._check_versions()
         return _LinearLossFunction.apply(xs, self._weight, self._bias, relevance, n, kind, sigma, False)
@@ -750,10 +848,11 @@ class LinearScorer(torch.nn.Module):
             self.weight._ltr_scorer_bias = self.bias          # (pytorchltr_amd.optim.SGD pairs them up by this)
 
     def forward(self, xs, n=None):
-        if not (torch.is_tensor(xs) and xs.dim() == 3 and xs.is_cuda and xs.dtype is torch.float32
+        if not (torch.is_tensor(xs) and xs.dim() == 3 and xs.is_cuda
+                and (xs.dtype is torch.float32 or _bf16_batch(xs))
                 and xs.shape[-1] == self.in_features and not torch.is_autocast_enabled()):
-            # not an fp32 (B, L, F) feature batch on the device (a value head, a gate, a 2-D input, half precision under
-            # autocast ...): the plain layer, with nn.Linear's dtype rules and errors
+            # not an fp32 (B, L, F) feature batch on the device, nor a bf16 one that needs no gradient (a value head, a
+            # gate, a 2-D input, half precision under autocast ...): the plain layer, with nn.Linear's dtype rules and errors
             return torch.nn.functional.linear(xs, self.weight, self.bias)
         if (self.lazy and torch.is_grad_enabled() and not xs.requires_grad and (xs.is_contiguous() or _padded_rows(xs) is not None)
                 and (self.weight.requires_grad or (self.bias is not None and self.bias.requires_grad))):

@@ -25,6 +25,11 @@ the optimizer changes.  How:
 Everything that is not plain SGD on a ``LinearScorer`` (momentum, weight decay, nesterov, maximize, other parameters, a
 non-uniform upstream gradient, gradient accumulation, shapes the register-tile kernel does not take) runs as
 ``torch.optim.SGD`` does, on gradients that are materialised on the spot: same numbers, more launches.
+
+A ``torch.bfloat16`` feature batch is such a case: there is no bf16 lazy launch.  The forward pass applies the pending
+update (``settle()``) and takes the ordinary bf16 path of ``fused`` (``ltr_linear_partials_bf16`` and the reduction, or
+the bf16 pieces), ``optimizer.step()`` is then ``torch.optim.SGD``'s on the materialised gradient: same numbers, more
+launches.
 """
 import weakref
 
