@@ -107,29 +107,24 @@ def _bf16_batch(xs):
             and not xs.requires_grad and not torch.is_autocast_enabled())
 
 
-def _prepare_features_bf16(xs):
-    """`_prepare_features` for a `_bf16_batch`: contiguous bf16 (B, L, F') with F' % 8 == 0 -- the batch itself where
-    F % 8 == 0 and it is contiguous, the (B, L, F8) tensor a marked `_padded_rows` view lives in, else ONE copy that
-    appends zero columns up to a multiple of 8 (as `_zero_pad` does for the MLP; the callers zero-pad the weights to
-    match and crop the gradient).  No fp32 copy is ever made."""
-    extra = (-xs.shape[2]) % 8
-    if extra == 0:
-        if xs.is_contiguous() and xs.data_ptr() % 16 != 0:      # (a contiguous view at an odd offset: rows off 16 bytes)
-            return xs.clone()
-        return xs if xs.is_contiguous() else xs.contiguous()
-    padded = _padded_rows(xs)
-    return padded if padded is not None else torch.nn.functional.pad(xs, (0, extra))
-
-
 def _prepare_features(xs, bf16=False):
     """The feature batch as the kernels take it: contiguous fp32 (B, L, F') on the device -- F' = F, or the padded
     row width of a `_padded_rows` view (the callers zero-pad the weights to match and crop the gradient).
-    `bf16`: the caller has the bf16 kernels -- a `_bf16_batch` stays bf16 (`_prepare_features_bf16`); every other
-    dtype, and every caller without them (the listwise steps, the lazy launch, the MLP's fp32 families), casts."""
+    `bf16`: the caller has the bf16 kernels (`_LINEAR_BF16`) -- a `_bf16_batch` stays bf16, contiguous with F' % 8 == 0:
+    the batch itself where F % 8 == 0 and it is contiguous, the (B, L, F8) tensor a marked `_padded_rows` view lives in,
+    else ONE copy that appends zero columns up to a multiple of 8 (as `_zero_pad` does for the MLP); no fp32 copy is ever
+    made.  Every other dtype, and every caller without them (the listwise steps, the lazy launch, the MLP's fp32
+    families), casts."""
     if xs.dtype is torch.float32 and xs.is_cuda and xs.dim() == 3 and xs.is_contiguous():
         return xs                                   # the common case: nothing to do
     if bf16 and _bf16_batch(xs):
-        return _prepare_features_bf16(xs)
+        extra = (-xs.shape[2]) % 8
+        if extra == 0:
+            if xs.is_contiguous() and xs.data_ptr() % 16 != 0:      # (a contiguous view at an odd offset: rows off 16 bytes)
+                return xs.clone()
+            return xs if xs.is_contiguous() else xs.contiguous()
+        padded = _padded_rows(xs)
+        return padded if padded is not None else torch.nn.functional.pad(xs, (0, extra))
     _C.require_device(xs, "xs")
     if xs.dim() != 3:
         raise ValueError("features must have shape (batch, list_size, features)")
@@ -192,56 +187,114 @@ def _linear_ws_bytes(B, L, F):
     return v
 
 
+class _LinearFamily(collections.namedtuple("_LinearFamily", "name dtype align scores grad grad_ws partials")):
+    """The Linear scorer's kernels for one element type of the batch (the twin of `_MLPFamily`): the type, the number of
+    values its rows are a multiple of in memory, and the names of its entry points -- scores, weight gradient and its
+    workspace size, and the fused step's per-query rows."""
+    __slots__ = ()
+
+
+_LINEAR_F32 = _LinearFamily("f32", torch.float32, 4, "ltr_linear_scores_f32", "ltr_linear_grad_f32",       # include/ltr_hip.h
+                            "ltr_linear_grad_workspace_bytes", "ltr_linear_partials_f32")
+_LINEAR_BF16 = _LinearFamily("bf16", torch.bfloat16, 8, "ltr_linear_scores_bf16", "ltr_linear_grad_bf16",  # include/ltr_linear_bf16.h
+                             "ltr_linear_grad_workspace_bytes_bf16", "ltr_linear_partials_bf16")
+
+
+def _linear_family_of(X):
+    """The family of a prepared batch."""
+    return _LINEAR_BF16 if X.dtype is torch.bfloat16 else _LINEAR_F32
+
+
+def _linear_prepare(xs, weight, relevance, n, kind, raw=None):
+    """Check and prepare the batch of a fused launch: ``(X, r, nn, (B, L, F), Fw)`` -- the batch as the kernels take it
+    (`_prepare_features`; bf16 stays bf16 for the pairwise kinds, the listwise step is fp32-only), labels and list
+    lengths as the C ABI takes them, F the row width in memory and Fw <= F the logical feature count.  The parameters are
+    not touched (`_linear_launch` flattens them): a lazily updated one answers every question through a Python hook.
+
+    The weight count is checked against the feature count of `xs`.  A listwise kind is handed the batch as the route
+    prepared it (the plan is asked about the rows in memory), so there the weight states the logical count and has to
+    fit the rows.  `raw`: the batch as linear_loss_step got it -- its feature count is taken unchecked (a weight of
+    another length fails where it is flattened)."""
+    listwise = isinstance(kind, _ListwiseKind)
+    X = _prepare_features(xs, bf16=not listwise)
+    B, L, F = X.shape                           # (F: the row width in memory, >= the logical feature count)
+    if raw is not None:
+        Fw = raw.shape[2]
+    else:
+        Fw = weight.numel()
+        if listwise:
+            if not F - 4 < Fw <= F:
+                raise ValueError("weight has %d elements, the feature rows %d" % (Fw, F))
+        elif Fw != xs.shape[2]:
+            raise ValueError("weight has %d elements, features have %d" % (Fw, xs.shape[2]))
+    r, nn = _labels_and_n(relevance, n, B, L, X.device)
+    return X, r, nn, (B, L, F), Fw
+
+
+def _linear_launch(kind, sigma, X, weight, bias, r, nn, dims, Fw, want_scores=False, empty=False):
+    """The fused launch on a prepared batch: ``(loss[B], rows, scores | None)`` -- the family's partials entry point
+    (ltr_linear_partials_f32 / _bf16) for a pairwise kind, ltr_linear_listwise_partials_f32 for a listwise one (ListMLE
+    draws its tie seed here, one per launch).  `rows`: the workspace, the (B, PF) per-query gradient rows first, which
+    `_reduce_rows` / ltr_linear_reduce_loss_f32 sum.  An empty batch launches nothing unless `empty` (linear_loss_step
+    hands it to the entry point)."""
+    B, L, F = dims
+    W = _pad_weight(_flat_f32(weight, Fw), F)
+    bvec = None if bias is None else _flat_f32(bias, 1)
+    dev = X.device
+    loss = torch.empty(B, dtype=torch.float32, device=dev)
+    ws = torch.empty(_linear_ws_bytes(B, L, F) // 4, dtype=torch.float32, device=dev)
+    scores = torch.empty((B, L), dtype=torch.float32, device=dev) if want_scores else None
+    if B > 0 or empty:
+        listwise = isinstance(kind, _ListwiseKind)
+        if listwise:
+            from . import _ties
+            sd = _ties.draw_seed(L, dev) if kind.loss == _C.LISTWISE_LISTMLE else None
+        with _C.device_ctx(X):
+            lib = _C.lib()
+            bp = None if bvec is None else bvec.data_ptr()
+            sp = None if scores is None else scores.data_ptr()
+            if listwise:
+                rc = lib.ltr_linear_listwise_partials_f32(
+                    kind.loss, int(kind.k or 0), X.data_ptr(), W.data_ptr(), bp, r.data_ptr(), _LABEL_CODE[r.dtype],
+                    nn.data_ptr(), *_ties.tie_args(sd), B, L, F, loss.data_ptr(), sp, ws.data_ptr(), _C.stream_of(X))
+            else:
+                rc = getattr(lib, _linear_family_of(X).partials)(
+                    kind, float(sigma), X.data_ptr(), W.data_ptr(), bp, r.data_ptr(), _LABEL_CODE[r.dtype],
+                    nn.data_ptr(), B, L, F, loss.data_ptr(), sp, ws.data_ptr(), _C.stream_of(X))
+            if rc != 0:
+                _C.check(rc)
+    return loss, ws, scores
+
+
 class _LinearLossFunction(torch.autograd.Function):
+    """loss[b] of `kind` -- a pairwise kind, or a `_ListwiseKind` on a batch `_linear_routed` prepared -- on
+    Linear(F, 1)(xs) as ONE launch; backward is the cross-query reduction of its rows (`_reduce_rows`)."""
+
     @staticmethod
     def forward(ctx, xs, weight, bias, relevance, n, kind, sigma, want_scores):
-        X = _prepare_features(xs, bf16=True)        # (a bf16 batch: the caller found it on the bf16 plan, _linear_route)
-        bf16 = X.dtype is torch.bfloat16
-        B, L, F = X.shape                           # (F: the row width in memory, >= the logical feature count)
-        Fw = xs.shape[2]
-        if weight.numel() != Fw:
-            raise ValueError("weight has %d elements, features have %d" % (weight.numel(), Fw))
-        dev = X.device
-        r, nn = _labels_and_n(relevance, n, B, L, dev)
+        X, r, nn, dims, Fw = _linear_prepare(xs, weight, relevance, n, kind)
+        B, L, F = dims
+        ctx.dims = (B, F)
+        ctx.Fw = Fw
+        ctx.w_shape = weight.shape
+        ctx.has_bias = bias is not None
         # parameters that pytorchltr_amd.optim.SGD updates lazily: the lazy launch (this batch's rows + the previous
         # step's update in ONE launch); its backward and the optimizer step then launch nothing
         st = getattr(weight, "_ltr_lazy", None)
         if st is not None:
-            # (there is no bf16 lazy launch: a bf16 batch settles the pending update and takes the ordinary path)
-            if (not bf16 and not want_scores and bias is not None and Fw == F and ctx.needs_input_grad[1]
-                    and ctx.needs_input_grad[2] and getattr(bias, "_ltr_lazy", None) is st):
+            # (there is no bf16 and no listwise lazy launch: such a step settles the pending update and takes the ordinary path)
+            if (X.dtype is torch.float32 and not want_scores and bias is not None and Fw == F and ctx.needs_input_grad[1]
+                    and ctx.needs_input_grad[2] and getattr(bias, "_ltr_lazy", None) is st
+                    and not isinstance(kind, _ListwiseKind)):
                 loss = st.forward(ctx, X, r, _LABEL_CODE[r.dtype], nn, kind, sigma)
                 if loss is not None:
                     ctx.lazy_loss = loss.detach()            # (an alias without the autograd node: no reference cycle)
                     ctx.save_for_backward(X, r, nn)
                     ctx.lazy_args = (kind, sigma)
-                    ctx.dims = (B, F)
-                    ctx.Fw = Fw
-                    ctx.w_shape = weight.shape
-                    ctx.has_bias = True
                     return loss
             st.settle()                                      # the ordinary path reads the weights: no update may be pending
-        W = _pad_weight(_flat_f32(weight, Fw), F)
-        bvec = None if bias is None else _flat_f32(bias, 1)
-        loss = torch.empty(B, dtype=torch.float32, device=dev)
-        # (B, PF) partials, then the kernel's scratch
-        ws = torch.empty(_linear_ws_bytes(B, L, F) // 4, dtype=torch.float32, device=dev)
-        scores = torch.empty((B, L), dtype=torch.float32, device=dev) if want_scores else None
-        if B > 0:
-            with _C.device_ctx(X):
-                entry = _C.lib().ltr_linear_partials_bf16 if bf16 else _C.lib().ltr_linear_partials_f32
-                rc = entry(
-                    kind, float(sigma), X.data_ptr(), W.data_ptr(),
-                    None if bvec is None else bvec.data_ptr(), r.data_ptr(), _LABEL_CODE[r.dtype],
-                    nn.data_ptr(), B, L, F, loss.data_ptr(),
-                    None if scores is None else scores.data_ptr(), ws.data_ptr(), _C.stream_of(X))
-                if rc != 0:
-                    _C.check(rc)
+        loss, ws, scores = _linear_launch(kind, sigma, X, weight, bias, r, nn, dims, Fw, want_scores)
         ctx.save_for_backward(ws)
-        ctx.dims = (B, F)
-        ctx.Fw = Fw
-        ctx.w_shape = weight.shape
-        ctx.has_bias = bias is not None
         if want_scores:
             ctx.mark_non_differentiable(scores)
             return loss, scores
@@ -264,12 +317,7 @@ class _LinearLossFunction(torch.autograd.Function):
             X, r, nn = ctx.saved_tensors
             B, L, F = X.shape
             kind, sigma = ctx.lazy_args
-            ws = torch.empty(_linear_ws_bytes(B, L, F) // 4, dtype=torch.float32, device=X.device)
-            scratch = torch.empty(B, dtype=torch.float32, device=X.device)
-            with _C.device_ctx(X):
-                _C.check(_C.lib().ltr_linear_partials_f32(
-                    kind, float(sigma), X.data_ptr(), st.w_raw.data_ptr(), st.b_raw.data_ptr(), r.data_ptr(),
-                    _LABEL_CODE[r.dtype], nn.data_ptr(), B, L, F, scratch.data_ptr(), None, ws.data_ptr(), _C.stream_of(X)))
+            _, ws, _ = _linear_launch(kind, sigma, X, st.w_raw, st.b_raw, r, nn, (B, L, F), F)
         else:
             (ws,) = ctx.saved_tensors
         dW, db = _reduce_rows(ctx, ws, grad_loss)
@@ -298,17 +346,35 @@ def _reduce_rows(ctx, ws, grad_loss):
     return dW[:ctx.Fw].reshape(ctx.w_shape), (db if ctx.has_bias else None)
 
 
-# ---------------------------------------------------------------------------------------------
-# The listwise losses (ListNet, ListMLE): ltr_linear_listwise_partials_f32, include/ltr_listwise.h
-# ---------------------------------------------------------------------------------------------
+def _listwise_pieces(scores, relevance, n, kind):
+    """The stand-alone listwise loss on computed scores (autograd-connected to them)."""
+    from .loss import listwise as _lw
+    if kind.loss == _C.LISTWISE_LISTMLE:
+        return _lw._ListMLEFunction.apply(scores, relevance, n, kind.k)
+    return _lw._ListwiseSoftmaxFunction.apply(scores, relevance, n)
+
+
+def _loss_pieces(scores, relevance, n, kind, sigma):
+    """The stand-alone loss of `kind`, pairwise or listwise, on computed scores."""
+    if isinstance(kind, _ListwiseKind):
+        return _listwise_pieces(scores, relevance, n, kind)
+    return _pairwise_pieces(scores, relevance, n, kind, sigma)
+
+
+# ---- the route table: which kernels a batch reaches from each caller (DESIGN.md 24) ----
+_LIN_F32, _LIN_BF16_FUSED, _LIN_LISTWISE = "f32 fused", "bf16 fused", "listwise fused"
+_LIN_F32_PIECES, _LIN_BF16_PIECES, _LIN_SCORES = "f32 pieces", "bf16 pieces", "scores"
+_LIN_PIECES = (_LIN_F32_PIECES, _LIN_BF16_PIECES)
 _listwise_plan_cache = {}
+_pieces_cache = {}
+_bf16_plan_cache = {}
 
 
 def _listwise_fused(kind, X):
     """True where the one-launch listwise step takes the prepared feature batch X (ltr_linear_listwise_plan: lists of
-    at most max_list_len() documents, rows of whole float4 that fit the LDS next to the ranked row), else the three
-    kernels -- scorer, listwise loss, weight gradient -- compute the same.  (The plan depends on the device: its launch
-    shapes follow the CU count.)"""
+    at most max_list_len() documents, rows of whole float4 that fit the LDS next to the ranked row, at a 16-byte
+    aligned address), else the three kernels -- scorer, listwise loss, weight gradient -- compute the same.  (The plan
+    depends on the device: its launch shapes follow the CU count.)"""
     B, L, F = X.shape
     key = (kind.loss, X.device.index, B, L, F)
     v = _listwise_plan_cache.get(key)
@@ -320,102 +386,6 @@ def _listwise_fused(kind, X):
     return v and X.data_ptr() % 16 == 0
 
 
-def _listwise_launch(kind, X, W, bvec, r, nn, loss, scores, ws):
-    """One ltr_linear_listwise_partials_f32 call; ListMLE draws its tie seed here, one per forward pass."""
-    from . import _ties
-    B, L, F = X.shape
-    sd = _ties.draw_seed(L, X.device) if kind.loss == _C.LISTWISE_LISTMLE else None
-    with _C.device_ctx(X):
-        _C.check(_C.lib().ltr_linear_listwise_partials_f32(
-            kind.loss, int(kind.k or 0), _C.ptr(X), _C.ptr(W), _C.ptr(bvec), _C.ptr(r), _LABEL_CODE[r.dtype], _C.ptr(nn),
-            *_ties.tie_args(sd), B, L, F, _C.ptr(loss), _C.ptr(scores), _C.ptr(ws), _C.stream_of(X)))
-
-
-def _listwise_pieces(scores, relevance, n, kind):
-    """The stand-alone listwise loss on computed scores (autograd-connected to them)."""
-    from .loss import listwise as _lw
-    if kind.loss == _C.LISTWISE_LISTMLE:
-        return _lw._ListMLEFunction.apply(scores, relevance, n, kind.k)
-    return _lw._ListwiseSoftmaxFunction.apply(scores, relevance, n)
-
-
-class _LinearListwiseFunction(torch.autograd.Function):
-    """loss[b] of a listwise kind on Linear(F, 1)(X) as ONE launch; backward is the cross-query reduction of
-    _LinearLossFunction.  X: a prepared batch that _listwise_fused takes."""
-
-    @staticmethod
-    def forward(ctx, X, weight, bias, relevance, n, kind, want_scores):
-        B, L, F = X.shape                           # (F: the row width in memory, >= the logical feature count)
-        Fw = weight.numel()
-        if not F - 4 < Fw <= F:
-            raise ValueError("weight has %d elements, the feature rows %d" % (Fw, F))
-        dev = X.device
-        r, nn = _labels_and_n(relevance, n, B, L, dev)
-        # parameters that pytorchltr_amd.optim.SGD updates lazily: there is no lazy one-launch step for the listwise
-        # losses; this launch reads the weights, so no update may be pending
-        st = getattr(weight, "_ltr_lazy", None)
-        if st is not None:
-            st.settle()
-        W = _pad_weight(_flat_f32(weight, Fw), F)
-        bvec = None if bias is None else _flat_f32(bias, 1)
-        loss = torch.empty(B, dtype=torch.float32, device=dev)
-        ws = torch.empty(_linear_ws_bytes(B, L, F) // 4, dtype=torch.float32, device=dev)
-        scores = torch.empty((B, L), dtype=torch.float32, device=dev) if want_scores else None
-        _listwise_launch(kind, X, W, bvec, r, nn, loss, scores, ws)
-        ctx.save_for_backward(ws)
-        ctx.dims = (B, F)
-        ctx.Fw = Fw
-        ctx.w_shape = weight.shape
-        ctx.has_bias = bias is not None
-        if want_scores:
-            ctx.mark_non_differentiable(scores)
-            return loss, scores
-        return loss
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_loss, *unused):
-        (ws,) = ctx.saved_tensors
-        dW, db = _reduce_rows(ctx, ws, grad_loss)
-        return (None, dW, db, None, None, None, None)
-
-
-def _listwise_linear_loss(xs, weight, bias, relevance, n, kind, want_scores):
-    """``loss_fn(Linear(F, 1)(xs), relevance, n)`` of a listwise loss: the fused launch where it applies, else the
-    three kernels with autograd between them."""
-    if weight.numel() != xs.shape[-1]:
-        raise ValueError("weight has %d elements, features have %d" % (weight.numel(), xs.shape[-1]))
-    X = _prepare_features(xs)
-    if _listwise_fused(kind, X):
-        return _LinearListwiseFunction.apply(X, weight, bias, relevance, n, kind, want_scores)
-    scores = _LinearScoreFunction.apply(xs, weight, bias, n)
-    loss = _listwise_pieces(scores, relevance, n, kind)
-    return (loss, scores.detach().squeeze(-1)) if want_scores else loss
-
-
-_pieces_cache = {}
-
-
-def _prefer_pieces(kind, B, L, F):
-    """True where the three-kernel pieces (streaming scorer, split-query loss, streaming weight gradient) beat the
-    one-kernel fused path: a few long lists that neither the cluster nor the parts kernel takes (cached per shape)."""
-    key = (kind, B, L, F)
-    v = _pieces_cache.get(key)
-    if v is None:
-        v = False
-        if B > 0 and _C.lib().ltr_pairwise_loss_workspace_bytes(kind, B, L) != 0 and \
-                _C.lib().ltr_linear_fused_plan(kind, B, L, F) not in (_C.PLAN_CLUSTER, _C.PLAN_PARTS):
-            cus = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
-            heavy_pairs = kind not in (_C.HINGE, _C.DCG_HINGE)
-            v = (2 * B <= cus) or (heavy_pairs and B <= cus and L > 768)
-        _pieces_cache[key] = v
-    return v
-
-
-_LIN_BF16_FUSED, _LIN_BF16_PIECES, _LIN_F32 = "bf16 fused", "bf16 pieces", "f32"
-_bf16_plan_cache = {}
-
-
 def _linear_bf16_plan(kind, B, L, F8):
     """True where ltr_linear_partials_bf16 takes the shape (ltr_linear_bf16_plan; F8: the row width in memory)."""
     key = (int(kind), B, L, F8)
@@ -425,42 +395,109 @@ def _linear_bf16_plan(kind, B, L, F8):
     return v
 
 
-def _prefer_pieces_bf16(kind, B, L, cus):
-    """`_prefer_pieces` for a bf16 batch on a device of `cus` CUs: the same rule -- a few lists cannot fill the GPU with
-    one workgroup per query -- without the cluster / parts exemptions, which have no bf16 kernel."""
-    if B <= 0 or _C.lib().ltr_pairwise_loss_workspace_bytes(int(kind), B, L) == 0:
-        return False
-    heavy_pairs = int(kind) not in (_C.HINGE, _C.DCG_HINGE)
-    return (2 * B <= cus) or (heavy_pairs and B <= cus and L > 768)
+def _prefer_pieces(kind, B, L, F, cus=None, plan=None, exempt=True):
+    """True where the three-kernel pieces (streaming scorer, split-query loss, streaming weight gradient) beat the
+    one-kernel fused step: a few long lists -- one workgroup per query cannot fill the GPU -- whose stand-alone loss has a
+    split-query form.  `exempt`: not where the cluster or the parts kernel takes the shape (`plan`: the answer of
+    ltr_linear_fused_plan, asked when None); they are fp32 kernels, a bf16 batch passes False.  `cus`: the device's CU
+    count, read from the current device when None.  The library's own answers are cached per shape.
 
-
-def _linear_route(caller, dtype, dim, is_cuda, requires_grad, autocast, kind, B, L, F, cus=None):
-    """Which kernels run ``loss_fn(Linear(F, 1)(xs), ...)`` for a batch of these plain values: _LIN_BF16_FUSED
-    (ltr_linear_partials_bf16 and the existing reduce), _LIN_BF16_PIECES (the bf16 scorer, the stand-alone loss on the
-    fp32 scores, the bf16 weight-gradient kernel) or _LIN_F32 -- today's routes, which cast anything that is not fp32.
-
-    `caller`: "step" (linear_loss_step: fused wherever the plan takes the shape) or "module" (FusedLinearLoss, a loss
-    module on LazyScores: the pieces also where `_prefer_pieces_bf16` prefers them; `cus`: the device's CU count, read
-    from the current device when None).  `kind`: a pairwise kind (a LongKind with its flag); the listwise kinds have no
-    bf16 fused step and cast.  `F`: the logical feature count; the bf16 rows are zero-padded to a multiple of 8."""
-    if dtype is not torch.bfloat16 or dim != 3 or not is_cuda or requires_grad or autocast or isinstance(kind, _ListwiseKind):
-        return _LIN_F32
-    if _long_pair_shape(kind, L) or not _linear_bf16_plan(kind, max(B, 1), L, (F + 7) & ~7):
-        return _LIN_BF16_PIECES
-    if caller == "module":
+    Measured on MI355X, fused kernel -> pieces, us (B x L x F; hinge / logistic / LambdaNDCG2):
+      32 x 1000 x 220:  78/136/173 -> 46/52/77      128 x 1000 x 220: 84/145/181 -> 55/66/93
+      256 x 1000 x 220: 86/145/183 -> 87/113/147    384 x 1000 x 220: 90/149/186 -> 114/149/204
+      128 x 600 x 136:  41/64/90 -> 39/47/72        256 x 600 x 136:  44/66/93 -> 48/60/89
+    The cluster kernel (features once, a query over several workgroups) beats the pieces wherever it applies:
+    32 x 1000 x 220 hinge 32 vs 46 us, logistic 43 vs 52 -- and so does the parts kernel (round 4, module forward +
+    backward replayed, pieces vs fused: 64 x 512 x 700 LambdaNDCG2 91 vs 48 us, 100 x 1000 x 700 hinge 120 vs 78)."""
+    cached = exempt and cus is None and plan is None
+    if cached:
+        v = _pieces_cache.get((kind, B, L, F))
+        if v is not None:
+            return v
+    v = False
+    if B > 0 and _C.lib().ltr_pairwise_loss_workspace_bytes(int(kind), B, L) != 0:
         if cus is None:
             cus = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
-        if _prefer_pieces_bf16(kind, B, L, cus):
-            return _LIN_BF16_PIECES
-    return _LIN_BF16_FUSED
+        heavy_pairs = kind not in (_C.HINGE, _C.DCG_HINGE)
+        v = (2 * B <= cus) or (heavy_pairs and B <= cus and L > 768)
+        if v and exempt:
+            if plan is None:
+                plan = _C.lib().ltr_linear_fused_plan(int(kind), B, L, F)
+            v = plan not in (_C.PLAN_CLUSTER, _C.PLAN_PARTS)
+    if cached:
+        _pieces_cache[(kind, B, L, F)] = v
+    return v
+
+
+def _linear_route(caller, dtype, dim, is_cuda, requires_grad, autocast, kind, B, L, F, cus=None, Fq=None,
+                  computed=False, fused_plan=None, listwise_plan=False):
+    """Which kernels run ``loss_fn(Linear(F, 1)(xs), ...)`` for a batch of these plain values: _LIN_F32 / _LIN_BF16_FUSED
+    (ltr_linear_partials_f32 / _bf16 and the reduction), _LIN_LISTWISE (ltr_linear_listwise_partials_f32 and the
+    reduction), _LIN_F32_PIECES / _LIN_BF16_PIECES (the scorer, the stand-alone loss on the fp32 scores, the
+    weight-gradient kernel: the fp32 pair, which casts anything that is not fp32, or the bf16 pair) or _LIN_SCORES (the
+    scores are computed, or have been: LazyScores.fused_loss answers None, as it does for the pieces).
+
+    `caller`: "step" (linear_loss_step: fused wherever a fused kernel takes the shape), "module" (FusedLinearLoss) or
+    "lazy" (a loss module on LazyScores; `computed`: the scores exist already) -- the last two also take the pieces where
+    `_prefer_pieces` prefers them.  `kind`: a pairwise kind (a LongKind with its flag) or a `_ListwiseKind`.  `F`: the
+    logical feature count (the bf16 rows are zero-padded to a multiple of 8); `Fq`: the count the fp32 pieces rule is
+    asked with where the caller has another one (FusedLinearLoss: in_features; LazyScores: F rounded up to 4 for a batch
+    that is not contiguous).  What only the library on a device answers comes in as plain values: `cus` and
+    `fused_plan` (`_prefer_pieces` asks where None) and `listwise_plan` (the caller's `_listwise_fused`: the listwise
+    plan takes the rows as they lie in memory, 16-byte aligned).  A batch that is no (B, L, F) device tensor takes the
+    fused fp32 route, whose prepare step raises."""
+    if computed:
+        return _LIN_SCORES
+    bf16 = dtype is torch.bfloat16 and dim == 3 and is_cuda and not requires_grad and not autocast   # (`_bf16_batch`)
+    pieces = _LIN_BF16_PIECES if bf16 else _LIN_F32_PIECES
+    if isinstance(kind, _ListwiseKind):                  # (no bf16 fused step: a bf16 batch on the plan is cast)
+        return _LIN_LISTWISE if listwise_plan else pieces
+    if kind == _LISTWISE_SOFTMAX:                        # (the stand-alone softmax kernel as a plain kind: real scores)
+        return _LIN_SCORES
+    if dim != 3 or not is_cuda:
+        return _LIN_F32
+    if _long_pair_shape(kind, L):
+        return pieces                                    # past max_list_len() (long_lists=True) they are the only path
+    if bf16:
+        if not _linear_bf16_plan(kind, max(B, 1), L, (F + 7) & ~7):
+            return pieces
+        if caller != "step" and _prefer_pieces(kind, B, L, F, cus, exempt=False):
+            return pieces
+        return _LIN_BF16_FUSED
+    if caller != "step" and _prefer_pieces(kind, B, L, F if Fq is None else Fq, cus, fused_plan):
+        return pieces
+    return _LIN_F32
+
+
+def _linear_routed(caller, xs, kind, Fq=None, computed=False):
+    """``(route, batch)``: `_linear_route` on a batch -- its dtype, shape and flags, the autocast state, the library's
+    answers -- and the batch to hand on: `xs`, or for a listwise kind the prepared fp32 batch the plan was asked about."""
+    if computed:
+        return _LIN_SCORES, xs
+    X, plan = xs, False
+    if isinstance(kind, _ListwiseKind):
+        X = _prepare_features(xs)
+        plan = _listwise_fused(kind, X)
+    elif not torch.is_tensor(xs) or xs.dim() != 3:
+        return _LIN_F32, xs
+    B, L, F = X.shape
+    if caller == "lazy" and not xs.is_contiguous():
+        Fq = (F + 3) & ~3
+    return _linear_route(caller, xs.dtype, 3, xs.is_cuda, xs.requires_grad, torch.is_autocast_enabled(), kind, B, L, F,
+                         None, Fq, False, None, plan), X
 
 
 def _linear_route_of(caller, xs, kind):
-    """`_linear_route` on a batch: its dtype, shape and flags and the autocast state."""
-    if not torch.is_tensor(xs) or xs.dim() != 3:
-        return _LIN_F32
-    B, L, F = xs.shape
-    return _linear_route(caller, xs.dtype, 3, xs.is_cuda, xs.requires_grad, torch.is_autocast_enabled(), kind, B, L, F)
+    """The route of `_linear_routed` alone."""
+    return _linear_routed(caller, xs, kind)[0]
+
+
+def _init_linear_parameters(weight, bias, in_features):
+    """The initialisation of ``torch.nn.Linear(in_features, 1)``."""
+    torch.nn.init.kaiming_uniform_(weight, a=math.sqrt(5))
+    if bias is not None:
+        bound = 1.0 / math.sqrt(in_features)
+        torch.nn.init.uniform_(bias, -bound, bound)
 
 
 class FusedLinearLoss(torch.nn.Module):
@@ -478,36 +515,19 @@ class FusedLinearLoss(torch.nn.Module):
         self.reset_parameters()
 
     def reset_parameters(self):
-        # same init as torch.nn.Linear(in_features, 1)
-        torch.nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
-        if self.bias is not None:
-            bound = 1.0 / math.sqrt(self.in_features)
-            torch.nn.init.uniform_(self.bias, -bound, bound)
+        _init_linear_parameters(self.weight, self.bias, self.in_features)
 
     def forward(self, xs, relevance, n, return_scores=False):
-        if isinstance(self.kind, _ListwiseKind):
-            return _listwise_linear_loss(xs, self.weight, self.bias, relevance, n, self.kind, bool(return_scores))
-        route = _linear_route_of("module", xs, self.kind)
-        if route == _LIN_BF16_PIECES or route == _LIN_F32 and xs.dim() == 3 and xs.is_cuda and (
-                _long_pair_shape(self.kind, xs.shape[1]) or self._pieces_cached(xs.shape[0], xs.shape[1])):
-            # a few long lists: one workgroup per query cannot fill the GPU; the balanced pieces
-            # (streaming scorer, split-query loss, streaming weight gradient) are faster -- and past
-            # max_list_len() documents (long_lists=True) they are the only path
+        if isinstance(self.kind, _ListwiseKind) and self.weight.numel() != xs.shape[-1]:
+            raise ValueError("weight has %d elements, features have %d" % (self.weight.numel(), xs.shape[-1]))
+        route, X = _linear_routed("module", xs, self.kind, self.in_features)
+        if route in _LIN_PIECES:
+            # a few long lists (the balanced pieces are faster), a shape no fused kernel takes (there they are the only path)
             scores = _LinearScoreFunction.apply(xs, self.weight, self.bias, n)
-            loss = _pairwise_pieces(scores, relevance, n, self.kind, self.sigma)
+            loss = _loss_pieces(scores, relevance, n, self.kind, self.sigma)
             return (loss, scores.detach().squeeze(-1)) if return_scores else loss
-        return _LinearLossFunction.apply(xs, self.weight, self.bias, relevance, n, self.kind,
-                                         self.sigma, bool(return_scores))
-
-    def _pieces_cached(self, B, L):
-        # measured on MI355X, fused kernel -> pieces, us (B x L x F; hinge / logistic / LambdaNDCG2):
-        #   32 x 1000 x 220:  78/136/173 -> 46/52/77      128 x 1000 x 220: 84/145/181 -> 55/66/93
-        #   256 x 1000 x 220: 86/145/183 -> 87/113/147    384 x 1000 x 220: 90/149/186 -> 114/149/204
-        #   128 x 600 x 136:  41/64/90 -> 39/47/72        256 x 600 x 136:  44/66/93 -> 48/60/89
-        # the cluster kernel (features once, a query over several workgroups) beats the pieces wherever it applies:
-        # 32 x 1000 x 220 hinge 32 vs 46 us, logistic 43 vs 52 -- and so does the parts kernel (round 4, module forward
-        # + backward replayed, pieces vs fused: 64 x 512 x 700 LambdaNDCG2 91 vs 48 us, 100 x 1000 x 700 hinge 120 vs 78)
-        return _prefer_pieces(self.kind, B, L, self.in_features)
+        return _LinearLossFunction.apply(X, self.weight, self.bias, relevance, n, self.kind, self.sigma,
+                                         bool(return_scores))
 
     def _prefer_pieces(self, B, L):
         return _prefer_pieces(self.kind, B, L, self.in_features)
@@ -521,40 +541,19 @@ def linear_loss_step(xs, weight, bias, relevance, n, loss="hinge", grad_out=None
     ``.mean()`` of the reference's training loop (1/B each).  Two launches: the fused
     scorer+loss kernel and the cross-query reduction (which also totals the loss)."""
     kind, sigma = _resolve_loss(loss)
-    route = _linear_route_of("step", xs, kind)
-    if route == _LIN_BF16_PIECES:                   # a bf16 batch off the plan of the bf16 fused step
+    route, X = _linear_routed("step", xs, kind)
+    if route in _LIN_PIECES:
         return _step_pieces(xs, weight, bias, relevance, n, kind, sigma, grad_out, return_scores, return_loss_sum)
-    bf16 = route == _LIN_BF16_FUSED
-    X = _prepare_features(xs, bf16=bf16)
-    listwise = isinstance(kind, _ListwiseKind)
-    if listwise and not _listwise_fused(kind, X):
-        return _step_pieces(xs, weight, bias, relevance, n, kind, sigma, grad_out, return_scores, return_loss_sum)
-    if not listwise and _long_pair_shape(kind, X.shape[1]):
-        return _step_pieces(xs, weight, bias, relevance, n, kind, sigma, grad_out, return_scores, return_loss_sum)
-    B, L, F = X.shape                               # (F: the row width in memory -- a padded view's F4)
-    Fw = xs.shape[2]
-    W = _pad_weight(_flat_f32(weight, Fw), F)
-    bvec = None if bias is None else _flat_f32(bias, 1)
-    r, nn = _labels_and_n(relevance, n, B, L, X.device)
-    lossv = torch.empty(B, dtype=torch.float32, device=X.device)
+    X, r, nn, dims, Fw = _linear_prepare(X, weight, relevance, n, kind, raw=xs)
+    B, L, F = dims                                  # (F: the row width in memory -- a padded view's F4)
+    lossv, ws, scores = _linear_launch(kind, sigma, X, weight, bias, r, nn, dims, Fw, return_scores, empty=True)
     dW = torch.empty(F, dtype=torch.float32, device=X.device)
     db = torch.empty(1, dtype=torch.float32, device=X.device)
     lsum = torch.zeros(1, dtype=torch.float32, device=X.device) if return_loss_sum else None
-    scores = torch.empty(B, L, dtype=torch.float32, device=X.device) if return_scores else None
-    ws_bytes = _C.lib().ltr_linear_workspace_bytes(B, L, F)
-    ws = torch.empty(max(ws_bytes, 4) // 4, dtype=torch.float32, device=X.device)
     go = None if grad_out is None else grad_out.reshape(B).float().contiguous()
     with _C.device_ctx(X):
-        st = _C.stream_of(X)
-        if listwise:
-            _listwise_launch(kind, X, W, bvec, r, nn, lossv, scores, ws)
-        else:
-            entry = _C.lib().ltr_linear_partials_bf16 if bf16 else _C.lib().ltr_linear_partials_f32
-            _C.check(entry(
-                kind, float(sigma), _C.ptr(X), _C.ptr(W), _C.ptr(bvec), _C.ptr(r), _C.label_dtype(r),
-                _C.ptr(nn), B, L, F, _C.ptr(lossv), _C.ptr(scores), _C.ptr(ws), st))
         _C.check(_C.lib().ltr_linear_reduce_loss_f32(
-            _C.ptr(ws), _C.ptr(go), _C.ptr(lossv), B, F, _C.ptr(dW), _C.ptr(db), _C.ptr(lsum), st))
+            _C.ptr(ws), _C.ptr(go), _C.ptr(lossv), B, F, _C.ptr(dW), _C.ptr(db), _C.ptr(lsum), _C.stream_of(X)))
     out = (lossv, dW[:Fw], db)
     if return_scores:
         out = out + (scores,)
@@ -565,16 +564,15 @@ def linear_loss_step(xs, weight, bias, relevance, n, loss="hinge", grad_out=None
 
 def _step_pieces(xs, weight, bias, relevance, n, kind, sigma, grad_out, return_scores, return_loss_sum):
     """linear_loss_step on a shape no fused launch takes (a listwise loss off its plan; a pairwise loss with
-    long_lists=True past max_list_len() documents): the scorer, the stand-alone loss and the weight-gradient kernel,
-    chained by autograd on detached copies of the parameters."""
+    long_lists=True past max_list_len() documents; a bf16 batch off the plan of its tile): the scorer, the stand-alone
+    loss and the weight-gradient kernel, chained by autograd on detached copies of the parameters."""
     B = xs.shape[0]
     with torch.enable_grad():
         w = weight.detach().float().reshape(1, -1).requires_grad_(True)
         b = (torch.zeros(1, dtype=torch.float32, device=xs.device) if bias is None
              else bias.detach().float().reshape(1)).requires_grad_(True)
         scores = _LinearScoreFunction.apply(xs, w, b, n)
-        lossv = (_listwise_pieces(scores, relevance, n, kind) if isinstance(kind, _ListwiseKind)
-                 else _pairwise_pieces(scores, relevance, n, kind, sigma))
+        lossv = _loss_pieces(scores, relevance, n, kind, sigma)
         go = (torch.full((B,), 1.0 / max(B, 1), dtype=torch.float32, device=xs.device) if grad_out is None
               else grad_out.reshape(B).float())
         (lossv * go).sum().backward()
@@ -636,8 +634,7 @@ class LazySGD:
             dev = X.device
             self.loss = torch.empty(B, dtype=torch.float32, device=dev)
             self.bucket = torch.zeros(F + 2, dtype=torch.float32, device=dev)
-            nb = _C.lib().ltr_linear_workspace_bytes(B, L, F)
-            self.ws = torch.empty(max(nb, 4) // 4, dtype=torch.float32, device=dev)
+            self.ws = torch.empty(_linear_ws_bytes(B, L, F) // 4, dtype=torch.float32, device=dev)
         elif tuple(X.shape) != self.shape:
             raise ValueError("every batch must have the shape of the first one %r (flush() and make a new LazySGD otherwise)" % (self.shape,))
         r, nn = _labels_and_n(relevance, n, B, L, X.device)
@@ -675,14 +672,14 @@ class _LinearScoreFunction(torch.autograd.Function):
         X = _prepare_features(xs, bf16=True)        # (a bf16 batch stays bf16: ltr_linear_scores_bf16 / ltr_linear_grad_bf16)
         B, L, F = X.shape                           # (F: the row width in memory -- a padded view's F4)
         Fw = xs.shape[2]
-        W = _pad_weight(weight.detach().reshape(Fw).float().contiguous(), F)
+        W = _pad_weight(_flat_f32(weight, Fw), F)
         ctx.Fw = Fw
-        bvec = None if bias is None else bias.detach().reshape(1).float().contiguous()
+        bvec = None if bias is None else _flat_f32(bias, 1)
         nn = None if n is None else prepare_n(n, B)
         scores = torch.empty(B, L, dtype=torch.float32, device=X.device)
         if B > 0:
             with _C.device_ctx(X):
-                entry = _C.lib().ltr_linear_scores_bf16 if X.dtype is torch.bfloat16 else _C.lib().ltr_linear_scores_f32
+                entry = getattr(_C.lib(), _linear_family_of(X).scores)
                 _C.check(entry(_C.ptr(X), _C.ptr(W), _C.ptr(bvec), _C.ptr(nn), B, L, F, _C.ptr(scores), _C.stream_of(X)))
         # (the layer's input needs a gradient only when it is not the feature batch itself -- a hidden
         # layer's output: the weight is kept for grad_xs = grad_scores (x) weight in that case)
@@ -703,11 +700,11 @@ class _LinearScoreFunction(torch.autograd.Function):
         g = grad_scores.reshape(B, L).float().contiguous()
         lib = _C.lib()
         out = torch.empty(F + 1, dtype=torch.float32, device=X.device)
-        bf16 = X.dtype is torch.bfloat16
-        ws_bytes = (lib.ltr_linear_grad_workspace_bytes_bf16 if bf16 else lib.ltr_linear_grad_workspace_bytes)(B, L, F)
+        family = _linear_family_of(X)
+        ws_bytes = getattr(lib, family.grad_ws)(B, L, F)
         ws = torch.empty(max(ws_bytes, 4) // 4, dtype=torch.float32, device=X.device)
         with _C.device_ctx(X):
-            _C.check((lib.ltr_linear_grad_bf16 if bf16 else lib.ltr_linear_grad_f32)(
+            _C.check(getattr(lib, family.grad)(
                 _C.ptr(X), _C.ptr(g), _C.ptr(nn) if ctx.has_n else None,
                 B, L, F, _C.ptr(out), _C.ptr(ws), ws_bytes, _C.stream_of(X)))
         gx = None
@@ -715,7 +712,7 @@ class _LinearScoreFunction(torch.autograd.Function):
             gm = g
             if ctx.has_n:                                       # padded documents were not scored
                 gm = g * (torch.arange(L, device=g.device)[None, :] < nn[:, None])
-            gx = (gm.unsqueeze(-1) * Wsaved[:ctx.Fw].reshape(1, 1, ctx.Fw)).reshape(ctx.xs_shape)
+            gx = (gm.unsqueeze(-1) * Wsaved.reshape(-1)[:ctx.Fw].reshape(1, 1, ctx.Fw)).reshape(ctx.xs_shape)
         return (gx, out[:ctx.Fw].reshape(ctx.w_shape), out[F:] if ctx.has_bias else None, None)
 
 
@@ -754,26 +751,11 @@ class LazyScores(torch.Tensor):
     def fused_loss(self, relevance, n, kind, sigma):
         """loss[b] of the loss `kind` (a pairwise kind or a _ListwiseKind) on these scores, or None when the scores have
         to be computed anyway."""
-        if self._real is not None:
-            return None
-        xs = self._xs
-        if isinstance(kind, _ListwiseKind):
-            X = _prepare_features(xs)
-            if not _listwise_fused(kind, X):
-                return None
-            self._check_versions()
-            return _LinearListwiseFunction.apply(X, self._weight, self._bias, relevance, n, kind, False)
-        if kind == _LISTWISE_SOFTMAX:
-            return None
-        B, L, F = xs.shape
-        route = _linear_route_of("module", xs, kind)
-        if route == _LIN_BF16_PIECES:
-            return None
-        if route == _LIN_F32 and (_long_pair_shape(kind, L)
-                                  or _prefer_pieces(kind, B, L, (F + 3) & ~3 if not xs.is_contiguous() else F)):
+        route, X = _linear_routed("lazy", self._xs, kind, computed=self._real is not None)
+        if route is _LIN_SCORES or route in _LIN_PIECES:
             return None
         self._check_versions()
-        return _LinearLossFunction.apply(xs, self._weight, self._bias, relevance, n, kind, sigma, False)
+        return _LinearLossFunction.apply(X, self._weight, self._bias, relevance, n, kind, sigma, False)
 
     @classmethod
     def __torch_function__(cls, func, types, args=(), kwargs=None):
@@ -785,27 +767,23 @@ class LazyScores(torch.Tensor):
             with torch._C.DisableTorchFunctionSubclass():
                 return func(*args, **kwargs)
 
-        def real(a):
-            if isinstance(a, LazyScores):
-                return a.materialize()
-            if isinstance(a, (list, tuple)):
-                return type(a)(real(v) for v in a)
-            return a
         with torch._C.DisableTorchFunctionSubclass():
-            return func(*[real(a) for a in args], **{k: real(v) for k, v in kwargs.items()})
-
+            return func(*[_real_scores(a) for a in args], **{k: _real_scores(v) for k, v in kwargs.items()})
 
     @classmethod
     def __torch_dispatch__(cls, func, types, args=(), kwargs=None):
         # (only reached by calls that bypass the Python API -- every torch function and Tensor method goes through
         # __torch_function__ above, where autograd still sees the real scores)
-        def real(a):
-            if isinstance(a, LazyScores):
-                return a.materialize()
-            if isinstance(a, (list, tuple)):
-                return type(a)(real(v) for v in a)
-            return a
-        return func(*[real(a) for a in args], **{k: real(v) for k, v in (kwargs or {}).items()})
+        return func(*[_real_scores(a) for a in args], **{k: _real_scores(v) for k, v in (kwargs or {}).items()})
+
+
+def _real_scores(a):
+    """`a` with every LazyScores in it (lists and tuples are searched) replaced by its real scores."""
+    if isinstance(a, LazyScores):
+        return a.materialize()
+    if isinstance(a, (list, tuple)):
+        return type(a)(_real_scores(v) for v in a)
+    return a
 
 
 _LISTWISE_SOFTMAX = 100                  # (_autograd.LISTWISE_SOFTMAX as a plain kind: the stand-alone kernel on real scores)
@@ -841,10 +819,8 @@ class LinearScorer(torch.nn.Module):
         self.lazy = lazy
         self.weight = torch.nn.Parameter(torch.empty(1, in_features))
         self.bias = torch.nn.Parameter(torch.empty(1)) if bias else None
-        torch.nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
+        _init_linear_parameters(self.weight, self.bias, in_features)
         if self.bias is not None:
-            bound = 1.0 / math.sqrt(in_features)
-            torch.nn.init.uniform_(self.bias, -bound, bound)
             self.weight._ltr_scorer_bias = self.bias          # (pytorchltr_amd.optim.SGD pairs them up by this)
 
     def forward(self, xs, n=None):

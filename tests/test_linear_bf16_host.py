@@ -175,7 +175,7 @@ def test_route_on_plain_values(lib):
     bf, f32 = torch.bfloat16, torch.float32
     route = fused._linear_route
     FUSED, PIECES, TODAY = fused._LIN_BF16_FUSED, fused._LIN_BF16_PIECES, fused._LIN_F32
-    assert (FUSED, PIECES, TODAY) == ("bf16 fused", "bf16 pieces", "f32")
+    assert (FUSED, PIECES, TODAY) == ("bf16 fused", "bf16 pieces", "f32 fused")
     for kind in KINDS:
         for caller in ("step", "module"):
             # on the plan (F = 220 counts as its padded 224)
@@ -192,8 +192,10 @@ def test_route_on_plain_values(lib):
                          (bf, 3, False, False, False), (bf, 2, True, False, False), (torch.float16, 3, True, False, False),
                          (torch.float64, 3, True, False, False)):
                 assert route(caller, *args, kind, 1024, 128, 136, cus=256) == TODAY, args
-    # the listwise kinds have no bf16 fused step: they cast
-    assert route("step", bf, 3, True, False, False, fused._ListwiseKind(_C.LISTWISE_LISTNET), 4, 10, 8, cus=256) == TODAY
+    # the listwise kinds have no bf16 fused step: on the plan of the fp32 one they cast, off it the bf16 scorer runs
+    listnet = fused._ListwiseKind(_C.LISTWISE_LISTNET)
+    assert route("step", bf, 3, True, False, False, listnet, 4, 10, 8, cus=256, listwise_plan=True) == fused._LIN_LISTWISE
+    assert route("step", bf, 3, True, False, False, listnet, 4, 10, 8, cus=256, listwise_plan=False) == PIECES
 
 
 def test_prefer_pieces_bf16_is_the_fp32_rule_without_the_exemptions(lib):
@@ -201,9 +203,13 @@ def test_prefer_pieces_bf16_is_the_fp32_rule_without_the_exemptions(lib):
     # where the stand-alone loss has no split-query form the fused step stays, whatever the batch size
     for kind in KINDS:
         small = lib.ltr_pairwise_loss_workspace_bytes(kind, 4, 128) != 0
-        assert fused._prefer_pieces_bf16(kind, 4, 128, 256) == small
-        assert not fused._prefer_pieces_bf16(kind, 0, 128, 256)
-        assert not fused._prefer_pieces_bf16(kind, 1024, 128, 256)
+        assert fused._prefer_pieces(kind, 4, 128, 8, cus=256, exempt=False) == small
+        assert not fused._prefer_pieces(kind, 0, 128, 8, cus=256, exempt=False)
+        assert not fused._prefer_pieces(kind, 1024, 128, 8, cus=256, exempt=False)
+        # ... and the fp32 rule is the same one behind the exemptions: the cluster / parts kernels keep the fused step
+        assert fused._prefer_pieces(kind, 4, 128, 8, cus=256, plan=_C.PLAN_GENERAL) == small
+        assert not fused._prefer_pieces(kind, 4, 128, 8, cus=256, plan=_C.PLAN_CLUSTER)
+        assert not fused._prefer_pieces(kind, 4, 128, 8, cus=256, plan=_C.PLAN_PARTS)
 
 
 def test_a_bf16_batch_is_judged_without_a_device():
