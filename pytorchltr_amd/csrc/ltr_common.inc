@@ -1396,4 +1396,44 @@ template <typename V> __device__ __forceinline__ V vzero();
 template <> __device__ __forceinline__ float4 vzero<float4>() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 template <> __device__ __forceinline__ float vzero<float>() { return 0.f; }
 
+// the same on a 16-byte vector of EIGHT bf16 (the Linear scorer on bf16 feature batches: the fused tile of
+// ltr_linear_bf16.inc and the streaming layer of ltr_scorer.inc).  A bf16 is the upper half of an fp32, so widening is a
+// shift or a mask and exact; the weights and every product and sum stay fp32.
+struct LbW8 { float4 a, b; };              // the weights (or a dW accumulator) of one column vector: columns 0-3, 4-7
+
+__device__ __forceinline__ float lb_lo(unsigned v) { return __uint_as_float(v << 16); }
+__device__ __forceinline__ float lb_hi(unsigned v) { return __uint_as_float(v & 0xffff0000u); }
+
+__device__ __forceinline__ float lb_dot(ltr_u32x4 v, const LbW8 &w)
+{
+    float s0 = lb_lo(v.x) * w.a.x, s1 = lb_hi(v.x) * w.a.y;
+    s0 = fmaf(lb_lo(v.y), w.a.z, s0); s1 = fmaf(lb_hi(v.y), w.a.w, s1);
+    s0 = fmaf(lb_lo(v.z), w.b.x, s0); s1 = fmaf(lb_hi(v.z), w.b.y, s1);
+    s0 = fmaf(lb_lo(v.w), w.b.z, s0); s1 = fmaf(lb_hi(v.w), w.b.w, s1);
+    return s0 + s1;
+}
+
+__device__ __forceinline__ void lb_fma(LbW8 &acc, float g, ltr_u32x4 v)
+{
+    acc.a.x = fmaf(g, lb_lo(v.x), acc.a.x); acc.a.y = fmaf(g, lb_hi(v.x), acc.a.y);
+    acc.a.z = fmaf(g, lb_lo(v.y), acc.a.z); acc.a.w = fmaf(g, lb_hi(v.y), acc.a.w);
+    acc.b.x = fmaf(g, lb_lo(v.z), acc.b.x); acc.b.y = fmaf(g, lb_hi(v.z), acc.b.y);
+    acc.b.z = fmaf(g, lb_lo(v.w), acc.b.z); acc.b.w = fmaf(g, lb_hi(v.w), acc.b.w);
+}
+
+__device__ __forceinline__ LbW8 lb_zero()
+{
+    LbW8 z;
+    z.a = make_float4(0.f, 0.f, 0.f, 0.f);
+    z.b = z.a;
+    return z;
+}
+
+// what every bf16 Linear entry point takes: a row starts on 16 bytes, at most 128 column vectors, rows indexed by an int
+constexpr int kLbMaxF = 1024;
+inline bool lb_shape_bad(int B, int L, int F)
+{
+    return B < 0 || L <= 0 || F <= 0 || F % 8 != 0 || F > kLbMaxF || (long long)B * L > 0x7fffffffLL;
+}
+
 }  // namespace

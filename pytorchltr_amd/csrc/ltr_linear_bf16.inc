@@ -1,16 +1,14 @@
-// ltr_linear_bf16.inc -- the Linear(F, 1) scorer on a bf16 feature batch (include/ltr_linear_bf16.h): the streaming
-// score and weight-gradient kernels of ltr_scorer.inc and a register-tile fused step in the mapping of
-// linear_regtile2_body (ltr_linear.inc), all on 16-byte vectors of EIGHT bf16.  Included by ltr_linear_bf16.hip behind
-// ltr_common.inc; the fp32 kernels are untouched.  DESIGN.md section 23.
+// ltr_linear_bf16.inc -- the fused step of the Linear(F, 1) scorer on a bf16 feature batch (include/ltr_linear_bf16.h):
+// a register tile in the mapping of linear_regtile2_body (ltr_linear.inc) on 16-byte vectors of EIGHT bf16, its plan
+// (ltr_linear_bf16_plan) and its entry point (ltr_linear_partials_bf16).  Included by ltr_linear_bf16.hip behind
+// ltr_common.inc, which has the vector helpers (LbW8, lb_dot, lb_fma) and the shape predicate (lb_shape_bad) that this
+// file shares with the streaming score and weight-gradient kernels: those are ltr_scorer.inc, in ltr_mlp.hip.
+// DESIGN.md section 23.
 //
 // Numerics: a bf16 is the upper half of an fp32, so widening is a shift (v << 16) or a mask (v & 0xffff0000) and exact;
 // W stays fp32 in registers, every product and sum is an fp32 VALU operation.  Nothing is rounded anywhere: the result
 // is the fp32 network on the values the batch holds, up to summation order.
 //
-//   scores  one wave per row, kLbUnr rows in flight, W in registers (8 floats per column vector); unconditional loads
-//           from clamped addresses, as linear_scores_kernel.
-//   grad    a workgroup takes kLbGradRows rows of one query: thread (column vector, row group) accumulates 8 floats, the
-//           row groups fold in LDS, one partial vector [dW | db] per workgroup; mlp_reduce_kernel adds them (fixed order).
 //   tile    one workgroup per query: thread t owns the vectors t, t + R C, ... of the query's n[b] F contiguous bf16
 //           (C = F / 8 column vectors per row, R = 512 / C rows per sweep), requested in ONE burst of NI buffer loads
 //           whose descriptor ends behind the last real row (rows past it read as 0, in hardware); four VGPRs per vector
@@ -22,184 +20,12 @@
 
 #include "ltr_linear_bf16.h"
 
-// (ltr_scorer.inc, in the translation unit that has mlp_reduce_kernel: out[i] = sum over the nPart partial vectors, fixed order)
-extern "C" __attribute__((visibility("hidden"))) int ltr_internal_reduce_partials(const float *part, int nPart, int P, int pitch,
-                                                                                  float *out, void *stream);
-
 namespace {
 
-constexpr int kLbMaxF = 1024;
-constexpr int kLbUnr = 4;                  // rows in flight per wave (scores) / per thread (gradient)
-constexpr int kLbStreamThreads = 256;
-constexpr int kLbScoreRows = 128;          // documents per job (query, chunk), scores kernel
-constexpr int kLbGradRows = 256;           // same, gradient kernel
 constexpr int kLbThreads = 512;            // the tile's workgroup
 constexpr int kLbMaxListLen = 256;         // the symmetric pair pass with one label per thread
 constexpr int kLbMaxSweeps = 16;
 
-struct LbW8 { float4 a, b; };              // the weights (or a dW accumulator) of one column vector: columns 0-3, 4-7
-
-__device__ __forceinline__ float lb_lo(unsigned v) { return __uint_as_float(v << 16); }
-__device__ __forceinline__ float lb_hi(unsigned v) { return __uint_as_float(v & 0xffff0000u); }
-
-__device__ __forceinline__ float lb_dot(ltr_u32x4 v, const LbW8 &w)
-{
-    float s0 = lb_lo(v.x) * w.a.x, s1 = lb_hi(v.x) * w.a.y;
-    s0 = fmaf(lb_lo(v.y), w.a.z, s0); s1 = fmaf(lb_hi(v.y), w.a.w, s1);
-    s0 = fmaf(lb_lo(v.z), w.b.x, s0); s1 = fmaf(lb_hi(v.z), w.b.y, s1);
-    s0 = fmaf(lb_lo(v.w), w.b.z, s0); s1 = fmaf(lb_hi(v.w), w.b.w, s1);
-    return s0 + s1;
-}
-
-__device__ __forceinline__ void lb_fma(LbW8 &acc, float g, ltr_u32x4 v)
-{
-    acc.a.x = fmaf(g, lb_lo(v.x), acc.a.x); acc.a.y = fmaf(g, lb_hi(v.x), acc.a.y);
-    acc.a.z = fmaf(g, lb_lo(v.y), acc.a.z); acc.a.w = fmaf(g, lb_hi(v.y), acc.a.w);
-    acc.b.x = fmaf(g, lb_lo(v.z), acc.b.x); acc.b.y = fmaf(g, lb_hi(v.z), acc.b.y);
-    acc.b.z = fmaf(g, lb_lo(v.w), acc.b.z); acc.b.w = fmaf(g, lb_hi(v.w), acc.b.w);
-}
-
-__device__ __forceinline__ LbW8 lb_zero()
-{
-    LbW8 z;
-    z.a = make_float4(0.f, 0.f, 0.f, 0.f);
-    z.b = z.a;
-    return z;
-}
-
-struct LbStreamParams {
-    const uint16_t *X;
-    const float *W, *bias, *g;
-    const int64_t *n;
-    float *out;                        // scores (scores kernel) or partials (grad kernel)
-    int B, L, F;
-    int chunks;                        // row chunks per query (jobs = B * chunks)
-};
-
-// A job is (query b, chunk of kLbScoreRows documents); the documents past n[b] are never touched (their scores are
-// written as 0).  NV >= ceil(C / 64) column vectors per lane.
-template <int NV>
-__global__ void __launch_bounds__(kLbStreamThreads)
-linear_bf16_scores_kernel(LbStreamParams p)
-{
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    constexpr int NW = kLbStreamThreads / 64;
-    const int C = p.F >> 3;
-    const int b = blockIdx.x / p.chunks;
-    const int l0 = (blockIdx.x - b * p.chunks) * kLbScoreRows;
-    const int l1 = min(p.L, l0 + kLbScoreRows);
-    const int nb = p.n ? clamp_n(p.n[b], p.L) : p.L;
-    const int lv = min(l1, nb);                                 // documents [l0, lv) are real
-    const size_t row0 = (size_t)b * p.L;
-    for (int l = max(l0, lv) + threadIdx.x; l < l1; l += kLbStreamThreads) p.out[row0 + l] = 0.f;
-    if (l0 >= lv) return;
-    LbW8 w[NV];
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = lane + 64 * i;
-        const int cc = min(c, C - 1);
-        w[i].a = reinterpret_cast<const float4 *>(p.W)[2 * cc];
-        w[i].b = reinterpret_cast<const float4 *>(p.W)[2 * cc + 1];
-        if (c >= C) w[i] = lb_zero();                           // columns past C: the clamped vector meets zero weights
-    }
-    const float bias = p.bias ? p.bias[0] : 0.f;
-    const uint16_t *Xq = p.X + row0 * (size_t)p.F;
-    constexpr int UNR = kLbUnr;
-    for (int la = l0 + wave; la < lv; la += NW * UNR) {
-        float acc[UNR];
-#pragma unroll
-        for (int u = 0; u < UNR; ++u) acc[u] = 0.f;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            // unconditional loads from clamped addresses (a per-lane condition around a load becomes a branch and a
-            // full wait, and serialises the rows in flight): rows past lv re-read row lv - 1 and their result is
-            // dropped, columns past C re-read column C - 1 against zero weights
-            const int cc = min(lane + 64 * i, C - 1);
-            ltr_u32x4 x[UNR];
-#pragma unroll
-            for (int u = 0; u < UNR; ++u) {
-                const int l = min(la + u * NW, lv - 1);
-                x[u] = reinterpret_cast<const ltr_u32x4 *>(Xq + (size_t)l * p.F)[cc];
-            }
-#pragma unroll
-            for (int u = 0; u < UNR; ++u) acc[u] += lb_dot(x[u], w[i]);
-        }
-#pragma unroll
-        for (int u = 0; u < UNR; ++u) {
-            const int l = la + u * NW;
-            const float s = wave_sum(acc[u]);
-            if (lane == 0 && l < lv) p.out[row0 + l] = s + bias;
-        }
-    }
-}
-
-// One partial vector [dW | db] per job (query, chunk of kLbGradRows rows).  C <= 128 column vectors: one tile of
-// C x RG threads, RG = 256 / C row groups.
-__global__ void __launch_bounds__(kLbStreamThreads)
-linear_bf16_grad_kernel(LbStreamParams p)
-{
-    constexpr int T = kLbStreamThreads;
-    __shared__ float4 dred[2 * T];                             // [half][row group][column vector]
-    __shared__ float gred[T / 64];
-    const int tid = threadIdx.x;
-    const int C = p.F >> 3;
-    const int b = blockIdx.x / p.chunks;
-    const int l0 = (blockIdx.x - b * p.chunks) * kLbGradRows;
-    const int nb = p.n ? clamp_n(p.n[b], p.L) : p.L;
-    const int lv = min(min(p.L, l0 + kLbGradRows), nb);        // documents [l0, lv) are real
-    const size_t row0 = (size_t)b * p.L;
-    const int pitch = (p.F + 1 + 3) & ~3;                      // partial rows start 16-byte aligned
-    float *part = p.out + (size_t)blockIdx.x * pitch;
-    if (l0 >= lv) {                                            // nothing real here: a zero partial
-        for (int i = tid; i <= p.F; i += T) part[i] = 0.f;
-        return;
-    }
-    const uint16_t *Xq = p.X + row0 * (size_t)p.F;
-    const float *gq = p.g + row0;
-    const int RG = T / C;
-    const int rg = tid / C, cl = tid - rg * C;
-    float gb = 0.f;
-    for (int l = l0 + tid; l < lv; l += T) gb += gq[l];
-    gb = wave_sum(gb);
-    if ((tid & 63) == 0) gred[tid >> 6] = gb;
-    LbW8 acc = lb_zero();
-    if (rg < RG) {
-        constexpr int UNR = kLbUnr;
-        for (int la = l0 + rg; la < lv; la += RG * UNR) {
-            ltr_u32x4 x[UNR];
-            float g[UNR];
-#pragma unroll
-            for (int u = 0; u < UNR; ++u) {                    // rows past lv: row lv - 1 again, with g = 0
-                const int l = la + u * RG;
-                const int lc = min(l, lv - 1);
-                const float gv = gq[lc];
-                g[u] = (l < lv) ? gv : 0.f;
-                x[u] = reinterpret_cast<const ltr_u32x4 *>(Xq + (size_t)lc * p.F)[cl];
-            }
-#pragma unroll
-            for (int u = 0; u < UNR; ++u) lb_fma(acc, g[u], x[u]);
-        }
-        dred[rg * C + cl] = acc.a;
-        dred[T + rg * C + cl] = acc.b;
-    }
-    __syncthreads();
-    if (tid < 2 * C) {                                         // float4 number tid of the row: column vector tid / 2, its half tid % 2
-        const float4 *src = dred + (tid & 1) * T + (tid >> 1);
-        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int q = 0; q < RG; ++q) vadd(s, src[q * C]);
-        reinterpret_cast<float4 *>(part)[tid] = s;
-    }
-    if (tid == 0) {
-        float s = 0.f;
-        for (int q = 0; q < T / 64; ++q) s += gred[q];
-        part[p.F] = s;
-    }
-}
-
-// ---------------------------------------------------------------------------------
-// The fused step
-// ---------------------------------------------------------------------------------
 struct LbTileParams {
     const uint16_t *X;
     const float *W, *bias;
@@ -407,63 +233,9 @@ int lb_launch_tile(const LbTileParams &p, int ni, size_t lds, hipStream_t stream
     }
 }
 
-inline bool lb_stream_shape_bad(int B, int L, int F)
-{
-    return B < 0 || L <= 0 || F <= 0 || F % 8 != 0 || F > kLbMaxF || (long long)B * L > 0x7fffffffLL;
-}
-
 }  // namespace
 
 extern "C" {
-
-int ltr_linear_scores_bf16(const uint16_t *X, const float *W, const float *bias, const int64_t *n, int B, int L,
-                           int F, float *scores, void *stream)
-{
-    LTR_CLEAR_STALE_ERROR();
-    if (lb_stream_shape_bad(B, L, F)) return LTR_ERR_SHAPE;
-    if (B == 0) return LTR_OK;
-    if (!X || !W || !scores) return LTR_ERR_NULL;
-    LbStreamParams p;
-    p.X = X; p.W = W; p.bias = bias; p.g = nullptr; p.n = n; p.out = scores;
-    p.B = B; p.L = L; p.F = F; p.chunks = (L + kLbScoreRows - 1) / kLbScoreRows;
-    const dim3 grid((unsigned)((long long)B * p.chunks)), block(kLbStreamThreads);
-    hipStream_t st = (hipStream_t)stream;
-    // Occupancy the streaming kernels are sized for (waves per SIMD): one column vector per lane (F <= 512) and the
-    // gradient kernel eight, <= 64 VGPRs; two column vectors per lane (F <= 1024) six, <= 80 VGPRs.
-    // tests/test_linear_bf16_host.py holds the compiler to them.
-    if (F / 8 <= 64) hipLaunchKernelGGL((linear_bf16_scores_kernel<1>), grid, block, 0, st, p);
-    else hipLaunchKernelGGL((linear_bf16_scores_kernel<2>), grid, block, 0, st, p);
-    return (int)hipGetLastError();
-}
-
-size_t ltr_linear_grad_workspace_bytes_bf16(int B, int L, int F)
-{
-    if (B <= 0 || lb_stream_shape_bad(B, L, F)) return 0;
-    const long long blocks = (long long)B * ((L + kLbGradRows - 1) / kLbGradRows);
-    return (size_t)blocks * (size_t)((F + 1 + 3) & ~3) * sizeof(float);
-}
-
-int ltr_linear_grad_bf16(const uint16_t *X, const float *g, const int64_t *n, int B, int L, int F, float *dW_db,
-                         void *workspace, size_t workspace_bytes, void *stream)
-{
-    LTR_CLEAR_STALE_ERROR();
-    if (lb_stream_shape_bad(B, L, F)) return LTR_ERR_SHAPE;
-    if (!dW_db) return LTR_ERR_NULL;
-    if (B > 0 && (!X || !g)) return LTR_ERR_NULL;
-    if (B > 0 && (!workspace || workspace_bytes < ltr_linear_grad_workspace_bytes_bf16(B, L, F)))
-        return LTR_ERR_WORKSPACE;
-    const int chunks = (L + kLbGradRows - 1) / kLbGradRows;
-    const int blocks = B * chunks;
-    if (B > 0) {
-        LbStreamParams p;
-        p.X = X; p.W = nullptr; p.bias = nullptr; p.g = g; p.n = n; p.out = (float *)workspace;
-        p.B = B; p.L = L; p.F = F; p.chunks = chunks;
-        hipLaunchKernelGGL(linear_bf16_grad_kernel, dim3((unsigned)blocks), dim3(kLbStreamThreads), 0, (hipStream_t)stream, p);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
-    }
-    return ltr_internal_reduce_partials((const float *)workspace, blocks, F + 1, (F + 1 + 3) & ~3, dW_db, stream);
-}
 
 int ltr_linear_bf16_plan(int kind, int B, int L, int F)
 {
@@ -479,7 +251,7 @@ int ltr_linear_partials_bf16(int kind, float sigma, const uint16_t *X, const flo
 {
     LTR_CLEAR_STALE_ERROR();
     if (const int rc = check_kind(kind, rel_dtype)) return rc;
-    if (lb_stream_shape_bad(B, L, F)) return LTR_ERR_SHAPE;
+    if (lb_shape_bad(B, L, F)) return LTR_ERR_SHAPE;
     if (L > kLbMaxListLen) return LTR_ERR_LIST_TOO_LONG;
     int ni;
     size_t lds;

@@ -1,7 +1,7 @@
 // ltr_mlp.hip -- translation unit of the fused MLP scorer + loss kernels (ltr_mlp.inc, ltr_mlp2.inc, ltr_mlp_listwise.inc),
 // the stand-alone MLP scorer (shared layer: ltr_mlp_stream.inc; f32 rows: ltr_mlp_rows.inc; bf16 features: ltr_mlp_bf16.inc;
-// wide rows: ltr_mlp_wide.inc) and the stand-alone Linear scorer layer (ltr_scorer.inc, which shares
-// the MLP's reduction kernel).
+// wide rows: ltr_mlp_wide.inc) and the stand-alone Linear scorer on f32 and bf16 rows (ltr_scorer.inc: one streaming layer
+// under both element types, which shares the MLP's reduction kernel).
 #include "ltr_common.inc"
 // the listwise slot of the training step: the ranked row (layout, ranking, scans) and the ListMLE row function
 #define LTR_RANKED_ROW_ONLY

@@ -8,6 +8,7 @@ kernels in the library may only go down (a ratchet: round 4 started at 99 of 430
 registers being live around its whole loop body on one path).
 No GPU needed: the library is cross-compiled by __graft_entry__.build()."""
 import os
+import re
 
 import pytest
 
@@ -130,3 +131,22 @@ def test_standalone_mlp_scorer_kernels_keep_their_occupancy():
         cap = 512 if "mlp_rows_kernel<14, true>" in n else 256
         assert r["vgpr_count"] + r.get("agpr_count", 0) <= cap, (n, r["vgpr_count"], r.get("agpr_count", 0))
     assert seen >= 4 + 4 + 14 + 2 + 2, seen
+
+
+def test_standalone_linear_scorer_f32_kernels_keep_their_occupancy():
+    """csrc/ltr_scorer.inc: the seven f32 instantiations of the streaming Linear scorer keep nothing in scratch and stay on
+    the occupancy step they were measured at (waves per SIMD = 512 / VGPRs in eights, at most 8), as VGPR caps; the bf16
+    ones are held by tests/test_linear_bf16_host.py.  linear_scores_kernel<4, 16> could never be launched (F <= 1024 is
+    at most four float4 per lane) and is not built."""
+    caps = {"linear_scores_kernel<4, 1>": 64, "linear_scores_kernel<4, 4>": 128, "linear_scores_kernel<1, 1>": 64,
+            "linear_scores_kernel<1, 4>": 64, "linear_scores_kernel<1, 16>": 168, "linear_grad_kernel<4>": 64,
+            "linear_grad_kernel<1>": 64}
+    ours = {}
+    for r in _records():
+        m = re.search(r"\b(linear_(?:scores|grad)_kernel<[^>]*>)", r.get("demangled", r["name"]))
+        if m:
+            ours[m.group(1)] = r
+    assert sorted(ours) == sorted(caps)                    # (and so no linear_scores_kernel<4, 16>)
+    for key, r in ours.items():
+        assert r.get("vgpr_spill_count", 0) == 0 and r.get("private_segment_fixed_size", 0) == 0, (key, r)
+        assert 0 < r["vgpr_count"] + r.get("agpr_count", 0) <= caps[key], (key, r)

@@ -120,7 +120,8 @@ def _on_plan(kind, B, L, F):
 # 1. the streaming kernels, through LinearScorer
 # ---------------------------------------------------------------------------------------------
 STREAM = [(1, 1, 8, "ragged"), (8, 16, 8, "ragged"), (5, 33, 136, (0, 1, 33, 38, 17)), (7, 33, 136, None),
-          (3, 1000, 224, "ragged"), (5, 77, 704, "ragged"), (2, 9, 1024, "ragged"), (300, 20, 48, "ragged")]
+          (3, 1000, 224, "ragged"), (5, 77, 704, "ragged"), (2, 9, 1024, "ragged"), (300, 20, 48, "ragged"),
+          (3, 300, 24, (0, 129, 300))]
 
 
 @pytest.mark.parametrize("shape", STREAM, ids=lambda s: "%dx%dx%d-%s" % (s[0], s[1], s[2], "n" if s[3] else "none"))

@@ -12,7 +12,7 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("shape", [(8, 16, 5), (64, 128, 136), (7, 33, 137), (3, 1000, 220), (5, 77, 700),
-                                   (2, 9, 1024), (300, 20, 46)])
+                                   (2, 9, 1024), (300, 20, 46), (3, 40, 301)])
 def test_forward_and_gradients_match_torch_linear(shape):
     from pytorchltr_amd.fused import LinearScorer
     dev = torch.device("cuda")
@@ -35,13 +35,21 @@ def test_forward_and_gradients_match_torch_linear(shape):
     assert torch.allclose(ours.bias.grad, ref.bias.grad, rtol=1e-4, atol=1e-4 * max(1.0, float(ref.bias.grad.abs().max())))
 
 
-def test_padded_documents_are_skipped_and_results_deterministic():
+@pytest.mark.parametrize("shape", [(50, 64, 136), (3, 300, 20), (3, 300, 301)])
+def test_padded_documents_are_skipped_and_results_deterministic(shape):
+    """(3, 300, F): an empty query, a full one (a second gradient chunk) and one whose third scores chunk holds a single
+    real document; F = 301 is the scalar path with two column tiles in the gradient kernel."""
     from pytorchltr_amd.fused import LinearScorer
     dev = torch.device("cuda")
-    B, L, F = 50, 64, 136
+    B, L, F = shape
     s, y, n, X, W, b = synth(B, L, 5, F=F)
     n[0], n[1] = 0, L
+    if B == 3:
+        n[2] = 129
+    torch.manual_seed(F)
     m = LinearScorer(F).to(dev)
+    ref = torch.nn.Linear(F, 1).to(dev)
+    ref.load_state_dict(m.state_dict())
     Xg = X.clone()
     for q in range(B):
         Xg[q, int(n[q]):] = float("nan")                         # garbage in the padded slots
@@ -57,6 +65,11 @@ def test_padded_documents_are_skipped_and_results_deterministic():
     (m(Xg.to(dev), n.to(dev)) * g).sum().backward()
     assert torch.equal(m.weight.grad, first[0]) and torch.equal(m.bias.grad, first[1])
     assert bool(torch.isfinite(m.weight.grad).all())
+    # ... and they are torch.nn.Linear's on the clean batch under the same masked g
+    (ref(X.to(dev)) * g).sum().backward()
+    scale = float(ref.weight.grad.abs().max())
+    assert torch.allclose(m.weight.grad, ref.weight.grad, rtol=1e-4, atol=1e-5 * max(1.0, scale))
+    assert torch.allclose(m.bias.grad, ref.bias.grad, rtol=1e-4, atol=1e-4 * max(1.0, float(ref.bias.grad.abs().max())))
 
 
 @pytest.mark.parametrize("kind", ["hinge", "ndcg2"])

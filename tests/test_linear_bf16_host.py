@@ -254,7 +254,8 @@ def test_bf16_linear_kernels_keep_their_occupancy_and_nothing_in_scratch():
         m = re.search(r"(linear_bf16_\w+?_kernel(?:<[^>]*>)?)", n)
         if m:
             ours[m.group(1)] = r
-    # the launchers' declared occupancies (csrc/ltr_linear_bf16.inc), as VGPR caps: 512 / waves per SIMD, in eights
+    # the declared occupancies (streaming kernels: csrc/ltr_scorer.inc; tile: csrc/ltr_linear_bf16.inc), as VGPR caps:
+    # 512 / waves per SIMD, in eights
     caps = {"linear_bf16_scores_kernel<1>": 64, "linear_bf16_scores_kernel<2>": 80, "linear_bf16_grad_kernel": 64}
     for kind in KINDS:
         for ni, cap in ((5, 64), (10, 80), (16, 128)):
