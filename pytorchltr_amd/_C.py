@@ -181,6 +181,7 @@ LONGPAIR_SIGNATURES = {
 # name -> (restype, argtypes); mirrors include/ltr_sched.h (hooks of the list-length scheduling and the lazy launch's hold-backs)
 SCHED_SIGNATURES = {
     "ltr_debug_sched_slots": (_i, [_i, _i, _i, _i, _vp, _vp]),
+    "ltr_debug_sched_slots_cu": (_i, [_i, _i, _i, _i, _i, _vp, _vp]),
     "ltr_debug_lazy_holdback": (_i, [_i]),
 }
 

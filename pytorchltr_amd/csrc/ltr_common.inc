@@ -122,9 +122,12 @@ __device__ __forceinline__ int clamp_n(int64_t n, int L)
 // without LDS traffic: one n per lane (8 x 64-byte segments), a radix select over the bits of n
 // with ballots (uniform control flow, ~100 instructions), ties by lane order.  A bijection inside
 // each group and a pure function of n[]; every output is indexed by the query, so results do not
-// depend on it.
+// depend on it.  (Which member rank a block id takes: sched_slot -- and, for the register tile on
+// grids of whole rounds of the CUs, sched_slot_cu, which deals by the CU that hosts the id.)
 constexpr int kSchedMaxPerCu = 4;        // register-tile kernel (B = 8 x #CUs: 22.1 -> 23.9 us with it)
 constexpr int kLossSchedMaxPerCu = 16;   // loss kernel, general fused kernel
+// (2 for the register tile, behind sched_slot_cu: the model's most loaded CU drops by 2-8 rows more, the lazy step does not
+// follow -- C2 12.04-12.13 -> 12.16-12.17 us, C3 and 768 queries equal; EXPERIMENTS.md)
 constexpr int kSchedLowBits = 3;         // low bits of n the selection ignores
 
 // Block id -> place in the list-length order: the sample group and the member rank (0 = the group's longest list) block `id` of a
@@ -192,13 +195,71 @@ __host__ __device__ inline SchedSlot sched_slot(int id, int B, int G, int cus, i
     return s;
 }
 
+// The register tile's dealing where the grid is WHOLE rounds of the CUs: a launch lasts as long as its most loaded CU, and what
+// sched_slot hands a CU is uneven by its arithmetic, not by the sampling.  (a) rank = jp * 8 + (pos & 7) and the block ids of a
+// CU share pos & 7: a CU gets the longest list of each eighth T times over, another the shortest T times (plain launch, the
+// five batches of bench.py, 256 CUs: rows per CU max / mean 1.20-1.27, one whole XCD +10.6 %).  (b) under the quiet rule
+// the non-quiet CUs host every (cus - nred)-th place, and the snake flips rounds of `cus`: C2's lazy launch, 220 non-quiet
+// CUs, max / mean 1.29-1.38 (383-398 rows against a mean of 285-299).
+// Here the ORDER INDEX o in [0, B) means (group, rank) = (o % G, o / G) -- every group complete, B % 64 == 0 --: index 0 is about
+// the longest list and consecutive indices walk the groups at one rank.  Block id i sits on CU slot i % cus in round i / cus
+// (scripts/cu_bytes.py --lazy confirms it on the GPU), so with `lead` workgroups without a query in front of the grid
+// (the lazy launch's reducers, fewer than the CUs) every slot hosts exactly T = B / cus query workgroups:
+//   quiet rule off: slot r's query workgroups are, in id order, its rounds t = 0 .. T - 1; NQ = cus slots, c = r;
+//   quiet rule on:  the slots r >= lead are the NQ = cus - lead non-quiet ones, c = r - lead, t = i / cus; the quiet workgroups
+//                   (r < lead, i >= cus) take the last B - T NQ order indices in id order -- the shortest lists, as in sched_slot.
+// Slot c deals itself o = t NQ + p_t(c) with permutations p_t of [0, NQ) whose sum over t does not depend on c:
+//   T = 4: straight, back, back, straight; T = 2: straight, back -- p(c) = c or NQ - 1 - c, the sum is exact;
+//   T = 3: straight, then the two halves of the slots by parity -- c = 2 h + e, H = ceil(NQ / 2):
+//          p_1 = e ? NQ - H - 1 - h : NQ - 1 - h,  p_2 = e ? NQ - 1 - h : H - 1 - h: the sum is exact for odd NQ and one place
+//          apart between even and odd slots otherwise (straight-back-back and straight-back-straight leave NQ - 1 places).
+// Lists linear in rank, n = 2 (64 - rank), 256 CUs: every CU 260 rows at T = 4 (sched_slot: 232-288), 130 at T = 2, 194-196 at
+// T = 3; 36 reducers and the quiet rule: 294-298 over the 220 non-quiet CUs (sched_slot: 232-384).  bench.py's batches, rows
+// per CU max / mean: plain 1.125-1.186, the quiet lazy launch's non-quiet CUs 1.087-1.123 (tests/test_sched_balance.py).
+// id -> (t, r) by sched_round's compares and ONE division, o / G, as in sched_slot.
+__host__ __device__ inline bool sched_cu_deal_applies(int B, int cus, int lead, bool quiet)
+{
+    if (cus <= 0 || (B & 63) != 0 || lead < 0 || lead >= cus || (quiet && lead == 0)) return false;
+    return B == 2 * cus || B == 3 * cus || B == 4 * cus;
+}
+__host__ __device__ inline SchedSlot sched_slot_cu(int id, int B, int G, int cus, int lead, bool quiet)
+{
+    int r;
+    int t = sched_round(id, cus, r);                             // (id < lead + B < 5 cus)
+    const bool three = B == 3 * cus;
+    const int T = three ? 3 : (B == 2 * cus ? 2 : 4);
+    int NQ = cus, c = r, o;
+    if (quiet) { NQ -= lead; c -= lead; }
+    else if (r < lead) t -= 1;                                   // (a reducer had this slot's round 0)
+    if (c < 0) {
+        o = T * NQ + (t - 1) * lead + r;                         // quiet: the tail of the order, in id order
+    } else {
+        int p = c;
+        if (three) {
+            const int H = (NQ + 1) >> 1, h = c >> 1, e = c & 1;
+            if (t == 1) p = (e ? NQ - H : NQ) - 1 - h;
+            else if (t == 2) p = (e ? NQ : H) - 1 - h;
+        } else if ((t ^ (t >> 1)) & 1) {
+            p = NQ - 1 - c;
+        }
+        o = t * NQ + p;
+    }
+    SchedSlot s;
+    s.rank = o / G;
+    s.group = o - s.rank * G;
+    return s;
+}
+
+// `pos`: the workgroup's place among the query workgroups -- or, for the register tile (round_cus > 0), its block id in a grid
+// with `lead` workgroups without a query in front (`quiet`: the quiet rule is on, sched_quiet)
 __device__ __forceinline__ int sched_query_sampled(const int64_t *__restrict__ n, int B, int L, int G, int tid,
-                                                   int &nb_out, int pos, int round_cus = 0, int nred = 0)
+                                                   int &nb_out, int pos, int round_cus = 0, int lead = 0, bool quiet = false)
 {
     __shared__ int s_sel[2];
     if (tid < 64) {
         const int lane = tid;
-        const SchedSlot slot = sched_slot(pos, B, G, round_cus, nred);
+        const SchedSlot slot = sched_cu_deal_applies(B, round_cus, lead, quiet) ? sched_slot_cu(pos, B, G, round_cus, lead, quiet)
+                             : sched_slot(quiet ? pos : pos - lead, B, G, round_cus, quiet ? lead : 0);
         const int gam = slot.group;
         int rho = slot.rank;                                     // this block's member number
         const int id = ((lane >> 3) * G + gam) * 8 + (lane & 7); // member `lane` of the group

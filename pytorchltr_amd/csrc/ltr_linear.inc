@@ -636,8 +636,9 @@ __device__ __forceinline__ void linear_regtile2_body(const LinearParams &p)
     }
     int b, nb;
     if (p.sched) {
-        b = sched_query_sampled(p.n, p.B, L, p.sched & 0xffff, (int)threadIdx.x, nb, qhold ? (int)blockIdx.x : qblock, p.sched >> 16,
-                                qhold ? p.pend_nred : 0);
+        // (the block id and the reducers in front of it: the dealing goes by the CU slot that hosts the id, sched_slot_cu)
+        b = sched_query_sampled(p.n, p.B, L, p.sched & 0xffff, (int)threadIdx.x, nb, (int)blockIdx.x, p.sched >> 16,
+                                lazy ? p.pend_nred : 0, qhold != 0);
     } else {
         b = qblock;
         nb = clamp_n(p.n[b], L);

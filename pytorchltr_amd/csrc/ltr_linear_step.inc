@@ -155,6 +155,12 @@ int linear_partials_launch(int kind, float sigma, const float *X, const float *W
         // (snake dealing of the rounds, sched_query_sampled: measured round 6 on 1024 x 128 x 136 with four workgroups per CU resident --
         // LambdaNDCG2 16.6 -> 16.1 us, logistic 14.0 -> 13.5, hinge 11.84 -> 11.82: the kinds with compute behind their loads are
         // bound by their most loaded CU.  EXPERIMENTS.md round 6)
+        // (on grids of whole rounds -- B = 2, 3 or 4 x #CUs, a multiple of 64 -- the kernel deals by the CU slot that hosts the block
+        // id instead, sched_slot_cu, for every kind, quiet rule on or off: same box, same call, both orders of lazy_ab.py, lazy step
+        // 1024 x 128 x 136: hinge 12.54-12.59 -> 12.05-12.06 us, DCG-hinge 12.87-12.91 -> 12.32-12.36, LambdaNDCG2 17.55 -> 17.33-17.35,
+        // logistic 14.52-14.75 -> 14.33-14.59 (below in three pairs of four, by less than the order bias: no win, no loss); hinge
+        // 768 x 128 x 136 11.73-11.79 -> 11.12-11.14, 512 x 128 x 136 9.95-9.98 -> 9.91-9.94 (inside the spread).  No kind or shape
+        // lost, so there is no rule function in front of it.  profiles/sched_balance_ab.txt)
         if (p.sched) p.sched |= device_cu_count() << 16;
         if (lazy) p.part_g = lazy->part_g;
         p.scores_out = LTR_TRACE_BUFFER(p.scores_out);      // (trace builds: the lazy step's launches have no score matrix to stamp)
@@ -195,6 +201,18 @@ LTR_DEBUG_HOOK int ltr_debug_sched_slots(int B, int G, int cus, int nred, int *g
     if (!group || !rank) return LTR_ERR_NULL;
     for (int i = 0; i < B; ++i) {
         const SchedSlot s = sched_slot(nred + i, B, G, cus, nred);
+        group[i] = s.group;
+        rank[i] = s.rank;
+    }
+    return LTR_OK;
+}
+
+LTR_DEBUG_HOOK int ltr_debug_sched_slots_cu(int B, int G, int cus, int nred, int quiet, int *group, int *rank)
+{
+    if (B <= 0 || G != (B + 63) / 64 || !sched_cu_deal_applies(B, cus, nred, quiet != 0)) return LTR_ERR_SHAPE;
+    if (!group || !rank) return LTR_ERR_NULL;
+    for (int i = 0; i < B; ++i) {
+        const SchedSlot s = sched_slot_cu(nred + i, B, G, cus, nred, quiet != 0);
         group[i] = s.group;
         rank[i] = s.rank;
     }
