@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI in ``include/ltr_hip.h``, ``include/ltr_eval.h``, ``include/ltr_listwise.h``,
-``include/ltr_longpair.h``, ``include/ltr_mlp_rows.h``, ``include/ltr_mlp_bf16.h``, ``include/ltr_mlp_wide.h``,
+``include/ltr_lambdarank.h``, ``include/ltr_longpair.h``, ``include/ltr_mlp_rows.h``, ``include/ltr_mlp_bf16.h``, ``include/ltr_mlp_wide.h``,
 ``include/ltr_linear_bf16.h`` and ``include/ltr_sched.h`` (pytorchltr_amd/csrc/libltr_hip.so).
 
 PyTorch supplies device memory and the current HIP stream; every call here hands raw device
@@ -137,6 +137,17 @@ LISTWISE_SIGNATURES = {
                              + [_i] * 5 + [_vp] * 5 + [_sz, _vp]),
 }
 
+# LambdaRank as a loss of the fused listwise Linear step: a Python-side code next to the two above (the library's
+# entry points for it are their own, below; ltr_linear_listwise_* answer LTR_ERR_KIND / 0 for it)
+LISTWISE_LAMBDARANK = 2
+
+# name -> (restype, argtypes); mirrors include/ltr_lambdarank.h (LambdaRank with NDCG@k swap weights, its fused Linear step)
+LAMBDARANK_SIGNATURES = {
+    "ltr_lambdarank_f32": (_i, [_vp, _vp, _i, _vp, _i, _f, _i, _i, _vp, _vp, _vp]),
+    "ltr_linear_lambdarank_plan": (_i, [_i, _i, _i]),
+    "ltr_linear_lambdarank_partials_f32": (_i, [_i, _f, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+}
+
 # name -> (restype, argtypes); mirrors include/ltr_mlp_rows.h (the MLP scorer on its own: scores and gradients, any length)
 MLP_ROWS_SIGNATURES = {
     "ltr_mlp_rows_scores_f32": (_i, [_vp] * 8 + [_i] * 5 + [_vp, _vp]),
@@ -218,7 +229,8 @@ def lib():
                 "There is no CPU fallback." % LIB_PATH)
         handle = _Library(LIB_PATH)
         for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(EVAL_SIGNATURES.items())
-                                          + list(LISTWISE_SIGNATURES.items()) + list(LONGPAIR_SIGNATURES.items())
+                                          + list(LISTWISE_SIGNATURES.items()) + list(LAMBDARANK_SIGNATURES.items())
+                                          + list(LONGPAIR_SIGNATURES.items())
                                           + list(MLP_ROWS_SIGNATURES.items()) + list(MLP_WIDE_SIGNATURES.items())
                                           + list(MLP_BF16_SIGNATURES.items()) + list(LINEAR_BF16_SIGNATURES.items())
                                           + list(SCHED_SIGNATURES.items())):

@@ -1,13 +1,14 @@
 // ltr_linear_listwise.inc -- the Linear(F, 1) scorer fused with the listwise losses, ListNet (the listwise softmax of
 // ltr_listwise_softmax_f32) and ListMLE (included by ltr_kernels.hip after ltr_listmle.inc; C ABI:
-// include/ltr_listwise.h; DESIGN.md 15).
+// include/ltr_listwise.h; DESIGN.md 15), and with LambdaRank (kLossLambdaRank below, an internal loss code: its entry
+// points are in ltr_lambdarank.inc, C ABI include/ltr_lambdarank.h; DESIGN.md 25).
 //
 // linear_listwise_kernel, one workgroup per query on the ranked-row core's launch shapes (metric_shape, launch_ranked):
 //   1. scores  s_j = X[b, j, :] . W + bias of the real documents j < n_b, one wave per row, straight into the slot the
 //      row function reads (sy[j].y); scores_out, when asked for, gets them too (0 for padded documents);
-//   2. the loss row: ListMLE -- listmle_row, the row function of listmle_kernel -- or ListNet, workgroup-wide max / sum
-//      of the scores and the labels; the gradient by document g_j ends in the icurve slot of the core's layout, which
-//      neither loss uses once the ranks are taken;
+//   2. the loss row: ListMLE -- listmle_row, the row function of listmle_kernel --, LambdaRank -- lambdarank_row, that
+//      of lambdarank_kernel -- or ListNet, workgroup-wide max / sum of the scores and the labels; the gradient by
+//      document g_j ends in the icurve slot of the core's layout, which no loss uses once its row is done;
 //   3. the weight-gradient row  dW_b = sum_{j < n_b} g_j X[b, j, :], db_b = sum_j g_j: threads as (row r, column
 //      vector c), R rows per iteration, the R partial rows added in order through LDS, stored as row b of the
 //      (B, partial_pitch(F)) matrix that ltr_linear_reduce_* consume.
@@ -15,15 +16,20 @@
 // sum in a fixed order: bit-identical run to run.  Behind the core's layout the dynamic LDS holds W float[F] and the
 // cross-row buffer float4[R * min(F / 4, T)].
 
+#include "ltr_lambdarank_row.inc"
+
 namespace {
+
+constexpr int kLossLambdaRank = 2;       // the third LOSS value of linear_listwise_kernel; not a code of ltr_listwise.h
 
 struct LinearListwiseParams {
     MetricParams m;          // the batch and the tie words (m.scores, m.out unused)
     const float *X, *W, *bias;
     float *loss, *scores_out, *part;
     int F;
-    int k;                   // ListMLE: <= 0 every factor
+    int k;                   // ListMLE: <= 0 every factor; LambdaRank: <= 0 no cutoff
     int R;                   // rows per workgroup iteration of phase 3
+    float sigma;             // LambdaRank
 };
 
 struct OpMax { static constexpr float id = -INFINITY; static __device__ __forceinline__ float f(float a, float b) { return fmaxf(a, b); } };
@@ -39,13 +45,13 @@ __host__ __device__ inline size_t linear_listwise_core_bytes(int loss, int L, bo
 constexpr int kListwiseUnr = 4;          // rows in flight per wave (phase 1) / per thread (phase 3)
 constexpr int kListwiseMaxR = 64;        // the R partial rows are added by one thread per column vector
 
-// (the launch bounds of the ranked-row core's kernels; ListNet has one instantiation, DPT = 0, for every shape)
+// The query of workgroup blockIdx.x, start to end: the body of linear_listwise_kernel and linear_lambdarank_kernel below.
 template <int LOSS, int DPT>
-__global__ void __launch_bounds__(1024, (DPT <= 0 ? 8 : 4))
-linear_listwise_kernel(LinearListwiseParams p)
+__device__ __forceinline__ void linear_listwise_query(const LinearListwiseParams &p)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr bool kSort = LOSS == LTR_LISTWISE_LISTMLE && DPT <= 0;
+    constexpr bool kSort = LOSS != LTR_LISTWISE_LISTNET && DPT <= 0;
+    constexpr bool kScoreFirst = LOSS == kLossLambdaRank;              // its row takes (score, label) pairs
     const MetricParams &m = p.m;
     const int b = blockIdx.x;
     const int L = m.L, F = p.F;
@@ -61,9 +67,9 @@ linear_listwise_kernel(LinearListwiseParams p)
     const size_t row = (size_t)b * L;
     const float *Xq = p.X + row * (size_t)F;
 
-    // (label, score) pairs, as listmle_kernel stages them
+    // (label, score) pairs, as listmle_kernel stages them; LambdaRank: (score, label), as lambdarank_kernel does
     for (int f = tid; f < F; f += T) wl[f] = p.W[f];
-    for (int j = tid; j < nb; j += T) q.sy[j].x = load_label(m.rel, m.rel_dtype, row + j);
+    for (int j = tid; j < nb; j += T) (kScoreFirst ? q.sy[j].y : q.sy[j].x) = load_label(m.rel, m.rel_dtype, row + j);
     const float bias = p.bias ? p.bias[0] : 0.f;
     __syncthreads();
 
@@ -91,7 +97,7 @@ linear_listwise_kernel(LinearListwiseParams p)
                 const int l = l0 + u * nwaves;
                 const float s = wave_sum(acc[u]) + bias;
                 if (lane == 0 && l < nb) {
-                    q.sy[l].y = s;
+                    (kScoreFirst ? q.sy[l].x : q.sy[l].y) = s;
                     if (p.scores_out) p.scores_out[row + l] = s;
                 }
             }
@@ -107,6 +113,14 @@ linear_listwise_kernel(LinearListwiseParams p)
         listmle_row<DPT>(m, q, nb, p.k > 0 ? min(p.k, nb) : nb, p.loss + b, true);
         for (int j = tid; j < nb; j += T) {
             const float v = q.curve[q.rank_s[j]];
+            g[j] = v;
+            gs += v;
+        }
+    } else if constexpr (LOSS == kLossLambdaRank) {
+        lambdarank_row<DPT>(m, q, nb, p.k > 0 ? min(p.k, nb) : nb, p.sigma, p.loss + b, true);
+        const float *gr = reinterpret_cast<const float *>(q.rank_y);
+        for (int j = tid; j < nb; j += T) {
+            const float v = gr[q.rank_s[j]];
             g[j] = v;
             gs += v;
         }
@@ -185,6 +199,22 @@ linear_listwise_kernel(LinearListwiseParams p)
     }
 }
 
+// (the launch bounds of the ranked-row core's kernels; ListNet has one instantiation, DPT = 0, for every shape)
+template <int LOSS, int DPT>
+__global__ void __launch_bounds__(1024, (DPT <= 0 ? 8 : 4))
+linear_listwise_kernel(LinearListwiseParams p)
+{
+    linear_listwise_query<LOSS, DPT>(p);
+}
+
+// LambdaRank in the loss slot: the six launch shapes of the core, under a name of their own
+template <int DPT>
+__global__ void __launch_bounds__(1024, (DPT <= 0 ? 8 : 4))
+linear_lambdarank_kernel(LinearListwiseParams p)
+{
+    linear_listwise_query<kLossLambdaRank, DPT>(p);
+}
+
 // The launch of (loss, B, L, F): the ranked-row core's shape -- ListNet, which ranks nothing, in the counting-rank
 // shapes' geometry at every length --, the LDS behind the core's layout and R.  False: the LDS does not fit.
 struct LinearListwiseShape { MetricShape sh; size_t extra; int R; };
@@ -217,7 +247,8 @@ int launch_linear_listwise(LinearListwiseParams &p, hipStream_t stream)
     if (!linear_listwise_shape(LOSS, p.m, p.F, s)) return LTR_ERR_CONFIG;
     p.R = s.R;
     return launch_ranked(s.sh, p.m.B, s.extra, stream, p, [](auto D) {
-        return &linear_listwise_kernel<LOSS, (LOSS == LTR_LISTWISE_LISTNET ? 0 : decltype(D)::value)>;
+        if constexpr (LOSS == kLossLambdaRank) return &linear_lambdarank_kernel<decltype(D)::value>;
+        else return &linear_listwise_kernel<LOSS, (LOSS == LTR_LISTWISE_LISTNET ? 0 : decltype(D)::value)>;
     });
 }
 

@@ -25,22 +25,28 @@ _KIND_BY_NAME = {
 
 class _ListwiseKind(collections.namedtuple("_ListwiseKind", "loss k", defaults=(None,))):
     """A listwise loss where the pairwise ones are an ``enum ltr_loss_kind`` value: the loss code of
-    ``include/ltr_listwise.h`` (ListNet, ListMLE) and ListMLE's ``k``."""
+    ``include/ltr_listwise.h`` (ListNet, ListMLE) and ListMLE's ``k`` -- or ``_C.LISTWISE_LAMBDARANK`` with LambdaRank's
+    cutoff ``k`` (include/ltr_lambdarank.h: a loss of the same fused Linear step; its sigma travels beside the kind)."""
     __slots__ = ()
 
 
-_LISTWISE_BY_NAME = {"softmax": _C.LISTWISE_LISTNET, "listnet": _C.LISTWISE_LISTNET, "listmle": _C.LISTWISE_LISTMLE}
+_LISTWISE_BY_NAME = {"softmax": _C.LISTWISE_LISTNET, "listnet": _C.LISTWISE_LISTNET, "listmle": _C.LISTWISE_LISTMLE,
+                     "lambdarank": _C.LISTWISE_LAMBDARANK}
 
 
 def _resolve_loss(loss):
     """Accepts a kind name or an instance of a pytorchltr_amd loss module: (kind, sigma); a listwise loss ("softmax" /
-    "listnet" / "listmle", ListwiseSoftmaxLoss, ListMLELoss(k)) resolves to a :class:`_ListwiseKind`; a pairwise module
+    "listnet" / "listmle", ListwiseSoftmaxLoss, ListMLELoss(k)) and LambdaRank ("lambdarank", LambdaRankLoss(sigma, k):
+    the loss slot of the listwise step) resolve to a :class:`_ListwiseKind`; a pairwise module
     built with ``long_lists=True`` to a :class:`_autograd.LongKind` (the same int, and the flag with it)."""
     if isinstance(loss, str):
         if loss in _LISTWISE_BY_NAME:
             return _ListwiseKind(_LISTWISE_BY_NAME[loss]), 1.0
         return _KIND_BY_NAME[loss], 1.0
     from .loss import listwise as _lw
+    from .loss import pairwise_lambda as _pl
+    if isinstance(loss, _pl.LambdaRankLoss):
+        return _ListwiseKind(_C.LISTWISE_LAMBDARANK, loss.k), float(loss.sigma)
     if isinstance(loss, _lw.ListMLELoss):
         return _ListwiseKind(_C.LISTWISE_LISTMLE, loss.k), 1.0
     if isinstance(loss, _lw.ListwiseSoftmaxLoss):
@@ -234,9 +240,9 @@ def _linear_prepare(xs, weight, relevance, n, kind, raw=None):
 def _linear_launch(kind, sigma, X, weight, bias, r, nn, dims, Fw, want_scores=False, empty=False):
     """The fused launch on a prepared batch: ``(loss[B], rows, scores | None)`` -- the family's partials entry point
     (ltr_linear_partials_f32 / _bf16) for a pairwise kind, ltr_linear_listwise_partials_f32 for a listwise one (ListMLE
-    draws its tie seed here, one per launch).  `rows`: the workspace, the (B, PF) per-query gradient rows first, which
-    `_reduce_rows` / ltr_linear_reduce_loss_f32 sum.  An empty batch launches nothing unless `empty` (linear_loss_step
-    hands it to the entry point)."""
+    draws its tie seed here, one per launch), ltr_linear_lambdarank_partials_f32 for LambdaRank.  `rows`: the workspace,
+    the (B, PF) per-query gradient rows first, which `_reduce_rows` / ltr_linear_reduce_loss_f32 sum.  An empty batch
+    launches nothing unless `empty` (linear_loss_step hands it to the entry point)."""
     B, L, F = dims
     W = _pad_weight(_flat_f32(weight, Fw), F)
     bvec = None if bias is None else _flat_f32(bias, 1)
@@ -253,7 +259,11 @@ def _linear_launch(kind, sigma, X, weight, bias, r, nn, dims, Fw, want_scores=Fa
             lib = _C.lib()
             bp = None if bvec is None else bvec.data_ptr()
             sp = None if scores is None else scores.data_ptr()
-            if listwise:
+            if listwise and kind.loss == _C.LISTWISE_LAMBDARANK:
+                rc = lib.ltr_linear_lambdarank_partials_f32(
+                    int(kind.k or 0), float(sigma), X.data_ptr(), W.data_ptr(), bp, r.data_ptr(), _LABEL_CODE[r.dtype],
+                    nn.data_ptr(), B, L, F, loss.data_ptr(), sp, ws.data_ptr(), _C.stream_of(X))
+            elif listwise:
                 rc = lib.ltr_linear_listwise_partials_f32(
                     kind.loss, int(kind.k or 0), X.data_ptr(), W.data_ptr(), bp, r.data_ptr(), _LABEL_CODE[r.dtype],
                     nn.data_ptr(), *_ties.tie_args(sd), B, L, F, loss.data_ptr(), sp, ws.data_ptr(), _C.stream_of(X))
@@ -346,9 +356,12 @@ def _reduce_rows(ctx, ws, grad_loss):
     return dW[:ctx.Fw].reshape(ctx.w_shape), (db if ctx.has_bias else None)
 
 
-def _listwise_pieces(scores, relevance, n, kind):
-    """The stand-alone listwise loss on computed scores (autograd-connected to them)."""
+def _listwise_pieces(scores, relevance, n, kind, sigma=1.0):
+    """The stand-alone listwise loss on computed scores (autograd-connected to them); `sigma`: LambdaRank's."""
     from .loss import listwise as _lw
+    if kind.loss == _C.LISTWISE_LAMBDARANK:
+        from .loss import pairwise_lambda as _pl
+        return _pl._LambdaRankFunction.apply(scores, relevance, n, kind.k, sigma)
     if kind.loss == _C.LISTWISE_LISTMLE:
         return _lw._ListMLEFunction.apply(scores, relevance, n, kind.k)
     return _lw._ListwiseSoftmaxFunction.apply(scores, relevance, n)
@@ -357,7 +370,7 @@ def _listwise_pieces(scores, relevance, n, kind):
 def _loss_pieces(scores, relevance, n, kind, sigma):
     """The stand-alone loss of `kind`, pairwise or listwise, on computed scores."""
     if isinstance(kind, _ListwiseKind):
-        return _listwise_pieces(scores, relevance, n, kind)
+        return _listwise_pieces(scores, relevance, n, kind, sigma)
     return _pairwise_pieces(scores, relevance, n, kind, sigma)
 
 
@@ -373,8 +386,8 @@ _bf16_plan_cache = {}
 def _listwise_fused(kind, X):
     """True where the one-launch listwise step takes the prepared feature batch X (ltr_linear_listwise_plan: lists of
     at most max_list_len() documents, rows of whole float4 that fit the LDS next to the ranked row, at a 16-byte
-    aligned address), else the three kernels -- scorer, listwise loss, weight gradient -- compute the same.  (The plan
-    depends on the device: its launch shapes follow the CU count.)"""
+    aligned address; LambdaRank: ltr_linear_lambdarank_plan, the same rule), else the three kernels -- scorer, listwise
+    loss, weight gradient -- compute the same.  (The plan depends on the device: its launch shapes follow the CU count.)"""
     B, L, F = X.shape
     key = (kind.loss, X.device.index, B, L, F)
     v = _listwise_plan_cache.get(key)
@@ -382,7 +395,11 @@ def _listwise_fused(kind, X):
         if len(_listwise_plan_cache) > 1024:
             _listwise_plan_cache.clear()
         with _C.device_ctx(X):
-            v = _listwise_plan_cache[key] = bool(_C.lib().ltr_linear_listwise_plan(kind.loss, B, L, F))
+            if kind.loss == _C.LISTWISE_LAMBDARANK:
+                v = bool(_C.lib().ltr_linear_lambdarank_plan(B, L, F))
+            else:
+                v = bool(_C.lib().ltr_linear_listwise_plan(kind.loss, B, L, F))
+            _listwise_plan_cache[key] = v
     return v and X.data_ptr() % 16 == 0
 
 
@@ -1265,6 +1282,9 @@ def mlp_loss_step(xs, params, relevance, n, loss="hinge", grad_out=None, return_
     """
     kind, sigma = _resolve_loss(loss)
     listwise = isinstance(kind, _ListwiseKind)
+    if listwise and kind.loss == _C.LISTWISE_LAMBDARANK:
+        raise TypeError("mlp_loss_step has no LambdaRank kernel (take loss_fn(MLPScorer(...)(xs, n), ys, n), or the "
+                        "Linear scorer: FusedLinearLoss, linear_loss_step, LinearScorer)")
     F, H1, H2 = params[0].shape[-1], params[0].shape[0], params[2].shape[0]    # (the network's: W1 is (H1, F))
     plan = not listwise or (xs.dim() == 3 and mlp_listwise_supported(kind, xs.shape[0], xs.shape[1], F, H1, H2))
     route = _mlp_route_of("step", xs, F, H1, H2, kind, plan)
@@ -1497,7 +1517,7 @@ class FusedMLPLoss(_FusedMLPBase):
 
 def _resolve_listwise_loss(loss):
     kind, sigma = _resolve_loss(loss)
-    if not isinstance(kind, _ListwiseKind):
+    if not isinstance(kind, _ListwiseKind) or kind.loss == _C.LISTWISE_LAMBDARANK:       # (no LambdaRank slot in the MLP step)
         raise TypeError("FusedMLPListwiseLoss takes the listwise losses only (\"listnet\" / \"softmax\", \"listmle\", "
                         "ListwiseSoftmaxLoss, ListMLELoss); the pairwise ones: FusedMLPLoss")
     return kind, sigma

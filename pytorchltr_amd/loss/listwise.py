@@ -16,7 +16,7 @@ from pytorchltr_amd import _ties
 from pytorchltr_amd._prepare import prepare as _prepare
 
 
-def _fused_step(scores, relevance, n, loss, k):
+def _fused_step(scores, relevance, n, loss, k, sigma=1.0):
     """Scores a LinearScorer has not computed yet (fused.LazyScores) are asked for the fused Linear step first --
     scorer, loss and weight-gradient rows in one launch, no score matrix written: (loss[b], None).  Where that step does
     not apply (ltr_linear_listwise_plan declines the shape, the scores were computed already) they are computed here,
@@ -25,7 +25,7 @@ def _fused_step(scores, relevance, n, loss, k):
     if fused is None:
         return None, scores
     from pytorchltr_amd.fused import _ListwiseKind
-    out = fused(relevance, n, _ListwiseKind(loss, k), 1.0)
+    out = fused(relevance, n, _ListwiseKind(loss, k), sigma)           # (sigma: LambdaRankLoss, loss/pairwise_lambda.py)
     return (None, scores.materialize()) if out is None else (out, None)
 
 

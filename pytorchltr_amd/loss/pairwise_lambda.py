@@ -10,9 +10,11 @@ Tie rule (documented deviation): score ties are broken by document index, not by
 reference's global-RNG permutation (utils/tensor_operations.py:43-45).
 """
 import torch as _torch
+from torch.autograd.function import once_differentiable as _once
 
 from pytorchltr_amd import _C
 from pytorchltr_amd._autograd import pairwise_loss as _pairwise_loss
+from pytorchltr_amd._prepare import prepare as _prepare
 
 
 class LambdaLoss(_torch.nn.Module):
@@ -70,3 +72,76 @@ class LambdaNDCGLoss2(LambdaLoss):
     dtype); the reference computes ``2 ** y`` on the integer tensor, where ``2 ** -1 == 0`` and the gain is -1.  Float
     labels of the same values agree with the reference."""
     _kind = _C.NDCG2
+
+
+class _LambdaRankFunction(_torch.autograd.Function):
+    """ltr_lambdarank_f32 (include/ltr_lambdarank.h): loss and d loss / d scores in one forward; backward is a row
+    scale.  Computes in fp32 whatever the score dtype (fp64 / half scores are cast in and the result cast back,
+    gradients included)."""
+
+    @staticmethod
+    def forward(ctx, scores, relevance, n, k, sigma):
+        s, r, nn = _prepare(scores, relevance, n, allow_f64=False)
+        B, L = s.shape
+        need_grad = ctx.needs_input_grad[0]
+        loss = _torch.empty(B, dtype=_torch.float32, device=s.device)
+        ds = _torch.empty(B, L, dtype=_torch.float32, device=s.device) if need_grad else None
+        if B > 0:
+            with _C.device_ctx(s):
+                _C.check(_C.lib().ltr_lambdarank_f32(_C.ptr(s), _C.ptr(r), _C.label_dtype(r), _C.ptr(nn), int(k or 0),
+                                                     float(sigma), B, L, _C.ptr(loss), _C.ptr(ds), _C.stream_of(s)))
+        if need_grad:
+            ctx.save_for_backward(ds)
+        ctx.in_shape, ctx.in_dtype = scores.shape, scores.dtype
+        return loss if scores.dtype is _torch.float32 else loss.to(scores.dtype)
+
+    @staticmethod
+    @_once
+    def backward(ctx, grad_out):
+        (ds,) = ctx.saved_tensors
+        out = ds * grad_out.reshape(-1, 1).to(ds.dtype)
+        return out.reshape(ctx.in_shape).to(ctx.in_dtype), None, None, None, None
+
+
+class LambdaRankLoss(_torch.nn.Module):
+    r"""LambdaRank (Burges et al. 2006; the objective of LambdaMART): the pairwise logistic loss with every pair
+    weighted by the change in NDCG@k when its two documents swap ranks.
+
+    With :math:`r_j` the 0-based rank of document :math:`j` by score (equal scores by document index, as for the other
+    Lambda losses), :math:`K = \min(k, n)` (:math:`K = n` without ``k``), :math:`d(r) = 1 / \log_2(2 + r)` for
+    :math:`r < K` and 0 from :math:`K` on, and :math:`G_j = (2^{y_j} - 1) / \mathrm{maxDCG@}K`:
+
+    .. math::
+        l(\mathbf{s}, \mathbf{y}) = \sum_{y_i > y_j} |G_i - G_j| \, |d(r_i) - d(r_j)| \,
+        \log_2(1 + e^{-\sigma (s_i - s_j)})
+
+    The ranking and the weights are constants of the gradient.  A pair with both documents below the cutoff has weight
+    0 and is never visited: the kernel evaluates about :math:`K n` pairs, not :math:`n^2 / 2`.  Padded documents take
+    no part; ``n <= 1`` gives 0; a query without a positive gain has maxDCG 1.  Negative grades take the float formula
+    :math:`2^y - 1`, as in :class:`LambdaNDCGLoss1`.  Lists of up to ``max_list_len()`` = 4096 documents; fp16, bf16 and
+    fp64 scores are computed in fp32.  The module has no parameters (an empty ``state_dict``).
+
+    Shape:
+        - scores: :math:`(N, \texttt{list\_size})` or :math:`(N, \texttt{list\_size}, 1)`
+        - relevance: :math:`(N, \texttt{list\_size})`
+        - n: :math:`(N)`
+        - output: :math:`(N)`
+    """
+
+    def __init__(self, sigma: float = 1.0, k=None):
+        super().__init__()
+        if k is not None:
+            if isinstance(k, bool) or int(k) != k or k < 1:
+                raise ValueError("k must be a positive integer or None, got %r" % (k,))
+            k = int(k)
+        self.sigma = sigma
+        self.k = k
+
+    def forward(self, scores: _torch.FloatTensor, relevance: _torch.LongTensor,
+                n: _torch.LongTensor) -> _torch.FloatTensor:
+        from pytorchltr_amd.loss.listwise import _fused_step
+        out, scores = _fused_step(scores, relevance, n, _C.LISTWISE_LAMBDARANK, self.k, self.sigma)
+        return out if out is not None else _LambdaRankFunction.apply(scores, relevance, n, self.k, self.sigma)
+
+    def extra_repr(self):
+        return "sigma=%s, k=%s" % (self.sigma, self.k)
