@@ -840,6 +840,13 @@ class LinearScorer(torch.nn.Module):
         if self.bias is not None:
             self.weight._ltr_scorer_bias = self.bias          # (pytorchltr_amd.optim.SGD pairs them up by this)
 
+    def __setstate__(self, state):
+        # (copy.deepcopy and unpickling -- torch.load of a whole model -- arrive here with new Parameter objects, which carry
+        # no attributes: pair them up again, or the copy would never reach the lazy step)
+        super().__setstate__(state)
+        if self.bias is not None:
+            self.weight._ltr_scorer_bias = self.bias
+
     def forward(self, xs, n=None):
         if not (torch.is_tensor(xs) and xs.dim() == 3 and xs.is_cuda
                 and (xs.dtype is torch.float32 or _bf16_batch(xs))

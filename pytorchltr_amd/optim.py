@@ -20,7 +20,18 @@ the optimizer changes.  How:
 * FLUSH ON READ: the scorer's parameters become :class:`_LazyParameter` (``nn.Parameter`` subclass; the objects stay the
   same, so ``model.parameters()``, ``state_dict()`` and checkpoints are unaffected).  Anything that reads them through
   torch -- an evaluation pass, ``state_dict()``, ``torch.save``, ``print``, another optimizer -- first applies the pending
-  update (one small launch), so nobody ever sees weights ``optimizer.step()`` has not reached yet.
+  update (one small launch), so nobody ever sees weights ``optimizer.step()`` has not reached yet.  That holds wherever the
+  parameter sits in the call: positional or keyword argument (``F.linear(x, weight=w)``, ``out=``), or inside lists, tuples
+  and dicts of any depth.  Pickling and copying (``torch.save(model)``, ``pickle``, ``copy.deepcopy``) apply the update and
+  give a plain ``nn.Parameter``: the lazy state stays with this optimizer.  What CANNOT hold: a detached alias taken earlier
+  (``p.data``, an EMA or bucket view of the storage) is an ordinary tensor, nothing is asked when it is read -- call
+  ``optimizer.flush()`` before reading through one.
+* THE GROUP: lr, and whether the group still is plain SGD, are read from the optimizer's CURRENT param group at every step.
+  ``load_state_dict`` and unpickling replace the group dicts: updates that are pending are applied first (with the lr of the
+  step that recorded them), then every scorer is bound to its new group -- a resumed run, and any scheduler attached
+  after the load, steer the lazy path like every other parameter; a loaded momentum or weight decay leaves it.
+* ``.grad``: ``p.grad.detach()`` of a gradient that has not been computed stays lazy and is an alias; ``clone()`` computes
+  it and is a copy that later in-place work on ``.grad`` (clipping, unscaling) does not reach.
 
 Everything that is not plain SGD on a ``LinearScorer`` (momentum, weight decay, nesterov, maximize, other parameters, a
 non-uniform upstream gradient, gradient accumulation, shapes the register-tile kernel does not take) runs as
@@ -89,8 +100,9 @@ class LazyGrad(torch.Tensor):
 
     @classmethod
     def __torch_dispatch__(cls, func, types, args=(), kwargs=None):
-        # (autograd's AccumulateGrad node works below the Python API: it detaches / aliases / clones the gradient it is
-        # handed before it stores it -- those stay lazy; anything else gets the values)
+        # (autograd's AccumulateGrad node works below the Python API: it detaches / aliases the gradient it is handed
+        # before it stores it -- those stay lazy: wrappers over the same gradient, as an alias is; anything else gets the
+        # values, and a clone is a copy of them that later in-place work on `.grad` -- clipping, unscaling -- cannot reach)
         if func in _GRAD_ALIASING and isinstance(args[0], LazyGrad) and args[0]._pg.real is None:
             a = args[0]
             return LazyGrad(a._pg, a._which, a.shape, a.device)
@@ -111,7 +123,7 @@ _GRAD_METADATA = {
     torch.Tensor.get_device, torch.Tensor.requires_grad.__get__, torch.Tensor.is_leaf.__get__, torch.Tensor.grad_fn.__get__,
     torch.Tensor.is_sparse.__get__,
 }
-_GRAD_ALIASING = {torch.ops.aten.detach.default, torch.ops.aten.alias.default, torch.ops.aten.clone.default}
+_GRAD_ALIASING = {torch.ops.aten.detach.default, torch.ops.aten.alias.default}
 
 
 # what may be asked of a lazily updated parameter without applying the pending update first: nothing that shows values
@@ -136,23 +148,53 @@ class _LazyParameter(torch.nn.Parameter):
     @classmethod
     def __torch_function__(cls, func, types, args=(), kwargs=None):
         if func not in _PARAM_NO_FLUSH:
-            for a in args:
-                st = getattr(a, "_ltr_lazy", None) if isinstance(a, _LazyParameter) else None
-                if st is not None and st.pending is not None:
-                    st.flush()
-                elif isinstance(a, (list, tuple)):
-                    for v in a:
-                        st = getattr(v, "_ltr_lazy", None) if isinstance(v, _LazyParameter) else None
-                        if st is not None and st.pending is not None:
-                            st.flush()
+            _flush_in(args)
+            if kwargs:
+                _flush_in(kwargs)
         return torch._C._disabled_torch_function_impl(func, types, args, kwargs or {})
 
     def __repr__(self):
-        st = getattr(self, "_ltr_lazy", None)
-        if st is not None and st.pending is not None:
-            st.flush()
+        _flush_in(self)
         with torch._C.DisableTorchFunctionSubclass():
             return "Parameter containing:\n" + torch.Tensor.__repr__(self.data)
+
+    def _plain(self, data):
+        """An ordinary ``nn.Parameter`` over `data` with this one's attributes except the lazy state (`_ltr_*`)."""
+        with torch._C.DisableTorchFunctionSubclass():
+            p = torch.nn.Parameter(data, self.requires_grad)
+            p.__dict__.update((k, v) for k, v in self.__dict__.items() if not k.startswith("_ltr_"))
+        return p
+
+    def __reduce_ex__(self, proto):
+        # (pickle, torch.save(model): the values with every update applied, as a plain Parameter -- the lazy state is the
+        # optimizer's, holds weak references and device buffers, and means nothing to whoever loads the file)
+        _flush_in(self)
+        with torch._C.DisableTorchFunctionSubclass():
+            return self._plain(self.data).__reduce_ex__(proto)
+
+    def __deepcopy__(self, memo):
+        if id(self) in memo:
+            return memo[id(self)]
+        _flush_in(self)
+        with torch._C.DisableTorchFunctionSubclass():
+            result = self._plain(self.data.clone(memory_format=torch.preserve_format))
+        memo[id(self)] = result
+        return result
+
+
+def _flush_in(a):
+    """Applies the pending update of every lazily updated parameter in `a`: a parameter, or any nesting of lists, tuples
+    and dicts (the positional and the keyword arguments of a torch function)."""
+    if isinstance(a, _LazyParameter):
+        st = getattr(a, "_ltr_lazy", None)
+        if st is not None and st.pending is not None:
+            st.flush()
+    elif isinstance(a, (list, tuple)):
+        for v in a:
+            _flush_in(v)
+    elif isinstance(a, dict):
+        for v in a.values():
+            _flush_in(v)
 
 
 class _Pending:
@@ -418,6 +460,29 @@ class SGD(torch.optim.SGD):
     def state_dict(self):
         self.flush()
         return super().state_dict()
+
+    def __setstate__(self, state):
+        """``load_state_dict`` (torch's ends here) and unpickling / ``copy.deepcopy``.  Both replace ``param_groups`` by new
+        dicts: updates that are pending are applied first, with the lr they were recorded with, and every scorer is then
+        bound to the group that holds its weight NOW -- its lr, and whether it still is plain SGD, are read there.  A
+        pickled or copied optimizer arrives without lazy state; its parameters are plain copies and it adopts what it can:
+        a scorer that was copied or unpickled BEFORE it in the same call (``copy.deepcopy((model, optimizer))``), whose
+        ``LinearScorer.__setstate__`` has paired weight and bias again.  In the other order, or copied alone, the copy
+        steps on the ordinary path: the same numbers as ``torch.optim.SGD``."""
+        lazy = self.__dict__.get("_lazy")
+        if lazy is not None:
+            self.flush()
+        super().__setstate__(state)
+        if lazy is None:
+            self._lazy = []
+            self._adopt()
+        else:
+            self._bind()
+
+    def _bind(self):
+        group_of = {id(p): g for g in self.param_groups for p in g["params"]}
+        for st in self._lazy:
+            st.group = group_of[id(st.weight)]
 
 
 def _noop_step(self, closure=None):
