@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI in ``include/ltr_hip.h``, ``include/ltr_eval.h``, ``include/ltr_listwise.h``,
-``include/ltr_lambdarank.h``, ``include/ltr_longpair.h``, ``include/ltr_mlp_rows.h``, ``include/ltr_mlp_bf16.h``, ``include/ltr_mlp_wide.h``,
+``include/ltr_lambdarank.h``, ``include/ltr_longpair.h``, ``include/ltr_lambdarank_long.h``, ``include/ltr_mlp_rows.h``, ``include/ltr_mlp_bf16.h``, ``include/ltr_mlp_wide.h``,
 ``include/ltr_linear_bf16.h`` and ``include/ltr_sched.h`` (pytorchltr_amd/csrc/libltr_hip.so).
 
 PyTorch supplies device memory and the current HIP stream; every call here hands raw device
@@ -189,6 +189,13 @@ LONGPAIR_SIGNATURES = {
     "ltr_debug_long_pairs_all": (_i, [_i]),
 }
 
+# name -> (restype, argtypes); mirrors include/ltr_lambdarank_long.h (LambdaRank past max_list_len() documents)
+LAMBDARANK_LONG_SIGNATURES = {
+    "ltr_lambdarank_long_workspace_bytes": (_sz, [_i, _i, _i]),
+    "ltr_lambdarank_long_f32": (_i, [_vp, _vp, _i, _vp, _i, _f, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "ltr_debug_lambdarank_long_all": (_i, [_i]),
+}
+
 # name -> (restype, argtypes); mirrors include/ltr_sched.h (hooks of the list-length scheduling and the lazy launch's hold-backs)
 SCHED_SIGNATURES = {
     "ltr_debug_sched_slots": (_i, [_i, _i, _i, _i, _vp, _vp]),
@@ -230,7 +237,7 @@ def lib():
         handle = _Library(LIB_PATH)
         for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(EVAL_SIGNATURES.items())
                                           + list(LISTWISE_SIGNATURES.items()) + list(LAMBDARANK_SIGNATURES.items())
-                                          + list(LONGPAIR_SIGNATURES.items())
+                                          + list(LONGPAIR_SIGNATURES.items()) + list(LAMBDARANK_LONG_SIGNATURES.items())
                                           + list(MLP_ROWS_SIGNATURES.items()) + list(MLP_WIDE_SIGNATURES.items())
                                           + list(MLP_BF16_SIGNATURES.items()) + list(LINEAR_BF16_SIGNATURES.items())
                                           + list(SCHED_SIGNATURES.items())):

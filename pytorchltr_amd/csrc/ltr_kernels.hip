@@ -1280,3 +1280,4 @@ int ltr_collate_pad_csr_f32(const int64_t *indptr, const int32_t *indices, const
 #include "ltr_listmle.inc"
 #include "ltr_linear_listwise.inc"
 #include "ltr_lambdarank.inc"
+#include "ltr_lambdarank_long.inc"

@@ -75,21 +75,34 @@ class LambdaNDCGLoss2(LambdaLoss):
 
 
 class _LambdaRankFunction(_torch.autograd.Function):
-    """ltr_lambdarank_f32 (include/ltr_lambdarank.h): loss and d loss / d scores in one forward; backward is a row
-    scale.  Computes in fp32 whatever the score dtype (fp64 / half scores are cast in and the result cast back,
-    gradients included)."""
+    """ltr_lambdarank_f32 (include/ltr_lambdarank.h), and past max_list_len() documents ltr_lambdarank_long_f32
+    (include/ltr_lambdarank_long.h): loss and d loss / d scores in one forward; backward is a row scale.  Computes in
+    fp32 whatever the score dtype (fp64 / half scores are cast in and the result cast back, gradients included)."""
 
     @staticmethod
     def forward(ctx, scores, relevance, n, k, sigma):
-        s, r, nn = _prepare(scores, relevance, n, allow_f64=False)
+        s, r, nn = _prepare(scores, relevance, n, allow_f64=False, limit_len=False)
         B, L = s.shape
+        if L > _C.max_pair_list_len():
+            raise ValueError("list_size %d exceeds max_pair_list_len() = %d, the bound of LambdaRankLoss (ListMLELoss and "
+                             "ListwiseSoftmaxLoss take longer lists)" % (L, _C.max_pair_list_len()))
         need_grad = ctx.needs_input_grad[0]
         loss = _torch.empty(B, dtype=_torch.float32, device=s.device)
         ds = _torch.empty(B, L, dtype=_torch.float32, device=s.device) if need_grad else None
         if B > 0:
+            lib = _C.lib()
+            kk = min(int(k or 0), 0x7FFFFFFF)
             with _C.device_ctx(s):
-                _C.check(_C.lib().ltr_lambdarank_f32(_C.ptr(s), _C.ptr(r), _C.label_dtype(r), _C.ptr(nn), int(k or 0),
-                                                     float(sigma), B, L, _C.ptr(loss), _C.ptr(ds), _C.stream_of(s)))
+                if L > _C.max_list_len():
+                    # past one workgroup's LDS: everything by rank in a workspace, owner tiles against the streamed anchors
+                    ws_bytes = int(lib.ltr_lambdarank_long_workspace_bytes(kk, B, L))
+                    ws = _torch.empty(ws_bytes, dtype=_torch.uint8, device=s.device)
+                    _C.check(lib.ltr_lambdarank_long_f32(_C.ptr(s), _C.ptr(r), _C.label_dtype(r), _C.ptr(nn), kk,
+                                                         float(sigma), B, L, _C.ptr(loss), _C.ptr(ds), _C.ptr(ws), ws_bytes,
+                                                         _C.stream_of(s)))
+                else:
+                    _C.check(lib.ltr_lambdarank_f32(_C.ptr(s), _C.ptr(r), _C.label_dtype(r), _C.ptr(nn), kk,
+                                                    float(sigma), B, L, _C.ptr(loss), _C.ptr(ds), _C.stream_of(s)))
         if need_grad:
             ctx.save_for_backward(ds)
         ctx.in_shape, ctx.in_dtype = scores.shape, scores.dtype
@@ -118,8 +131,15 @@ class LambdaRankLoss(_torch.nn.Module):
     The ranking and the weights are constants of the gradient.  A pair with both documents below the cutoff has weight
     0 and is never visited: the kernel evaluates about :math:`K n` pairs, not :math:`n^2 / 2`.  Padded documents take
     no part; ``n <= 1`` gives 0; a query without a positive gain has maxDCG 1.  Negative grades take the float formula
-    :math:`2^y - 1`, as in :class:`LambdaNDCGLoss1`.  Lists of up to ``max_list_len()`` = 4096 documents; fp16, bf16 and
-    fp64 scores are computed in fp32.  The module has no parameters (an empty ``state_dict``).
+    :math:`2^y - 1`, as in :class:`LambdaNDCGLoss1`.  fp16, bf16 and fp64 scores are computed in fp32.  The module has
+    no parameters (an empty ``state_dict``).
+
+    Lists of up to ``max_pair_list_len()`` = 65 536 documents.  Up to ``max_list_len()`` = 4096 a query is one
+    workgroup (``ltr_lambdarank_f32``); longer lists take ``ltr_lambdarank_long_f32`` by themselves, there is no flag to
+    set: with a cutoff the work stays about :math:`K n` (two passes over the anchors' pairs with the tail, behind two
+    sorts of the list).  **Without a cutoff, or with a very large one, the work past 4096 documents is quadratic**,
+    :math:`n^2` pair evaluations per query -- 4.3e9 at the bound -- as for the pairwise losses with
+    ``long_lists=True``.
 
     Shape:
         - scores: :math:`(N, \texttt{list\_size})` or :math:`(N, \texttt{list\_size}, 1)`
