@@ -30,7 +30,8 @@ extern "C" {
  *     the ranking from the long key sort (ties in document-index order), maxDCG@K_b from the label sort;
  *     (score, label) and (G, d) written BY RANK, d = 0 from rank K_b on;
  *     a query is cut into tiles of 1024 ranks, one workgroup each, which keeps its ranks in registers and streams
- *     the anchors [0, K_b) through LDS, 1024 at a time: the whole gradient of a rank >= K_b, the part within the top
+ *     the anchors [0, K_b) through LDS, 1024 at a time (the `owner_docs` and `chunk_docs` of ltr_long_pair_geometry,
+ *     ltr_longpair.h: one geometry for both pair passes): the whole gradient of a rank >= K_b, the part within the top
  *     K_b of an anchor, and the loss of every pair, counted once by its lower-ranked member;
  *     the anchors' pairs with the tail [K_b, n_b) are those same evaluations with the other sign (what a pair gives
  *     one document it takes from the other), so they are spread over the tail as its tiles are: every tile that owns

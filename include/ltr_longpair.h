@@ -28,6 +28,8 @@ extern "C" {
  *   once from each end: no atomics, every sum in a fixed order (per chunk, then over the chunks, then over the
  *   tiles in tile order) -- bit-identical run to run.  The rankings inside LambdaNDCG1 / 2 come from the long key
  *   sort of ltr_rank_by_score_long_f32 with ties in document-index order, maxDCG from the label sort.
+ *   ltr_long_pair_geometry describes the pair pass of ltr_lambdarank_long_f32 (ltr_lambdarank_long.h) as well: its
+ *   tiles of ranks are `owner_docs` wide and its anchors are streamed `chunk_docs` at a time.
  *   The work is QUADRATIC: L^2 pair evaluations per query, 4.3e9 at the bound, which also keeps ranks and pair
  *   counts exact in fp32.  Past the bound: ListMLE (ltr_listwise.h) and ListNet (ltr_listwise_softmax_f32) are
  *   O(L log L) / O(L) and take lists up to ltr_max_sort_list_len() / of any length.

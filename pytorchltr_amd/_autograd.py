@@ -14,7 +14,6 @@ from ._prepare import prepare
 
 _LABEL_CODE = {torch.int64: _C.LABEL_I64, torch.float32: _C.LABEL_F32, torch.int32: _C.LABEL_I32}
 _ws_cache = {}          # (kind, B, L) -> workspace bytes of ltr_pairwise_loss_ws_f32 (0 = plain path)
-_long_ws_cache = {}     # (kind, B, L) -> workspace bytes of ltr_pairwise_loss_long_f32
 LISTWISE_SOFTMAX = 100  # pseudo-kind of this module: ltr_listwise_softmax_f32 (not a pairwise loss)
 
 
@@ -56,14 +55,6 @@ class LongKind(int):
     (``long_lists=True``): an int wherever a kind is expected, and the flag travels with it (fused._resolve_loss,
     LazyScores.fused_loss)."""
     long_lists = True
-
-
-def _long_workspace_bytes(kind, B, L):
-    key = (kind, B, L)
-    ws = _long_ws_cache.get(key)
-    if ws is None:
-        ws = _long_ws_cache[key] = int(_C.lib().ltr_pairwise_loss_long_workspace_bytes(kind, B, L))
-    return ws
 
 
 def _check_list_len(L, long_lists):
@@ -120,11 +111,10 @@ class PairwiseLossFunction(torch.autograd.Function):
                                                    loss.data_ptr(), dsp, st)
                 elif L > _C.max_list_len():
                     # past one workgroup's LDS (long_lists=True): owner tiles against the streamed query
-                    ws_bytes = _long_workspace_bytes(kind, B, L)
-                    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+                    ws, ws_bytes = _C.workspace(lib.ltr_pairwise_loss_long_workspace_bytes(kind, B, L), dev)
                     rc = lib.ltr_pairwise_loss_long_f32(
                         kind, float(sigma), s.data_ptr(), r.data_ptr(), _LABEL_CODE[r.dtype],
-                        nn.data_ptr(), B, L, loss.data_ptr(), dsp, ws.data_ptr(), ws_bytes, st)
+                        nn.data_ptr(), B, L, loss.data_ptr(), dsp, _C.ptr(ws), ws_bytes, st)
                 else:
                     # long lists on a small batch: several workgroups share a query (needs scratch)
                     ws_bytes = _workspace_bytes(kind, B, L)

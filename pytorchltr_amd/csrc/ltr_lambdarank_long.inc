@@ -2,15 +2,16 @@
 // ltr_longsort.inc, ltr_longpair.inc and ltr_lambdarank.inc; C ABI: include/ltr_lambdarank_long.h; DESIGN.md 26).
 //
 // The loss is the one of ltr_lambdarank.inc; lambdarank_kernel keeps a whole query in LDS, which stops at 4096
-// documents.  Past that everything is laid out BY RANK in the caller's workspace and the pair pass has the shape of
-// ltr_longpair.inc:
+// documents.  Past that everything is laid out BY RANK in the caller's workspace and the pair pass is built on the
+// owner-tile core of ltr_longpair.inc (its geometry, tile decode, float4 rounds and loss partials; the two sorts and
+// the maxDCG head of its NDCG preparation):
 //   1. the ranking: the long key sort on the scores, ties in document-index order;
 //   2. maxDCG@K_b: the label sort, then tile partials of gain x discount over the ranks below K_b = min(k, n_b), added
 //      in tile order (lambdarank_row's terms: ndcg_gain, inv_discount, one fma per rank);
 //   3. an epilogue over the sorted score keys writes (score, label) and (G, d) by rank -- d = 0 from rank K_b on --
 //      and the document behind each rank;
-//   4. the pair pass, one workgroup per tile of kLrOwn ranks: a thread OWNS kLrDpt ranks in registers, the workgroup
-//      streams the anchors [0, K_b) through LDS, kLrChunk at a time, every thread reading the same LDS address per
+//   4. the pair pass, one workgroup per tile of kPairOwn ranks: a thread OWNS kPairDpt ranks in registers, the workgroup
+//      streams the anchors [0, K_b) through LDS, kPairChunk at a time, every thread reading the same LDS address per
 //      step (broadcast), and evaluates lambdarank_pair itself.  That is every pair an owner has: the whole gradient
 //      of a rank >= K_b, the part within the top K_b of an anchor, and the loss of every pair, counted once by its
 //      lower-ranked member (a < r).
@@ -31,21 +32,11 @@
 
 namespace {
 
-constexpr int kLrThreads = 256;
-constexpr int kLrWaves = kLrThreads / 64;
-constexpr int kLrDpt = 4;                        // owner ranks per thread
-constexpr int kLrOwn = kLrThreads * kLrDpt;
-constexpr int kLrChunk = 1024;                   // anchors staged in LDS per step (16 KiB)
 constexpr int kLrSub = 256;                      // anchors whose wave sums are handed over at a time (4 KiB)
-static_assert(kLrChunk % 4 == 0 && kLrChunk % kLrThreads == 0, "whole read rounds, whole staging rounds");
-static_assert(kLrSub % 4 == 0 && kLrSub <= kLrThreads && kLrChunk % kLrSub == 0, "one thread per handed-over anchor");
+static_assert(kLrSub % 4 == 0 && kLrSub <= kPairThreads && kPairChunk % kLrSub == 0, "one thread per handed-over anchor");
 
 int g_lambdarank_long_all = 0;                   // ltr_debug_lambdarank_long_all
-inline bool lambdarank_long(int L)
-{
-    return L > kMaxListLen || __atomic_load_n(&g_lambdarank_long_all, __ATOMIC_RELAXED) != 0;
-}
-inline int lambdarank_long_tiles(int L) { return (L + kLrOwn - 1) / kLrOwn; }
+inline bool lambdarank_long(int L) { return long_or_forced(L, g_lambdarank_long_all); }
 
 struct LambdaRankLongParams {
     const float *scores;
@@ -61,9 +52,9 @@ struct LambdaRankLongParams {
     float *graw;             // (B, L) by rank: the owners' gradient in units of sigma / ln 2
     float *part;             // (B, tiles) loss partials
     float *ganch;            // (B, ttiles, kcap): the anchors' partial gradients from the tiles that own ranks of the tail
-    int tiles;               // ceil(L / kLrOwn)
+    int tiles;               // long_pair_tiles(L)
     int kcap;                // k where a tail can exist (0 < k < L), else 0
-    int ttile0, ttiles;      // the first tile with a rank >= kcap, floor(kcap / kLrOwn); tiles - ttile0
+    int ttile0, ttiles;      // the first tile with a rank >= kcap, floor(kcap / kPairOwn); tiles - ttile0
 };
 
 __device__ __forceinline__ int lambdarank_cutoff(int k, int nb) { return k > 0 ? min(k, nb) : nb; }
@@ -93,80 +84,75 @@ lambdarank_long_byrank_kernel(LongKeyParams k, const unsigned long long *__restr
 {
     const EpiTile t = epi_tile(k, ptiles);
     const int K = lambdarank_cutoff(p.k, t.nb);
-    float maxdcg = 0.f;
-    for (int i = 0; i < ptiles; ++i) maxdcg += part[(size_t)t.q * ptiles + i];    // every thread, same order
-    if (maxdcg == 0.0f) maxdcg = 1.0f;
-    const float inv_maxdcg = 1.0f / maxdcg;
+    const float inv = inv_maxdcg(part, t.q, ptiles);
     for (int x = threadIdx.x; x < t.real; x += kEpiThreads) {
         const int r = t.r0 + x;
         const int doc = long_doc(k, sorted[t.base + r], t.seed);
         const float y = load_label(p.rel, p.rel_dtype, t.base + doc);
         p.sl[t.base + r] = make_float2(p.scores[t.base + doc], y);
-        p.gd[t.base + r] = make_float2(ndcg_gain(y) * inv_maxdcg, r < K ? inv_discount((float)r) : 0.f);
+        p.gd[t.base + r] = make_float2(ndcg_gain(y) * inv, r < K ? inv_discount((float)r) : 0.f);
         p.doc[t.base + r] = doc;
     }
 }
 
-// 4. the pair pass: the ranks [tile kLrOwn, ...) of query b against the anchors [0, K_b), for the tiles
+// 4. the pair pass: the ranks [tile kPairOwn, ...) of query b against the anchors [0, K_b), for the tiles
 // [tile0, tile0 + ntiles) of every query.  FEEDS: these tiles may own ranks of the tail and then leave the anchors' share
-// of their pairs (the host launches the tiles below floor(k / kLrOwn), a forward-only call and a call without a cutoff
+// of their pairs (the host launches the tiles below floor(k / kPairOwn), a forward-only call and a call without a cutoff
 // with FEEDS = false: no wave sums, half the LDS, fewer registers).  Both forms add the loss in the same order.
 template <bool FEEDS>
-__global__ void __launch_bounds__(kLrThreads)
+__global__ void __launch_bounds__(kPairThreads)
 lambdarank_long_pass_kernel(LambdaRankLongParams p, int tile0, int ntiles)
 {
-    constexpr int SUB = FEEDS ? kLrSub : kLrChunk;                                // anchors between two hand-overs of wave sums
-    __shared__ __attribute__((aligned(16))) float4 s[kLrChunk];                   // (score, label, G, d) by rank
-    __shared__ __attribute__((aligned(16))) float wsum[FEEDS ? kLrWaves : 1][FEEDS ? kLrSub : 4];   // per anchor and wave
+    constexpr int SUB = FEEDS ? kLrSub : kPairChunk;                              // anchors between two hand-overs of wave sums
+    __shared__ __attribute__((aligned(16))) float4 s[kPairChunk];                 // (score, label, G, d) by rank
+    __shared__ __attribute__((aligned(16))) float wsum[FEEDS ? kPairWaves : 1][FEEDS ? kLrSub : 4];   // per anchor and wave
     __shared__ float red[32];
+    OwnerTile t;
+    if (!owner_tile(p.n, p.L, tile0, ntiles, t)) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int L = p.L;
-    const int b = blockIdx.x / ntiles, tile = tile0 + (blockIdx.x - b * ntiles);
-    const int nb = clamp_n(p.n[b], L);
+    const int nb = t.nb, o0 = t.o0;
     const int K = lambdarank_cutoff(p.k, nb);
-    const int o0 = tile * kLrOwn;
-    if (o0 >= nb) return;                                   // uniform: the finish kernel never reads this tile
-    const size_t row = (size_t)b * L;
+    const size_t row = t.row;
     const float c1 = p.sigma * kLog2e;
     const bool grad = p.dscores != nullptr;
     // this tile owns ranks of the tail: it also leaves the anchors' share of its pairs (K < n_b: K = kcap)
-    const bool feeds = FEEDS && grad && K < nb && o0 + kLrOwn > K;
-    float *anch = feeds ? p.ganch + ((size_t)b * p.ttiles + (size_t)(tile - p.ttile0)) * (size_t)p.kcap : nullptr;
+    const bool feeds = FEEDS && grad && K < nb && o0 + kPairOwn > K;
+    float *anch = feeds ? p.ganch + ((size_t)t.b * p.ttiles + (size_t)(t.tile - p.ttile0)) * (size_t)p.kcap : nullptr;
 
-    float2 own[kLrDpt], ogd[kLrDpt];
-    float gk[kLrDpt];
+    float2 own[kPairDpt], ogd[kPairDpt];
+    float gk[kPairDpt];
     int nc = 0;                                             // owner groups of this wave with a rank below n_b
 #pragma unroll
-    for (int c = 0; c < kLrDpt; ++c) {
-        const int r = o0 + tid + c * kLrThreads;
+    for (int c = 0; c < kPairDpt; ++c) {
+        const int r = o0 + tid + c * kPairThreads;
         const bool valid = r < nb;
         // an idle owner: a NaN label, so both orientation tests of lambdarank_pair fail
         own[c] = valid ? p.sl[row + r] : make_float2(0.f, __builtin_nanf(""));
         ogd[c] = valid ? p.gd[row + r] : make_float2(0.f, 0.f);
         gk[c] = 0.f;
-        nc += (o0 + (tid & ~63) + c * kLrThreads) < nb ? 1 : 0;
+        nc += (o0 + (tid & ~63) + c * kPairThreads) < nb ? 1 : 0;
     }
     nc = __builtin_amdgcn_readfirstlane(nc);
 
     float ltot = 0.f;
-    for (int m0 = 0; m0 < K; m0 += kLrChunk) {
-        const int len = min(kLrChunk, K - m0);
+    for (int m0 = 0; m0 < K; m0 += kPairChunk) {
+        const int len = min(kPairChunk, K - m0);
         __syncthreads();                                    // the chunk before this one has been read
-        for (int x = tid; x < len; x += kLrThreads) {
+        for (int x = tid; x < len; x += kPairThreads) {
             const float2 a = p.sl[row + m0 + x], g = p.gd[row + m0 + x];
             s[x] = make_float4(a.x, a.y, g.x, g.y);
         }
         __syncthreads();
-        float lc = 0.f, gc[kLrDpt];
+        float lc = 0.f, gc[kPairDpt];
 #pragma unroll
-        for (int c = 0; c < kLrDpt; ++c) gc[c] = 0.f;
+        for (int c = 0; c < kPairDpt; ++c) gc[c] = 0.f;
         // one streamed anchor `a` against the owned ranks; returns what this thread's tail owners received from it
         auto visit = [&](float4 v, int a) {
             float tail = 0.f;
 #pragma unroll
-            for (int c = 0; c < kLrDpt; ++c) {
+            for (int c = 0; c < kPairDpt; ++c) {
                 if (c < nc) {
-                    const int r = o0 + tid + c * kLrThreads;
+                    const int r = o0 + tid + c * kPairThreads;
                     float d = 0.f;
                     lambdarank_pair(own[c], ogd[c], make_float2(v.x, v.y), make_float2(v.z, v.w), c1, a < r, d, lc);
                     gc[c] += d;
@@ -177,50 +163,38 @@ lambdarank_long_pass_kernel(LambdaRankLongParams p, int tile0, int ntiles)
         };
         for (int q0 = 0; q0 < len; q0 += SUB) {
             const int qlen = min(SUB, len - q0);
-            // wave-uniform LDS addresses (broadcast reads), four ds_read_b128 per round
-            const int full = qlen & ~3;
-            for (int m = 0; m < full; m += 4) {
-                float4 v[4];
+            float4_rounds(s + q0, qlen, [&](const auto &v, int m) {
+                constexpr int N = sizeof(v) / sizeof(float4);
+                float w[N];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = s[q0 + m + j];
-                float t[4];
+                for (int j = 0; j < N; ++j) w[j] = visit(v[j], m0 + q0 + m + j);
+                if (feeds) {                                // uniform; one ds_write_b128 per full round
 #pragma unroll
-                for (int j = 0; j < 4; ++j) t[j] = visit(v[j], m0 + q0 + m + j);
-                if (feeds) {                                // uniform
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) t[j] = wave_sum(t[j]);
-                    if (lane == 0) *reinterpret_cast<float4 *>(&wsum[wave][m]) = make_float4(t[0], t[1], t[2], t[3]);
+                    for (int j = 0; j < N; ++j) w[j] = wave_sum(w[j]);
+                    if (lane == 0) __builtin_memcpy(__builtin_assume_aligned(&wsum[wave][m], sizeof(w)), w, sizeof(w));
                 }
-            }
-            for (int m = full; m < qlen; ++m) {
-                float t = visit(s[q0 + m], m0 + q0 + m);
-                if (feeds) {
-                    t = wave_sum(t);
-                    if (lane == 0) wsum[wave][m] = t;
-                }
-            }
+            });
             if (feeds) {
                 __syncthreads();
                 if (tid < qlen) {
-                    float t = wsum[0][tid];
+                    float a = wsum[0][tid];
 #pragma unroll
-                    for (int w = 1; w < kLrWaves; ++w) t += wsum[w][tid];         // wave order
-                    anch[m0 + q0 + tid] = -t;
+                    for (int w = 1; w < kPairWaves; ++w) a += wsum[w][tid];       // wave order
+                    anch[m0 + q0 + tid] = -a;
                 }
                 __syncthreads();                            // before the next hand-over overwrites the sums
             }
         }
         ltot += lc;
 #pragma unroll
-        for (int c = 0; c < kLrDpt; ++c) gk[c] += gc[c];
+        for (int c = 0; c < kPairDpt; ++c) gk[c] += gc[c];
     }
 
-    const float total = block_sum(ltot, red);               // fixed order
-    if (tid == 0) p.part[(size_t)b * p.tiles + tile] = total;
+    tile_loss(ltot, red, p.part, t, p.tiles);
     if (!grad) return;
 #pragma unroll
-    for (int c = 0; c < kLrDpt; ++c) {
-        const int r = o0 + tid + c * kLrThreads;
+    for (int c = 0; c < kPairDpt; ++c) {
+        const int r = o0 + tid + c * kPairThreads;
         if (r < nb) p.graw[row + r] = gk[c];
     }
 }
@@ -236,12 +210,7 @@ lambdarank_long_finish_kernel(LambdaRankLongParams p)
     const int L = p.L;
     const int nb = clamp_n(p.n[b], L);
     const int K = lambdarank_cutoff(p.k, nb);
-    const int used = (nb + kLrOwn - 1) / kLrOwn;
-    if (blockIdx.y == 0 && threadIdx.x == 0) {
-        float total = 0.f;
-        for (int t = 0; t < used; ++t) total += p.part[(size_t)b * p.tiles + t];
-        p.loss[b] = total;
-    }
+    if (blockIdx.y == 0 && threadIdx.x == 0) p.loss[b] = tile_loss_sum(p.part, b, p.tiles, nb);
     if (p.dscores == nullptr) return;
     const int x = blockIdx.y * blockDim.x + threadIdx.x;
     if (x >= L) return;
@@ -252,7 +221,7 @@ lambdarank_long_finish_kernel(LambdaRankLongParams p)
     }
     float g = p.graw[row + x];
     if (x < K && K < nb)
-        for (int t = p.ttile0; t < used; ++t) g += p.ganch[((size_t)b * p.ttiles + (size_t)(t - p.ttile0)) * (size_t)p.kcap + x];
+        for (int t = p.ttile0; t < long_pair_tiles(nb); ++t) g += p.ganch[((size_t)b * p.ttiles + (size_t)(t - p.ttile0)) * (size_t)p.kcap + x];
     p.dscores[row + p.doc[row + x]] = g * (p.sigma * kLog2e);
 }
 
@@ -271,13 +240,13 @@ inline LambdaRankLongWorkspace lambdarank_long_workspace(Carver &c, int k, int B
     LambdaRankLongWorkspace w{};
     const size_t BL = (size_t)B * (size_t)L;
     w.kcap = (k > 0 && k < L) ? k : 0;
-    w.ttile0 = w.kcap / kLrOwn;
-    w.ttiles = w.kcap ? lambdarank_long_tiles(L) - w.ttile0 : 0;
+    w.ttile0 = w.kcap / kPairOwn;
+    w.ttiles = w.kcap ? long_pair_tiles(L) - w.ttile0 : 0;
     w.sl = c.take<float2>(BL); c.align256();
     w.gd = c.take<float2>(BL); c.align256();
     w.doc = c.take<int>(BL); c.align256();
     w.graw = c.take<float>(BL); c.align256();
-    w.part = c.take<float>((size_t)B * (size_t)lambdarank_long_tiles(L)); c.align256();
+    w.part = c.take<float>((size_t)B * (size_t)long_pair_tiles(L)); c.align256();
     w.ganch = c.take<float>((size_t)B * (size_t)w.ttiles * (size_t)w.kcap); c.align256();
     w.sort = long_workspace(c, B, L, true);
     return w;
@@ -287,26 +256,24 @@ int launch_lambdarank_long(LambdaRankLongParams p, const LambdaRankLongWorkspace
 {
     const int B = p.B, L = p.L;
     p.sl = w.sl; p.gd = w.gd; p.doc = w.doc; p.graw = w.graw; p.part = w.part; p.ganch = w.ganch;
-    p.tiles = lambdarank_long_tiles(L);
+    p.tiles = long_pair_tiles(L);
     p.kcap = w.kcap; p.ttile0 = w.ttile0; p.ttiles = w.ttiles;
     const int etiles = long_epi_tiles(L);
     const dim3 egrid((unsigned)((size_t)B * etiles)), eblock(kEpiThreads);
-    // maxDCG: the ideal ranking (label keys, index words), its terms below the cutoff per tile
-    const LongKeyParams ik = long_key_params(nullptr, p.rel, p.rel_dtype, p.n, nullptr, 0, 0, nullptr, L, w.sort, s);
-    const unsigned long long *ideal = long_sort(ik, B, w.sort, nullptr, s);
-    hipLaunchKernelGGL(lambdarank_long_maxdcg_kernel, egrid, eblock, 0, s, ik, ideal, p.k, w.sort.part, etiles);
-    // the ranking by score, ties in document-index order; everything by rank
-    const LongKeyParams sk = long_key_params(p.scores, p.rel, p.rel_dtype, p.n, nullptr, 0, 0, nullptr, L, w.sort, s);
-    const unsigned long long *sorted = long_sort(sk, B, w.sort, nullptr, s);
-    hipLaunchKernelGGL(lambdarank_long_byrank_kernel, egrid, eblock, 0, s, sk, sorted, (const float *)w.sort.part, etiles, p);
+    // maxDCG: the ideal ranking's terms below the cutoff per tile; then everything by rank
+    const RankedKeys r = long_ndcg_sorts(p.scores, p.rel, p.rel_dtype, p.n, B, L, w.sort, s,
+                                         [&](const LongKeyParams &ik, const unsigned long long *ideal) {
+        hipLaunchKernelGGL(lambdarank_long_maxdcg_kernel, egrid, eblock, 0, s, ik, ideal, p.k, w.sort.part, etiles);
+    });
+    hipLaunchKernelGGL(lambdarank_long_byrank_kernel, egrid, eblock, 0, s, r.k, r.sorted, (const float *)w.sort.part, etiles, p);
     // the tiles that cannot own a rank of the tail, then those that can (none in a forward-only call or without a cutoff)
     const int split = (p.dscores != nullptr && p.kcap > 0) ? p.ttile0 : p.tiles;
     if (split > 0)
-        hipLaunchKernelGGL(lambdarank_long_pass_kernel<false>, dim3((unsigned)((size_t)B * split)), dim3(kLrThreads), 0, s,
+        hipLaunchKernelGGL(lambdarank_long_pass_kernel<false>, dim3((unsigned)((size_t)B * split)), dim3(kPairThreads), 0, s,
                            p, 0, split);
     if (split < p.tiles)
         hipLaunchKernelGGL(lambdarank_long_pass_kernel<true>, dim3((unsigned)((size_t)B * (p.tiles - split))),
-                           dim3(kLrThreads), 0, s, p, split, p.tiles - split);
+                           dim3(kPairThreads), 0, s, p, split, p.tiles - split);
     hipLaunchKernelGGL(lambdarank_long_finish_kernel, dim3((unsigned)B, (unsigned)((L + 255) / 256)), dim3(256), 0, s, p);
     return (int)hipGetLastError();
 }

@@ -14,12 +14,16 @@
 //     kPairChunk * kPairDpt terms, then at most 64 chunk sums), so no running sum is 65 536 terms long;
 //   * the workgroup writes the raw gradient of its documents and one loss partial; a finish kernel adds the
 //     tile partials in tile order, applies the loss modifier and scales the gradient.
-// The LambdaNDCG kinds first leave per document what ndcg_prepare_kernel leaves for the split-query launch:
-// that kernel itself up to kLossSymMaxLen documents, else the ranking from the long key sort (ties in
-// document-index order) and maxDCG from the label sort and the DCG tile partials of ltr_dcg_long_f32.
+// The LambdaNDCG kinds first leave per document what ndcg_prepare_kernel leaves for the split-query launch, at every
+// length from the two sorts: the ranking from the long key sort (ties in document-index order) and maxDCG from the
+// label sort and the DCG tile partials of ltr_dcg_long_f32.
 // LambdaNDCG2's delta_{|rank_i - rank_j|} is evaluated inline (two v_log_f32, two v_rcp_f32): the table does
 // not fit LDS at 65 536 ranks (DESIGN.md 16).
 // All memory is the caller's workspace; nothing synchronises with the host: capturable.
+// The geometry, the owner-tile core (tile decode, float4 rounds, tile epilogue, partial sum) and the NDCG preparation
+// (the two sorts, the maxDCG head) below also serve LambdaRank's pass, ltr_lambdarank_long.inc.  The chunk loop around
+// the rounds stays with each kernel: lifted into a shared function it cost 3.5 to 9 % of the tile kernels' time
+// (DESIGN.md 16).
 
 #include "ltr_longpair.h"
 
@@ -27,14 +31,90 @@ namespace {
 
 constexpr int kMaxPairListLen = 65536;       // <= 4.3e9 pair evaluations per query; ranks and counts exact in fp32
 constexpr int kPairThreads = 256;
+constexpr int kPairWaves = kPairThreads / 64;
 constexpr int kPairDpt = 4;                  // owner documents per thread
 constexpr int kPairOwn = kPairThreads * kPairDpt;
 constexpr int kPairChunk = 1024;             // documents staged in LDS per step (8 KiB; 16 KiB for LambdaNDCG2)
 static_assert(kPairChunk % 8 == 0 && kPairChunk % kPairThreads == 0, "whole float4 groups, whole staging rounds");
 
+// past one workgroup's LDS, or forced there by a debug hook
+inline bool long_or_forced(int L, const int &hook) { return L > kMaxListLen || __atomic_load_n(&hook, __ATOMIC_RELAXED) != 0; }
 int g_long_pairs_all = 0;                    // ltr_debug_long_pairs_all
-inline bool long_pairs(int L) { return L > kMaxListLen || __atomic_load_n(&g_long_pairs_all, __ATOMIC_RELAXED) != 0; }
-inline int long_pair_tiles(int L) { return (L + kPairOwn - 1) / kPairOwn; }
+inline bool long_pairs(int L) { return long_or_forced(L, g_long_pairs_all); }
+__host__ __device__ inline int long_pair_tiles(int L) { return (L + kPairOwn - 1) / kPairOwn; }
+
+// ---- the owner-tile core ----
+struct OwnerTile { int b, tile, nb, o0; size_t row; };    // query, tile, n[b], the tile's first owner, b * L
+
+// Block -> (query, tile) of a launch over the tiles [tile0, tile0 + ntiles) of every query.  False (uniform): the
+// tile starts at or past n[b], and the finish kernel never reads its partial.
+__device__ __forceinline__ bool owner_tile(const int64_t *n, int L, int tile0, int ntiles, OwnerTile &t)
+{
+    t.b = blockIdx.x / ntiles;
+    t.tile = tile0 + (blockIdx.x - t.b * ntiles);
+    t.nb = clamp_n(n[t.b], L);
+    t.o0 = t.tile * kPairOwn;
+    t.row = (size_t)t.b * L;
+    return t.o0 < t.nb;
+}
+
+// The broadcast rounds over s[0, len) of a float4 chunk: wave-uniform LDS addresses, four ds_read_b128 per round,
+// then the remainder (< 4 documents) one by one.  round(v, m): v is an array of the 4 or 1 documents from m on.
+template <typename Round>
+__device__ __forceinline__ void float4_rounds(const float4 *s, int len, Round round)
+{
+    const int full = len - len % 4;
+    for (int m = 0; m < full; m += 4) {
+        float4 v[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = s[m + j];
+        round(v, m);
+    }
+    for (int m = full; m < len; ++m) {
+        const float4 v[1] = {s[m]};
+        round(v, m);
+    }
+}
+
+// The tile epilogue: the workgroup's loss in a fixed order, into part[b][tile].
+__device__ __forceinline__ void tile_loss(float ltot, float *red, float *part, const OwnerTile &t, int tiles)
+{
+    const float total = block_sum(ltot, red);
+    if (threadIdx.x == 0) part[(size_t)t.b * tiles + t.tile] = total;
+}
+
+// The finish kernels' loss of query b: the partials of the tiles below nb, in tile order.
+__device__ __forceinline__ float tile_loss_sum(const float *part, int b, int tiles, int nb)
+{
+    float total = 0.f;
+    for (int t = 0; t < long_pair_tiles(nb); ++t) total += part[(size_t)b * tiles + t];
+    return total;
+}
+
+// ---- the preparation of the NDCG-weighted losses: two sorts around the maxDCG tile partials ----
+struct RankedKeys { LongKeyParams k; const unsigned long long *sorted; };
+
+// The label sort (the ideal ranking: label keys, index words), the caller's launch partial(keys, sorted) that leaves
+// the maxDCG terms per epilogue tile in ws.part, then the ranking by score, ties in document-index order.
+template <typename Partial>
+RankedKeys long_ndcg_sorts(const float *scores, const void *rel, int rel_dtype, const int64_t *n, int B, int L,
+                           const LongWorkspace &ws, hipStream_t s, Partial partial)
+{
+    const LongKeyParams ik = long_key_params(nullptr, rel, rel_dtype, n, nullptr, 0, 0, nullptr, L, ws, s);
+    partial(ik, long_sort(ik, B, ws, nullptr, s));
+    const LongKeyParams sk = long_key_params(scores, rel, rel_dtype, n, nullptr, 0, 0, nullptr, L, ws, s);
+    return {sk, long_sort(sk, B, ws, nullptr, s)};
+}
+
+// The head of the epilogues over the sorted score keys: 1 / maxDCG of query q from its tile partials, added in tile
+// order by every thread; maxDCG == 0 -> 1 (pairwise_lambda.py:227).
+__device__ __forceinline__ float inv_maxdcg(const float *part, int q, int ptiles)
+{
+    float maxdcg = 0.f;
+    for (int i = 0; i < ptiles; ++i) maxdcg += part[(size_t)q * ptiles + i];
+    if (maxdcg == 0.0f) maxdcg = 1.0f;
+    return 1.0f / maxdcg;
+}
 
 // ---- preparation of the LambdaNDCG kinds from the sorted score keys ----
 // prep[b][doc] = (a_doc, 0) for LambdaNDCG1, (G_doc / maxDCG, rank_doc) for LambdaNDCG2 (prepare_ndcg's formulas);
@@ -45,14 +125,11 @@ longpair_prep_kernel(LongKeyParams k, const unsigned long long *__restrict__ sor
                      int ptiles, float2 *__restrict__ prep)
 {
     const EpiTile t = epi_tile(k, ptiles);
-    float maxdcg = 0.f;
-    for (int i = 0; i < ptiles; ++i) maxdcg += part[(size_t)t.q * ptiles + i];    // every thread, same order
-    if (maxdcg == 0.0f) maxdcg = 1.0f;                                            // pairwise_lambda.py:227
-    const float inv_maxdcg = 1.0f / maxdcg;
+    const float inv = inv_maxdcg(part, t.q, ptiles);
     for (int x = threadIdx.x; x < t.real; x += kEpiThreads) {
         const int r = t.r0 + x;
         const int doc = long_doc(k, sorted[t.base + r], t.seed);
-        const float G = ndcg_gain(load_label(k.rel, k.rel_dtype, t.base + doc)) * inv_maxdcg;
+        const float G = ndcg_gain(load_label(k.rel, k.rel_dtype, t.base + doc)) * inv;
         prep[t.base + doc] = KIND == LTR_NDCG1 ? make_float2(G * inv_discount((float)r), 0.f) : make_float2(G, (float)r);
     }
 }
@@ -86,13 +163,10 @@ longpair_tile_kernel(LossParams p, const float2 *__restrict__ prep, float *__res
     using Doc = typename PairDoc<KIND>::type;
     __shared__ __attribute__((aligned(16))) Doc s[kPairChunk];
     __shared__ float red[32];
-    const int b = blockIdx.x / tiles, tile = blockIdx.x - b * tiles;
-    const int tid = threadIdx.x;
-    const int L = p.L;
-    const int nb = clamp_n(p.n[b], L);
-    const int k0 = tile * kPairOwn;
-    if (k0 >= nb) return;                                   // uniform: the finish kernel never reads this tile
-    const size_t row = (size_t)b * L;
+    OwnerTile t;
+    if (!owner_tile(p.n, p.L, 0, tiles, t)) return;
+    const int tid = threadIdx.x, L = p.L, nb = t.nb, k0 = t.o0;
+    const size_t row = t.row;
     const float c1 = p.sigma * kLog2e;
     constexpr bool kAllPairs = KIND == LTR_ARP1 || KIND == LTR_NDCG1;
 
@@ -155,40 +229,33 @@ longpair_tile_kernel(LossParams p, const float2 *__restrict__ prep, float *__res
                 }
             }
         };
-        // wave-uniform LDS addresses (broadcast reads), four ds_read_b128 per round
-        constexpr int MU = (KIND == LTR_NDCG2) ? 4 : 8;    // documents per round
-        const float4 *s4 = reinterpret_cast<const float4 *>(s);
-        const int full = len - len % MU;
-        for (int m = 0; m < full; m += MU) {
-            float4 v[4];
+        if constexpr (KIND == LTR_NDCG2) {
+            float4_rounds(s, len, [&](const auto &v, int) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) v[j] = s4[(KIND == LTR_NDCG2 ? m : m / 2) + j];
+                for (const float4 &d : v) visit(d.x, d.y, d.z, d.w);
+            });
+        } else {
+            // the float2 kinds: eight documents per round of four ds_read_b128
+            const float4 *s4 = reinterpret_cast<const float4 *>(s);
+            const int full = len - len % 8;
+            for (int m = 0; m < full; m += 8) {
+                float4 v[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (KIND == LTR_NDCG2) {
-                    visit(v[j].x, v[j].y, v[j].z, v[j].w);
-                } else {
+                for (int j = 0; j < 4; ++j) v[j] = s4[m / 2 + j];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
                     visit(v[j].x, v[j].y, 0.f, 0.f);
                     visit(v[j].z, v[j].w, 0.f, 0.f);
                 }
             }
-        }
-        for (int m = full; m < len; ++m) {                  // remainder (< MU documents)
-            if constexpr (KIND == LTR_NDCG2) {
-                const float4 v = s[m];
-                visit(v.x, v.y, v.z, v.w);
-            } else {
-                const float2 v = s[m];
-                visit(v.x, v.y, 0.f, 0.f);
-            }
+            for (int m = full; m < len; ++m) visit(s[m].x, s[m].y, 0.f, 0.f);
         }
         ltot += lc;
 #pragma unroll
         for (int c = 0; c < kPairDpt; ++c) gk[c] += gc[c];
     }
 
-    const float total = block_sum(ltot, red);               // fixed order
-    if (tid == 0) part[(size_t)b * tiles + tile] = total;
+    tile_loss(ltot, red, part, t, tiles);
     if (p.dscores != nullptr) {
 #pragma unroll
         for (int c = 0; c < kPairDpt; ++c) {
@@ -207,9 +274,7 @@ longpair_finish_kernel(LossParams p, const float *__restrict__ part, int tiles)
     const int b = blockIdx.x;
     const int L = p.L;
     const int nb = clamp_n(p.n[b], L);
-    const int used = (nb + kPairOwn - 1) / kPairOwn;
-    float total = 0.f;
-    for (int t = 0; t < used; ++t) total += part[(size_t)b * tiles + t];          // every thread, same order
+    float total = tile_loss_sum(part, b, tiles, nb);        // every thread, same order
     float gscale = 1.0f;
     if (KIND == LTR_DCG_HINGE) {
         const float lg = logf(2.0f + total);
@@ -248,39 +313,27 @@ inline LongPairWorkspace long_pair_workspace(Carver &c, int kind, int B, int L)
 }
 
 template <int KIND>
-int launch_long_pair_prep(const LossParams &p, const LongPairWorkspace &w, hipStream_t s)
+void launch_long_pair_prep(const LossParams &p, const LongPairWorkspace &w, hipStream_t s)
 {
-    constexpr int PK = (KIND == LTR_NDCG1 || KIND == LTR_NDCG2) ? KIND : LTR_NDCG1;
-    const int B = p.B, L = p.L;
-    if (L <= kLossSymMaxLen && !long_path(L)) {
-        // (the lengths the split-query launch runs it on)
-        const size_t plds = loss_lds_bytes(PK, (L + 63) & ~63, ((L + 63) & ~63) > kSymMaxLen ? 4 : 16);
-        LTR_ENSURE_LDS((ndcg_prepare_kernel<PK>), plds);
-        hipLaunchKernelGGL((ndcg_prepare_kernel<PK>), dim3((unsigned)B), dim3(1024), plds, s, p, w.prep);
-        return LTR_OK;
-    }
-    const int etiles = long_epi_tiles(L);
+    const int B = p.B, etiles = long_epi_tiles(p.L);
     const dim3 grid((unsigned)((size_t)B * etiles)), block(kEpiThreads);
-    // maxDCG: the ideal ranking (label keys, index words) and its DCG terms over the real documents, per tile
-    LongMetricParams ip{};
-    ip.k = long_key_params(nullptr, p.rel, p.rel_dtype, p.n, nullptr, 0, 0, nullptr, L, w.sort, s);
-    ip.ideal = 1; ip.use_exp = 1; ip.lim = -1;
-    ip.tiles = ip.ptiles = etiles;
-    ip.part = w.sort.part;
-    ip.sorted = long_sort(ip.k, B, w.sort, nullptr, s);
-    hipLaunchKernelGGL(longsort_partial_kernel<METRIC_DCG>, grid, block, 0, s, ip);
-    // the ranking by score, ties in document-index order
-    const LongKeyParams sk = long_key_params(p.scores, p.rel, p.rel_dtype, p.n, nullptr, 0, 0, nullptr, L, w.sort, s);
-    const unsigned long long *sorted = long_sort(sk, B, w.sort, nullptr, s);
-    hipLaunchKernelGGL((longpair_prep_kernel<PK>), grid, block, 0, s, sk, sorted, (const float *)w.sort.part, etiles, w.prep);
-    return LTR_OK;
+    // maxDCG: the DCG terms of the ideal ranking over the real documents, per tile
+    const RankedKeys r = long_ndcg_sorts(p.scores, p.rel, p.rel_dtype, p.n, B, p.L, w.sort, s,
+                                         [&](const LongKeyParams &ik, const unsigned long long *ideal) {
+        LongMetricParams ip{};
+        ip.k = ik; ip.sorted = ideal;
+        ip.ideal = 1; ip.use_exp = 1; ip.lim = -1;
+        ip.tiles = ip.ptiles = etiles;
+        ip.part = w.sort.part;
+        hipLaunchKernelGGL(longsort_partial_kernel<METRIC_DCG>, grid, block, 0, s, ip);
+    });
+    hipLaunchKernelGGL((longpair_prep_kernel<KIND>), grid, block, 0, s, r.k, r.sorted, (const float *)w.sort.part, etiles, w.prep);
 }
 
 template <int KIND>
 int launch_long_pair(const LossParams &p, const LongPairWorkspace &w, hipStream_t s)
 {
-    if (KIND == LTR_NDCG1 || KIND == LTR_NDCG2)
-        if (const int rc = launch_long_pair_prep<KIND>(p, w, s)) return rc;
+    if constexpr (KIND == LTR_NDCG1 || KIND == LTR_NDCG2) launch_long_pair_prep<KIND>(p, w, s);
     const int tiles = long_pair_tiles(p.L);
     hipLaunchKernelGGL((longpair_tile_kernel<KIND>), dim3((unsigned)((size_t)p.B * tiles)), dim3(kPairThreads), 0, s, p,
                        (const float2 *)w.prep, w.part, tiles);

@@ -95,8 +95,7 @@ class _LambdaRankFunction(_torch.autograd.Function):
             with _C.device_ctx(s):
                 if L > _C.max_list_len():
                     # past one workgroup's LDS: everything by rank in a workspace, owner tiles against the streamed anchors
-                    ws_bytes = int(lib.ltr_lambdarank_long_workspace_bytes(kk, B, L))
-                    ws = _torch.empty(ws_bytes, dtype=_torch.uint8, device=s.device)
+                    ws, ws_bytes = _C.workspace(lib.ltr_lambdarank_long_workspace_bytes(kk, B, L), s.device)
                     _C.check(lib.ltr_lambdarank_long_f32(_C.ptr(s), _C.ptr(r), _C.label_dtype(r), _C.ptr(nn), kk,
                                                          float(sigma), B, L, _C.ptr(loss), _C.ptr(ds), _C.ptr(ws), ws_bytes,
                                                          _C.stream_of(s)))

@@ -189,8 +189,8 @@ def test_loss_only_narrow_workgroups(mode):
 @pytest.mark.parametrize("sorted_preparation", [False, True], ids=["prepare_kernel", "sorted_preparation"])
 def test_loss_only_forced_long_pair_path(sorted_preparation, mode):
     """ltr_pairwise_loss_long_f32 forced onto lists of 300 documents: the owner tiles against the streamed query behind
-    ndcg_prepare_kernel (what the long path launches below 2048 documents) and, under ltr_debug_long_sort_all, behind the
-    key sort and the label sort with ltr_longpair.inc's own maxDCG from the tile partials."""
+    the key sort and the label sort with ltr_longpair.inc's own maxDCG from the tile partials -- the long path's one
+    preparation, so both ids run it, the second with ltr_debug_long_sort_all set as well."""
     from pytorchltr_amd import _C
     lib = _C.lib()
     prev = lib.ltr_debug_long_pairs_all(1)

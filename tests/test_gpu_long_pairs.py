@@ -154,8 +154,9 @@ def test_forced_long_path_vs_existing_kernels(kind):
 
 @pytest.mark.parametrize("kind", ["ndcg1", "ndcg2"])
 def test_sorted_preparation_vs_ndcg_prepare_kernel(kind):
-    """Below 2048 documents the forced long path launches ndcg_prepare_kernel; under ltr_debug_long_sort_all it takes the
-    key sort and the label sort instead -- both against the one-workgroup kernels, at a length of more than one tile."""
+    """The long path prepares the LambdaNDCG kinds from the key sort and the label sort at every length (the forced
+    lengths of test_forced_long_path_vs_existing_kernels included); here once more with ltr_debug_long_sort_all set,
+    against the one-workgroup kernels and their ndcg_prepare_kernel, at a length of more than one tile."""
     from pytorchltr_amd import _C
     own, _ = _C.long_pair_geometry()
     _forced_vs_existing(kind, own + 1, sort_all=True)

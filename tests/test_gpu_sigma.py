@@ -40,7 +40,7 @@ Which case reaches which sigma site (each case asserts its plan, workspace or ho
                                       documents), the plain one (logistic, arp1, arp2 on every parts shape) and the polling one
                                       (kPollInPass: the hinge kinds in the one-sided kernel on lists of several parts,
                                       24 x 420 x 16 -- sigma is handed over and must be ignored, check (c))
-  ltr_longpair.inc c1 and finisher    test_loss_only_forced_long_pair_path (both preparations), test_loss_only_long_pair_path_past_the_limit
+  ltr_longpair.inc c1 and finisher    test_loss_only_forced_long_pair_path (both ids), test_loss_only_long_pair_path_past_the_limit
   ltr_f64.inc                         test_loss_only_fp64_scores
   past the fused MLP limit            test_mlp_step_past_the_fused_limit: the stand-alone loss kernel between the row kernels
 """
@@ -162,7 +162,8 @@ def test_loss_only_narrow_workgroups():
 @pytest.mark.parametrize("sorted_preparation", [False, True], ids=["prepare_kernel", "sorted_preparation"])
 def test_loss_only_forced_long_pair_path(sorted_preparation):
     """ltr_pairwise_loss_long_f32 forced onto lists of 300 documents (ltr_longpair.inc: its own c1 in the tile kernel, its
-    own sigma / ln 2 in the finisher), behind ndcg_prepare_kernel and, under ltr_debug_long_sort_all, behind the sorts."""
+    own sigma / ln 2 in the finisher), behind the two sorts -- the long path's one preparation, so both ids run it, the
+    second with ltr_debug_long_sort_all set as well."""
     from pytorchltr_amd import _C
     lib = _C.lib()
     prev = lib.ltr_debug_long_pairs_all(1)
