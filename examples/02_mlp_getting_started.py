@@ -10,10 +10,11 @@ split of the same shape (136 features, ragged queries, 5 relevance grades that d
 features through a fixed random network), so the printed ndcg@10 must RISE from its untrained
 value.  Pass an SVMrank file pair to train on real data instead:
 
-    python examples/02_mlp_getting_started.py [--loss {hinge,listnet,listmle}] [train.txt test.txt]
+    python examples/02_mlp_getting_started.py [--loss {hinge,listnet,listmle,lambdarank}] [train.txt test.txt]
 
 --loss listnet / listmle trains the same network on a listwise loss (FusedMLPListwiseLoss: the same kernel with
-ListNet or ListMLE in its loss slot); the default is the guide's hinge loss.
+ListNet or ListMLE in its loss slot), --loss lambdarank on LambdaRank with the NDCG@10 swap weights
+(FusedMLPLambdaRankLoss, k = 10: the metric this script reports); the default is the guide's hinge loss.
 """
 import argparse
 import os
@@ -25,7 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from pytorchltr_amd.datasets import RaggedQueries, UniformSampler, load_svmrank  # noqa: E402
 from pytorchltr_amd.evaluation import ndcg  # noqa: E402
-from pytorchltr_amd.fused import FusedMLPListwiseLoss, FusedMLPLoss  # noqa: E402
+from pytorchltr_amd.fused import FusedMLPLambdaRankLoss, FusedMLPListwiseLoss, FusedMLPLoss  # noqa: E402
 from pytorchltr_amd.loss import PairwiseHingeLoss  # noqa: E402
 
 
@@ -52,6 +53,8 @@ def run(train_path=None, test_path=None, epochs=5, device="cuda", log=print, los
         test = synthetic_split(200, 136, 2, device)
     if loss == "hinge":
         model = FusedMLPLoss(train.features.shape[1], PairwiseHingeLoss()).to(device)
+    elif loss == "lambdarank":
+        model = FusedMLPLambdaRankLoss(train.features.shape[1], k=10).to(device)
     else:
         model = FusedMLPListwiseLoss(train.features.shape[1], loss=loss).to(device)
     optimizer = torch.optim.Adagrad(model.parameters(), lr=0.1)
@@ -83,7 +86,7 @@ def run(train_path=None, test_path=None, epochs=5, device="cuda", log=print, los
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("--loss", choices=("hinge", "listnet", "listmle"), default="hinge")
+    ap.add_argument("--loss", choices=("hinge", "listnet", "listmle", "lambdarank"), default="hinge")
     ap.add_argument("files", nargs="*", help="train.txt test.txt (SVMrank); default: a synthetic split")
     args = ap.parse_args()
     run(*(args.files[:2] if len(args.files) >= 2 else ()), loss=args.loss)

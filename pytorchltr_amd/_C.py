@@ -148,6 +148,12 @@ LAMBDARANK_SIGNATURES = {
     "ltr_linear_lambdarank_partials_f32": (_i, [_i, _f, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
 }
 
+# name -> (restype, argtypes); mirrors include/ltr_mlp_lambdarank.h (the fused MLP step with LambdaRank in its loss slot)
+MLP_LAMBDARANK_SIGNATURES = {
+    "ltr_mlp_lambdarank_plan": (_i, [_i, _i, _i, _i, _i]),
+    "ltr_mlp_lambdarank_f32": (_i, [_i, _f] + [_vp] * 7 + [_vp, _i, _vp, _vp] + [_i] * 5 + [_vp] * 5 + [_sz, _vp]),
+}
+
 # name -> (restype, argtypes); mirrors include/ltr_mlp_rows.h (the MLP scorer on its own: scores and gradients, any length)
 MLP_ROWS_SIGNATURES = {
     "ltr_mlp_rows_scores_f32": (_i, [_vp] * 8 + [_i] * 5 + [_vp, _vp]),
@@ -238,6 +244,7 @@ def lib():
         for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(EVAL_SIGNATURES.items())
                                           + list(LISTWISE_SIGNATURES.items()) + list(LAMBDARANK_SIGNATURES.items())
                                           + list(LONGPAIR_SIGNATURES.items()) + list(LAMBDARANK_LONG_SIGNATURES.items())
+                                          + list(MLP_LAMBDARANK_SIGNATURES.items())
                                           + list(MLP_ROWS_SIGNATURES.items()) + list(MLP_WIDE_SIGNATURES.items())
                                           + list(MLP_BF16_SIGNATURES.items()) + list(LINEAR_BF16_SIGNATURES.items())
                                           + list(SCHED_SIGNATURES.items())):

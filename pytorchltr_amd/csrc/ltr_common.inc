@@ -665,15 +665,17 @@ __host__ __device__ constexpr size_t ndcg2_delta_floats(size_t L4)
 // the MLP kernels' KIND parameter, never part of the C ABI (whose listwise codes are LTR_LISTWISE_*, ltr_listwise.h).
 constexpr int LTR_MLP_LISTNET = 16;
 constexpr int LTR_MLP_LISTMLE = 17;
+constexpr int LTR_MLP_LAMBDARANK = 18;     // (ltr_mlp_lambdarank_f32, include/ltr_mlp_lambdarank.h)
 constexpr size_t kRowScratchBytes = (32 + 64) * 4;      // red + scan of the ranked-row layout (ltr_ranked.inc)
 
 __host__ __device__ constexpr size_t loss_lds_bytes(int kind, int L, int msplit)
 {
     const size_t L4 = (size_t)((L + 3) & ~3);
     // the listwise slot of the MLP kernels: ListNet keeps sy and the reduction scratch, ListMLE the whole ranked-row
-    // layout of the counting rank (ranked_row_layout(L, false).end: sy, two rank arrays, 16 B of keys per document)
+    // layout of the counting rank (ranked_row_layout(L, false).end: sy, two rank arrays, 16 B of keys per document),
+    // and so does LambdaRank
     if (kind == LTR_MLP_LISTNET) return 8 * L4 + kRowScratchBytes;
-    if (kind == LTR_MLP_LISTMLE) return 32 * L4 + kRowScratchBytes;
+    if (kind == LTR_MLP_LISTMLE || kind == LTR_MLP_LAMBDARANK) return 32 * L4 + kRowScratchBytes;
     size_t bytes = 8 * L4;
     if (kind == LTR_NDCG2) bytes += 16 * L4 + 4 * ndcg2_delta_floats(L4);
     size_t g = 4 * L4 * (size_t)msplit;
@@ -703,8 +705,9 @@ __device__ __forceinline__ QueryLds carve_query_lds(unsigned char *base, int L4,
     unsigned char *cur = base + 8 * (size_t)L4;
     q.q4 = nullptr;
     q.delta = nullptr;
-    if (KIND == LTR_MLP_LISTNET || KIND == LTR_MLP_LISTMLE) {
-        // (label, score) pairs in sy; the rest of the block is carved by mlp_listwise_slot (ltr_mlp_listwise.inc)
+    if (KIND == LTR_MLP_LISTNET || KIND == LTR_MLP_LISTMLE || KIND == LTR_MLP_LAMBDARANK) {
+        // (label, score) pairs in sy -- LambdaRank: (score, label); the rest of the block is carved by the listwise
+        // slot (mlp_listwise_slot / mlp_lambdarank_slot, ltr_mlp_listwise.inc)
         q.gpart = nullptr; q.rank_s = nullptr; q.rank_y = nullptr; q.gbytes = 0;
         q.red = nullptr;
         return q;

@@ -1,7 +1,8 @@
 // ltr_lambdarank_row.inc -- the LambdaRank (NDCG@k swap weights) row of one staged query on the ranked-row core's LDS
-// layout (ltr_ranked.inc).  Included by ltr_linear_listwise.inc (the loss slot of the fused Linear step) and, through
-// it, by ltr_lambdarank.inc (lambdarank_kernel).  The loss, the passes and their orders are described at the top of
-// ltr_lambdarank.inc.
+// layout (ltr_ranked.inc), which is all it needs in front of it.  Included by ltr_linear_listwise.inc (the loss slot of
+// the fused Linear step) and, through it, by ltr_lambdarank.inc (lambdarank_kernel); and by ltr_mlp.hip (the loss slot
+// of the fused MLP step, mlp_lambdarank_slot in ltr_mlp_listwise.inc).  The loss, the passes and their orders are
+// described at the top of ltr_lambdarank.inc.
 #pragma once
 
 namespace {

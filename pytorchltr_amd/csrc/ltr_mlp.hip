@@ -3,7 +3,7 @@
 // wide rows: ltr_mlp_wide.inc) and the stand-alone Linear scorer on f32 and bf16 rows (ltr_scorer.inc: one streaming layer
 // under both element types, which shares the MLP's reduction kernel).
 #include "ltr_common.inc"
-// the listwise slot of the training step: the ranked row (layout, ranking, scans) and the ListMLE row function
+// the listwise slot of the training step: the ranked row (layout, ranking, scans), the ListMLE and LambdaRank row functions
 #define LTR_RANKED_ROW_ONLY
 // In this translation unit the row helpers read the thread index through an empty asm (row_tid(), ltr_ranked.inc).  As
 // plain threadIdx.x reads their lane-derived LDS addresses are loop invariants of the MLP kernels' query loop: hoisted
@@ -13,6 +13,7 @@
 #define LTR_ROW_TID_OPAQUE
 #include "ltr_ranked.inc"
 #include "ltr_listmle_row.inc"
+#include "ltr_lambdarank_row.inc"
 #include "ltr_mlp.inc"
 #include "ltr_mlp_stream.inc"
 #include "ltr_mlp_rows.inc"

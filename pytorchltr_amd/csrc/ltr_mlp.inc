@@ -34,6 +34,7 @@
 #include <type_traits>
 
 #include "ltr_listwise.h"
+#include "ltr_mlp_lambdarank.h"
 #include "ltr_mlp_listwise.inc"
 
 typedef float mlp_f4 __attribute__((ext_vector_type(4)));
@@ -63,7 +64,7 @@ struct MlpParams {
     int P;                           // parameter count = length of one partial vector
     int pitch;                       // floats between consecutive partial vectors (P rounded up to 4)
     int fwd_only;                    // 1: scores only (evaluation) -- no pair pass, no backward
-    MlpListwiseArgs lw{};            // KIND = LTR_MLP_LISTNET / LTR_MLP_LISTMLE only (ltr_mlp_listwise.inc)
+    MlpListwiseArgs lw{};            // KIND = LTR_MLP_LISTNET / LTR_MLP_LISTMLE, and LTR_MLP_LAMBDARANK's k (ltr_mlp_listwise.inc)
 };
 
 __host__ __device__ inline int mlp_param_count(int F, int H1, int H2)
@@ -326,6 +327,7 @@ mlp_pairwise_kernel(MlpParams p)
     constexpr int FS = 16 * NT + 4;                 // LDS pitch of W1 (zero padded to the bucket)
     constexpr int Lt = kMlpMaxLen;
     constexpr bool kListwise = KIND == LTR_MLP_LISTNET || KIND == LTR_MLP_LISTMLE;   // sy holds (label, score)
+    constexpr bool kLambdaRank = KIND == LTR_MLP_LAMBDARANK;                         // (score, label), its own slot
 
     float *W1s = reinterpret_cast<float *>(smem);                 // [64][FS]
     float *H1s = W1s + (size_t)kMlpH1 * FS;                       // [128][72]  H1, later dH1
@@ -555,6 +557,9 @@ mlp_pairwise_kernel(MlpParams p)
         if constexpr (kListwise) {
             mlp_listwise_slot<KIND, T, Lt>(smem + qoff, p.lw, nb, p.grad_out ? p.grad_out[b] : 1.0f / (float)p.B,
                                            p.loss + b, gfin);
+        } else if constexpr (kLambdaRank) {
+            mlp_lambdarank_slot<T, Lt>(smem + qoff, p.lw.k, p.sigma, nb, p.grad_out ? p.grad_out[b] : 1.0f / (float)p.B,
+                                       p.loss + b, gfin);
         } else {
             float gscale;
             if (KIND == LTR_NDCG1 || KIND == LTR_NDCG2) {
@@ -1022,15 +1027,20 @@ inline bool bad_mlp_listwise_loss(int loss) { return loss != LTR_LISTWISE_LISTNE
 
 // The plan rule behind the shape checks: the list fits the layouts that take F, and the LDS of every layout the call
 // may be steered to (ltr_debug_mlp_layout) -- the static part and the loss slot's row -- fits the workgroup.
-inline bool mlp_listwise_fits(int loss, int L, int F)
+// (`kind`: LTR_MLP_LISTNET, LTR_MLP_LISTMLE or LTR_MLP_LAMBDARANK)
+inline bool mlp_slot_fits(int kind, int L, int F)
 {
-    const int kind = loss == LTR_LISTWISE_LISTNET ? LTR_MLP_LISTNET : LTR_MLP_LISTMLE;
     if (L > (mlp2_takes(F) ? kM2MaxLen : kMlpMaxLen)) return false;
     if (mlp2_takes(F) &&
         mlp2_lds_bytes(kind, mlp_bucket(F), L <= kM2ParkLen ? kM2ParkLen : kM2MaxLen) > kLdsBudget / kM2Wgs)
         return false;
     if (L <= kMlpMaxLen && mlp_lds_bytes(kind, F) > kLdsBudget) return false;
     return true;
+}
+
+inline bool mlp_listwise_fits(int loss, int L, int F)
+{
+    return mlp_slot_fits(loss == LTR_LISTWISE_LISTNET ? LTR_MLP_LISTNET : LTR_MLP_LISTMLE, L, F);
 }
 
 // B, L, the network and its limits as every launching entry point of this file checks them
@@ -1144,6 +1154,42 @@ int ltr_mlp_listwise_f32(int loss, int k, const float *X, const float *W1, const
         rc = tile ? launch_mlp2_kind<LTR_MLP_LISTNET>(p, grid, s) : launch_mlp_kind<LTR_MLP_LISTNET>(p, grid, s);
     else
         rc = tile ? launch_mlp2_kind<LTR_MLP_LISTMLE>(p, grid, s) : launch_mlp_kind<LTR_MLP_LISTMLE>(p, grid, s);
+    if (rc != 0) return rc;
+    return mlp_reduce_launch(workspace, grid, P, grads, loss_out, B, loss_sum, s);
+}
+
+// ---- the LambdaRank step (include/ltr_mlp_lambdarank.h; DESIGN.md 27) ----
+int ltr_mlp_lambdarank_plan(int B, int L, int F, int H1, int H2)
+{
+    if (B <= 0 || L <= 0 || H1 <= 0 || H2 <= 0 || H1 > kMlpH1 || H2 > kMlpH2) return 0;
+    if (F <= 0 || (F & 3) || F > 16 * 14) return 0;
+    return mlp_slot_fits(LTR_MLP_LAMBDARANK, L, F) ? 1 : 0;
+}
+
+int ltr_mlp_lambdarank_f32(int k, float sigma, const float *X, const float *W1, const float *b1, const float *W2,
+                           const float *b2, const float *W3, const float *b3, const void *rel, int rel_dtype,
+                           const int64_t *n, const float *grad_out, int B, int L, int F, int H1, int H2, float *loss_out,
+                           float *scores_out, float *grads, float *loss_sum, void *workspace, size_t workspace_bytes,
+                           void *stream)
+{
+    LTR_CLEAR_STALE_ERROR();
+    if (bad_label_dtype(rel_dtype)) return LTR_ERR_KIND;
+    // (sigma: the guard of ltr_lambdarank_f32, check_lambdarank in ltr_lambdarank.inc)
+    if (mlp_step_bad_network(B, L, F, H1, H2) || !std::isfinite(sigma)) return LTR_ERR_SHAPE;
+    if (L > (mlp2_takes(F) ? kM2MaxLen : kMlpMaxLen)) return LTR_ERR_LIST_TOO_LONG;
+    if (B == 0) return LTR_OK;
+    if (!X || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !rel || !n || !loss_out || !grads) return LTR_ERR_NULL;
+    const int P = mlp_param_count(F, H1, H2);
+    const bool tile = mlp_use_tile_layout(F, B, L);
+    const int grid = tile ? mlp2_grid(B) : mlp_grid(B);
+    if (!workspace || workspace_bytes < (size_t)grid * mlp_pitch(P) * sizeof(float)) return LTR_ERR_WORKSPACE;
+    if (!mlp_slot_fits(LTR_MLP_LAMBDARANK, L, F)) return LTR_ERR_CONFIG;
+    hipStream_t s = (hipStream_t)stream;
+    MlpParams p = mlp_step_params(X, W1, b1, W2, b2, W3, b3, n, B, L, F, H1, H2);
+    p.rel = rel; p.rel_dtype = rel_dtype; p.grad_out = grad_out; p.sigma = sigma;
+    p.loss = loss_out; p.scores_out = scores_out; p.part = (float *)workspace;
+    p.lw.k = k;
+    const int rc = tile ? launch_mlp2_kind<LTR_MLP_LAMBDARANK>(p, grid, s) : launch_mlp_kind<LTR_MLP_LAMBDARANK>(p, grid, s);
     if (rc != 0) return rc;
     return mlp_reduce_launch(workspace, grid, P, grads, loss_out, B, loss_sum, s);
 }

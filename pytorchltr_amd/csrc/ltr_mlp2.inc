@@ -111,6 +111,7 @@ mlp_tile_kernel(MlpParams p)
     constexpr int IP = 16 * NT + 4;                 // image pitch (floats): odd number of 16-byte units
     constexpr int Lt = LT;
     constexpr bool kListwise = KIND == LTR_MLP_LISTNET || KIND == LTR_MLP_LISTMLE;   // sy holds (label, score)
+    constexpr bool kLambdaRank = KIND == LTR_MLP_LAMBDARANK;                         // (score, label), its own slot
     constexpr bool kPark = LT <= kM2ParkLen;        // else: forward again in the backward pass
     constexpr int kSlots = kPark ? kM2ParkLen / kM2Docs - 1 : 0;
     constexpr int KP = (kM2Docs * 4 * NT + T - 1) / T;     // float4 units of a fill per thread
@@ -353,7 +354,7 @@ mlp_tile_kernel(MlpParams p)
         // loop as well, the register allocator spills (ListNet at F = 136: 6 VGPRs, ListMLE: 28).  Opaque lane indices
         // keep the address arithmetic inside the loop: a few VALU instructions per query, no spill (the row functions'
         // own reads of the thread index: ltr_mlp.hip).
-        if constexpr (kListwise) asm volatile("" : "+v"(c16), "+v"(g), "+v"(tid));
+        if constexpr (kListwise || kLambdaRank) asm volatile("" : "+v"(c16), "+v"(g), "+v"(tid));
         const int b = __builtin_amdgcn_readfirstlane(query_at(qi));
         const int nb = __builtin_amdgcn_readfirstlane(nb_next);
         const size_t row0 = (size_t)b * L;
@@ -434,6 +435,9 @@ mlp_tile_kernel(MlpParams p)
         if constexpr (kListwise) {
             mlp_listwise_slot<KIND, T, Lt>(smem + qoff, p.lw, nb, p.grad_out ? p.grad_out[b] : 1.0f / (float)p.B,
                                            p.loss + b, gfin);
+        } else if constexpr (kLambdaRank) {
+            mlp_lambdarank_slot<T, Lt>(smem + qoff, p.lw.k, p.sigma, nb, p.grad_out ? p.grad_out[b] : 1.0f / (float)p.B,
+                                       p.loss + b, gfin);
         } else {
             float gscale;
             if (KIND == LTR_NDCG1 || KIND == LTR_NDCG2) {

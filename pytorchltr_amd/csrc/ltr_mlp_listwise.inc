@@ -9,8 +9,10 @@
 //            ranked-row layout (ranked_row_lds) carved where the pairwise kinds keep their QueryLds; the ranking is the
 //            counting rank (DPT = 1) with the workgroup cut into owners x slices by the query's own length;
 //   ListNet  workgroup-wide max / sum of the scores and the labels (phase 2 of linear_listwise_kernel).
+// KIND = LTR_MLP_LAMBDARANK (C ABI: ltr_mlp_lambdarank_f32, include/ltr_mlp_lambdarank.h; DESIGN.md 27) takes
+// mlp_lambdarank_slot: lambdarank_row (ltr_lambdarank_row.inc) on the same layout and workgroup cut as ListMLE.
 // The forward chain stages (label, score) pairs -- sy[j].x the label, sy[j].y the score -- where the pairwise kinds
-// stage (score, label): that is the order the row functions read.  The row functions synchronise with __syncthreads();
+// and LambdaRank stage (score, label): that is the order the row functions read.  The row functions synchronise with __syncthreads();
 // the slot's own last barrier is the caller's lds_barrier().  No atomics on floats, every sum in a fixed order.
 #pragma once
 
@@ -20,13 +22,16 @@ struct MlpListwiseArgs {
     const int64_t *tie_seed_dev;
     unsigned long long tie_seed;
     int use_seed;
-    int k;                           // ListMLE: <= 0 every factor
+    int k;                           // ListMLE: <= 0 every factor; LambdaRank: <= 0 no cutoff
 };
 
 // the slot carves ranked_row_lds where loss_lds_bytes reserved room for it
 static_assert(ranked_row_layout(128, false).end == loss_lds_bytes(LTR_MLP_LISTMLE, 128, 4) &&
               ranked_row_layout(256, false).end == loss_lds_bytes(LTR_MLP_LISTMLE, 256, 4),
               "loss_lds_bytes(LTR_MLP_LISTMLE) is the ranked-row layout of the counting rank");
+static_assert(ranked_row_layout(128, false).end == loss_lds_bytes(LTR_MLP_LAMBDARANK, 128, 4) &&
+              ranked_row_layout(256, false).end == loss_lds_bytes(LTR_MLP_LAMBDARANK, 256, 4),
+              "loss_lds_bytes(LTR_MLP_LAMBDARANK) is the ranked-row layout of the counting rank");
 
 struct MlpOpMax { static constexpr float id = -INFINITY; static __device__ __forceinline__ float f(float a, float b) { return fmaxf(a, b); } };
 
@@ -83,4 +88,24 @@ __device__ __forceinline__ void mlp_listwise_slot(unsigned char *qbase, const Ml
         }
         if (tid == 0) *loss = nb > 0 ? (logf(zs) - dot * inv_zy) : 0.f;
     }
+}
+
+// The slot of KIND = LTR_MLP_LAMBDARANK (ltr_mlp_lambdarank_f32; DESIGN.md 27): lambdarank_row, the row function of
+// lambdarank_kernel and of the fused Linear step, on the same ranked-row layout and with the same owners x slices cut
+// as ListMLE above.  nb <= LT documents staged as (score, label); ties in document-index order (no tie words); k <= 0:
+// no cutoff.  The row leaves the gradient by rank, in units of the loss, in the rank_y slot.  Same barrier contract.
+template <int T, int LT>
+__device__ __forceinline__ void mlp_lambdarank_slot(unsigned char *qbase, int k, float sigma, int nb, float weight,
+                                                    float *loss, float *gfin)
+{
+    const int tid = row_tid();
+    const RankedRowLds r = ranked_row_lds(qbase, LT, false);
+    MetricParams m{};
+    m.L = LT;
+    const int owners = nb <= 64 ? 64 : (nb <= 128 ? 128 : 256);
+    m.msplit = T / (owners < T ? owners : T);
+    const int K = k > 0 ? min(k, nb) : nb;
+    lambdarank_row<1>(m, r, nb, K, sigma, loss, true);
+    const float *gr = reinterpret_cast<const float *>(r.rank_y);
+    for (int j = tid; j < LT; j += T) gfin[j] = j < nb ? gr[r.rank_s[j]] * weight : 0.f;
 }

@@ -999,6 +999,14 @@ def mlp_listwise_supported(kind, B, L, F, H1, H2):
     return B == 0 or bool(_C.lib().ltr_mlp_listwise_plan(kind.loss, B, L, F, H1, H2))
 
 
+def mlp_lambdarank_supported(B, L, F, H1, H2):
+    """True where the fused MLP kernels take LambdaRank at this shape (ltr_mlp_lambdarank_plan: the shapes of
+    :func:`mlp_listwise_supported`).  An empty batch counts as taken."""
+    if not mlp_supported(L, F, H1, H2):
+        return False
+    return B == 0 or bool(_C.lib().ltr_mlp_lambdarank_plan(B, L, F, H1, H2))
+
+
 _mlp_rows_ws = {}        # (device index, B, L, F, H1, H2, family) -> *_grad_workspace_bytes (grows with the CU count)
 
 
@@ -1198,7 +1206,7 @@ def _f4(F):
 
 def _mlp_route(caller, dtype, dim, is_cuda, requires_grad, grad_enabled, autocast, L, F, H1, H2, kind=None, plan=True):
     """Which kernels compute ``mlp(xs)`` (and, for a caller with a loss `kind`, the step): plain values in, one of
-    _FUSED (the one-launch step, ltr_mlp_pairwise_f32 / ltr_mlp_listwise_f32), _PER_QUERY (ltr_mlp_scores_f32), _ROWS,
+    _FUSED (the one-launch step, ltr_mlp_pairwise_f32 / ltr_mlp_listwise_f32 / ltr_mlp_lambdarank_f32), _PER_QUERY (ltr_mlp_scores_f32), _ROWS,
     _WIDE, _BF16 (the three families) or _TORCH out -- the three ``nn.Linear`` layers in a module, ValueError in a
     function, which has none.  A family's ValueError (bf16: a network it does not take) is raised by `_mlp_prepare`.
 
@@ -1248,7 +1256,7 @@ def _mlp_step_pieces(X, flat_params, H1, H2, relevance, n, kind, sigma, grad_out
     scores = _mlp_rows_scores(X, flat_params, H1, H2, nn)       # (a bf16 X: the bf16 kernels, here and below)
     with torch.enable_grad():
         s = scores.unsqueeze(-1).requires_grad_(True)
-        lossv = (_listwise_pieces(s, r, nn, kind) if isinstance(kind, _ListwiseKind)
+        lossv = (_listwise_pieces(s, r, nn, kind, sigma) if isinstance(kind, _ListwiseKind)
                  else _pairwise_pieces(s, r, nn, kind, sigma))
         go = (torch.full((B,), 1.0 / max(B, 1), dtype=torch.float32, device=dev) if grad_out is None
               else grad_out.reshape(B).float())
@@ -1288,12 +1296,40 @@ def mlp_loss_step(xs, params, relevance, n, loss="hinge", grad_out=None, return_
         (valid for documents < n only) and ``loss_sum`` (1,).
     """
     kind, sigma = _resolve_loss(loss)
+    if isinstance(kind, _ListwiseKind) and kind.loss == _C.LISTWISE_LAMBDARANK:
+        raise TypeError("mlp_loss_step has no LambdaRank slot: take mlp_lambdarank_step (the module: "
+                        "FusedMLPLambdaRankLoss), or the Linear scorer: FusedLinearLoss, linear_loss_step, LinearScorer")
+    return _mlp_step(xs, params, relevance, n, kind, sigma, grad_out, return_scores, return_loss_sum, out)
+
+
+def mlp_lambdarank_step(xs, params, relevance, n, sigma=1.0, k=None, grad_out=None, return_scores=False,
+                        return_loss_sum=False, out=None):
+    """:func:`mlp_loss_step` for LambdaRank (:class:`pytorchltr_amd.loss.LambdaRankLoss` ``(sigma, k)``): one fused
+    forward+backward step of ``LambdaRankLoss(sigma, k)(mlp(xs), relevance, n)`` without autograd, by
+    ``ltr_mlp_lambdarank_f32`` (include/ltr_mlp_lambdarank.h) -- the NDCG@k swap weights and the top-k pair pass in the
+    loss slot of the two fused MLP kernels.  ``k=None``: no cutoff.  The other arguments, the returned tuple and the
+    shapes are those of :func:`mlp_loss_step`; off the plan (:func:`mlp_lambdarank_supported`: longer lists, a
+    ``torch.bfloat16`` batch) the step runs as the three pieces -- the row score kernel, the stand-alone LambdaRank
+    kernel (past ``max_list_len()`` documents its long path), the row gradient kernel."""
+    from .loss import pairwise_lambda as _pl
+    k = _pl.LambdaRankLoss(sigma, k).k                      # (its check of k)
+    return _mlp_step(xs, params, relevance, n, _ListwiseKind(_C.LISTWISE_LAMBDARANK, k), float(sigma), grad_out,
+                     return_scores, return_loss_sum, out)
+
+
+def _mlp_listwise_plan(kind, B, L, F, H1, H2):
+    """The `plan` of `_mlp_route` for a listwise `kind`: the plan of the entry point that has its slot."""
+    if kind.loss == _C.LISTWISE_LAMBDARANK:
+        return mlp_lambdarank_supported(B, L, F, H1, H2)
+    return mlp_listwise_supported(kind, B, L, F, H1, H2)
+
+
+def _mlp_step(xs, params, relevance, n, kind, sigma, grad_out, return_scores, return_loss_sum, out):
+    """The step behind mlp_loss_step, mlp_lambdarank_step and the loss modules (`_MLPLossFunction`), on a resolved
+    (kind, sigma): a pairwise kind, or a :class:`_ListwiseKind` of ListNet, ListMLE or LambdaRank."""
     listwise = isinstance(kind, _ListwiseKind)
-    if listwise and kind.loss == _C.LISTWISE_LAMBDARANK:
-        raise TypeError("mlp_loss_step has no LambdaRank kernel (take loss_fn(MLPScorer(...)(xs, n), ys, n), or the "
-                        "Linear scorer: FusedLinearLoss, linear_loss_step, LinearScorer)")
     F, H1, H2 = params[0].shape[-1], params[0].shape[0], params[2].shape[0]    # (the network's: W1 is (H1, F))
-    plan = not listwise or (xs.dim() == 3 and mlp_listwise_supported(kind, xs.shape[0], xs.shape[1], F, H1, H2))
+    plan = not listwise or (xs.dim() == 3 and _mlp_listwise_plan(kind, xs.shape[0], xs.shape[1], F, H1, H2))
     route = _mlp_route_of("step", xs, F, H1, H2, kind, plan)
     if route is _TORCH:
         _mlp_not_taken(xs, params, True)
@@ -1318,7 +1354,15 @@ def mlp_loss_step(xs, params, relevance, n, loss="hinge", grad_out=None, return_
     with _C.device_ctx(X):
         st = _C.stream_of(X)
         ws = _mlp_workspace(dev, st, ws_bytes)
-        if listwise:
+        if listwise and kind.loss == _C.LISTWISE_LAMBDARANK:
+            if B == 0:
+                flat.zero_()                # (launches nothing for an empty batch, like the listwise entry point)
+            rc = lib.ltr_mlp_lambdarank_f32(
+                min(int(kind.k or 0), 0x7FFFFFFF), float(sigma), X.data_ptr(), *[t.data_ptr() for t in flat_params],
+                r.data_ptr(), _LABEL_CODE[r.dtype], nn.data_ptr(), None if go is None else go.data_ptr(),
+                B, L, F, H1, H2, lossv.data_ptr(), None if scores is None else scores.data_ptr(), flat.data_ptr(),
+                None if lsum is None else lsum.data_ptr(), ws.data_ptr(), ws_bytes, st)
+        elif listwise:
             from . import _ties
             if B == 0:
                 flat.zero_()                # (the listwise entry point launches nothing for an empty batch)
@@ -1392,10 +1436,9 @@ class _MLPLossFunction(torch.autograd.Function):
     def forward(ctx, xs, relevance, n, kind_sigma, mean, *params):
         B = xs.shape[0]
         go = None if mean else torch.ones(B, dtype=torch.float32, device=xs.device)
-        loss = _KindProxy(*kind_sigma)
+        kind, sigma = kind_sigma
         xs, w1, extra = _zero_pad(xs, params[0], 4)
-        lossv, grads, lsum = mlp_loss_step(xs, (w1,) + tuple(params[1:]), relevance, n, loss=loss,
-                                           grad_out=go, return_loss_sum=True)
+        lossv, grads, lsum = _mlp_step(xs, (w1,) + tuple(params[1:]), relevance, n, kind, sigma, go, False, True, None)
         ctx.save_for_backward(grads[0]._base)       # the flat buffer: one scale in backward
         ctx.dims = (xs.shape[2], params[0].shape[0], params[2].shape[0])
         ctx.extra = extra
@@ -1415,6 +1458,8 @@ class _MLPLossFunction(torch.autograd.Function):
 
 
 class _KindProxy:
+    """A resolved (kind, sigma) in the shape `_resolve_loss` takes a loss module in (what `loss=` accepts)."""
+
     def __init__(self, kind, sigma):
         self._kind = kind
         self.sigma = sigma
@@ -1524,9 +1569,10 @@ class FusedMLPLoss(_FusedMLPBase):
 
 def _resolve_listwise_loss(loss):
     kind, sigma = _resolve_loss(loss)
-    if not isinstance(kind, _ListwiseKind) or kind.loss == _C.LISTWISE_LAMBDARANK:       # (no LambdaRank slot in the MLP step)
+    if not isinstance(kind, _ListwiseKind) or kind.loss == _C.LISTWISE_LAMBDARANK:       # (LambdaRank has a class of its own)
         raise TypeError("FusedMLPListwiseLoss takes the listwise losses only (\"listnet\" / \"softmax\", \"listmle\", "
-                        "ListwiseSoftmaxLoss, ListMLELoss); the pairwise ones: FusedMLPLoss")
+                        "ListwiseSoftmaxLoss, ListMLELoss); the pairwise ones: FusedMLPLoss; LambdaRank: "
+                        "FusedMLPLambdaRankLoss")
     return kind, sigma
 
 
@@ -1550,6 +1596,33 @@ class FusedMLPListwiseLoss(_FusedMLPBase):
 
     def _pieces(self, scores, relevance, n):
         return _listwise_pieces(scores, relevance, n, self.kind)
+
+
+class FusedMLPLambdaRankLoss(_FusedMLPBase):
+    """:class:`FusedMLPLoss` for LambdaRank, the NDCG@k objective of :class:`pytorchltr_amd.loss.LambdaRankLoss`:
+    ``sigma`` and ``k`` (``None``: no cutoff) are that loss's, or come from a ``LambdaRankLoss`` module passed as
+    ``loss``.  Same layers, ``state_dict``, ``score()``, ``last_losses`` and feature padding; the fused step is
+    ``ltr_mlp_lambdarank_f32`` (include/ltr_mlp_lambdarank.h), the row function of the stand-alone LambdaRank kernel in
+    the loss slot of the same two MFMA kernels.  Shapes its plan declines (:func:`mlp_lambdarank_supported`) run as the
+    unfused composition of ``score()`` with autograd and the stand-alone kernel, as for :class:`FusedMLPListwiseLoss`;
+    lists past ``max_list_len()`` documents, up to ``max_pair_list_len()``, take that kernel's long path."""
+
+    def __init__(self, in_features, loss=None, sigma=1.0, k=None, hidden=(50, 10), reduction="mean"):
+        from .loss import pairwise_lambda as _pl
+        if loss is None:
+            loss = _pl.LambdaRankLoss(sigma, k)             # (its check of k)
+        elif not isinstance(loss, _pl.LambdaRankLoss):
+            raise TypeError("FusedMLPLambdaRankLoss takes a LambdaRankLoss module, or sigma and k (the pairwise losses: "
+                            "FusedMLPLoss; ListNet and ListMLE: FusedMLPListwiseLoss)")
+        super().__init__(in_features, loss, hidden, reduction)
+
+    _resolve = staticmethod(_resolve_loss)
+
+    def _plan(self, B, L, F4, H1, H2):
+        return mlp_lambdarank_supported(B, L, F4, H1, H2)
+
+    def _pieces(self, scores, relevance, n):
+        return _listwise_pieces(scores, relevance, n, self.kind, self.sigma)
 
 
 class MLPScorer(_MLPLayers):
