@@ -10,11 +10,13 @@ split of the same shape (136 features, ragged queries, 5 relevance grades that d
 features through a fixed random network), so the printed ndcg@10 must RISE from its untrained
 value.  Pass an SVMrank file pair to train on real data instead:
 
-    python examples/02_mlp_getting_started.py [--loss {hinge,listnet,listmle,lambdarank}] [train.txt test.txt]
+    python examples/02_mlp_getting_started.py [--loss {hinge,listnet,listmle,lambdarank}] [--trainer] [train.txt test.txt]
 
 --loss listnet / listmle trains the same network on a listwise loss (FusedMLPListwiseLoss: the same kernel with
 ListNet or ListMLE in its loss slot), --loss lambdarank on LambdaRank with the NDCG@10 swap weights
 (FusedMLPLambdaRankLoss, k = 10: the metric this script reports); the default is the guide's hinge loss.
+--trainer replaces the loop body -- loss, zero_grad, backward, torch.optim.Adagrad.step -- by MLPTrainer.step: the same
+Adagrad (lr 0.1) applied inside the step's reduction launch, two launches a step and no autograd.
 """
 import argparse
 import os
@@ -26,7 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from pytorchltr_amd.datasets import RaggedQueries, UniformSampler, load_svmrank  # noqa: E402
 from pytorchltr_amd.evaluation import ndcg  # noqa: E402
-from pytorchltr_amd.fused import FusedMLPLambdaRankLoss, FusedMLPListwiseLoss, FusedMLPLoss  # noqa: E402
+from pytorchltr_amd.fused import FusedMLPLambdaRankLoss, FusedMLPListwiseLoss, FusedMLPLoss, MLPTrainer  # noqa: E402
 from pytorchltr_amd.loss import PairwiseHingeLoss  # noqa: E402
 
 
@@ -43,7 +45,7 @@ def synthetic_split(queries, features, seed, device):
     return RaggedQueries(xs, ys, offsets, device=device)
 
 
-def run(train_path=None, test_path=None, epochs=5, device="cuda", log=print, loss="hinge"):
+def run(train_path=None, test_path=None, epochs=5, device="cuda", log=print, loss="hinge", trainer=False):
     torch.manual_seed(42)
     if train_path:
         train = load_svmrank(train_path, normalize=True, filter_queries=True, device=device)
@@ -57,7 +59,10 @@ def run(train_path=None, test_path=None, epochs=5, device="cuda", log=print, los
         model = FusedMLPLambdaRankLoss(train.features.shape[1], k=10).to(device)
     else:
         model = FusedMLPListwiseLoss(train.features.shape[1], loss=loss).to(device)
-    optimizer = torch.optim.Adagrad(model.parameters(), lr=0.1)
+    if trainer:
+        trainer = MLPTrainer(model, optimizer="adagrad", lr=0.1)
+    else:
+        optimizer = torch.optim.Adagrad(model.parameters(), lr=0.1)
 
     def evaluate():
         loader = torch.utils.data.DataLoader(test, batch_size=16, collate_fn=test.collate_fn())
@@ -75,6 +80,9 @@ def run(train_path=None, test_path=None, epochs=5, device="cuda", log=print, los
             train, batch_size=16, shuffle=True,
             collate_fn=train.collate_fn(UniformSampler(max_list_size=20)))
         for batch in loader:
+            if trainer:
+                trainer.step(batch.features, batch.relevance, batch.n)  # the four lines below as one call
+                continue
             loss = model(batch.features, batch.relevance, batch.n)      # = loss_fn(model(xs), ys, n).mean()
             optimizer.zero_grad()
             loss.backward()
@@ -87,6 +95,7 @@ def run(train_path=None, test_path=None, epochs=5, device="cuda", log=print, los
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--loss", choices=("hinge", "listnet", "listmle", "lambdarank"), default="hinge")
+    ap.add_argument("--trainer", action="store_true", help="MLPTrainer.step in place of the autograd loop body")
     ap.add_argument("files", nargs="*", help="train.txt test.txt (SVMrank); default: a synthetic split")
     args = ap.parse_args()
-    run(*(args.files[:2] if len(args.files) >= 2 else ()), loss=args.loss)
+    run(*(args.files[:2] if len(args.files) >= 2 else ()), loss=args.loss, trainer=args.trainer)

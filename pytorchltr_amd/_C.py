@@ -1,6 +1,6 @@
 """ctypes binding of the C ABI in ``include/ltr_hip.h``, ``include/ltr_eval.h``, ``include/ltr_listwise.h``,
 ``include/ltr_lambdarank.h``, ``include/ltr_longpair.h``, ``include/ltr_lambdarank_long.h``, ``include/ltr_mlp_rows.h``, ``include/ltr_mlp_bf16.h``, ``include/ltr_mlp_wide.h``,
-``include/ltr_linear_bf16.h`` and ``include/ltr_sched.h`` (pytorchltr_amd/csrc/libltr_hip.so).
+``include/ltr_linear_bf16.h``, ``include/ltr_mlp_train.h`` and ``include/ltr_sched.h`` (pytorchltr_amd/csrc/libltr_hip.so).
 
 PyTorch supplies device memory and the current HIP stream; every call here hands raw device
 pointers to the library.  The library must exist -- there is deliberately no fallback.
@@ -154,6 +154,27 @@ MLP_LAMBDARANK_SIGNATURES = {
     "ltr_mlp_lambdarank_f32": (_i, [_i, _f] + [_vp] * 7 + [_vp, _i, _vp, _vp] + [_i] * 5 + [_vp] * 5 + [_sz, _vp]),
 }
 
+# include/ltr_mlp_train.h: the update rules, the loss families of a step and the hyper-parameter struct
+OPT_SGD, OPT_ADAGRAD, OPT_ADAM = 0, 1, 2
+MLP_TRAIN_PAIRWISE, MLP_TRAIN_LISTWISE, MLP_TRAIN_LAMBDARANK = 0, 1, 2
+
+
+class MLPOptim(ctypes.Structure):
+    """``struct ltr_mlp_optim``."""
+    _fields_ = [("algo", _i), ("nesterov", _i)] + [(name, ctypes.c_double) for name in (
+        "lr", "weight_decay", "momentum", "dampening", "lr_decay", "eps", "beta1", "beta2")]
+
+
+_optp = ctypes.POINTER(MLPOptim)
+
+# name -> (restype, argtypes); mirrors include/ltr_mlp_train.h (the fused MLP step with the optimizer update in-launch)
+MLP_TRAIN_SIGNATURES = {
+    "ltr_mlp_train_state_floats": (_sz, [_i, _i, _i, _i]),
+    "ltr_mlp_train_step_f32": (_i, [_i, _i, _i, _f] + [_vp] * 7 + [_i, _vp, _vp, _i, _vp, _vp, _i, ctypes.c_uint64, _vp, _vp]
+                               + [_i] * 5 + [_vp] * 4 + [_optp, _vp, _vp, _sz, _vp]),
+    "ltr_mlp_apply_update_f32": (_i, [_vp] * 7 + [_i, _vp, _optp, _i, _i, _i, _vp]),
+}
+
 # name -> (restype, argtypes); mirrors include/ltr_mlp_rows.h (the MLP scorer on its own: scores and gradients, any length)
 MLP_ROWS_SIGNATURES = {
     "ltr_mlp_rows_scores_f32": (_i, [_vp] * 8 + [_i] * 5 + [_vp, _vp]),
@@ -244,7 +265,7 @@ def lib():
         for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(EVAL_SIGNATURES.items())
                                           + list(LISTWISE_SIGNATURES.items()) + list(LAMBDARANK_SIGNATURES.items())
                                           + list(LONGPAIR_SIGNATURES.items()) + list(LAMBDARANK_LONG_SIGNATURES.items())
-                                          + list(MLP_LAMBDARANK_SIGNATURES.items())
+                                          + list(MLP_LAMBDARANK_SIGNATURES.items()) + list(MLP_TRAIN_SIGNATURES.items())
                                           + list(MLP_ROWS_SIGNATURES.items()) + list(MLP_WIDE_SIGNATURES.items())
                                           + list(MLP_BF16_SIGNATURES.items()) + list(LINEAR_BF16_SIGNATURES.items())
                                           + list(SCHED_SIGNATURES.items())):

@@ -21,7 +21,7 @@ OBJ_DIR = os.path.join(_ROOT, "build", "obj")
 DEPENDS = SOURCES + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".inc")) + \
     [os.path.join(_ROOT, "include", h) for h in ("ltr_hip.h", "ltr_eval.h", "ltr_listwise.h", "ltr_lambdarank.h", "ltr_longpair.h",
                                                 "ltr_lambdarank_long.h", "ltr_linear_bf16.h", "ltr_mlp_bf16.h", "ltr_mlp_rows.h", "ltr_mlp_wide.h",
-                                                "ltr_mlp_lambdarank.h", "ltr_sched.h")]
+                                                "ltr_mlp_lambdarank.h", "ltr_mlp_train.h", "ltr_sched.h")]
 ARCH = "gfx950"
 IO_LIB_PATH = os.path.join(CSRC, "libltr_io.so")
 IO_SOURCES = [os.path.join(CSRC, "svmrank_parser.cpp")]

@@ -15,6 +15,8 @@
 #include "ltr_listmle_row.inc"
 #include "ltr_lambdarank_row.inc"
 #include "ltr_mlp.inc"
+// the training step with the optimizer update in the reduction launch (include/ltr_mlp_train.h)
+#include "ltr_mlp_train.inc"
 #include "ltr_mlp_stream.inc"
 #include "ltr_mlp_rows.inc"
 #include "ltr_mlp_bf16.inc"

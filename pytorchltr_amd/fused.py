@@ -1641,3 +1641,355 @@ class MLPScorer(_MLPLayers):
     def forward(self, xs, n=None):
         _C.require_device(xs, "xs")
         return self._score(xs, n, _mlp_route_of("scorer", xs, None, *self._hidden()))
+
+
+# ---- MLPTrainer: the fused MLP step with the optimizer update inside the reduction launch (include/ltr_mlp_train.h) ----
+_TRAIN_ALGO = {"sgd": _C.OPT_SGD, "adagrad": _C.OPT_ADAGRAD, "adam": _C.OPT_ADAM}
+_TRAIN_TORCH = {"sgd": "SGD", "adagrad": "Adagrad", "adam": "Adam"}
+_TRAIN_STATE_NAMES = {"sgd": ("momentum_buffer",), "adagrad": ("sum",), "adam": ("exp_avg", "exp_avg_sq")}
+_TRAIN_REFUSED = ("maximize", "amsgrad", "differentiable")
+_TRAIN_IGNORED = ("foreach", "capturable", "fused")             # how torch runs its own kernels: nothing to choose here
+
+
+def _train_hyper(optimizer, lr, hyper):
+    """The hyper-parameters of `optimizer` as torch.optim holds them (its names, defaults and ValueErrors: the torch
+    class itself judges them, on a parameter of its own that is never stepped)."""
+    if optimizer not in _TRAIN_ALGO:
+        raise ValueError("optimizer must be 'sgd', 'adagrad' or 'adam'; got %r" % (optimizer,))
+    hyper = dict(hyper)
+    for name in _TRAIN_REFUSED:
+        if hyper.pop(name, False):
+            raise NotImplementedError("MLPTrainer has no %s=True (torch.optim.%s on model.parameters() has)"
+                                      % (name, _TRAIN_TORCH[optimizer]))
+    for name in _TRAIN_IGNORED:
+        hyper.pop(name, None)
+    if lr is not None:
+        hyper["lr"] = lr
+    if torch.is_tensor(hyper.get("lr")):
+        raise ValueError("MLPTrainer takes lr as a number (a tensor lr belongs to torch's capturable optimizers)")
+    probe = getattr(torch.optim, _TRAIN_TORCH[optimizer])([torch.zeros(1, requires_grad=True)], **hyper)
+    return {k: v for k, v in probe.defaults.items() if k not in _TRAIN_REFUSED + _TRAIN_IGNORED}
+
+
+def _train_param_shapes(F, H1, H2):
+    return ((H1, F), (H1,), (H2, H1), (H2,), (1, H2), (1,))
+
+
+def mlp_train_state_to_torch(optimizer, flat, t, F, H1, H2, w1_cols=None, initial=False):
+    """The ``state`` of the matching torch.optim optimizer's state_dict (parameter index -> its state) from the
+    trainer's flat state: `flat` holds the buffers of include/ltr_mlp_train.h back to back (one of P floats, Adam two,
+    each laid out [W1 | b1 | W2 | b2 | W3 | b3] with W1 rows of F floats, of which the first `w1_cols` are the
+    parameter's), `t` the step count.  A pure function on tensors (any device).  Where torch has no state yet -- SGD
+    without momentum or before its first step, Adam before its first step -- the dict is empty."""
+    names = _TRAIN_STATE_NAMES[optimizer]
+    P = sum(a * b for a, b in ((H1, F), (H1, 1), (H2, H1), (H2, 1), (H2, 1), (1, 1)))
+    if optimizer != "adagrad" and (t == 0 or flat is None):
+        return {}
+    out = {i: {} for i in range(6)}
+    for b, name in enumerate(names):
+        parts = _crop_grads(_split_grads(flat[b * P:(b + 1) * P], F, H1, H2), F - (w1_cols or F))
+        for i, (part, shape) in enumerate(zip(parts, _train_param_shapes(w1_cols or F, H1, H2))):
+            out[i][name] = part.reshape(shape).clone()
+    if optimizer != "sgd":
+        for i in range(6):
+            out[i]["step"] = torch.tensor(float(t))
+    return out
+
+
+def mlp_train_state_from_torch(optimizer, state, F, H1, H2, w1_cols=None, fill=0.0, device=None):
+    """The inverse of :func:`mlp_train_state_to_torch`: ``(flat, t)`` from the ``state`` of a torch.optim state_dict
+    (keys 0 .. 5 in the order of ``model.parameters()``; an empty or partial state counts as "no step taken": the
+    buffers hold `fill`).  W1's state is zero-padded from `w1_cols` columns to rows of F floats."""
+    names = _TRAIN_STATE_NAMES[optimizer]
+    shapes = _train_param_shapes(w1_cols or F, H1, H2)
+    P = sum(a * b for a, b in ((H1, F), (H1, 1), (H2, H1), (H2, 1), (H2, 1), (1, 1)))
+    have = all(i in state and all(state[i].get(name) is not None for name in names) for i in range(6))
+    flat = torch.full((len(names) * P,), float(fill), dtype=torch.float32, device=device)
+    if not have:
+        return flat, 0
+    for b, name in enumerate(names):
+        pieces = []
+        for i, shape in enumerate(shapes):
+            v = state[i][name].detach().to(device=device, dtype=torch.float32)
+            if tuple(v.shape) != shape:
+                raise ValueError("state %r of parameter %d has shape %s, not %s" % (name, i, tuple(v.shape), shape))
+            if i == 0 and shape[1] != F:
+                v = torch.nn.functional.pad(v, (0, F - shape[1]))
+            pieces.append(v.reshape(-1))
+        flat[b * P:(b + 1) * P] = torch.cat(pieces)
+    if optimizer == "sgd":
+        return flat, 1                       # (torch keeps no count: a momentum buffer means "not the first step")
+    steps = {int(float(state[i]["step"])) for i in range(6)}
+    if len(steps) != 1:
+        raise ValueError("the six parameters' step counts differ: %s" % sorted(steps))
+    return flat, steps.pop()
+
+
+class MLPTrainer:
+    """The guide's loop body -- ``zero_grad / loss / backward / optimizer.step`` -- on a fused MLP loss module as ONE
+    call without autograd: ``loss = trainer.step(xs, relevance, n)`` runs the module's fused step with the optimizer
+    update and its state inside the reduction launch (ltr_mlp_train_step_f32: two launches), and returns the reduced
+    loss as a 0-dim device tensor.
+
+    Args:
+        model: a :class:`FusedMLPLoss`, :class:`FusedMLPListwiseLoss` or :class:`FusedMLPLambdaRankLoss` on the device;
+            its loss, sigma, k and reduction are read at every step, its six ``nn.Linear`` parameters (fp32) are
+            updated in place -- no autograd graph, no ``.grad``.
+        optimizer: ``"sgd"``, ``"adagrad"`` or ``"adam"``; `lr` and the keyword hyper-parameters are those of
+            ``torch.optim.SGD / Adagrad / Adam`` (names, defaults, ValueErrors).  ``maximize``, ``amsgrad`` and
+            ``differentiable`` raise NotImplementedError; ``foreach``, ``capturable`` and ``fused`` mean nothing here.
+
+    ``trainer.lr`` is a plain attribute, read at every eager step (schedulers set it).  ``state_dict()`` /
+    ``load_state_dict()`` speak the format of the matching torch optimizer built on ``model.parameters()``, in both
+    directions.  Batches off the fused route (longer lists, wide rows, bf16, a listwise loss off its plan) run the
+    pieces of :func:`mlp_loss_step` into a flat gradient and one update launch (ltr_mlp_apply_update_f32); shapes no
+    kernel takes raise the ValueError of :func:`mlp_loss_step`.  The tensors `step` returns (the loss, ``last_losses``,
+    the gradient views) are buffers of the trainer, overwritten by the next step on the same shape."""
+
+    def __init__(self, model, optimizer="adagrad", lr=None, **hyper):
+        if not isinstance(model, _FusedMLPBase):
+            raise TypeError("MLPTrainer takes a FusedMLPLoss, FusedMLPListwiseLoss or FusedMLPLambdaRankLoss module")
+        self.model = model
+        self.optimizer = optimizer
+        self.hyper = _train_hyper(optimizer, lr, hyper)
+        self.lr = self.hyper.pop("lr")
+        self._optim = _C.MLPOptim()
+        self._state = None               # the flat state of include/ltr_mlp_train.h (device), made at the first step
+        self._pending = None             # a loaded state (torch's form) waiting for the device
+        self._buffers = {}               # (B, L, F) -> the step's loss / total / weight / workspace / gradient buffers
+
+    # -- the network and its state --
+    def _dims(self):
+        H1, H2 = self.model._hidden()
+        return self.model.in_features, H1, H2
+
+    def _params(self):
+        params = self.model._params()
+        for p in params:
+            if p.dtype is not torch.float32 or not p.is_contiguous() or not p.is_cuda:
+                raise ValueError("MLPTrainer updates contiguous float32 parameters on the device in place")
+        return params
+
+    def _fill(self):
+        return float(self.hyper.get("initial_accumulator_value", 0.0))
+
+    def _state_for(self, Fp, dev):
+        """The flat state for rows of Fp floats on `dev`: zeroed (Adagrad: `sum` at its initial value), or what was
+        loaded; a state made for another row width or device is carried over through torch's form."""
+        if self._state is not None and self._state_Fp == Fp and self._state.device == dev:
+            return self._state
+        F, H1, H2 = self._dims()
+        source = self._torch_state() if self._state is not None else (self._pending or {})
+        flat, t = mlp_train_state_from_torch(self.optimizer, source, Fp, H1, H2, F, self._fill(), dev)
+        count = int(_C.lib().ltr_mlp_train_state_floats(_TRAIN_ALGO[self.optimizer], Fp, H1, H2))
+        state = torch.zeros(count, dtype=torch.float32, device=dev)
+        state[:flat.numel()] = flat
+        state[count - 4:].view(torch.int32)[0] = int(t)
+        self._state, self._state_Fp, self._pending = state, Fp, None
+        return state
+
+    @property
+    def steps(self):
+        """The number of steps taken: the device counter (a host read: it synchronises)."""
+        if self._state is None:
+            return 0 if self._pending is None else mlp_train_state_from_torch(
+                self.optimizer, self._pending, *self._dims())[1]
+        return int(self._state[-4:].view(torch.int32)[0].item())
+
+    def _torch_state(self):
+        if self._state is None:
+            if self._pending is not None:
+                return self._pending
+            F, H1, H2 = self._dims()
+            if self.optimizer != "adagrad":
+                return {}
+            P = int(sum(a * b for a, b in ((H1, F), (H1, 1), (H2, H1), (H2, 1), (H2, 1), (1, 1))))
+            return mlp_train_state_to_torch("adagrad", torch.full((P,), self._fill()), 0, F, H1, H2)
+        F, H1, H2 = self._dims()
+        state = mlp_train_state_to_torch(self.optimizer, self._state, self.steps, self._state_Fp, H1, H2, F)
+        if self.optimizer == "sgd" and self.hyper["momentum"] == 0:
+            return {}
+        return state
+
+    def _param_groups(self):
+        probe = getattr(torch.optim, _TRAIN_TORCH[self.optimizer])(
+            [torch.zeros(1, requires_grad=True) for _ in range(6)], lr=self.lr, **self.hyper)
+        return probe.state_dict()["param_groups"]
+
+    def state_dict(self):
+        """The state_dict of ``torch.optim.<Optimizer>(model.parameters(), ...)`` at this point: same keys, parameter
+        order and per-parameter names (``momentum_buffer``; ``sum``, ``step``; ``exp_avg``, ``exp_avg_sq``, ``step``).
+        Reads the device step counter (synchronises)."""
+        return {"state": self._torch_state(), "param_groups": self._param_groups()}
+
+    def load_state_dict(self, state_dict):
+        """Takes a state_dict of this class or of the matching torch.optim optimizer on ``model.parameters()``: the
+        per-parameter state and the group's hyper-parameters (``lr`` included)."""
+        groups = state_dict["param_groups"]
+        if len(groups) != 1 or len(groups[0]["params"]) != 6:
+            raise ValueError("MLPTrainer takes one parameter group of the model's six parameters")
+        group = {k: v for k, v in groups[0].items() if k != "params"}
+        for name in _TRAIN_REFUSED:
+            if group.get(name):
+                raise NotImplementedError("MLPTrainer has no %s=True" % name)
+        hyper = _train_hyper(self.optimizer, None, {k: v for k, v in group.items() if k in dict(self.hyper, lr=0)})
+        self.lr = hyper.pop("lr")
+        self.hyper = hyper
+        keys = sorted(state_dict["state"])
+        # (copies: the dict's own tensors stay the caller's -- a torch optimizer that loaded it steps them in place)
+        state = {i: {name: v.detach().clone() if torch.is_tensor(v) else v for name, v in state_dict["state"][k].items()}
+                 for i, k in enumerate(keys)} if len(keys) == 6 else {}
+        F, H1, H2 = self._dims()
+        mlp_train_state_from_torch(self.optimizer, state, F, H1, H2)        # (its shape checks, now)
+        self._state, self._pending = None, state
+
+    # -- the step --
+    def _fill_optim(self):
+        o, h = self._optim, self.hyper
+        o.algo = _TRAIN_ALGO[self.optimizer]
+        o.lr = float(self.lr)
+        o.weight_decay = float(h["weight_decay"])
+        o.nesterov = 1 if h.get("nesterov") else 0
+        o.momentum, o.dampening = float(h.get("momentum", 0.0)), float(h.get("dampening", 0.0))
+        o.lr_decay, o.eps = float(h.get("lr_decay", 0.0)), float(h.get("eps", 0.0))
+        o.beta1, o.beta2 = [float(b) for b in h.get("betas", (0.0, 0.0))]
+        return o
+
+    def _buffers_for(self, B, L, Fp, H1, H2, dev):
+        key = (B, L, Fp, dev.index)
+        buf = self._buffers.get(key)
+        if buf is None:
+            P, ws_bytes = _mlp_sizes_for(B, Fp, H1, H2)
+            if len(self._buffers) > 16:
+                self._buffers.clear()
+            buf = self._buffers[key] = dict(
+                loss=torch.empty(B, dtype=torch.float32, device=dev), lsum=torch.empty(1, dtype=torch.float32, device=dev),
+                total=torch.empty((), dtype=torch.float32, device=dev), ones=torch.ones(B, dtype=torch.float32, device=dev),
+                ws=torch.empty(max(ws_bytes, 16) // 4, dtype=torch.float32, device=dev), ws_bytes=ws_bytes,
+                grads=torch.empty(P, dtype=torch.float32, device=dev), P=P)
+        return buf
+
+    def _prime(self, xs):
+        """The state and the buffers of a batch shape, made ahead of a capture (their initialisation must not be
+        replayed: it would reset the step count)."""
+        B, L, F = xs.shape
+        H1, H2 = self.model._hidden()
+        Fp = F + (-F) % (8 if xs.dtype is torch.bfloat16 else 4)
+        self._state_for(Fp, xs.device)
+        if B > 0:
+            self._buffers_for(B, L, Fp, H1, H2, xs.device)
+
+    def step(self, xs, relevance, n, return_grads=False):
+        """One training step on a batch: the reduced loss (a 0-dim device tensor), and with ``return_grads=True`` also
+        the six gradient views ``(dW1, db1, dW2, db2, dW3, db3)`` of the gradient the update consumed.  Sets
+        ``model.last_losses``.  An empty batch changes nothing and returns 0.  Never synchronises; on the fused route it
+        allocates nothing after the first call on a shape, so ``torch.cuda.graph`` captures it (:meth:`graphed`)."""
+        model = self.model
+        _C.require_device(xs, "xs")
+        if xs.dim() != 3:
+            raise ValueError("features must have shape (batch, list_size, features)")
+        params = self._params()
+        B, L, F = xs.shape
+        H1, H2 = model._hidden()
+        dev = xs.device
+        if params[0].shape[1] != F:
+            raise ValueError("the model takes %d features, the batch has %d" % (params[0].shape[1], F))
+        kind, sigma, mean = model.kind, model.sigma, model.reduction == "mean"
+        if B == 0:
+            model.last_losses = torch.zeros(0, dtype=torch.float32, device=dev)
+            zero = torch.zeros((), dtype=torch.float32, device=dev)
+            return (zero, tuple(torch.zeros_like(p) for p in params)) if return_grads else zero
+        xp, w1p, extra = _zero_pad(xs, params[0], 8 if xs.dtype is torch.bfloat16 else 4)
+        Fp = F + extra
+        listwise = isinstance(kind, _ListwiseKind)
+        plan = not listwise or _mlp_listwise_plan(kind, B, L, Fp, H1, H2)
+        route = _mlp_route_of("step", xp, Fp, H1, H2, kind, plan)
+        if route is _TORCH and _mlp_route_of("loss", xp, Fp, H1, H2, kind, plan) is _WIDE:
+            route = _WIDE                                   # (the module's wide rows: the functions have no such route)
+        step_params = (w1p,) + tuple(params[1:])
+        if route is _TORCH:
+            _mlp_not_taken(xp, step_params, True)
+        X, flat_params, H1, H2, _, _ = _mlp_prepare(xp, step_params, _ROUTE_FAMILY[route], pad=False)
+        state = self._state_for(Fp, dev)
+        optim = self._fill_optim()
+        buf = self._buffers_for(B, L, Fp, H1, H2, dev)
+        lib = _C.lib()
+        if route is not _FUSED:
+            lossv, _, lsum = _mlp_step_pieces(X, flat_params, H1, H2, relevance, n, kind, sigma,
+                                              None if mean else buf["ones"], False, True, buf["grads"])
+            with _C.device_ctx(X):
+                _C.check(lib.ltr_mlp_apply_update_f32(
+                    buf["grads"].data_ptr(), *[p.data_ptr() for p in params], F, state.data_ptr(), ctypes.byref(optim),
+                    Fp, H1, H2, _C.stream_of(X)))
+            buf["lsum"].copy_(lsum)
+        else:
+            r, nn = _labels_and_n(relevance, n, B, L, dev)
+            lossv = buf["loss"]
+            if not listwise:
+                family, code, k, tie = _C.MLP_TRAIN_PAIRWISE, kind, 0, (None, 0, 0, None)
+            elif kind.loss == _C.LISTWISE_LAMBDARANK:
+                family, code, k, tie = _C.MLP_TRAIN_LAMBDARANK, 0, min(int(kind.k or 0), 0x7FFFFFFF), (None, 0, 0, None)
+            else:
+                from . import _ties
+                sd = _ties.draw_seed(L, dev) if kind.loss == _C.LISTWISE_LISTMLE else None
+                family, code, k, tie = _C.MLP_TRAIN_LISTWISE, kind.loss, int(kind.k or 0), _ties.tie_args(sd)
+            with _C.device_ctx(X):
+                rc = lib.ltr_mlp_train_step_f32(
+                    family, code, k, float(sigma), X.data_ptr(), *[p.data_ptr() for p in params], F,
+                    flat_params[0].data_ptr() if extra else None, r.data_ptr(), _LABEL_CODE[r.dtype], nn.data_ptr(),
+                    *tie, None if mean else buf["ones"].data_ptr(), B, L, Fp, H1, H2, lossv.data_ptr(), None,
+                    buf["lsum"].data_ptr(), state.data_ptr(), ctypes.byref(optim),
+                    buf["grads"].data_ptr() if return_grads else None, buf["ws"].data_ptr(), buf["ws_bytes"],
+                    _C.stream_of(X))
+                if rc != 0:
+                    _C.check(rc)
+        model.last_losses = lossv
+        if mean:
+            total = torch.div(buf["lsum"].view(()), B, out=buf["total"])
+        else:
+            total = buf["lsum"].view(())
+        if return_grads:
+            return total, _crop_grads(_split_grads(buf["grads"], Fp, H1, H2), extra, [p.shape for p in params])
+        return total
+
+    def graphed(self, example_batch, warmup=3):
+        """``trainer.step`` on batches of one shape as a captured graph: returns a callable like
+        :class:`pytorchltr_amd.graphed.GraphedStep`'s -- ``loss = call(xs, relevance, n)`` copies the batch into static
+        buffers, replays the two launches and returns the static 0-dim loss.  `warmup` eager steps on `example_batch`
+        run first and DO update the parameters.  The step counter lives on the device, so Adam's and Adagrad's
+        t-dependent factors and SGD's first-step rule replay correctly; the learning rate is a kernel argument and
+        stays at the value ``trainer.lr`` had at capture -- capture again after changing it."""
+        return _GraphedTrainerStep(self, example_batch, warmup)
+
+
+class _GraphedTrainerStep:
+    def __init__(self, trainer, example_batch, warmup):
+        self._trainer = trainer
+        self._static = [t.clone() for t in example_batch]
+        if len(self._static) != 3 or not self._static[0].is_cuda:
+            raise ValueError("graphed() needs the device tensors (xs, relevance, n) of an example batch")
+        trainer._params()
+        trainer._prime(self._static[0])
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(max(0, warmup)):
+                trainer.step(*self._static)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        self._graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self._graph, capture_error_mode="thread_local"):
+            self._loss = trainer.step(*self._static)
+        torch.cuda.synchronize()
+        self._keep = (trainer._state, list(trainer._buffers.values()))      # what the graph's launches point into
+
+    def __call__(self, *batch):
+        if len(batch) != len(self._static):
+            raise ValueError("expected %d tensors, got %d" % (len(self._static), len(batch)))
+        for dst, src in zip(self._static, batch):
+            if dst.shape != src.shape:
+                raise ValueError("batch shape %s differs from the captured shape %s (pad batches "
+                                 "to a fixed list size)" % (tuple(src.shape), tuple(dst.shape)))
+            dst.copy_(src, non_blocking=True)
+        self._graph.replay()
+        return self._loss
