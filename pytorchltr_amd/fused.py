@@ -1790,7 +1790,11 @@ class MLPTrainer:
 
     @property
     def steps(self):
-        """The number of steps taken: the device counter (a host read: it synchronises)."""
+        """The number of steps taken: the device counter (a host read: it synchronises).  Adagrad and Adam carry it
+        through a loaded state_dict and through a change of the batch's row width (fp32 and bf16 batches pad the
+        features differently, and the flat state is re-laid through torch's form).  torch's SGD state holds no count,
+        so after either the SGD count restarts: 1 where a momentum buffer came along, else 0 -- all the first-step
+        rule asks is whether t is 0, which it cannot tell from the truth."""
         if self._state is None:
             return 0 if self._pending is None else mlp_train_state_from_torch(
                 self.optimizer, self._pending, *self._dims())[1]
@@ -1824,7 +1828,8 @@ class MLPTrainer:
 
     def load_state_dict(self, state_dict):
         """Takes a state_dict of this class or of the matching torch.optim optimizer on ``model.parameters()``: the
-        per-parameter state and the group's hyper-parameters (``lr`` included)."""
+        per-parameter state and the group's hyper-parameters (``lr`` included).  The state holds no entry (no step
+        taken) or the six parameters'; any other count is a ValueError, and the trainer stays as it was."""
         groups = state_dict["param_groups"]
         if len(groups) != 1 or len(groups[0]["params"]) != 6:
             raise ValueError("MLPTrainer takes one parameter group of the model's six parameters")
@@ -1832,10 +1837,13 @@ class MLPTrainer:
         for name in _TRAIN_REFUSED:
             if group.get(name):
                 raise NotImplementedError("MLPTrainer has no %s=True" % name)
+        keys = sorted(state_dict["state"])
+        if len(keys) not in (0, 6):                # (refused before anything of the trainer changes)
+            raise ValueError("the state holds %d per-parameter entries; MLPTrainer takes none (no step taken) or the "
+                             "model's six" % len(keys))
         hyper = _train_hyper(self.optimizer, None, {k: v for k, v in group.items() if k in dict(self.hyper, lr=0)})
         self.lr = hyper.pop("lr")
         self.hyper = hyper
-        keys = sorted(state_dict["state"])
         # (copies: the dict's own tensors stay the caller's -- a torch optimizer that loaded it steps them in place)
         state = {i: {name: v.detach().clone() if torch.is_tensor(v) else v for name, v in state_dict["state"][k].items()}
                  for i, k in enumerate(keys)} if len(keys) == 6 else {}

@@ -1,6 +1,7 @@
 """The three update rules of include/ltr_mlp_train.h (torch.optim's SGD, Adagrad, Adam) restated in fp64 numpy, with the
 bound a correct fp32 evaluation of the same chain stays within.  tests/test_mlp_train_host.py pins the rules to
-torch.optim on float64 tensors; tests/test_gpu_mlp_train.py holds the kernels to the bound.
+torch.optim on float64 tensors and holds `step_f32` (the chain in np.float32) to the bound on every corner of `CORNERS`;
+tests/test_gpu_mlp_train.py and tests/test_gpu_mlp_update.py hold the kernels to it.
 
 ``step(algo, hyper, p, g, state, t)`` takes one tensor's parameters `p`, gradient `g`, state (a dict of arrays by torch's
 names) and the number of steps already taken `t`, all as they are in memory (fp32 on the device; any float dtype works),
@@ -104,6 +105,88 @@ def step(algo, hyper, p, g, state, t):
         out[name] = x.v
         bound[name] = x.bound()
     return p.v, out, bound
+
+
+def step_f32(algo, hyper, p, g, state, t):
+    """The chain of `step` evaluated operation by operation in np.float32, as include/ltr_mlp_train.h words it: wd, lr,
+    mu, 1 - dampening, eps, the betas and 1 - beta rounded to fp32 from the double, the scalars that depend on t
+    evaluated in fp64 and rounded once, no fused multiply-add.  Returns ``(p', state')`` as float32 arrays: one correct
+    fp32 evaluation, which `step`'s bound must hold (tests/test_mlp_train_host.py)."""
+    f = np.float32
+    p, g = np.asarray(p, dtype=f), np.asarray(g, dtype=f)
+    wd, lr = f(hyper.get("weight_decay", 0.0)), f(hyper["lr"])
+    if wd != 0:
+        g = g + wd * p
+    new = {}
+    if algo == "sgd":
+        mu = f(hyper.get("momentum", 0.0))
+        if mu != 0:
+            if t == 0:
+                buf = g
+            else:
+                omd = f(1.0 - float(hyper.get("dampening", 0.0)))
+                buf = mu * np.asarray(state["momentum_buffer"], dtype=f) + omd * g
+            new["momentum_buffer"] = buf
+            g = g + mu * buf if hyper.get("nesterov") else buf
+        p = p - lr * g
+    elif algo == "adagrad":
+        clr = f(float(hyper["lr"]) / (1.0 + t * float(hyper.get("lr_decay", 0.0))))
+        s = np.asarray(state["sum"], dtype=f) + g * g
+        new["sum"] = s
+        p = p - clr * (g / (np.sqrt(s) + f(hyper.get("eps", 1e-10))))
+    elif algo == "adam":
+        b1, b2 = [float(b) for b in hyper.get("betas", (0.9, 0.999))]
+        m = f(b1) * np.asarray(state["exp_avg"], dtype=f) + f(1.0 - b1) * g
+        v = f(b2) * np.asarray(state["exp_avg_sq"], dtype=f) + f(1.0 - b2) * (g * g)
+        new["exp_avg"], new["exp_avg_sq"] = m, v
+        step_size = f(float(hyper["lr"]) / (1.0 - b1 ** (t + 1)))
+        bc2_sqrt = f((1.0 - b2 ** (t + 1)) ** 0.5)
+        p = p - step_size * (m / (np.sqrt(v) / bc2_sqrt + f(hyper.get("eps", 1e-8))))
+    else:
+        raise ValueError(algo)
+    assert p.dtype == f and all(x.dtype == f for x in new.values())
+    return p, new
+
+
+# The corner grid of the update rules: every zero-coefficient short cut of the kernels taken and not taken, one full
+# set per rule.  (id, algo, torch.optim's keyword arguments); CPU and GPU tiers share it.
+CORNERS = [
+    ("sgd-plain", "sgd", dict(lr=0.05)),
+    ("sgd-wd", "sgd", dict(lr=0.05, weight_decay=0.01)),
+    ("sgd-mu", "sgd", dict(lr=0.05, momentum=0.9)),
+    ("sgd-mu-damp-wd", "sgd", dict(lr=0.05, momentum=0.9, dampening=0.3, weight_decay=0.02)),
+    ("sgd-nesterov-wd", "sgd", dict(lr=0.05, momentum=0.8, nesterov=True, weight_decay=0.01)),
+    ("sgd-lr0-mu", "sgd", dict(lr=0.0, momentum=0.9)),
+    ("adagrad-defaults", "adagrad", dict(lr=0.1)),
+    ("adagrad-decay", "adagrad", dict(lr=0.1, lr_decay=0.05)),
+    ("adagrad-wd", "adagrad", dict(lr=0.1, weight_decay=0.01)),
+    ("adagrad-init", "adagrad", dict(lr=0.1, initial_accumulator_value=0.5)),
+    ("adagrad-full", "adagrad", dict(lr=0.1, lr_decay=0.05, weight_decay=0.01, initial_accumulator_value=0.5, eps=1e-6)),
+    ("adam-defaults", "adam", dict(lr=0.01)),
+    ("adam-wd", "adam", dict(lr=0.01, weight_decay=0.03)),
+    ("adam-beta1-0", "adam", dict(lr=0.01, betas=(0.0, 0.999))),
+    ("adam-beta2-0", "adam", dict(lr=0.01, betas=(0.9, 0.0))),
+    ("adam-full", "adam", dict(lr=0.01, betas=(0.7, 0.95), eps=1e-5, weight_decay=0.03)),
+]
+CORNER = {name: (algo, hyper) for name, algo, hyper in CORNERS}
+STATE_NAMES = {"sgd": ("momentum_buffer",), "adagrad": ("sum",), "adam": ("exp_avg", "exp_avg_sq")}
+POSITIVE_STATE = ("sum", "exp_avg_sq")
+
+
+def synthetic_gradient(rng, count):
+    """`count` float32 gradients: magnitudes log-uniform in [1e-3, 10], random signs, one element in eight exactly 0."""
+    g = np.exp(rng.uniform(np.log(1e-3), np.log(10.0), count)) * rng.choice([-1.0, 1.0], count)
+    g[rng.permutation(count)[:max(1, count // 8)]] = 0.0
+    return g.astype(np.float32)
+
+
+def random_state(rng, algo, count):
+    """Random float32 state buffers by torch's names; `sum` and `exp_avg_sq` positive."""
+    out = {}
+    for name in STATE_NAMES[algo]:
+        x = rng.normal(0.0, 1.0, count)
+        out[name] = (np.abs(x) + 1e-3 if name in POSITIVE_STATE else x).astype(np.float32)
+    return out
 
 
 def initial_state(algo, hyper, like):

@@ -28,8 +28,21 @@ SHAPES = {
     "4x300x136": (4, 300, 136, HIDDEN, torch.float32),    # off the fused route: the row kernels + apply
     "4x40x452": (4, 40, 452, HIDDEN, torch.float32),      # wide rows + apply
     "6x20x136-bf16": (6, 20, 136, HIDDEN, torch.bfloat16),  # the bf16 kernels + apply
+    # the padded routes: w1_pitch < the gradient's row width, so the update meets columns that are no parameters
+    "2x300x46": (2, 300, 46, HIDDEN, torch.float32),      # the row kernels + apply, pad 2
+    "2x20x699": (2, 20, 699, HIDDEN, torch.float32),      # wide rows + apply, pad 1
+    "3x20x44-bf16": (3, 20, 44, HIDDEN, torch.bfloat16),  # bf16 pads to 8: a whole float4 of every W1 row is padding
+    "3x20x46-bf16": (3, 20, 46, HIDDEN, torch.bfloat16),  # pad 2
+    "3x9x46": (3, 9, 46, HIDDEN, torch.float32),          # fused, pad 2
 }
-FUSED = ("3x5x8", "40x20x136", "520x4x12", "6x9x5", "1x7x8", "5x6x8-degenerate")
+PADDED = ("2x300x46", "2x20x699", "3x20x44-bf16", "3x20x46-bf16", "3x9x46")
+FUSED = ("3x5x8", "40x20x136", "520x4x12", "6x9x5", "1x7x8", "5x6x8-degenerate", "3x9x46")
+# batches of the tests that bring their own network (hidden sizes: the test's)
+OTHER = {
+    "3x9x44": (3, 9, 44, (5, 3), torch.float32),          # fused, Fp = 44
+    "3x9x44-bf16": (3, 9, 44, (5, 3), torch.bfloat16),    # the bf16 kernels + apply, Fp = 48
+    "4x6x8": (4, 6, 8, None, torch.float32),
+}
 OPTIMS = {
     "sgd": dict(lr=0.05, momentum=0.9, dampening=0.3, weight_decay=0.02),
     "sgd-nesterov": dict(lr=0.05, momentum=0.8, nesterov=True, weight_decay=0.01),
@@ -82,7 +95,7 @@ def _model(family, F, hidden, reduction="mean", seed=5):
 
 
 def _batches(shape, count, seed=0):
-    B, L, F, _, dtype = SHAPES[shape]
+    B, L, F, _, dtype = SHAPES[shape] if shape in SHAPES else OTHER[shape]
     rng = np.random.default_rng(100 * B + L + seed)
     out = []
     for _ in range(count):
@@ -133,7 +146,7 @@ def _check_against_reference(name, before, grads, trainer, factor=1.0, after=Non
     params1 = after if after is not None else [p.detach().cpu().numpy() for p in trainer.model._params()]
     state1 = trainer.state_dict()["state"] if after is None else None
     for i, (p0, g) in enumerate(zip(params0, grads)):
-        st = {k: v.cpu().numpy() for k, v in state0.get(i, {}).items() if k != "step"}
+        st = {k: v.cpu().numpy() for k, v in state0.get(i, {}).items() if k != "step" and v is not None}
         if not st:
             st = ref.initial_state(algo, hyper, p0)
         want_p, want_state, bound = ref.step(algo, hyper, p0, g.cpu().numpy(), st, t)
@@ -196,7 +209,7 @@ def test_sum_reduction_listmle_and_the_other_sgd_forms():
 
 # ---- 3. ten consecutive steps on every shape ----
 @pytest.mark.parametrize("name", ["sgd", "adagrad", "adam"])
-@pytest.mark.parametrize("shape", list(SHAPES))
+@pytest.mark.parametrize("shape", [s for s in SHAPES if s not in PADDED])
 def test_ten_consecutive_steps(shape, name):
     B, L, F, hidden, _ = SHAPES[shape]
     family = {"sgd": "pairwise", "adagrad": "lambdarank", "adam": "listnet"}[name]
@@ -371,14 +384,25 @@ def test_two_trainers_stay_bit_identical(shape):
 
 
 # ---- 7. capture ----
-@pytest.mark.parametrize("name", ["adam", "sgd"])
+@pytest.mark.parametrize("name", ["adam", "sgd", "adagrad"])
 def test_graphed_replays_equal_eager_steps(name):
+    """(Adagrad with lr_decay: its clr is the one factor linear in t, read from the device header on replay.)"""
+    _graphed_replays_equal_eager_steps(name, "pairwise")
+
+
+def test_graphed_listmle_in_index_tie_order():
+    from pytorchltr_amd.utils import tie_breaking
+    with tie_breaking("index"):
+        _graphed_replays_equal_eager_steps("adam", "listmle")
+
+
+def _graphed_replays_equal_eager_steps(name, family):
     shape = "40x20x136"
     B, L, F, hidden, _ = SHAPES[shape]
     batches = _batches(shape, 7)
-    _trainer(_model("pairwise", F, hidden), name).step(*batches[0])       # one-time launch set-up, outside any capture
+    _trainer(_model(family, F, hidden), name).step(*batches[0])           # one-time launch set-up, outside any capture
     torch.cuda.synchronize()
-    a, b = _model("pairwise", F, hidden), _model("pairwise", F, hidden)
+    a, b = _model(family, F, hidden), _model(family, F, hidden)
     graphed_trainer, eager = _trainer(a, name), _trainer(b, name)
     call = graphed_trainer.graphed(batches[0], warmup=0)                    # so that the first REPLAY is the step t = 0
     assert graphed_trainer.steps == 0
@@ -429,3 +453,180 @@ def test_bad_input():
         _trainer(big, "sgd").step(xs, ys, n)
     assert str(ours.value) == str(theirs.value)
     assert trainer.steps == 0
+
+
+# ---- 10. the padded routes: the update meets gradient columns that are no parameters ----
+@pytest.mark.parametrize("name", ["sgd", "adagrad", "adam"])
+@pytest.mark.parametrize("shape", PADDED)
+def test_three_steps_on_the_padded_routes(shape, name):
+    B, L, F, hidden, _ = SHAPES[shape]
+    family = {"sgd": "pairwise", "adagrad": "lambdarank", "adam": "listnet"}[name]
+    model = _model(family, F, hidden)
+    weight = model.l1.weight
+    ptr = weight.data_ptr()
+    trainer = _trainer(model, name)
+    if name == "sgd" and shape not in FUSED:
+        trainer.lr = 2e-4               # (as test_ten_consecutive_steps: pair sums in the hundreds)
+    for step, batch in enumerate(_batches(shape, 3)):
+        _, grads, _ = _existing_step(model, *batch)
+        assert all(torch.isfinite(g).all() for g in grads)
+        before = _snapshot(trainer)
+        loss, got = trainer.step(*batch, return_grads=True)
+        for g, w, p in zip(got, grads, model._params()):
+            assert g.shape == w.shape == p.shape and torch.equal(g, w)
+        assert torch.isfinite(loss)
+        _check_against_reference(name, before, grads, trainer)
+        assert trainer.steps == step + 1
+        assert model.l1.weight is weight and weight.data_ptr() == ptr and weight.shape == (hidden[0], F)
+
+
+# ---- 11. one trainer, two row widths: the state re-laid through torch's form ----
+@pytest.mark.parametrize("name", ["adagrad", "adam", "sgd"])
+def test_one_trainer_two_row_widths(name):
+    """F = 44: an fp32 batch has rows of 44 floats, a bf16 batch (padded to 8) of 48, and the trainer re-lays its flat
+    state at each change.  Two fp32 steps, two bf16 steps, two fp32 steps, each within the bound from its snapshot;
+    the state after a change is the state before it bit for bit on the real columns, zero on the padding.  The step
+    count runs on for Adagrad and Adam; SGD's restarts at 1 (MLPTrainer.steps says why)."""
+    F, hidden = 44, (5, 3)
+    model = _model("pairwise", F, hidden)
+    trainer = _trainer(model, name)
+    plan = [("3x9x44", 0), ("3x9x44", 1), ("3x9x44-bf16", 0), ("3x9x44-bf16", 1), ("3x9x44", 2), ("3x9x44", 3)]
+    want_steps = [1, 2, 2, 3, 2, 3] if name == "sgd" else [1, 2, 3, 4, 5, 6]
+    width = None
+    for step, (shape, which) in enumerate(plan):
+        batch = _batches(shape, 4)[which]
+        if width is not None and width != shape:
+            params0, state0, t0 = _snapshot(trainer)
+            trainer._prime(batch[0])                      # (what graphed() calls ahead of a capture: the re-lay alone)
+            Fp = 48 if shape.endswith("bf16") else 44
+            assert trainer._state_Fp == Fp
+            state1 = trainer.state_dict()["state"]
+            assert sorted(state1) == sorted(state0) == list(range(6))
+            for i in state0:
+                for key in state0[i]:
+                    assert state1[i][key].shape == state0[i][key].shape and torch.equal(state1[i][key], state0[i][key])
+            rows = trainer._state[:hidden[0] * Fp].view(hidden[0], Fp)
+            assert Fp == F or (rows[:, F:] == 0).all()
+            assert trainer.steps == (1 if name == "sgd" else t0)
+        width = shape
+        _, grads, _ = _existing_step(model, *batch)
+        before = _snapshot(trainer)
+        _, got = trainer.step(*batch, return_grads=True)
+        assert all(torch.equal(g, w) for g, w in zip(got, grads))
+        _check_against_reference(name, before, grads, trainer)
+        assert trainer.steps == want_steps[step]
+
+
+# ---- 12. hidden sizes on the fused route ----
+@pytest.mark.parametrize("layout", ["tile", "wide"])
+@pytest.mark.parametrize("name", ["sgd", "adagrad", "adam"])
+@pytest.mark.parametrize("hidden", [(1, 1), (17, 5), (64, 16)], ids=["1x1", "17x5", "64x16"])
+def test_hidden_sizes_on_the_fused_route(hidden, name, layout):
+    B, L, F, _, _ = OTHER["4x6x8"]
+    model = _model("pairwise", F, hidden)
+    (batch,) = _batches("4x6x8", 1)
+    trainer = _trainer(model, name)
+    with _Layout(layout):
+        _, grads, _ = _existing_step(model, *batch)
+        before = _snapshot(trainer)
+        _, got = trainer.step(*batch, return_grads=True)
+        for g, w in zip(got, grads):
+            assert g.shape == w.shape and torch.equal(g, w)
+    _check_against_reference(name, before, grads, trainer)
+    assert trainer.steps == 1
+
+
+# ---- 13. from torch to the trainer ----
+@pytest.mark.parametrize("name", list(OPTIMS))
+def test_load_a_torch_optimizers_state(name):
+    """torch.optim on the model's own parameters takes three steps on the library's gradients; its state_dict goes
+    into a fresh MLPTrainer on a copy of the model; step 4 of both against the reference of that step from the loaded
+    state -- the trainer at factor 1, torch at factor 2."""
+    from pytorchltr_amd import fused
+    shape = "6x9x5"
+    B, L, F, hidden, _ = SHAPES[shape]
+    model = _model("pairwise", F, hidden)
+    batches = _batches(shape, 4)
+    params = list(model._params())
+    opt = _TORCH[_algo(name)](params, foreach=False, **OPTIMS[name])
+
+    def torch_step(batch):
+        _, grads, _ = _existing_step(model, *batch)
+        for p, g in zip(params, grads):
+            p.grad = g.clone()
+        opt.step()
+        return grads
+
+    for batch in batches[:3]:
+        torch_step(batch)
+    twin = copy.deepcopy(model)
+    for p in twin.parameters():
+        p.grad = None
+    trainer = fused.MLPTrainer(twin, _algo(name), lr=123.0)
+    trainer.load_state_dict(opt.state_dict())
+    # (torch's SGD keeps no count: a momentum buffer reads as 1, none -- plain SGD has no state at all -- as 0)
+    assert trainer.steps == {"sgd": 1, "sgd-nesterov": 1, "sgd-plain": 0}.get(name, 3)
+    assert trainer.lr == OPTIMS[name]["lr"]
+    before = _snapshot(trainer)
+    assert all(np.array_equal(a, p.detach().cpu().numpy()) for a, p in zip(before[0], params))
+    grads = torch_step(batches[3])
+    theirs = [p.detach().cpu().numpy() for p in params]
+    trainer.step(*batches[3])
+    _check_against_reference(name, before, grads, trainer)
+    _check_against_reference(name, before, grads, trainer, factor=2.0, after=theirs)
+    for p in params:
+        p.grad = None
+
+
+def test_load_a_torch_sgd_that_never_stepped():
+    """Its state is empty: the trainer's first step takes the t == 0 rule (the buffer becomes g, not 0.7 g)."""
+    from pytorchltr_amd import fused
+    shape, name = "6x9x5", "sgd"
+    B, L, F, hidden, _ = SHAPES[shape]
+    model = _model("pairwise", F, hidden)
+    (batch,) = _batches(shape, 1)
+    opt = torch.optim.SGD(list(model._params()), **OPTIMS[name])
+    trainer = fused.MLPTrainer(model, "sgd", lr=123.0)
+    trainer.load_state_dict(opt.state_dict())
+    assert trainer.steps == 0 and trainer.state_dict()["state"] == {}
+    _, grads, _ = _existing_step(model, *batch)
+    before = _snapshot(trainer)
+    assert before[2] == 0
+    trainer.step(*batch)
+    _check_against_reference(name, before, grads, trainer)
+    assert trainer.steps == 1
+
+
+# ---- 14. a learning-rate schedule ----
+@pytest.mark.parametrize("name", ["adagrad", "sgd-nesterov"])
+def test_a_schedule_set_through_lr(name):
+    """trainer.lr = lr0 * 0.5 ** (step // 2) before each of six eager steps, against torch.optim under LambdaLR with
+    the same factor: per step, from the trainer's snapshot (parameters and state go into the torch optimizer, its
+    learning rate stays the scheduler's), torch at factor 2 and the trainer at factor 1 of the reference."""
+    shape = "3x5x8"
+    B, L, F, hidden, _ = SHAPES[shape]
+    model = _model("pairwise", F, hidden)
+    trainer = _trainer(model, name)
+    lr0 = OPTIMS[name]["lr"]
+    params = [torch.nn.Parameter(p.detach().clone()) for p in model._params()]
+    opt = _TORCH[_algo(name)](params, foreach=False, **OPTIMS[name])
+    sched = torch.optim.lr_scheduler.LambdaLR(opt, lambda epoch: 0.5 ** (epoch // 2))
+    for step, batch in enumerate(_batches(shape, 6)):
+        trainer.lr = lr0 * 0.5 ** (step // 2)
+        assert opt.param_groups[0]["lr"] == trainer.lr
+        _, grads, _ = _existing_step(model, *batch)
+        before = _snapshot(trainer)
+        sd = opt.state_dict()
+        sd["state"] = copy.deepcopy(before[1])            # (torch keeps and steps the tensors it loads, in place)
+        opt.load_state_dict(sd)
+        with torch.no_grad():
+            for p, q, g in zip(params, model._params(), grads):
+                p.copy_(q)
+                p.grad = g.clone()
+        opt.step()
+        sched.step()
+        theirs = [p.detach().cpu().numpy() for p in params]
+        trainer.step(*batch)
+        _check_against_reference(name, before, grads, trainer)
+        _check_against_reference(name, before, grads, trainer, factor=2.0, after=theirs)
+    assert trainer.lr == lr0 * 0.25 and trainer.steps == 6

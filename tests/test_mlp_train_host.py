@@ -187,7 +187,17 @@ CONFIGS = [
 _TORCH = {"sgd": torch.optim.SGD, "adagrad": torch.optim.Adagrad, "adam": torch.optim.Adam}
 
 
-@pytest.mark.parametrize("algo, hyper", CONFIGS, ids=["%s-%d" % (a, i) for i, (a, _) in enumerate(CONFIGS)])
+def test_the_corner_grid_holds_the_earlier_configurations():
+    grid = [(algo, hyper) for _, algo, hyper in ref.CORNERS]
+    assert all(c in grid for c in CONFIGS) and len({name for name, _, _ in ref.CORNERS}) == len(grid) == 16
+
+
+# (the eight earlier configurations keep their ids; the corners they do not hold follow under their own names)
+_NEW_CORNERS = [c for c in ref.CORNERS if c[1:] not in CONFIGS]
+
+
+@pytest.mark.parametrize("algo, hyper", CONFIGS + [c[1:] for c in _NEW_CORNERS],
+                         ids=["%s-%d" % (a, i) for i, (a, _) in enumerate(CONFIGS)] + [c[0] for c in _NEW_CORNERS])
 def test_reference_rules_are_torch_optims_in_float64(algo, hyper):
     gen = torch.Generator().manual_seed(7)
     p = torch.randn(6, 7, dtype=torch.float64, generator=gen).requires_grad_(True)
@@ -214,6 +224,38 @@ def test_the_bound_counts_roundings_and_sees_cancellation():
     assert b["p"][0] == pytest.approx(3 * ref.U * (1.0 + 0.125) * (1 + 2.0 ** -10) + 0.5 * np.spacing(np.float32(0.875)))
     q, _, b = ref.step("sgd", dict(lr=0.25, weight_decay=0.5), p, np.float32([-0.5]), {}, 0)
     assert q[0] == 1.0 and b["p"][0] > 5 * ref.U * (1.0 + 0.25 * 1.0)
+
+
+STEP_COUNTS = (0, 1, 7, 999, 10 ** 6)
+
+
+@pytest.mark.parametrize("name", [c[0] for c in ref.CORNERS])
+def test_an_fp32_evaluation_stays_within_the_bound_at_every_corner(name):
+    """ref.step_f32 -- the header's chain in np.float32, operation by operation -- against ref.step at factor 1, on the
+    inputs the GPU tier uses: gradients log-uniform in [1e-3, 10] with one exact zero in eight, parameters N(0, 1), a
+    random state (and, from t = 0, also the state torch starts from: a zero accumulator under a zero gradient).  No
+    corner needed narrower inputs.  Prints the worst error / bound per corner (a record, not a threshold)."""
+    algo, hyper = ref.CORNER[name]
+    rng = np.random.default_rng(sum(name.encode()))
+    count, worst = 4096, 0.0
+    for t in STEP_COUNTS:
+        p = rng.normal(0.0, 1.0, count).astype(np.float32)
+        g = ref.synthetic_gradient(rng, count)
+        assert (g == 0).sum() == count // 8 and np.abs(g[g != 0]).min() >= 1e-3 * (1 - 1e-6) and np.abs(g).max() <= 10.0
+        states = [ref.random_state(rng, algo, count)]
+        if t == 0:
+            states.append({k: v.astype(np.float32) for k, v in ref.initial_state(algo, hyper, p).items()})
+        for state in states:
+            want_p, want_state, bound = ref.step(algo, hyper, p, g, state, t)
+            got_p, got_state = ref.step_f32(algo, hyper, p, g, state, t)
+            assert sorted(got_state) == sorted(want_state)
+            for key, got, want in [("p", got_p, want_p)] + [(k, got_state[k], want_state[k]) for k in want_state]:
+                err = np.abs(got.astype(np.float64) - want)
+                assert np.isfinite(want).all() and np.isfinite(bound[key]).all(), (name, t, key)
+                ratio = float((err / bound[key]).max())
+                assert (err <= bound[key]).all(), (name, t, key, ratio)
+                worst = max(worst, ratio)
+    print("%s: worst error / bound %.3f" % (name, worst))
 
 
 # ---- the state_dict conversion ----
@@ -288,6 +330,29 @@ def test_load_state_dict_takes_the_groups_hyper_parameters():
         trainer.load_state_dict({"state": {}, "param_groups": [dict(opt.state_dict()["param_groups"][0], params=[0, 1])]})
     with pytest.raises(NotImplementedError):
         trainer.load_state_dict(torch.optim.Adam(model.parameters(), amsgrad=True).state_dict())
+
+
+def test_load_state_dict_refuses_a_partial_state():
+    """One to five per-parameter entries are no state of the six parameters: a ValueError that names the count, and the
+    trainer as it was.  None (no step taken) and six load as before."""
+    from pytorchltr_amd import fused
+    model = _model()
+    opt = torch.optim.Adam(model.parameters(), lr=0.02)
+    for p in model.parameters():
+        p.grad = torch.ones_like(p)
+    opt.step()
+    full = opt.state_dict()
+    trainer = fused.MLPTrainer(model, "adam", lr=0.5)
+    for count in (1, 3, 5):
+        part = {"state": {k: full["state"][k] for k in range(count)}, "param_groups": full["param_groups"]}
+        with pytest.raises(ValueError, match=r"\b%d per-parameter entries" % count):
+            trainer.load_state_dict(part)
+        assert trainer.lr == 0.5 and trainer.steps == 0 and trainer.state_dict()["state"] == {}
+    trainer.load_state_dict({"state": {}, "param_groups": full["param_groups"]})
+    assert trainer.lr == 0.02 and trainer.steps == 0 and trainer.state_dict()["state"] == {}
+    trainer.load_state_dict(full)
+    assert trainer.steps == 1
+    _assert_same_state(trainer.state_dict()["state"], full["state"])
 
 
 # ---- the constructor ----
