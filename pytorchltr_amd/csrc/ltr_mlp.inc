@@ -1,5 +1,6 @@
 // ltr_mlp.inc -- fused ReLU-MLP scorer (F -> H1 -> H2 -> 1) + pairwise loss + backward on MFMA.
-// Included by ltr_kernels.hip (uses its LDS carve, label staging and symmetric pair pass).
+// Included by ltr_mlp.hip (uses ltr_common.inc's LDS carve, label staging and symmetric pair pass); this file is the
+// 8-wave kernel and its launchers -- the reduction is in ltr_mlp_reduce.inc, the step's host side in ltr_mlp_step.inc.
 //
 // SURVEY.md section 8 f-2: the documented training step
 //     loss_fn(model(xs), ys, n).mean().backward()          docs/source/getting-started.rst:40-101
@@ -27,7 +28,7 @@
 //                                     documents; chunk registers then take the next query's X
 // dW1 tiles are disjoint between the waves and live in registers across all the queries of the
 // workgroup; the small sums fold over the waves in LDS; one partial vector per workgroup is
-// written at the end and mlp_reduce_kernel adds the partials in a fixed order (deterministic).
+// written at the end and mlp_reduce_kernel (ltr_mlp_reduce.inc) adds the partials in a fixed order (deterministic).
 // f32 MFMA is an exact k-ordered fma chain (no reduced precision): dtype stays "f32".
 // DESIGN.md section 10 has the measurements and the history of this kernel.
 #pragma once
@@ -35,7 +36,6 @@
 
 #include "ltr_listwise.h"
 #include "ltr_mlp_lambdarank.h"
-#include "ltr_mlp_listwise.inc"
 
 typedef float mlp_f4 __attribute__((ext_vector_type(4)));
 
@@ -71,9 +71,6 @@ __host__ __device__ inline int mlp_param_count(int F, int H1, int H2)
 {
     return H1 * F + H1 + H2 * H1 + 2 * H2 + 1;
 }
-
-// floats between the partial vectors of consecutive workgroups (16-byte aligned rows)
-__host__ __device__ inline int mlp_pitch(int P) { return (P + 3) & ~3; }
 
 // LDS floats ahead of the per-query block of the loss code
 __host__ __device__ inline int mlp_bucket(int F)
@@ -829,149 +826,11 @@ mlp_pairwise_kernel(MlpParams p)
     MLP_STAMP(9);                                  // partial vector written
 }
 
-// grads[i] = sum over the workgroups' partial vectors, fixed order; loss_sum[0] = sum_b loss[b].
-// `pitch` = floats between consecutive partial vectors (>= P).
-// Block = 64 parameters x 16 slices of the partial rows (1024 threads): every thread adds its rows
-// with four independent chains, the 16 slices meet in LDS.
-constexpr int kMlpRedSlices = 32;
-constexpr int kMlpRedCols = 32;      // 32 parameters x 32 row slices per block: P / 32 blocks (232 at the
-                                     // guide's network) cover the chip; 64 x 16 left half of the CUs idle
-                                     // (reduce kernel 6.5 -> measured below)
-__global__ void __launch_bounds__(kMlpRedCols * kMlpRedSlices)
-mlp_reduce_kernel(const float *__restrict__ part, int nPart, int P, int pitch, float *__restrict__ grads,
-                  const float *__restrict__ loss, int B, float *__restrict__ loss_sum)
-{
-    __shared__ float red[kMlpRedSlices][kMlpRedCols];
-    __shared__ float lred[16];
-    const int tid = threadIdx.x;
-    const int col = tid % kMlpRedCols, slice = tid / kMlpRedCols;
-    const int i = blockIdx.x * kMlpRedCols + col;
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    if (i < P) {
-        // 16 rows per round, all 16 loads in flight before the first add (the kernel is bound by the
-        // round trips of its strided 4-byte loads: 6.3 -> measured below with 4 loads in flight)
-        const float *src = part + i;
-        for (int r0 = slice; r0 < nPart; r0 += 16 * kMlpRedSlices) {
-            float v[16];
-#pragma unroll
-            for (int k = 0; k < 16; ++k) {
-                const int r = r0 + k * kMlpRedSlices;
-                v[k] = src[(size_t)(r < nPart ? r : r0) * pitch];
-            }
-#pragma unroll
-            for (int k = 0; k < 16; k += 4) {
-                a0 += (r0 + k * kMlpRedSlices < nPart) ? v[k] : 0.f;
-                a1 += (r0 + (k + 1) * kMlpRedSlices < nPart) ? v[k + 1] : 0.f;
-                a2 += (r0 + (k + 2) * kMlpRedSlices < nPart) ? v[k + 2] : 0.f;
-                a3 += (r0 + (k + 3) * kMlpRedSlices < nPart) ? v[k + 3] : 0.f;
-            }
-        }
-    }
-    red[slice][col] = (a0 + a1) + (a2 + a3);
-    __syncthreads();
-    if (slice == 0 && i < P) {
-        float t = 0.f;
-#pragma unroll
-        for (int k = 0; k < kMlpRedSlices; ++k) t += red[k][col];
-        grads[i] = t;
-    }
-    if (loss_sum && blockIdx.x == 0) {
-        float s = 0.f;
-        for (int b = tid; b < B; b += kMlpRedCols * kMlpRedSlices) s += loss[b];
-        s = block_sum(s, lred);
-        if (tid == 0) loss_sum[0] = s;
-    }
-}
-
-// The same sum with 16-byte loads: a block takes COLS4 float4 columns x 1024 / COLS4 row slices (every
-// load instruction of a wave moves COLS4 * 16 contiguous bytes of 64 / COLS4 rows -- four times fewer, wider
-// requests than the 4-byte version for the same 15 MB), the slices meet in LDS in two levels.  Fixed order.
-constexpr int kMlpRedCols4 = 16;
-template <int COLS4>
-__global__ void __launch_bounds__(1024)
-mlp_reduce4_kernel(const float *__restrict__ part, int nPart, int P, int pitch, float *__restrict__ grads,
-                   const float *__restrict__ loss, int B, float *__restrict__ loss_sum)
-{
-    constexpr int SL = 1024 / COLS4;
-    static_assert(SL % 16 == 0, "two-level fold: 16 groups of slices");
-    __shared__ float4 red[SL][COLS4];
-    __shared__ float4 red2[16][COLS4];
-    __shared__ float lred[16];
-    const int tid = threadIdx.x;
-    const int col = tid % COLS4, slice = tid / COLS4;
-    const int c4 = blockIdx.x * COLS4 + col;
-    const int P4 = pitch >> 2;
-    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (c4 < P4) {
-        const float4 *src = reinterpret_cast<const float4 *>(part) + c4;
-        for (int r0 = slice; r0 < nPart; r0 += 8 * SL) {
-            float4 v[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const int r = r0 + k * SL;
-                v[k] = src[(size_t)(r < nPart ? r : r0) * P4];
-            }
-#pragma unroll
-            for (int k = 0; k < 8; ++k)
-                if (r0 + k * SL < nPart) vadd(a, v[k]);
-        }
-    }
-    red[slice][col] = a;
-    __syncthreads();
-    if (tid < 16 * COLS4) {
-        const int g = tid / COLS4;
-        float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int j = 0; j < SL / 16; ++j) vadd(t, red[g + 16 * j][col]);
-        red2[g][col] = t;
-    }
-    __syncthreads();
-    if (tid < COLS4 && c4 < P4) {
-        float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int g = 0; g < 16; ++g) vadd(t, red2[g][col]);
-        const int i = 4 * c4;
-        if (i + 3 < P) {
-            *reinterpret_cast<float4 *>(grads + i) = t;
-        } else {
-            if (i < P) grads[i] = t.x;
-            if (i + 1 < P) grads[i + 1] = t.y;
-            if (i + 2 < P) grads[i + 2] = t.z;
-        }
-    }
-    if (loss_sum && blockIdx.x == 0) {
-        float s = 0.f;
-        for (int b = tid; b < B; b += 1024) s += loss[b];
-        s = block_sum(s, lred);
-        if (tid == 0) loss_sum[0] = s;
-    }
-}
-
 // ---- host side ----
 inline int mlp_grid(int B)
 {
     const int cus = device_cu_count();
     return B < cus ? B : cus;
-}
-
-#include "ltr_mlp2.inc"
-
-// ltr_debug_mlp_layout(1) keeps the training step on the 8-wave kernel of this file (A/B measurements,
-// tests of both kernels; the 4-wave tile kernel of ltr_mlp2.inc is the default where it applies)
-inline int &mlp_layout_choice() { static int choice = 0; return choice; }
-
-// auto (0): the tile kernel where the batch gives every CU its two workgroups (B >= 2 x CUs) or the
-// lists are longer than the 8-wave kernel takes; below that the 8-wave kernel is 1.5-2 us faster
-// (B = 64 .. 384 at the guide's network: 27.5 / 29.1 / 32.9 / 42.3 against 29.7 / 30.9 / 34.6 / 44.3 us;
-// 512: 47.4 / 46.6, 768: 58.0 / 49.5).  1: 8-wave kernel wherever it applies, 2: tile kernel likewise.
-inline bool mlp_use_tile_layout(int F, int B, int L)
-{
-    if (!mlp2_takes(F)) return false;
-    if (L > kMlpMaxLen) return true;
-    const int choice = mlp_layout_choice();
-    if (choice == 1) return false;
-    if (choice == 2) return true;
-    return B >= 2 * device_cu_count();
 }
 
 template <int KIND, int NT, bool FWD = false>
@@ -1004,229 +863,3 @@ int launch_mlp_kind(const MlpParams &p, int grid, hipStream_t stream)
     default: return launch_mlp_nt<KIND, 14>(p, grid, stream);
     }
 }
-
-// the cross-workgroup sum of the partial vectors (and loss_sum) behind a training step of either entry point
-inline int mlp_reduce_launch(void *workspace, int grid, int P, float *grads, const float *loss, int B, float *loss_sum,
-                             hipStream_t s)
-{
-    // (grads as float4 needs a 16-byte aligned output; otherwise the 4-byte version)
-    if ((reinterpret_cast<uintptr_t>(grads) & 15) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0) {
-        const int P4 = mlp_pitch(P) >> 2;
-        hipLaunchKernelGGL(mlp_reduce4_kernel<kMlpRedCols4>, dim3((unsigned)((P4 + kMlpRedCols4 - 1) / kMlpRedCols4)),
-                           dim3(1024), 0, s, (const float *)workspace, grid, P, mlp_pitch(P), grads, loss, B, loss_sum);
-        return (int)hipGetLastError();
-    }
-    hipLaunchKernelGGL(mlp_reduce_kernel, dim3((unsigned)((P + kMlpRedCols - 1) / kMlpRedCols)),
-                       dim3(kMlpRedCols * kMlpRedSlices), 0, s,
-                       (const float *)workspace, grid, P, mlp_pitch(P), grads, loss, B, loss_sum);
-    return (int)hipGetLastError();
-}
-
-// ---- the listwise step (ltr_mlp_listwise_f32) ----
-inline bool bad_mlp_listwise_loss(int loss) { return loss != LTR_LISTWISE_LISTNET && loss != LTR_LISTWISE_LISTMLE; }
-
-// The plan rule behind the shape checks: the list fits the layouts that take F, and the LDS of every layout the call
-// may be steered to (ltr_debug_mlp_layout) -- the static part and the loss slot's row -- fits the workgroup.
-// (`kind`: LTR_MLP_LISTNET, LTR_MLP_LISTMLE or LTR_MLP_LAMBDARANK)
-inline bool mlp_slot_fits(int kind, int L, int F)
-{
-    if (L > (mlp2_takes(F) ? kM2MaxLen : kMlpMaxLen)) return false;
-    if (mlp2_takes(F) &&
-        mlp2_lds_bytes(kind, mlp_bucket(F), L <= kM2ParkLen ? kM2ParkLen : kM2MaxLen) > kLdsBudget / kM2Wgs)
-        return false;
-    if (L <= kMlpMaxLen && mlp_lds_bytes(kind, F) > kLdsBudget) return false;
-    return true;
-}
-
-inline bool mlp_listwise_fits(int loss, int L, int F)
-{
-    return mlp_slot_fits(loss == LTR_LISTWISE_LISTNET ? LTR_MLP_LISTNET : LTR_MLP_LISTMLE, L, F);
-}
-
-// B, L, the network and its limits as every launching entry point of this file checks them
-inline bool mlp_step_bad_network(int B, int L, int F, int H1, int H2)
-{
-    return B < 0 || L <= 0 || F <= 0 || H1 <= 0 || H2 <= 0 || (F & 3) || F > 16 * 14 || H1 > kMlpH1 || H2 > kMlpH2;
-}
-
-// the params of a launch without a loss: float labels at X (not used; any readable address for the prefetch); the rest is the caller's
-inline MlpParams mlp_step_params(const float *X, const float *W1, const float *b1, const float *W2, const float *b2,
-                                 const float *W3, const float *b3, const int64_t *n, int B, int L, int F, int H1, int H2)
-{
-    MlpParams p;
-    p.X = X; p.W1 = W1; p.b1 = b1; p.W2 = W2; p.b2 = b2; p.W3 = W3; p.b3 = b3;
-    p.rel = X; p.n = n; p.grad_out = nullptr;
-    p.loss = nullptr; p.scores_out = nullptr; p.part = nullptr;
-    p.B = B; p.L = L; p.F = F; p.H1 = H1; p.H2 = H2;
-    p.sigma = 1.0f; p.rel_dtype = LTR_LABEL_F32; p.P = mlp_param_count(F, H1, H2); p.pitch = mlp_pitch(p.P); p.fwd_only = 0;
-    return p;
-}
-
-extern "C" {
-
-LTR_DEBUG_HOOK void ltr_debug_mlp_layout(int layout) { mlp_layout_choice() = layout; }
-
-int ltr_mlp_max_list_len(int F)
-{
-    if (F <= 0 || (F & 3) || F > 16 * 14) return 0;
-    return mlp2_takes(F) ? kM2MaxLen : kMlpMaxLen;
-}
-
-size_t ltr_mlp_param_count(int F, int H1, int H2)
-{
-    if (F <= 0 || H1 <= 0 || H2 <= 0) return 0;
-    return (size_t)mlp_param_count(F, H1, H2);
-}
-
-size_t ltr_mlp_workspace_bytes(int B, int F, int H1, int H2)
-{
-    if (B <= 0 || F <= 0 || H1 <= 0 || H2 <= 0) return 0;
-    // (the larger of the two layouts' grids)
-    return (size_t)mlp2_grid(B) * (size_t)mlp_pitch(mlp_param_count(F, H1, H2)) * sizeof(float);
-}
-
-int ltr_mlp_pairwise_f32(int kind, float sigma, const float *X, const float *W1, const float *b1,
-                         const float *W2, const float *b2, const float *W3, const float *b3,
-                         const void *rel, int rel_dtype, const int64_t *n, const float *grad_out,
-                         int B, int L, int F, int H1, int H2, float *loss, float *scores_out,
-                         float *grads, float *loss_sum, void *workspace, size_t workspace_bytes,
-                         void *stream)
-{
-    LTR_CLEAR_STALE_ERROR();
-    if (mlp_step_bad_network(B, L, F, H1, H2)) return LTR_ERR_SHAPE;
-    if (L > (mlp2_takes(F) ? kM2MaxLen : kMlpMaxLen)) return LTR_ERR_LIST_TOO_LONG;
-    if (kind < LTR_HINGE || kind > LTR_NDCG2) return LTR_ERR_KIND;
-    if (rel_dtype < LTR_LABEL_I64 || rel_dtype > LTR_LABEL_I32) return LTR_ERR_KIND;
-    if (!W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !grads) return LTR_ERR_NULL;
-    if (B > 0 && (!X || !rel || !n || !loss)) return LTR_ERR_NULL;
-    const int P = mlp_param_count(F, H1, H2);
-    const bool tile = mlp_use_tile_layout(F, B, L);
-    const int grid = B > 0 ? (tile ? mlp2_grid(B) : mlp_grid(B)) : 0;
-    if (B > 0 && (!workspace || workspace_bytes < (size_t)grid * mlp_pitch(P) * sizeof(float)))
-        return LTR_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    if (B > 0) {
-        MlpParams p = mlp_step_params(X, W1, b1, W2, b2, W3, b3, n, B, L, F, H1, H2);
-        p.rel = rel; p.rel_dtype = rel_dtype; p.grad_out = grad_out; p.sigma = sigma;
-        p.loss = loss; p.scores_out = scores_out; p.part = (float *)workspace;
-        const int rc = tile ? with_kind(kind, [&](auto K) { return launch_mlp2_kind<K>(p, grid, s); })
-                            : with_kind(kind, [&](auto K) { return launch_mlp_kind<K>(p, grid, s); });
-        if (rc != 0) return rc;
-    }
-    return mlp_reduce_launch(workspace, grid, P, grads, loss, B, loss_sum, s);
-}
-
-int ltr_mlp_listwise_plan(int loss, int B, int L, int F, int H1, int H2)
-{
-    if (bad_mlp_listwise_loss(loss) || B <= 0 || L <= 0 || H1 <= 0 || H2 <= 0 || H1 > kMlpH1 || H2 > kMlpH2) return 0;
-    if (F <= 0 || (F & 3) || F > 16 * 14) return 0;
-    return mlp_listwise_fits(loss, L, F) ? 1 : 0;
-}
-
-int ltr_mlp_listwise_f32(int loss, int k, const float *X, const float *W1, const float *b1, const float *W2,
-                         const float *b2, const float *W3, const float *b3, const void *rel, int rel_dtype,
-                         const int64_t *n, const int32_t *tie, int use_seed, uint64_t seed, const int64_t *seed_dev,
-                         const float *grad_out, int B, int L, int F, int H1, int H2, float *loss_out, float *scores_out,
-                         float *grads, float *loss_sum, void *workspace, size_t workspace_bytes, void *stream)
-{
-    LTR_CLEAR_STALE_ERROR();
-    if (bad_mlp_listwise_loss(loss) || bad_label_dtype(rel_dtype)) return LTR_ERR_KIND;
-    if (mlp_step_bad_network(B, L, F, H1, H2)) return LTR_ERR_SHAPE;
-    if (L > (mlp2_takes(F) ? kM2MaxLen : kMlpMaxLen)) return LTR_ERR_LIST_TOO_LONG;
-    if (B == 0) return LTR_OK;
-    if (!X || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !rel || !n || !loss_out || !grads) return LTR_ERR_NULL;
-    const int P = mlp_param_count(F, H1, H2);
-    const bool tile = mlp_use_tile_layout(F, B, L);
-    const int grid = tile ? mlp2_grid(B) : mlp_grid(B);
-    if (!workspace || workspace_bytes < (size_t)grid * mlp_pitch(P) * sizeof(float)) return LTR_ERR_WORKSPACE;
-    if (!mlp_listwise_fits(loss, L, F)) return LTR_ERR_CONFIG;
-    hipStream_t s = (hipStream_t)stream;
-    MlpParams p = mlp_step_params(X, W1, b1, W2, b2, W3, b3, n, B, L, F, H1, H2);
-    p.rel = rel; p.rel_dtype = rel_dtype; p.grad_out = grad_out;
-    p.loss = loss_out; p.scores_out = scores_out; p.part = (float *)workspace;
-    p.lw.k = k;
-    if (loss == LTR_LISTWISE_LISTMLE) {           // (ListNet ranks nothing: the tie arguments are ignored)
-        if (use_seed) { p.lw.use_seed = 1; p.lw.tie_seed = seed; p.lw.tie_seed_dev = seed_dev; }
-        else p.lw.tie = tie;
-    }
-    int rc;
-    if (loss == LTR_LISTWISE_LISTNET)
-        rc = tile ? launch_mlp2_kind<LTR_MLP_LISTNET>(p, grid, s) : launch_mlp_kind<LTR_MLP_LISTNET>(p, grid, s);
-    else
-        rc = tile ? launch_mlp2_kind<LTR_MLP_LISTMLE>(p, grid, s) : launch_mlp_kind<LTR_MLP_LISTMLE>(p, grid, s);
-    if (rc != 0) return rc;
-    return mlp_reduce_launch(workspace, grid, P, grads, loss_out, B, loss_sum, s);
-}
-
-// ---- the LambdaRank step (include/ltr_mlp_lambdarank.h; DESIGN.md 27) ----
-int ltr_mlp_lambdarank_plan(int B, int L, int F, int H1, int H2)
-{
-    if (B <= 0 || L <= 0 || H1 <= 0 || H2 <= 0 || H1 > kMlpH1 || H2 > kMlpH2) return 0;
-    if (F <= 0 || (F & 3) || F > 16 * 14) return 0;
-    return mlp_slot_fits(LTR_MLP_LAMBDARANK, L, F) ? 1 : 0;
-}
-
-int ltr_mlp_lambdarank_f32(int k, float sigma, const float *X, const float *W1, const float *b1, const float *W2,
-                           const float *b2, const float *W3, const float *b3, const void *rel, int rel_dtype,
-                           const int64_t *n, const float *grad_out, int B, int L, int F, int H1, int H2, float *loss_out,
-                           float *scores_out, float *grads, float *loss_sum, void *workspace, size_t workspace_bytes,
-                           void *stream)
-{
-    LTR_CLEAR_STALE_ERROR();
-    if (bad_label_dtype(rel_dtype)) return LTR_ERR_KIND;
-    // (sigma: the guard of ltr_lambdarank_f32, check_lambdarank in ltr_lambdarank.inc)
-    if (mlp_step_bad_network(B, L, F, H1, H2) || !std::isfinite(sigma)) return LTR_ERR_SHAPE;
-    if (L > (mlp2_takes(F) ? kM2MaxLen : kMlpMaxLen)) return LTR_ERR_LIST_TOO_LONG;
-    if (B == 0) return LTR_OK;
-    if (!X || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !rel || !n || !loss_out || !grads) return LTR_ERR_NULL;
-    const int P = mlp_param_count(F, H1, H2);
-    const bool tile = mlp_use_tile_layout(F, B, L);
-    const int grid = tile ? mlp2_grid(B) : mlp_grid(B);
-    if (!workspace || workspace_bytes < (size_t)grid * mlp_pitch(P) * sizeof(float)) return LTR_ERR_WORKSPACE;
-    if (!mlp_slot_fits(LTR_MLP_LAMBDARANK, L, F)) return LTR_ERR_CONFIG;
-    hipStream_t s = (hipStream_t)stream;
-    MlpParams p = mlp_step_params(X, W1, b1, W2, b2, W3, b3, n, B, L, F, H1, H2);
-    p.rel = rel; p.rel_dtype = rel_dtype; p.grad_out = grad_out; p.sigma = sigma;
-    p.loss = loss_out; p.scores_out = scores_out; p.part = (float *)workspace;
-    p.lw.k = k;
-    const int rc = tile ? launch_mlp2_kind<LTR_MLP_LAMBDARANK>(p, grid, s) : launch_mlp_kind<LTR_MLP_LAMBDARANK>(p, grid, s);
-    if (rc != 0) return rc;
-    return mlp_reduce_launch(workspace, grid, P, grads, loss_out, B, loss_sum, s);
-}
-
-// bench.py `extra.mlp_scorer_fused.launch_ceiling` (include/ltr_hip.h): the launch geometry of the fused MLP training
-// step on the tile layout -- fills, image, barriers, MFMA streams -- with nothing else (mlp_tile_kernel<..., PROBE>)
-LTR_DEBUG_HOOK int ltr_debug_mlp_probe_f32(const float *X, const float *W1, const float *b1, const float *W2, const float *b2,
-                            const float *W3, const float *b3, const int64_t *n, int B, int L, int F, int H1, int H2,
-                            float *out, void *stream)
-{
-    LTR_CLEAR_STALE_ERROR();
-    if (B <= 0 || L <= 0 || L > kM2ParkLen || F != 136 || H1 <= 0 || H2 <= 0 || H1 > kMlpH1 || H2 > kMlpH2) return LTR_ERR_SHAPE;
-    if (!X || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !n || !out) return LTR_ERR_NULL;
-    MlpParams p = mlp_step_params(X, W1, b1, W2, b2, W3, b3, n, B, L, F, H1, H2);
-    p.loss = out;
-    const size_t lds = mlp2_lds_bytes(LTR_HINGE, 9, kM2ParkLen);
-    LTR_ENSURE_LDS((mlp_tile_kernel<LTR_HINGE, 9, 34, kM2ParkLen, false, true>), lds);
-    hipLaunchKernelGGL((mlp_tile_kernel<LTR_HINGE, 9, 34, kM2ParkLen, false, true>), dim3((unsigned)mlp2_grid(B)), dim3(kM2Threads), lds,
-                       (hipStream_t)stream, p);
-    return (int)hipGetLastError();
-}
-
-int ltr_mlp_scores_f32(const float *X, const float *W1, const float *b1, const float *W2,
-                       const float *b2, const float *W3, const float *b3, const int64_t *n, int B,
-                       int L, int F, int H1, int H2, float *scores_out, void *stream)
-{
-    LTR_CLEAR_STALE_ERROR();
-    if (mlp_step_bad_network(B, L, F, H1, H2)) return LTR_ERR_SHAPE;
-    const bool tile_scores = L > kMlpMaxLen && mlp2_takes(F);       // 129 .. 256 documents: the tile kernel
-    if (L > (tile_scores ? kM2MaxLen : kMlpMaxLen)) return LTR_ERR_LIST_TOO_LONG;
-    if (!W1 || !b1 || !W2 || !b2 || !W3 || !b3) return LTR_ERR_NULL;
-    if (B == 0) return LTR_OK;
-    if (!X || !n || !scores_out) return LTR_ERR_NULL;
-    MlpParams p = mlp_step_params(X, W1, b1, W2, b2, W3, b3, n, B, L, F, H1, H2);
-    p.scores_out = scores_out; p.fwd_only = 1;
-    if (tile_scores) return launch_mlp2_scores(p, mlp2_grid(B), (hipStream_t)stream);
-    return launch_mlp_scores(p, mlp_grid(B), (hipStream_t)stream);
-}
-
-}  // extern "C"

@@ -1,6 +1,6 @@
 // ltr_mlp2.inc -- the training step of the fused ReLU-MLP scorer (F -> H1 -> H2 -> 1) + pairwise
 // loss + backward, second layout: FOUR-wave workgroups, TWO per CU, every wave owns one 16-row
-// tile of the first hidden layer.  Included by ltr_mlp.inc (whose kernel keeps the evaluation half
+// tile of the first hidden layer.  Included behind ltr_mlp.inc (whose kernel keeps the evaluation half
 // and the widest feature bucket).  Same contract: the reference guide's training step
 //     loss_fn(model(xs), ys, n).mean().backward()          docs/source/getting-started.rst:40-101
 // with `model` = Linear(F,50) / ReLU / Linear(50,10) / ReLU / Linear(10,1), losses of

@@ -1,5 +1,5 @@
-// ltr_mlp_listwise.inc -- the listwise loss slot of the fused MLP training step (included by ltr_mlp.inc, in front of
-// its kernels; C ABI: ltr_mlp_listwise_f32, include/ltr_listwise.h; DESIGN.md 17).
+// ltr_mlp_listwise.inc -- the listwise loss slot of the fused MLP training step (included by ltr_mlp.hip, in front of
+// both kernels; C ABI: ltr_mlp_listwise_f32, include/ltr_listwise.h; DESIGN.md 17).
 //
 // Both MLP kernels (mlp_tile_kernel, ltr_mlp2.inc; mlp_pairwise_kernel, ltr_mlp.inc) have one loss slot between the
 // forward and the backward chain: the whole query's scores and labels sit in LDS, and the slot leaves

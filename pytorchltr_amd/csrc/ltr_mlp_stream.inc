@@ -1,7 +1,7 @@
 // ltr_mlp_stream.inc -- what the stand-alone ReLU-MLP scorer kernels (F -> H1 -> H2 -> 1) share: the device layer under
 // ltr_mlp_rows.inc (f32 rows), ltr_mlp_bf16.inc (bf16 rows) and ltr_mlp_wide.inc (K-streamed wide rows), the one
 // streaming kernel body of the first two, and the host glue of all three.  Included by ltr_mlp.hip behind ltr_mlp.inc,
-// whose mfma16, reduction kernel and padding rules it uses, and in front of those three files.
+// whose mfma16 and padding rules it uses (the reduction: ltr_mlp_reduce.inc), and in front of those three files.
 //
 // The unit of work is a TILE of 32 consecutive FLAT rows of the (B * L, F) matrix; a row is real iff
 // row % L < n[row / L].  Four waves; wave w owns hidden-1 rows 16w .. 16w+15 (W1 / W2 fragments in registers, transposed

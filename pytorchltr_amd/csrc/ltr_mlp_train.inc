@@ -1,7 +1,8 @@
 // ltr_mlp_train.inc -- the fused MLP training step with the optimizer update inside the reduction launch
-// (include/ltr_mlp_train.h; DESIGN.md 28).  Included behind ltr_mlp.inc, whose MFMA kernels, launchers and guards it
-// uses as they are; the two reduce-and-update kernels repeat the geometry and the summation order of mlp_reduce4_kernel
-// and mlp_reduce_kernel and put the update rule behind the final sum, in the thread that holds it.
+// (include/ltr_mlp_train.h; DESIGN.md 28, 29).  Included behind ltr_mlp_step.inc, whose launch path and guards it uses
+// as they are; the two reduce-and-update kernels are the reduction cores of ltr_mlp_reduce.inc -- the geometry and the
+// summation order of mlp_reduce4_kernel and mlp_reduce_kernel -- with the update rule as their epilogue, behind the
+// final sum, in the thread that holds it.
 #include "ltr_mlp_train.h"
 
 // What the update kernels get: the six parameter tensors, the flat layout's segment starts, the state and the rule's
@@ -90,8 +91,6 @@ __device__ inline void mlp_train_rule(const MlpTrainArgs &a, const MlpTrainStep 
     }
 }
 
-__device__ inline bool mlp_train_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // The epilogue of a thread that holds N consecutive gradients from flat index `i` (N = 1 or 4), in two halves: the loads
 // of the parameters and their state (mlp_train_load: they depend on nothing the launch computes, so a reduction issues
 // them ahead of its last fold), then the rule and the stores (mlp_train_finish).  The segment starts are no multiples of
@@ -114,10 +113,10 @@ __device__ inline void mlp_train_load(const MlpTrainArgs &a, int i, MlpTrainElem
     e.vec = false;
     if (N == 4) {
         e.vec = e.pp[0] && e.pp[N > 1 ? 1 : 0] == e.pp[0] + 1 && e.pp[N > 2 ? 2 : 0] == e.pp[0] + 2 &&
-                e.pp[N > 3 ? 3 : 0] == e.pp[0] + 3 && mlp_train_aligned16(e.pp[0]);
+                e.pp[N > 3 ? 3 : 0] == e.pp[0] + 3 && mlp_aligned16(e.pp[0]);
     }
-    e.vec0 = N == 4 && need0 && e.vec && mlp_train_aligned16(s0);
-    e.vec1 = N == 4 && need1 && e.vec && mlp_train_aligned16(s1);
+    e.vec0 = N == 4 && need0 && e.vec && mlp_aligned16(s0);
+    e.vec1 = N == 4 && need1 && e.vec && mlp_aligned16(s1);
     if (e.vec) {
         const float4 v = *reinterpret_cast<const float4 *>(e.pp[0]);
         e.p[0] = v.x; e.p[N > 1 ? 1 : 0] = v.y; e.p[N > 2 ? 2 : 0] = v.z; e.p[N > 3 ? 3 : 0] = v.w;
@@ -146,7 +145,7 @@ __device__ inline void mlp_train_finish(const MlpTrainArgs &a, const MlpTrainSte
                                         MlpTrainElems<N> &e)
 {
     if (a.grads_out) {
-        if (N == 4 && i + 3 < a.P && mlp_train_aligned16(a.grads_out + i)) {
+        if (N == 4 && i + 3 < a.P && mlp_aligned16(a.grads_out + i)) {
             *reinterpret_cast<float4 *>(a.grads_out + i) = make_float4(g[0], g[N > 1 ? 1 : 0], g[N > 2 ? 2 : 0], g[N > 3 ? 3 : 0]);
         } else {
 #pragma unroll
@@ -189,116 +188,56 @@ __device__ inline void mlp_train_update(const MlpTrainArgs &a, const MlpTrainSte
     mlp_train_finish<N>(a, st, i, g, e);
 }
 
-// mlp_reduce_kernel (same block, same chains, same order) with the update behind the sum of column i
+// The update as the epilogue of a reduction core (ltr_mlp_reduce.inc): the gradient it consumes is the core's sum, the
+// very additions of mlp_reduce_kernel / mlp_reduce4_kernel.  In the float4 core the owners of the block's columns fetch
+// their parameters and state ahead of the two folds, and thread 1023 takes the ticket between the barriers with the t
+// it read at kernel entry; the 4-byte core (one barrier, the fallback of an unaligned workspace) begins in its kernel
+// and loads behind its fold.
+template <int N>
+struct MlpTrainEpilogue {
+    const MlpTrainArgs &a;
+    MlpTrainStep *step;            // LDS; written by between() (N = 4) or by the kernel ahead of the core (N = 1)
+    unsigned t_read;               // N = 4, thread 1023: mlp_train_read_t at kernel entry
+    MlpTrainElems<N> el;           // (left as it is until fetch: only the owners' are ever read)
+    __device__ __forceinline__ MlpTrainEpilogue(const MlpTrainArgs &a, MlpTrainStep *step, unsigned t_read)
+        : a(a), step(step), t_read(t_read) {}
+    __device__ __forceinline__ void fetch(int i) { mlp_train_load<N>(a, i, el); }
+    __device__ __forceinline__ void between()
+    {
+        if (threadIdx.x == 1023) mlp_train_ticket(a, t_read, step);
+    }
+    __device__ __forceinline__ void finish(int i, const float *g)
+    {
+        if (N == 1) mlp_train_load<N>(a, i, el);
+        mlp_train_finish<N>(a, *step, i, g, el);
+    }
+};
+
+// mlp_reduce_kernel (mlp_reduce_core) with the update behind the sum of column i
 __global__ void __launch_bounds__(kMlpRedCols * kMlpRedSlices)
 mlp_reduce_update_kernel(const float *__restrict__ part, int nPart, int pitch, const float *__restrict__ loss, int B,
                          float *__restrict__ loss_sum, MlpTrainArgs a)
 {
-    __shared__ float red[kMlpRedSlices][kMlpRedCols];
-    __shared__ float lred[16];
     __shared__ MlpTrainStep step;
-    const int tid = threadIdx.x;
-    const int P = a.P;
-    if (tid == 0) mlp_train_begin(a, &step);
-    const int col = tid % kMlpRedCols, slice = tid / kMlpRedCols;
-    const int i = blockIdx.x * kMlpRedCols + col;
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    if (i < P) {
-        const float *src = part + i;
-        for (int r0 = slice; r0 < nPart; r0 += 16 * kMlpRedSlices) {
-            float v[16];
-#pragma unroll
-            for (int k = 0; k < 16; ++k) {
-                const int r = r0 + k * kMlpRedSlices;
-                v[k] = src[(size_t)(r < nPart ? r : r0) * pitch];
-            }
-#pragma unroll
-            for (int k = 0; k < 16; k += 4) {
-                a0 += (r0 + k * kMlpRedSlices < nPart) ? v[k] : 0.f;
-                a1 += (r0 + (k + 1) * kMlpRedSlices < nPart) ? v[k + 1] : 0.f;
-                a2 += (r0 + (k + 2) * kMlpRedSlices < nPart) ? v[k + 2] : 0.f;
-                a3 += (r0 + (k + 3) * kMlpRedSlices < nPart) ? v[k + 3] : 0.f;
-            }
-        }
-    }
-    red[slice][col] = (a0 + a1) + (a2 + a3);
-    __syncthreads();
-    if (slice == 0 && i < P) {
-        float t = 0.f;
-#pragma unroll
-        for (int k = 0; k < kMlpRedSlices; ++k) t += red[k][col];
-        mlp_train_update<1>(a, step, i, &t);
-    }
-    if (loss_sum && blockIdx.x == 0) {
-        float s = 0.f;
-        for (int b = tid; b < B; b += kMlpRedCols * kMlpRedSlices) s += loss[b];
-        s = block_sum(s, lred);
-        if (tid == 0) loss_sum[0] = s;
-    }
+    if (threadIdx.x == 0) mlp_train_begin(a, &step);
+    MlpTrainEpilogue<1> update(a, &step, 0);
+    mlp_reduce_core(part, nPart, a.P, pitch, update);
+    if (loss_sum && blockIdx.x == 0) mlp_reduce_loss_sum(loss, B, loss_sum);
 }
 
-// mlp_reduce4_kernel (same block, same two-level fold, same order) with the update behind the float4 at 4 * c4
+// mlp_reduce4_kernel (mlp_reduce4_core) with the update behind the float4 at 4 * c4
 template <int COLS4>
 __global__ void __launch_bounds__(1024)
 mlp_reduce_update4_kernel(const float *__restrict__ part, int nPart, int pitch, const float *__restrict__ loss, int B,
                           float *__restrict__ loss_sum, MlpTrainArgs a)
 {
-    constexpr int SL = 1024 / COLS4;
-    static_assert(SL % 16 == 0, "two-level fold: 16 groups of slices");
-    __shared__ float4 red[SL][COLS4];
-    __shared__ float4 red2[16][COLS4];
-    __shared__ float lred[16];
     __shared__ MlpTrainStep step;
-    const int tid = threadIdx.x;
     // the last thread (a wave with nothing to do behind the first barrier) reads t now and takes the ticket there
     unsigned t_read = 0;
-    if (tid == 1023) t_read = mlp_train_read_t(a);
-    const int col = tid % COLS4, slice = tid / COLS4;
-    const int c4 = blockIdx.x * COLS4 + col;
-    const int P4 = pitch >> 2;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (c4 < P4) {
-        const float4 *src = reinterpret_cast<const float4 *>(part) + c4;
-        for (int r0 = slice; r0 < nPart; r0 += 8 * SL) {
-            float4 v[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const int r = r0 + k * SL;
-                v[k] = src[(size_t)(r < nPart ? r : r0) * P4];
-            }
-#pragma unroll
-            for (int k = 0; k < 8; ++k)
-                if (r0 + k * SL < nPart) vadd(acc, v[k]);
-        }
-    }
-    // the owners of the block's columns fetch their parameters and state ahead of the two folds
-    const bool owner = tid < COLS4 && c4 < P4;
-    MlpTrainElems<4> el;
-    if (owner) mlp_train_load<4>(a, 4 * c4, el);
-    red[slice][col] = acc;
-    __syncthreads();
-    if (tid == 1023) mlp_train_ticket(a, t_read, &step);          // (published by the barrier below)
-    if (tid < 16 * COLS4) {
-        const int g = tid / COLS4;
-        float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int j = 0; j < SL / 16; ++j) vadd(t, red[g + 16 * j][col]);
-        red2[g][col] = t;
-    }
-    __syncthreads();
-    if (owner) {
-        float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int g = 0; g < 16; ++g) vadd(t, red2[g][col]);
-        const float g4[4] = {t.x, t.y, t.z, t.w};
-        mlp_train_finish<4>(a, step, 4 * c4, g4, el);
-    }
-    if (loss_sum && blockIdx.x == 0) {
-        float s = 0.f;
-        for (int b = tid; b < B; b += 1024) s += loss[b];
-        s = block_sum(s, lred);
-        if (tid == 0) loss_sum[0] = s;
-    }
+    if (threadIdx.x == 1023) t_read = mlp_train_read_t(a);
+    MlpTrainEpilogue<4> update(a, &step, t_read);
+    mlp_reduce4_core<COLS4>(part, nPart, pitch, update);
+    if (loss_sum && blockIdx.x == 0) mlp_reduce_loss_sum(loss, B, loss_sum);
 }
 
 // the update alone, on a flat gradient already summed: 256 threads x 4 parameters a block
@@ -312,7 +251,7 @@ mlp_apply_update_kernel(const float *__restrict__ grads, MlpTrainArgs a)
     const int i = 4 * (blockIdx.x * kMlpApplyThreads + threadIdx.x);
     if (i >= a.P) return;
     float g[4];
-    if (i + 3 < a.P && mlp_train_aligned16(grads + i)) {
+    if (i + 3 < a.P && mlp_aligned16(grads + i)) {
         const float4 v = *reinterpret_cast<const float4 *>(grads + i);
         g[0] = v.x; g[1] = v.y; g[2] = v.z; g[3] = v.w;
     } else {
@@ -367,17 +306,11 @@ inline MlpTrainArgs mlp_train_args(float *W1, float *b1, float *W2, float *b2, f
 inline int mlp_reduce_update_launch(void *workspace, int grid, const MlpTrainArgs &a, const float *loss, int B,
                                     float *loss_sum, hipStream_t s)
 {
-    const int P = a.P;
-    if ((reinterpret_cast<uintptr_t>(workspace) & 15) == 0) {
-        const int P4 = mlp_pitch(P) >> 2;
-        hipLaunchKernelGGL(mlp_reduce_update4_kernel<kMlpRedCols4>,
-                           dim3((unsigned)((P4 + kMlpRedCols4 - 1) / kMlpRedCols4)), dim3(1024), 0, s,
-                           (const float *)workspace, grid, mlp_pitch(P), loss, B, loss_sum, a);
-        return (int)hipGetLastError();
-    }
-    hipLaunchKernelGGL(mlp_reduce_update_kernel, dim3((unsigned)((P + kMlpRedCols - 1) / kMlpRedCols)),
-                       dim3(kMlpRedCols * kMlpRedSlices), 0, s, (const float *)workspace, grid, mlp_pitch(P), loss, B,
-                       loss_sum, a);
+    // (no flat output that must be a float4: the epilogue moves 16 bytes only where its own addresses allow it)
+    const bool vec4 = mlp_aligned16(workspace);
+    const auto kernel = vec4 ? mlp_reduce_update4_kernel<kMlpRedCols4> : mlp_reduce_update_kernel;
+    hipLaunchKernelGGL(kernel, mlp_reduce_blocks(a.P, vec4), dim3(kMlpRedThreads), 0, s, (const float *)workspace, grid,
+                       mlp_pitch(a.P), loss, B, loss_sum, a);
     return (int)hipGetLastError();
 }
 
@@ -406,41 +339,18 @@ int ltr_mlp_train_step_f32(int family, int code, int k, float sigma, const float
     if (mlp_step_bad_network(B, L, F, H1, H2)) return LTR_ERR_SHAPE;
     if (family == LTR_MLP_TRAIN_LAMBDARANK && !std::isfinite(sigma)) return LTR_ERR_SHAPE;
     if (w1_pitch < 1 || w1_pitch > F || mlp_train_bad_optim(*optim)) return LTR_ERR_SHAPE;
-    if (L > (mlp2_takes(F) ? kM2MaxLen : kMlpMaxLen)) return LTR_ERR_LIST_TOO_LONG;
+    if (L > mlp_step_max_len(F)) return LTR_ERR_LIST_TOO_LONG;
     if (B == 0) return LTR_OK;
     if (!X || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !rel || !n || !loss) return LTR_ERR_NULL;
     if ((!state && mlp_train_needs_state(*optim)) || (w1_pitch < F && !W1_rows)) return LTR_ERR_NULL;
-    const int P = mlp_param_count(F, H1, H2);
-    const bool tile = mlp_use_tile_layout(F, B, L);
-    const int grid = tile ? mlp2_grid(B) : mlp_grid(B);
-    if (!workspace || workspace_bytes < (size_t)grid * mlp_pitch(P) * sizeof(float)) return LTR_ERR_WORKSPACE;
-    const int slot = family == LTR_MLP_TRAIN_LAMBDARANK ? LTR_MLP_LAMBDARANK
-                     : code == LTR_LISTWISE_LISTNET ? LTR_MLP_LISTNET : LTR_MLP_LISTMLE;
-    if (family != LTR_MLP_TRAIN_PAIRWISE && !mlp_slot_fits(slot, L, F)) return LTR_ERR_CONFIG;
+    // the MFMA launch of the family's entry point: the same call description through the same launch path
+    const int slot = family == LTR_MLP_TRAIN_PAIRWISE ? code
+                     : family == LTR_MLP_TRAIN_LAMBDARANK ? LTR_MLP_LAMBDARANK : mlp_listwise_slot_of(code);
+    const MlpStepCall call{slot, sigma, k, tie, use_seed, seed, seed_dev, X, W1_rows ? W1_rows : W1, b1, W2, b2, W3, b3,
+                           rel, rel_dtype, n, grad_out, B, L, F, H1, H2, loss, scores_out, workspace, workspace_bytes};
     hipStream_t s = (hipStream_t)stream;
-    // the MFMA launch of the family's entry point, argument for argument
-    MlpParams p = mlp_step_params(X, W1_rows ? W1_rows : W1, b1, W2, b2, W3, b3, n, B, L, F, H1, H2);
-    p.rel = rel; p.rel_dtype = rel_dtype; p.grad_out = grad_out;
-    p.loss = loss; p.scores_out = scores_out; p.part = (float *)workspace;
-    int rc;
-    if (family == LTR_MLP_TRAIN_PAIRWISE) {
-        p.sigma = sigma;
-        rc = tile ? with_kind(code, [&](auto K) { return launch_mlp2_kind<K>(p, grid, s); })
-                  : with_kind(code, [&](auto K) { return launch_mlp_kind<K>(p, grid, s); });
-    } else if (family == LTR_MLP_TRAIN_LISTWISE) {
-        p.lw.k = k;
-        if (code == LTR_LISTWISE_LISTMLE) {
-            if (use_seed) { p.lw.use_seed = 1; p.lw.tie_seed = seed; p.lw.tie_seed_dev = seed_dev; }
-            else p.lw.tie = tie;
-        }
-        if (code == LTR_LISTWISE_LISTNET)
-            rc = tile ? launch_mlp2_kind<LTR_MLP_LISTNET>(p, grid, s) : launch_mlp_kind<LTR_MLP_LISTNET>(p, grid, s);
-        else
-            rc = tile ? launch_mlp2_kind<LTR_MLP_LISTMLE>(p, grid, s) : launch_mlp_kind<LTR_MLP_LISTMLE>(p, grid, s);
-    } else {
-        p.sigma = sigma; p.lw.k = k;
-        rc = tile ? launch_mlp2_kind<LTR_MLP_LAMBDARANK>(p, grid, s) : launch_mlp_kind<LTR_MLP_LAMBDARANK>(p, grid, s);
-    }
+    int grid;
+    const int rc = mlp_step_launch(call, grid, s);
     if (rc != 0) return rc;
     return mlp_reduce_update_launch(workspace, grid, mlp_train_args(W1, b1, W2, b2, W3, b3, w1_pitch, state, *optim,
                                                                     grads_out, F, H1, H2), loss, B, loss_sum, s);

@@ -1,6 +1,6 @@
 // ltr_scorer.inc -- the Linear(F, 1) candidate scorer on its own: scores = X.W + b and its weight
 // gradient, as two HBM-streaming kernels, on rows of f32 (include/ltr_hip.h) or of bf16 (include/ltr_linear_bf16.h).
-// Included by ltr_mlp.hip behind ltr_mlp.inc, whose reduction kernel adds the gradient's partial vectors.
+// Included by ltr_mlp.hip behind ltr_mlp_reduce.inc, whose reduction kernel adds the gradient's partial vectors.
 // One scores body and one gradient body; a FRONT (LinFrontF32<4>: rows of float4, LinFrontF32<1>: rows of float for
 // F % 4 != 0, LinFrontBf16: rows of eight bf16) supplies what depends on the element type, and the six entry points
 // at the end differ in their shape predicate and in the kernel they name.  The bf16 fused step is ltr_linear_bf16.inc.

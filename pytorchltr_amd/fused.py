@@ -1324,6 +1324,25 @@ def _mlp_listwise_plan(kind, B, L, F, H1, H2):
     return mlp_listwise_supported(kind, B, L, F, H1, H2)
 
 
+_NO_TIE = (None, 0, 0, None)
+
+
+def _mlp_family_call(kind, sigma, L, dev):
+    """What a fused step call takes from its resolved `kind`, once for `_mlp_step` and `MLPTrainer.step`:
+    ``(family, code, k, tie, entry, lead, empty_is_noop)`` -- the trainer's family and code, k clamped to the C int, the
+    four tie arguments (one seed draw per call, for ListMLE only), the family's own entry point, its leading arguments,
+    and whether that entry point launches nothing for an empty batch (so the caller zeroes the gradient)."""
+    if not isinstance(kind, _ListwiseKind):
+        return _C.MLP_TRAIN_PAIRWISE, kind, 0, _NO_TIE, "ltr_mlp_pairwise_f32", (kind, float(sigma)), False
+    if kind.loss == _C.LISTWISE_LAMBDARANK:
+        k = min(int(kind.k or 0), 0x7FFFFFFF)
+        return _C.MLP_TRAIN_LAMBDARANK, 0, k, _NO_TIE, "ltr_mlp_lambdarank_f32", (k, float(sigma)), True
+    from . import _ties
+    k = int(kind.k or 0)
+    tie = _ties.tie_args(_ties.draw_seed(L, dev) if kind.loss == _C.LISTWISE_LISTMLE else None)
+    return _C.MLP_TRAIN_LISTWISE, kind.loss, k, tie, "ltr_mlp_listwise_f32", (kind.loss, k), True
+
+
 def _mlp_step(xs, params, relevance, n, kind, sigma, grad_out, return_scores, return_loss_sum, out):
     """The step behind mlp_loss_step, mlp_lambdarank_step and the loss modules (`_MLPLossFunction`), on a resolved
     (kind, sigma): a pairwise kind, or a :class:`_ListwiseKind` of ListNet, ListMLE or LambdaRank."""
@@ -1351,36 +1370,17 @@ def _mlp_step(xs, params, relevance, n, kind, sigma, grad_out, return_scores, re
         lsum = (torch.empty if B > 0 else torch.zeros)(1, dtype=torch.float32, device=dev)
     scores = torch.zeros(B, L, dtype=torch.float32, device=dev) if return_scores else None
     go = None if grad_out is None else grad_out.reshape(B).float().contiguous()
+    family, _, _, tie, entry, lead, empty_is_noop = _mlp_family_call(kind, sigma, L, dev)
     with _C.device_ctx(X):
         st = _C.stream_of(X)
         ws = _mlp_workspace(dev, st, ws_bytes)
-        if listwise and kind.loss == _C.LISTWISE_LAMBDARANK:
-            if B == 0:
-                flat.zero_()                # (launches nothing for an empty batch, like the listwise entry point)
-            rc = lib.ltr_mlp_lambdarank_f32(
-                min(int(kind.k or 0), 0x7FFFFFFF), float(sigma), X.data_ptr(), *[t.data_ptr() for t in flat_params],
-                r.data_ptr(), _LABEL_CODE[r.dtype], nn.data_ptr(), None if go is None else go.data_ptr(),
-                B, L, F, H1, H2, lossv.data_ptr(), None if scores is None else scores.data_ptr(), flat.data_ptr(),
-                None if lsum is None else lsum.data_ptr(), ws.data_ptr(), ws_bytes, st)
-        elif listwise:
-            from . import _ties
-            if B == 0:
-                flat.zero_()                # (the listwise entry point launches nothing for an empty batch)
-            sd = _ties.draw_seed(L, dev) if kind.loss == _C.LISTWISE_LISTMLE else None
-            rc = lib.ltr_mlp_listwise_f32(
-                kind.loss, int(kind.k or 0), X.data_ptr(), *[t.data_ptr() for t in flat_params],
-                r.data_ptr(), _LABEL_CODE[r.dtype], nn.data_ptr(), *_ties.tie_args(sd),
-                None if go is None else go.data_ptr(), B, L, F, H1, H2, lossv.data_ptr(),
-                None if scores is None else scores.data_ptr(), flat.data_ptr(),
-                None if lsum is None else lsum.data_ptr(), ws.data_ptr(), ws_bytes, st)
-        else:
-            rc = lib.ltr_mlp_pairwise_f32(
-                kind, float(sigma), X.data_ptr(), flat_params[0].data_ptr(), flat_params[1].data_ptr(),
-                flat_params[2].data_ptr(), flat_params[3].data_ptr(), flat_params[4].data_ptr(),
-                flat_params[5].data_ptr(), r.data_ptr(), _LABEL_CODE[r.dtype], nn.data_ptr(),
-                None if go is None else go.data_ptr(), B, L, F, H1, H2, lossv.data_ptr(),
-                None if scores is None else scores.data_ptr(), flat.data_ptr(),
-                None if lsum is None else lsum.data_ptr(), ws.data_ptr(), ws_bytes, st)
+        if B == 0 and empty_is_noop:
+            flat.zero_()                    # (the listwise and LambdaRank entry points launch nothing for an empty batch)
+        rc = getattr(lib, entry)(
+            *lead, X.data_ptr(), *[t.data_ptr() for t in flat_params], r.data_ptr(), _LABEL_CODE[r.dtype],
+            nn.data_ptr(), *(tie if family == _C.MLP_TRAIN_LISTWISE else ()), None if go is None else go.data_ptr(),
+            B, L, F, H1, H2, lossv.data_ptr(), None if scores is None else scores.data_ptr(), flat.data_ptr(),
+            None if lsum is None else lsum.data_ptr(), ws.data_ptr(), ws_bytes, st)
         if rc != 0:
             _C.check(rc)
     res = (lossv, _split_grads(flat, F, H1, H2))
@@ -1933,14 +1933,7 @@ class MLPTrainer:
         else:
             r, nn = _labels_and_n(relevance, n, B, L, dev)
             lossv = buf["loss"]
-            if not listwise:
-                family, code, k, tie = _C.MLP_TRAIN_PAIRWISE, kind, 0, (None, 0, 0, None)
-            elif kind.loss == _C.LISTWISE_LAMBDARANK:
-                family, code, k, tie = _C.MLP_TRAIN_LAMBDARANK, 0, min(int(kind.k or 0), 0x7FFFFFFF), (None, 0, 0, None)
-            else:
-                from . import _ties
-                sd = _ties.draw_seed(L, dev) if kind.loss == _C.LISTWISE_LISTMLE else None
-                family, code, k, tie = _C.MLP_TRAIN_LISTWISE, kind.loss, int(kind.k or 0), _ties.tie_args(sd)
+            family, code, k, tie = _mlp_family_call(kind, sigma, L, dev)[:4]
             with _C.device_ctx(X):
                 rc = lib.ltr_mlp_train_step_f32(
                     family, code, k, float(sigma), X.data_ptr(), *[p.data_ptr() for p in params], F,

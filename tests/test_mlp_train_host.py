@@ -150,6 +150,53 @@ def test_train_step_shape_rules_are_the_entry_points(lib):
         assert pw == lib.ltr_mlp_train_step_f32(*[a[x] for x in _ARGS]) != 0, change
 
 
+# One bad argument through all four entry points of the fused step.  The expected codes are the answers of the build
+# before the four shared one launch path, as literals: (change, the pairwise entry point's code, the code of the listwise
+# and the LambdaRank entry points).  One bad argument at a time: where two are wrong the orders differ (the pairwise entry
+# point answers SHAPE and LIST_TOO_LONG ahead of KIND, the other three KIND first), which the tables above and those of
+# test_mlp_listwise_host.py and test_mlp_lambdarank_host.py pin.  No legal shape makes ltr_mlp_listwise_plan or ltr_mlp_lambdarank_plan
+# answer 0 at a list length ltr_mlp_max_list_len allows (every F <= 224 in steps of 4 was asked at L = 16, 64, 128, 129,
+# 200, 256), so LTR_ERR_CONFIG has no case here: no argument reaches it.
+SAME_BAD_ARGUMENT = [
+    (dict(F=6), SHAPE, SHAPE), (dict(F=228), SHAPE, SHAPE), (dict(H1=65), SHAPE, SHAPE), (dict(H2=17), SHAPE, SHAPE),
+    (dict(L=257), TOO_LONG, TOO_LONG), (dict(L=129, F=148), TOO_LONG, TOO_LONG),
+    (dict(rel_dtype=3), KIND, KIND),
+    (dict(workspace_bytes=16), WORKSPACE, WORKSPACE), (dict(workspace=None), WORKSPACE, WORKSPACE),
+]
+
+
+def _four_entry_points(lib, change):
+    """{name: code} of the change on ltr_mlp_pairwise_f32, ltr_mlp_listwise_f32 (ListNet, ListMLE), ltr_mlp_lambdarank_f32
+    and on ltr_mlp_train_step_f32 in each of the three families."""
+    a = dict(_VALID, **change)
+    a["w1_pitch"] = a["F"]
+    a["optim"] = ctypes.byref(_optim())
+    net = [a[x] for x in ("X", "W1", "b1", "W2", "b2", "W3", "b3")]
+    dims = [a[x] for x in ("B", "L", "F", "H1", "H2")]
+    tail = [a["loss"], None, P, None, a["workspace"], a["workspace_bytes"], None]      # loss, scores, grads, loss_sum, ...
+    got = {"pairwise": lib.ltr_mlp_pairwise_f32(0, 1.0, *net, a["rel"], a["rel_dtype"], a["n"], None, *dims, *tail),
+           "lambdarank": lib.ltr_mlp_lambdarank_f32(10, 1.0, *net, a["rel"], a["rel_dtype"], a["n"], None, *dims, *tail)}
+    for name, code in (("listnet", 0), ("listmle", 1)):
+        got[name] = lib.ltr_mlp_listwise_f32(code, 0, *net, a["rel"], a["rel_dtype"], a["n"], None, 0, 0, None, None,
+                                             *dims, *tail)
+    for name, family, code in (("train-pairwise", 0, 0), ("train-listnet", 1, 0), ("train-listmle", 1, 1),
+                               ("train-lambdarank", 2, 0)):
+        got[name] = lib.ltr_mlp_train_step_f32(*[dict(a, family=family, code=code, k=10)[x] for x in _ARGS])
+    return got
+
+
+@pytest.mark.parametrize("i", range(len(SAME_BAD_ARGUMENT)))
+def test_one_bad_argument_through_all_four_entry_points(lib, i):
+    change, pairwise, rows = SAME_BAD_ARGUMENT[i]
+    got = _four_entry_points(lib, change)
+    # the trainer's code for a family is that family's own entry point's
+    assert got["train-pairwise"] == got["pairwise"] == pairwise, (change, got)
+    assert got["train-listnet"] == got["listnet"] and got["train-listmle"] == got["listmle"], (change, got)
+    assert got["train-lambdarank"] == got["lambdarank"], (change, got)
+    # the three entry points that are not the pairwise one give one code
+    assert {got[name] for name in got if "pairwise" not in name} == {rows}, (change, got)
+
+
 _APPLY = ["grads", "W1", "b1", "W2", "b2", "W3", "b3", "w1_pitch", "state", "optim", "F", "H1", "H2", "stream"]
 _APPLY_VALID = dict(grads=P, W1=P, b1=P, W2=P, b2=P, W3=P, b3=P, w1_pitch=8, state=P, optim="adagrad", F=8, H1=5, H2=3,
                     stream=None)
