@@ -10,13 +10,15 @@ split of the same shape (136 features, ragged queries, 5 relevance grades that d
 features through a fixed random network), so the printed ndcg@10 must RISE from its untrained
 value.  Pass an SVMrank file pair to train on real data instead:
 
-    python examples/02_mlp_getting_started.py [--loss {hinge,listnet,listmle,lambdarank}] [--trainer] [train.txt test.txt]
+    python examples/02_mlp_getting_started.py [--loss {hinge,listnet,listmle,lambdarank}] [--trainer] [--bf16-step] [train.txt test.txt]
 
 --loss listnet / listmle trains the same network on a listwise loss (FusedMLPListwiseLoss: the same kernel with
 ListNet or ListMLE in its loss slot), --loss lambdarank on LambdaRank with the NDCG@10 swap weights
 (FusedMLPLambdaRankLoss, k = 10: the metric this script reports); the default is the guide's hinge loss.
 --trainer replaces the loop body -- loss, zero_grad, backward, torch.optim.Adagrad.step -- by MLPTrainer.step: the same
 Adagrad (lr 0.1) applied inside the step's reduction launch, two launches a step and no autograd.
+--bf16-step trains on the batches kept as torch.bfloat16 with the module's opt-in `fuse_bf16`: the step stays one launch
+(ltr_mlp_step_bf16, the first layer on the bf16 MFMA; W1 stays an fp32 master weight), with and without --trainer.
 """
 import argparse
 import os
@@ -45,7 +47,7 @@ def synthetic_split(queries, features, seed, device):
     return RaggedQueries(xs, ys, offsets, device=device)
 
 
-def run(train_path=None, test_path=None, epochs=5, device="cuda", log=print, loss="hinge", trainer=False):
+def run(train_path=None, test_path=None, epochs=5, device="cuda", log=print, loss="hinge", trainer=False, bf16_step=False):
     torch.manual_seed(42)
     if train_path:
         train = load_svmrank(train_path, normalize=True, filter_queries=True, device=device)
@@ -59,6 +61,7 @@ def run(train_path=None, test_path=None, epochs=5, device="cuda", log=print, los
         model = FusedMLPLambdaRankLoss(train.features.shape[1], k=10).to(device)
     else:
         model = FusedMLPListwiseLoss(train.features.shape[1], loss=loss).to(device)
+    model.fuse_bf16 = bool(bf16_step)       # opt-in: a bf16 batch takes the one-launch bf16 step, not the three pieces
     if trainer:
         trainer = MLPTrainer(model, optimizer="adagrad", lr=0.1)
     else:
@@ -80,10 +83,11 @@ def run(train_path=None, test_path=None, epochs=5, device="cuda", log=print, los
             train, batch_size=16, shuffle=True,
             collate_fn=train.collate_fn(UniformSampler(max_list_size=20)))
         for batch in loader:
+            xs = batch.features.bfloat16() if bf16_step else batch.features    # (a stored bf16 split needs no cast)
             if trainer:
-                trainer.step(batch.features, batch.relevance, batch.n)  # the four lines below as one call
+                trainer.step(xs, batch.relevance, batch.n)              # the four lines below as one call
                 continue
-            loss = model(batch.features, batch.relevance, batch.n)      # = loss_fn(model(xs), ys, n).mean()
+            loss = model(xs, batch.relevance, batch.n)                  # = loss_fn(model(xs), ys, n).mean()
             optimizer.zero_grad()
             loss.backward()
             optimizer.step()
@@ -96,6 +100,8 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--loss", choices=("hinge", "listnet", "listmle", "lambdarank"), default="hinge")
     ap.add_argument("--trainer", action="store_true", help="MLPTrainer.step in place of the autograd loop body")
+    ap.add_argument("--bf16-step", action="store_true", help="bf16 batches on the one-launch bf16 step (fuse_bf16)")
     ap.add_argument("files", nargs="*", help="train.txt test.txt (SVMrank); default: a synthetic split")
     args = ap.parse_args()
-    run(*(args.files[:2] if len(args.files) >= 2 else ()), loss=args.loss, trainer=args.trainer)
+    run(*(args.files[:2] if len(args.files) >= 2 else ()), loss=args.loss, trainer=args.trainer,
+        bf16_step=args.bf16_step)

@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI in ``include/ltr_hip.h``, ``include/ltr_eval.h``, ``include/ltr_listwise.h``,
-``include/ltr_lambdarank.h``, ``include/ltr_longpair.h``, ``include/ltr_lambdarank_long.h``, ``include/ltr_mlp_rows.h``, ``include/ltr_mlp_bf16.h``, ``include/ltr_mlp_wide.h``,
+``include/ltr_lambdarank.h``, ``include/ltr_longpair.h``, ``include/ltr_lambdarank_long.h``, ``include/ltr_mlp_rows.h``, ``include/ltr_mlp_bf16.h``, ``include/ltr_mlp_step_bf16.h``, ``include/ltr_mlp_wide.h``,
 ``include/ltr_linear_bf16.h``, ``include/ltr_mlp_train.h`` and ``include/ltr_sched.h`` (pytorchltr_amd/csrc/libltr_hip.so).
 
 PyTorch supplies device memory and the current HIP stream; every call here hands raw device
@@ -189,6 +189,18 @@ MLP_BF16_SIGNATURES = {
     "ltr_mlp_bf16_grad": (_i, [_vp] * 9 + [_i] * 5 + [_vp, _vp, _sz, _vp]),
 }
 
+# name -> (restype, argtypes); mirrors include/ltr_mlp_step_bf16.h (the fused MLP training step on a bf16 feature batch:
+# one bf16-MFMA launch plus the reduction, and the trainer's step with the update in the reduction)
+_STEP_BF16_HEAD = [_i, _i, _i, _f]                                                     # family, code, k, sigma
+_STEP_BF16_LOSS = [_vp, _i, _vp, _vp, _i, ctypes.c_uint64, _vp, _vp] + [_i] * 5         # rel .. grad_out, B L F H1 H2
+MLP_STEP_BF16_SIGNATURES = {
+    "ltr_mlp_step_bf16_plan": (_i, [_i] * 7),
+    "ltr_mlp_step_bf16_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "ltr_mlp_step_bf16": (_i, _STEP_BF16_HEAD + [_vp] * 7 + _STEP_BF16_LOSS + [_vp] * 5 + [_sz, _vp]),
+    "ltr_mlp_train_step_bf16": (_i, _STEP_BF16_HEAD + [_vp] * 7 + [_i, _vp] + _STEP_BF16_LOSS + [_vp] * 4
+                                + [_optp, _vp, _vp, _sz, _vp]),
+}
+
 # name -> (restype, argtypes); mirrors include/ltr_linear_bf16.h (the Linear(F, 1) scorer on a bf16 feature batch: the
 # streaming score / gradient kernels, the fused register-tile step and its plan, the bf16 collate)
 LINEAR_BF16_SIGNATURES = {
@@ -268,6 +280,7 @@ def lib():
                                           + list(MLP_LAMBDARANK_SIGNATURES.items()) + list(MLP_TRAIN_SIGNATURES.items())
                                           + list(MLP_ROWS_SIGNATURES.items()) + list(MLP_WIDE_SIGNATURES.items())
                                           + list(MLP_BF16_SIGNATURES.items()) + list(LINEAR_BF16_SIGNATURES.items())
+                                          + list(MLP_STEP_BF16_SIGNATURES.items())
                                           + list(SCHED_SIGNATURES.items())):
             if name.startswith("ltr_debug_") and not hasattr(handle, name):
                 continue                     # a production build (-DLTR_NO_DEBUG_HOOKS) leaves the test hooks out

@@ -23,5 +23,6 @@
 #include "ltr_mlp_stream.inc"     // the stand-alone MLP scorer's streaming core and host glue; needs MlpParams' helpers and mlp_reduce_launch
 #include "ltr_mlp_rows.inc"       // f32 rows of any length; needs the streaming core
 #include "ltr_mlp_bf16.inc"       // bf16 feature batches; needs the streaming core
-#include "ltr_mlp_wide.inc"       // wide rows (K-streamed); needs the streaming core's host glue and mlp_reduce_launch
+#include "ltr_mlp2_bf16.inc"      // the 4-wave tile kernel of the training step on a bf16 batch, mlp_tile_bf16_kernel; needs the tile kernel's geometry and the bf16 front
+#include "ltr_mlp_wide.inc"     // wide rows (K-streamed); needs the streaming core's host glue and mlp_reduce_launch
 #include "ltr_scorer.inc"         // the stand-alone Linear scorer on f32 and bf16 rows; needs mlp_reduce_kernel

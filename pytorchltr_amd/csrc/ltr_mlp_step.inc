@@ -4,7 +4,14 @@
 // ltr_mlp_train_step_f32, is in ltr_mlp_train.inc.  An entry point is its own guards in its documented order, the
 // launch path, and its reduction (mlp_reduce_launch, ltr_mlp_reduce.inc; the trainer: mlp_reduce_update_launch).
 // Needs the launchers of both kernels (ltr_mlp.inc, ltr_mlp2.inc).  No GPU code.  DESIGN.md 29.
+// A bf16 feature batch (MlpStepCall::x_bf16; include/ltr_mlp_step_bf16.h, DESIGN.md 30) goes down the same path to the
+// kernel of ltr_mlp2_bf16.inc, which stands behind this file: its launcher and its plan rule are declared here.
 #pragma once
+
+#include "ltr_mlp_step_bf16.h"
+
+inline bool mlp_step_bf16_fits(int kind, int L, int F);                             // ltr_mlp2_bf16.inc
+int launch_mlp2_bf16(int slot, const MlpParams &p, int grid, hipStream_t stream);   // ltr_mlp2_bf16.inc
 
 // ltr_debug_mlp_layout(1) keeps the training step on the 8-wave kernel of ltr_mlp.inc (A/B measurements,
 // tests of both kernels; the 4-wave tile kernel of ltr_mlp2.inc is the default where it applies)
@@ -33,6 +40,17 @@ inline bool mlp_step_bad_network(int B, int L, int F, int H1, int H2)
 {
     return B < 0 || L <= 0 || H1 <= 0 || H2 <= 0 || mlp_step_bad_width(F) || H1 > kMlpH1 || H2 > kMlpH2;
 }
+
+// the same for a bf16 batch: rows of whole 16-byte pieces (8 values), lists of at most four fills
+inline bool mlp_step_bf16_bad_network(int B, int L, int F, int H1, int H2)
+{
+    return B < 0 || L <= 0 || H1 <= 0 || H2 <= 0 || F <= 0 || (F & 7) || F > 16 * 14 || H1 > kMlpH1 || H2 > kMlpH2;
+}
+inline bool mlp_step_bad_shape(bool x_bf16, int B, int L, int F, int H1, int H2)
+{
+    return x_bf16 ? mlp_step_bf16_bad_network(B, L, F, H1, H2) : mlp_step_bad_network(B, L, F, H1, H2);
+}
+inline int mlp_step_max_len_of(bool x_bf16, int F) { return x_bf16 ? kM2ParkLen : mlp_step_max_len(F); }
 
 inline bool bad_mlp_listwise_loss(int loss) { return loss != LTR_LISTWISE_LISTNET && loss != LTR_LISTWISE_LISTMLE; }
 inline int mlp_listwise_slot_of(int loss) { return loss == LTR_LISTWISE_LISTNET ? LTR_MLP_LISTNET : LTR_MLP_LISTMLE; }
@@ -85,7 +103,8 @@ struct MlpStepCall {
     int use_seed;
     uint64_t seed;
     const int64_t *seed_dev;
-    const float *X, *W1, *b1, *W2, *b2, *W3, *b3;
+    const void *X;                 // float rows; x_bf16: bf16 rows
+    const float *W1, *b1, *W2, *b2, *W3, *b3;
     const void *rel;
     int rel_dtype;
     const int64_t *n;
@@ -94,6 +113,7 @@ struct MlpStepCall {
     float *loss, *scores_out;
     void *workspace;               // one partial vector per workgroup of the launch
     size_t workspace_bytes;
+    bool x_bf16 = false;           // the element type of X: the tile kernel of ltr_mlp2_bf16.inc takes the call
 };
 
 // From the validated arguments to the MFMA launch: the layout and its grid (returned in `grid` for the caller's
@@ -101,12 +121,14 @@ struct MlpStepCall {
 inline int mlp_step_launch(const MlpStepCall &c, int &grid, hipStream_t s)
 {
     const bool row_slot = c.slot > LTR_NDCG2;
-    const bool tile = mlp_use_tile_layout(c.F, c.B, c.L);
+    const bool tile = c.x_bf16 || mlp_use_tile_layout(c.F, c.B, c.L);
     grid = tile ? mlp2_grid(c.B) : mlp_grid(c.B);
     const int P = mlp_param_count(c.F, c.H1, c.H2);
     if (!c.workspace || c.workspace_bytes < (size_t)grid * mlp_pitch(P) * sizeof(float)) return LTR_ERR_WORKSPACE;
-    if (row_slot && !mlp_slot_fits(c.slot, c.L, c.F)) return LTR_ERR_CONFIG;
-    MlpParams p = mlp_step_params(c.X, c.W1, c.b1, c.W2, c.b2, c.W3, c.b3, c.n, c.B, c.L, c.F, c.H1, c.H2);
+    if (c.x_bf16 ? !mlp_step_bf16_fits(c.slot, c.L, c.F) : row_slot && !mlp_slot_fits(c.slot, c.L, c.F))
+        return LTR_ERR_CONFIG;
+    // (MlpParams::X of a bf16 batch: the pointer only, mlp_tile_bf16_kernel reads bf16 behind it)
+    MlpParams p = mlp_step_params(static_cast<const float *>(c.X), c.W1, c.b1, c.W2, c.b2, c.W3, c.b3, c.n, c.B, c.L, c.F, c.H1, c.H2);
     p.rel = c.rel; p.rel_dtype = c.rel_dtype; p.grad_out = c.grad_out;
     p.loss = c.loss; p.scores_out = c.scores_out; p.part = (float *)c.workspace;
     if (c.slot != LTR_MLP_LISTNET && c.slot != LTR_MLP_LISTMLE) p.sigma = c.sigma;
@@ -115,6 +137,7 @@ inline int mlp_step_launch(const MlpStepCall &c, int &grid, hipStream_t s)
         if (c.use_seed) { p.lw.use_seed = 1; p.lw.tie_seed = c.seed; p.lw.tie_seed_dev = c.seed_dev; }
         else p.lw.tie = c.tie;
     }
+    if (c.x_bf16) return launch_mlp2_bf16(c.slot, p, grid, s);
     return with_mlp_slot(c.slot, [&](auto K) {
         return tile ? launch_mlp2_kind<K>(p, grid, s) : launch_mlp_kind<K>(p, grid, s);
     });
@@ -224,6 +247,55 @@ int ltr_mlp_lambdarank_f32(int k, float sigma, const float *X, const float *W1, 
     const int rc = mlp_step_launch(call, grid, s);
     if (rc != 0) return rc;
     return mlp_reduce_launch(workspace, grid, mlp_param_count(F, H1, H2), grads, loss_out, B, loss_sum, s);
+}
+
+// ---- the step on a bf16 feature batch (include/ltr_mlp_step_bf16.h; DESIGN.md 30) ----
+// family / code -> the kernels' slot, or -1 (the check of ltr_mlp_train_step_f32)
+inline int mlp_step_slot_of(int family, int code)
+{
+    if (family == LTR_MLP_TRAIN_PAIRWISE) return code < LTR_HINGE || code > LTR_NDCG2 ? -1 : code;
+    if (family == LTR_MLP_TRAIN_LISTWISE) return bad_mlp_listwise_loss(code) ? -1 : mlp_listwise_slot_of(code);
+    return family == LTR_MLP_TRAIN_LAMBDARANK ? LTR_MLP_LAMBDARANK : -1;
+}
+
+int ltr_mlp_step_bf16_plan(int family, int code, int B, int L, int F, int H1, int H2)
+{
+    const int slot = mlp_step_slot_of(family, code);
+    if (slot < 0 || B == 0 || mlp_step_bf16_bad_network(B, L, F, H1, H2)) return 0;
+    return mlp_step_bf16_fits(slot, L, F) ? 1 : 0;
+}
+
+size_t ltr_mlp_step_bf16_workspace_bytes(int B, int F, int H1, int H2)
+{
+    if (B <= 0 || mlp_step_bf16_bad_network(B, 1, F, H1, H2)) return 0;
+    return (size_t)mlp2_grid(B) * (size_t)mlp_pitch(mlp_param_count(F, H1, H2)) * sizeof(float);
+}
+
+// (KIND ahead of SHAPE and LIST_TOO_LONG, as the listwise and LambdaRank entry points and the trainer decide; the
+// parameter pointers even at B == 0, where the reduction still runs, as in ltr_mlp_pairwise_f32)
+int ltr_mlp_step_bf16(int family, int code, int k, float sigma, const uint16_t *X, const float *W1, const float *b1,
+                      const float *W2, const float *b2, const float *W3, const float *b3, const void *rel, int rel_dtype,
+                      const int64_t *n, const int32_t *tie, int use_seed, uint64_t seed, const int64_t *seed_dev,
+                      const float *grad_out, int B, int L, int F, int H1, int H2, float *loss, float *scores_out,
+                      float *grads, float *loss_sum, void *workspace, size_t workspace_bytes, void *stream)
+{
+    LTR_CLEAR_STALE_ERROR();
+    const int slot = mlp_step_slot_of(family, code);
+    if (slot < 0 || bad_label_dtype(rel_dtype)) return LTR_ERR_KIND;
+    if (mlp_step_bf16_bad_network(B, L, F, H1, H2)) return LTR_ERR_SHAPE;
+    if (family == LTR_MLP_TRAIN_LAMBDARANK && !std::isfinite(sigma)) return LTR_ERR_SHAPE;
+    if (L > kM2ParkLen) return LTR_ERR_LIST_TOO_LONG;
+    if (!W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !grads) return LTR_ERR_NULL;
+    if (B > 0 && (!X || !rel || !n || !loss)) return LTR_ERR_NULL;
+    hipStream_t s = (hipStream_t)stream;
+    int grid = 0;
+    if (B > 0) {
+        const MlpStepCall call{slot, sigma, k, tie, use_seed, seed, seed_dev, X, W1, b1, W2, b2, W3, b3, rel, rel_dtype,
+                               n, grad_out, B, L, F, H1, H2, loss, scores_out, workspace, workspace_bytes, true};
+        const int rc = mlp_step_launch(call, grid, s);
+        if (rc != 0) return rc;
+    }
+    return mlp_reduce_launch(workspace, grid, mlp_param_count(F, H1, H2), grads, loss, B, loss_sum, s);
 }
 
 // bench.py `extra.mlp_scorer_fused.launch_ceiling` (include/ltr_hip.h): the launch geometry of the fused MLP training

@@ -314,6 +314,42 @@ inline int mlp_reduce_update_launch(void *workspace, int grid, const MlpTrainArg
     return (int)hipGetLastError();
 }
 
+// the step of both element types of X: the guards of include/ltr_mlp_train.h in their order, the MFMA launch of the
+// family through mlp_step_launch, the reduce-and-update launch
+inline int mlp_train_step(bool x_bf16, int family, int code, int k, float sigma, const void *X, float *W1, float *b1, float *W2,
+                           float *b2, float *W3, float *b3, int w1_pitch, const float *W1_rows, const void *rel,
+                           int rel_dtype, const int64_t *n, const int32_t *tie, int use_seed, uint64_t seed,
+                           const int64_t *seed_dev, const float *grad_out, int B, int L, int F, int H1, int H2,
+                           float *loss, float *scores_out, float *loss_sum, float *state,
+                           const struct ltr_mlp_optim *optim, float *grads_out, void *workspace,
+                           size_t workspace_bytes, void *stream)
+{
+    LTR_CLEAR_STALE_ERROR();
+    if (!optim) return LTR_ERR_NULL;
+    if (family < LTR_MLP_TRAIN_PAIRWISE || family > LTR_MLP_TRAIN_LAMBDARANK || bad_label_dtype(rel_dtype)) return LTR_ERR_KIND;
+    if (family == LTR_MLP_TRAIN_PAIRWISE && (code < LTR_HINGE || code > LTR_NDCG2)) return LTR_ERR_KIND;
+    if (family == LTR_MLP_TRAIN_LISTWISE && bad_mlp_listwise_loss(code)) return LTR_ERR_KIND;
+    if (optim->algo < LTR_OPT_SGD || optim->algo > LTR_OPT_ADAM) return LTR_ERR_KIND;
+    if (mlp_step_bad_shape(x_bf16, B, L, F, H1, H2)) return LTR_ERR_SHAPE;
+    if (family == LTR_MLP_TRAIN_LAMBDARANK && !std::isfinite(sigma)) return LTR_ERR_SHAPE;
+    if (w1_pitch < 1 || w1_pitch > F || mlp_train_bad_optim(*optim)) return LTR_ERR_SHAPE;
+    if (L > mlp_step_max_len_of(x_bf16, F)) return LTR_ERR_LIST_TOO_LONG;
+    if (B == 0) return LTR_OK;
+    if (!X || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !rel || !n || !loss) return LTR_ERR_NULL;
+    if ((!state && mlp_train_needs_state(*optim)) || (w1_pitch < F && !W1_rows)) return LTR_ERR_NULL;
+    // the MFMA launch of the family's entry point: the same call description through the same launch path
+    const int slot = family == LTR_MLP_TRAIN_PAIRWISE ? code
+                     : family == LTR_MLP_TRAIN_LAMBDARANK ? LTR_MLP_LAMBDARANK : mlp_listwise_slot_of(code);
+    const MlpStepCall call{slot, sigma, k, tie, use_seed, seed, seed_dev, X, W1_rows ? W1_rows : W1, b1, W2, b2, W3, b3,
+                           rel, rel_dtype, n, grad_out, B, L, F, H1, H2, loss, scores_out, workspace, workspace_bytes, x_bf16};
+    hipStream_t s = (hipStream_t)stream;
+    int grid;
+    const int rc = mlp_step_launch(call, grid, s);
+    if (rc != 0) return rc;
+    return mlp_reduce_update_launch(workspace, grid, mlp_train_args(W1, b1, W2, b2, W3, b3, w1_pitch, state, *optim,
+                                                                    grads_out, F, H1, H2), loss, B, loss_sum, s);
+}
+
 extern "C" {
 
 size_t ltr_mlp_train_state_floats(int algo, int F, int H1, int H2)
@@ -330,30 +366,24 @@ int ltr_mlp_train_step_f32(int family, int code, int k, float sigma, const float
                            const struct ltr_mlp_optim *optim, float *grads_out, void *workspace,
                            size_t workspace_bytes, void *stream)
 {
-    LTR_CLEAR_STALE_ERROR();
-    if (!optim) return LTR_ERR_NULL;
-    if (family < LTR_MLP_TRAIN_PAIRWISE || family > LTR_MLP_TRAIN_LAMBDARANK || bad_label_dtype(rel_dtype)) return LTR_ERR_KIND;
-    if (family == LTR_MLP_TRAIN_PAIRWISE && (code < LTR_HINGE || code > LTR_NDCG2)) return LTR_ERR_KIND;
-    if (family == LTR_MLP_TRAIN_LISTWISE && bad_mlp_listwise_loss(code)) return LTR_ERR_KIND;
-    if (optim->algo < LTR_OPT_SGD || optim->algo > LTR_OPT_ADAM) return LTR_ERR_KIND;
-    if (mlp_step_bad_network(B, L, F, H1, H2)) return LTR_ERR_SHAPE;
-    if (family == LTR_MLP_TRAIN_LAMBDARANK && !std::isfinite(sigma)) return LTR_ERR_SHAPE;
-    if (w1_pitch < 1 || w1_pitch > F || mlp_train_bad_optim(*optim)) return LTR_ERR_SHAPE;
-    if (L > mlp_step_max_len(F)) return LTR_ERR_LIST_TOO_LONG;
-    if (B == 0) return LTR_OK;
-    if (!X || !W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !rel || !n || !loss) return LTR_ERR_NULL;
-    if ((!state && mlp_train_needs_state(*optim)) || (w1_pitch < F && !W1_rows)) return LTR_ERR_NULL;
-    // the MFMA launch of the family's entry point: the same call description through the same launch path
-    const int slot = family == LTR_MLP_TRAIN_PAIRWISE ? code
-                     : family == LTR_MLP_TRAIN_LAMBDARANK ? LTR_MLP_LAMBDARANK : mlp_listwise_slot_of(code);
-    const MlpStepCall call{slot, sigma, k, tie, use_seed, seed, seed_dev, X, W1_rows ? W1_rows : W1, b1, W2, b2, W3, b3,
-                           rel, rel_dtype, n, grad_out, B, L, F, H1, H2, loss, scores_out, workspace, workspace_bytes};
-    hipStream_t s = (hipStream_t)stream;
-    int grid;
-    const int rc = mlp_step_launch(call, grid, s);
-    if (rc != 0) return rc;
-    return mlp_reduce_update_launch(workspace, grid, mlp_train_args(W1, b1, W2, b2, W3, b3, w1_pitch, state, *optim,
-                                                                    grads_out, F, H1, H2), loss, B, loss_sum, s);
+    return mlp_train_step(false, family, code, k, sigma, X, W1, b1, W2, b2, W3, b3, w1_pitch, W1_rows, rel, rel_dtype, n,
+                          tie, use_seed, seed, seed_dev, grad_out, B, L, F, H1, H2, loss, scores_out, loss_sum, state,
+                          optim, grads_out, workspace, workspace_bytes, stream);
+}
+
+// the same step on a bf16 feature batch (include/ltr_mlp_step_bf16.h): the launch of ltr_mlp_step_bf16 in front of
+// the reduce-and-update launch
+int ltr_mlp_train_step_bf16(int family, int code, int k, float sigma, const uint16_t *X, float *W1, float *b1, float *W2,
+                            float *b2, float *W3, float *b3, int w1_pitch, const float *W1_rows, const void *rel,
+                            int rel_dtype, const int64_t *n, const int32_t *tie, int use_seed, uint64_t seed,
+                            const int64_t *seed_dev, const float *grad_out, int B, int L, int F, int H1, int H2,
+                            float *loss, float *scores_out, float *loss_sum, float *state,
+                            const struct ltr_mlp_optim *optim, float *grads_out, void *workspace,
+                            size_t workspace_bytes, void *stream)
+{
+    return mlp_train_step(true, family, code, k, sigma, X, W1, b1, W2, b2, W3, b3, w1_pitch, W1_rows, rel, rel_dtype, n,
+                          tie, use_seed, seed, seed_dev, grad_out, B, L, F, H1, H2, loss, scores_out, loss_sum, state,
+                          optim, grads_out, workspace, workspace_bytes, stream);
 }
 
 int ltr_mlp_apply_update_f32(const float *grads, float *W1, float *b1, float *W2, float *b2, float *W3, float *b3,

@@ -1196,7 +1196,18 @@ class _MLPScoreFunction(torch.autograd.Function):
 
 # ---- the route table: which kernels a batch reaches from each caller ----
 _FUSED, _PER_QUERY, _ROWS, _WIDE, _BF16, _TORCH = "fused step", "per-query scores", "rows", "wide", "bf16", "torch layers"
-_ROUTE_FAMILY = {_FUSED: _MLP_ROWS, _PER_QUERY: _MLP_ROWS, _ROWS: _MLP_ROWS, _WIDE: _MLP_WIDE, _BF16: _MLP_BF16}
+_FUSED_BF16 = "fused bf16 step"
+_ROUTE_FAMILY = {_FUSED: _MLP_ROWS, _PER_QUERY: _MLP_ROWS, _ROWS: _MLP_ROWS, _WIDE: _MLP_WIDE, _BF16: _MLP_BF16,
+                 _FUSED_BF16: _MLP_BF16}
+MLP_STEP_BF16_MAX_LIST_LEN = 128
+MLP_STEP_BF16_MAX_FEATURES = 160
+
+
+def mlp_step_bf16_supported(L, F, H1, H2):
+    """Shapes the one-launch step on a ``torch.bfloat16`` batch takes (include/ltr_mlp_step_bf16.h; the answer of
+    ltr_mlp_step_bf16_plan for every loss): the networks of the bf16 kernels up to 160 features, lists of at most 128
+    documents."""
+    return 0 < L <= MLP_STEP_BF16_MAX_LIST_LEN and F <= MLP_STEP_BF16_MAX_FEATURES and _MLP_BF16.takes(F, H1, H2)
 
 
 def _f4(F):
@@ -1204,7 +1215,8 @@ def _f4(F):
     return (F + 3) & ~3
 
 
-def _mlp_route(caller, dtype, dim, is_cuda, requires_grad, grad_enabled, autocast, L, F, H1, H2, kind=None, plan=True):
+def _mlp_route(caller, dtype, dim, is_cuda, requires_grad, grad_enabled, autocast, L, F, H1, H2, kind=None, plan=True,
+               fuse_bf16=False):
     """Which kernels compute ``mlp(xs)`` (and, for a caller with a loss `kind`, the step): plain values in, one of
     _FUSED (the one-launch step, ltr_mlp_pairwise_f32 / ltr_mlp_listwise_f32 / ltr_mlp_lambdarank_f32), _PER_QUERY (ltr_mlp_scores_f32), _ROWS,
     _WIDE, _BF16 (the three families) or _TORCH out -- the three ``nn.Linear`` layers in a module, ValueError in a
@@ -1214,13 +1226,18 @@ def _mlp_route(caller, dtype, dim, is_cuda, requires_grad, grad_enabled, autocas
     (mlp_loss_step), "scores" (mlp_scores).  `plan`: False where a listwise `kind` is off the plan of the fused
     step (:func:`mlp_listwise_supported`, asked by the caller: this function calls nothing).
     The modules zero-pad the feature count to a multiple of 4 (bf16: 8), the functions take it as it is.
+    `fuse_bf16`: the caller's opt-in to _FUSED_BF16 (ltr_mlp_step_bf16, the one-launch step on the bf16 batch), returned
+    only where the answer is otherwise _BF16, the caller has a loss and :func:`mlp_step_bf16_supported` accepts.
     """
     if dim != 3 or not is_cuda or L <= 0:
         return _TORCH
     module = caller in ("scorer", "score", "loss")
     data = not requires_grad and not autocast           # a batch that needs no gradient itself, outside autocast
     if dtype is torch.bfloat16 and data and (module or (caller == "step" and F % 8 == 0)):
-        return _BF16                                     # at every list length: the fused kernels are fp32-only
+        if (fuse_bf16 and kind is not None and caller in ("loss", "step")
+                and mlp_step_bf16_supported(L, (F + 7) & ~7, H1, H2)):
+            return _FUSED_BF16                           # opt-in: one bf16-MFMA launch, lists up to 128 documents
+        return _BF16                                     # at every list length: the default fused kernels are fp32-only
     if module:
         F = _f4(F)                                       # (everything below computes in fp32)
     if kind is not None and plan and mlp_supported(L, F, H1, H2):
@@ -1238,13 +1255,13 @@ def _mlp_route(caller, dtype, dim, is_cuda, requires_grad, grad_enabled, autocas
     return _ROWS if rows and f32_data else _WIDE if wide and f32_data else _TORCH
 
 
-def _mlp_route_of(caller, xs, F, H1, H2, kind=None, plan=True):
+def _mlp_route_of(caller, xs, F, H1, H2, kind=None, plan=True, fuse_bf16=False):
     """`_mlp_route` on a batch: its dtype, shape and flags, the grad mode and the autocast state (F None: the batch's)."""
     if not torch.is_tensor(xs) or xs.dim() != 3:
         return _TORCH
     _, L, Fx = xs.shape
     return _mlp_route(caller, xs.dtype, 3, xs.is_cuda, xs.requires_grad, torch.is_grad_enabled(),
-                      torch.is_autocast_enabled(), L, Fx if F is None else F, H1, H2, kind, plan)
+                      torch.is_autocast_enabled(), L, Fx if F is None else F, H1, H2, kind, plan, fuse_bf16)
 
 
 def _mlp_step_pieces(X, flat_params, H1, H2, relevance, n, kind, sigma, grad_out, return_scores, return_loss_sum, out):
@@ -1271,12 +1288,15 @@ def _mlp_step_pieces(X, flat_params, H1, H2, relevance, n, kind, sigma, grad_out
 
 
 def mlp_loss_step(xs, params, relevance, n, loss="hinge", grad_out=None, return_scores=False,
-                  return_loss_sum=False, out=None):
+                  return_loss_sum=False, out=None, fuse_bf16=False):
     """One fused forward+backward step of ``loss_fn(mlp(xs), relevance, n)`` without autograd.
 
     Args:
         xs: (B, L, F) float32 features on the device; a ``torch.bfloat16`` batch with F % 8 == 0 runs, at every list
             length, as the three pieces below on the bf16 kernels (:func:`mlp_scores_bf16`, :func:`mlp_grad_bf16`).
+        fuse_bf16: True: a bf16 batch of lists up to 128 documents (:func:`mlp_step_bf16_supported`) runs as ONE
+            bf16-MFMA launch plus the reduction (ltr_mlp_step_bf16; F <= 160) instead of those pieces -- the same function (W1
+            rounded to bf16 for the first layer), the same returned tuple.  Nothing else changes.
         loss: a pairwise kind name or module, or a listwise loss -- ``"listnet"`` / ``"softmax"``, ``"listmle"``,
             ``ListwiseSoftmaxLoss()``, ``ListMLELoss(k)`` (ltr_mlp_listwise_f32; ListMLE draws one tie seed per call,
             as ``ListMLELoss`` does, and ``utils.tie_breaking("index")`` turns it off).
@@ -1299,22 +1319,23 @@ def mlp_loss_step(xs, params, relevance, n, loss="hinge", grad_out=None, return_
     if isinstance(kind, _ListwiseKind) and kind.loss == _C.LISTWISE_LAMBDARANK:
         raise TypeError("mlp_loss_step has no LambdaRank slot: take mlp_lambdarank_step (the module: "
                         "FusedMLPLambdaRankLoss), or the Linear scorer: FusedLinearLoss, linear_loss_step, LinearScorer")
-    return _mlp_step(xs, params, relevance, n, kind, sigma, grad_out, return_scores, return_loss_sum, out)
+    return _mlp_step(xs, params, relevance, n, kind, sigma, grad_out, return_scores, return_loss_sum, out, fuse_bf16)
 
 
 def mlp_lambdarank_step(xs, params, relevance, n, sigma=1.0, k=None, grad_out=None, return_scores=False,
-                        return_loss_sum=False, out=None):
+                        return_loss_sum=False, out=None, fuse_bf16=False):
     """:func:`mlp_loss_step` for LambdaRank (:class:`pytorchltr_amd.loss.LambdaRankLoss` ``(sigma, k)``): one fused
     forward+backward step of ``LambdaRankLoss(sigma, k)(mlp(xs), relevance, n)`` without autograd, by
     ``ltr_mlp_lambdarank_f32`` (include/ltr_mlp_lambdarank.h) -- the NDCG@k swap weights and the top-k pair pass in the
     loss slot of the two fused MLP kernels.  ``k=None``: no cutoff.  The other arguments, the returned tuple and the
     shapes are those of :func:`mlp_loss_step`; off the plan (:func:`mlp_lambdarank_supported`: longer lists, a
     ``torch.bfloat16`` batch) the step runs as the three pieces -- the row score kernel, the stand-alone LambdaRank
-    kernel (past ``max_list_len()`` documents its long path), the row gradient kernel."""
+    kernel (past ``max_list_len()`` documents its long path), the row gradient kernel.  ``fuse_bf16=True``: a bf16
+    batch on :func:`mlp_step_bf16_supported` runs as one launch (ltr_mlp_step_bf16), as in :func:`mlp_loss_step`."""
     from .loss import pairwise_lambda as _pl
     k = _pl.LambdaRankLoss(sigma, k).k                      # (its check of k)
     return _mlp_step(xs, params, relevance, n, _ListwiseKind(_C.LISTWISE_LAMBDARANK, k), float(sigma), grad_out,
-                     return_scores, return_loss_sum, out)
+                     return_scores, return_loss_sum, out, fuse_bf16)
 
 
 def _mlp_listwise_plan(kind, B, L, F, H1, H2):
@@ -1343,17 +1364,17 @@ def _mlp_family_call(kind, sigma, L, dev):
     return _C.MLP_TRAIN_LISTWISE, kind.loss, k, tie, "ltr_mlp_listwise_f32", (kind.loss, k), True
 
 
-def _mlp_step(xs, params, relevance, n, kind, sigma, grad_out, return_scores, return_loss_sum, out):
+def _mlp_step(xs, params, relevance, n, kind, sigma, grad_out, return_scores, return_loss_sum, out, fuse_bf16=False):
     """The step behind mlp_loss_step, mlp_lambdarank_step and the loss modules (`_MLPLossFunction`), on a resolved
     (kind, sigma): a pairwise kind, or a :class:`_ListwiseKind` of ListNet, ListMLE or LambdaRank."""
     listwise = isinstance(kind, _ListwiseKind)
     F, H1, H2 = params[0].shape[-1], params[0].shape[0], params[2].shape[0]    # (the network's: W1 is (H1, F))
     plan = not listwise or (xs.dim() == 3 and _mlp_listwise_plan(kind, xs.shape[0], xs.shape[1], F, H1, H2))
-    route = _mlp_route_of("step", xs, F, H1, H2, kind, plan)
+    route = _mlp_route_of("step", xs, F, H1, H2, kind, plan, fuse_bf16)
     if route is _TORCH:
         _mlp_not_taken(xs, params, True)
     X, flat_params, H1, H2, _, _ = _mlp_prepare(xs, params, _ROUTE_FAMILY[route], pad=False)
-    if route is not _FUSED:
+    if route is not _FUSED and route is not _FUSED_BF16:
         # past the fused kernels' list lengths or listwise plan, or a bf16 batch (they are fp32-only): three pieces
         return _mlp_step_pieces(X, flat_params, H1, H2, relevance, n, kind, sigma, grad_out, return_scores,
                                 return_loss_sum, out)
@@ -1370,7 +1391,12 @@ def _mlp_step(xs, params, relevance, n, kind, sigma, grad_out, return_scores, re
         lsum = (torch.empty if B > 0 else torch.zeros)(1, dtype=torch.float32, device=dev)
     scores = torch.zeros(B, L, dtype=torch.float32, device=dev) if return_scores else None
     go = None if grad_out is None else grad_out.reshape(B).float().contiguous()
-    family, _, _, tie, entry, lead, empty_is_noop = _mlp_family_call(kind, sigma, L, dev)
+    family, code, k, tie, entry, lead, empty_is_noop = _mlp_family_call(kind, sigma, L, dev)
+    takes_tie = family == _C.MLP_TRAIN_LISTWISE
+    if route is _FUSED_BF16:
+        # one entry point for the three families (include/ltr_mlp_step_bf16.h): it always takes the tie arguments, and
+        # an empty batch still runs its reduction
+        entry, lead, takes_tie, empty_is_noop = "ltr_mlp_step_bf16", (family, code, k, float(sigma)), True, False
     with _C.device_ctx(X):
         st = _C.stream_of(X)
         ws = _mlp_workspace(dev, st, ws_bytes)
@@ -1378,7 +1404,7 @@ def _mlp_step(xs, params, relevance, n, kind, sigma, grad_out, return_scores, re
             flat.zero_()                    # (the listwise and LambdaRank entry points launch nothing for an empty batch)
         rc = getattr(lib, entry)(
             *lead, X.data_ptr(), *[t.data_ptr() for t in flat_params], r.data_ptr(), _LABEL_CODE[r.dtype],
-            nn.data_ptr(), *(tie if family == _C.MLP_TRAIN_LISTWISE else ()), None if go is None else go.data_ptr(),
+            nn.data_ptr(), *(tie if takes_tie else ()), None if go is None else go.data_ptr(),
             B, L, F, H1, H2, lossv.data_ptr(), None if scores is None else scores.data_ptr(), flat.data_ptr(),
             None if lsum is None else lsum.data_ptr(), ws.data_ptr(), ws_bytes, st)
         if rc != 0:
@@ -1436,9 +1462,10 @@ class _MLPLossFunction(torch.autograd.Function):
     def forward(ctx, xs, relevance, n, kind_sigma, mean, *params):
         B = xs.shape[0]
         go = None if mean else torch.ones(B, dtype=torch.float32, device=xs.device)
-        kind, sigma = kind_sigma
-        xs, w1, extra = _zero_pad(xs, params[0], 4)
-        lossv, grads, lsum = _mlp_step(xs, (w1,) + tuple(params[1:]), relevance, n, kind, sigma, go, False, True, None)
+        kind, sigma, *fuse_bf16 = kind_sigma              # (a third entry: the module's opt-in on its bf16 batch, kept as bf16)
+        xs, w1, extra = _zero_pad(xs, params[0], 8 if fuse_bf16 else 4)
+        lossv, grads, lsum = _mlp_step(xs, (w1,) + tuple(params[1:]), relevance, n, kind, sigma, go, False, True, None,
+                                       bool(fuse_bf16))
         ctx.save_for_backward(grads[0]._base)       # the flat buffer: one scale in backward
         ctx.dims = (xs.shape[2], params[0].shape[0], params[2].shape[0])
         ctx.extra = extra
@@ -1498,11 +1525,15 @@ class _FusedMLPBase(_MLPLayers):
     """What FusedMLPLoss and FusedMLPListwiseLoss share: ``score()``, the fused step where the route is `_FUSED` and the
     unfused composition (``_pieces``) where it is not."""
 
-    def __init__(self, in_features, loss, hidden, reduction):
+    fuse_bf16 = False        # plain attribute, the opt-in: a bf16 batch on mlp_step_bf16_supported takes ltr_mlp_step_bf16
+
+    def __init__(self, in_features, loss, hidden, reduction, fuse_bf16=False):
         if reduction not in ("mean", "sum"):
             raise ValueError("reduction must be 'mean' or 'sum'")
         super().__init__(in_features, hidden)
         self.reduction = reduction
+        if fuse_bf16:
+            self.fuse_bf16 = True
         self.kind, self.sigma = self._resolve(loss)
         self.last_losses = None
 
@@ -1530,10 +1561,12 @@ class _FusedMLPBase(_MLPLayers):
         _C.require_device(xs, "xs")
         B, L, F = xs.shape
         H1, H2 = self._hidden()
-        route = _mlp_route_of("loss", xs, F, H1, H2, self.kind, self._plan(B, L, _f4(F), H1, H2))
-        if route is _FUSED:
+        route = _mlp_route_of("loss", xs, F, H1, H2, self.kind, self._plan(B, L, _f4(F), H1, H2),
+                              self.fuse_bf16)
+        if route is _FUSED or route is _FUSED_BF16:
             total, per_query = _MLPLossFunction.apply(
-                xs, relevance, n, (self.kind, self.sigma), self.reduction == "mean", *self._params())
+                xs, relevance, n, (self.kind, self.sigma) + ((True,) if route is _FUSED_BF16 else ()),
+                self.reduction == "mean", *self._params())
             self.last_losses = per_query
             return total
         per_query = self._pieces(self._score(xs, n, route), relevance, n)
@@ -1554,12 +1587,16 @@ class FusedMLPLoss(_FusedMLPBase):
     a loss module built with ``long_lists=True`` takes them past ``max_list_len()`` documents.  More than 224
     features, up to 704 (Yahoo: 699), at every list length: the same three pieces on the wide-row kernels
     (ltr_mlp_wide_*_f32).  A ``torch.bfloat16`` batch (up to 224 features): the same three pieces on the bf16 kernels
-    (ltr_mlp_bf16_*, :func:`mlp_scores_bf16`) at every list length -- the one-launch fused step is fp32-only.  More than 704 features or hidden sizes past (64, 16): the torch layers + the HIP loss kernel.  ``score(xs)`` evaluates the
+    (ltr_mlp_bf16_*, :func:`mlp_scores_bf16`) at every list length -- the one-launch fused step is fp32-only unless the
+    module is built with ``fuse_bf16=True``: then a bf16 batch of lists up to 128 documents runs as one bf16-MFMA launch
+    plus the reduction (ltr_mlp_step_bf16; :func:`mlp_step_bf16_supported`).  The flag is the plain attribute
+    ``model.fuse_bf16``, which :class:`FusedMLPListwiseLoss`, :class:`FusedMLPLambdaRankLoss` (set it after
+    construction) and :class:`MLPTrainer` read as well.  More than 704 features or hidden sizes past (64, 16): the torch layers + the HIP loss kernel.  ``score(xs)`` evaluates the
     network alone (for the metrics).  The seven pairwise losses; the listwise ones: :class:`FusedMLPListwiseLoss`.
     """
 
-    def __init__(self, in_features, loss="hinge", hidden=(50, 10), reduction="mean"):
-        super().__init__(in_features, loss, hidden, reduction)
+    def __init__(self, in_features, loss="hinge", hidden=(50, 10), reduction="mean", fuse_bf16=False):
+        super().__init__(in_features, loss, hidden, reduction, fuse_bf16)
 
     _resolve = staticmethod(_resolve_pairwise_loss)
 
@@ -1584,7 +1621,9 @@ class FusedMLPListwiseLoss(_FusedMLPBase):
     with autograd and the stand-alone listwise loss kernel: lists longer than 256 (128 beyond 144 features), ListMLE
     at any length, on the row score and row gradient kernels (ltr_mlp_rows_*_f32); more than 224 features, up to 704,
     at every list length on the wide-row kernels (ltr_mlp_wide_*_f32); hidden sizes past (64, 16) or more than 704
-    features on the torch layers.  ListMLE breaks label ties as :class:`pytorchltr_amd.loss.ListMLELoss` does."""
+    features on the torch layers.  ListMLE breaks label ties as :class:`pytorchltr_amd.loss.ListMLELoss` does.  The
+    opt-in to the one-launch step on a bf16 batch is the plain attribute: ``model.fuse_bf16 = True`` (the constructor
+    keeps the arguments it had)."""
 
     def __init__(self, in_features, loss="listnet", hidden=(50, 10), reduction="mean"):
         super().__init__(in_features, loss, hidden, reduction)
@@ -1605,7 +1644,9 @@ class FusedMLPLambdaRankLoss(_FusedMLPBase):
     ``ltr_mlp_lambdarank_f32`` (include/ltr_mlp_lambdarank.h), the row function of the stand-alone LambdaRank kernel in
     the loss slot of the same two MFMA kernels.  Shapes its plan declines (:func:`mlp_lambdarank_supported`) run as the
     unfused composition of ``score()`` with autograd and the stand-alone kernel, as for :class:`FusedMLPListwiseLoss`;
-    lists past ``max_list_len()`` documents, up to ``max_pair_list_len()``, take that kernel's long path."""
+    lists past ``max_list_len()`` documents, up to ``max_pair_list_len()``, take that kernel's long path.  The opt-in
+    to the one-launch step on a bf16 batch is the plain attribute: ``model.fuse_bf16 = True`` (the constructor keeps the
+    arguments it had)."""
 
     def __init__(self, in_features, loss=None, sigma=1.0, k=None, hidden=(50, 10), reduction="mean"):
         from .loss import pairwise_lambda as _pl
@@ -1742,7 +1783,9 @@ class MLPTrainer:
     ``trainer.lr`` is a plain attribute, read at every eager step (schedulers set it).  ``state_dict()`` /
     ``load_state_dict()`` speak the format of the matching torch optimizer built on ``model.parameters()``, in both
     directions.  Batches off the fused route (longer lists, wide rows, bf16, a listwise loss off its plan) run the
-    pieces of :func:`mlp_loss_step` into a flat gradient and one update launch (ltr_mlp_apply_update_f32); shapes no
+    pieces of :func:`mlp_loss_step` into a flat gradient and one update launch (ltr_mlp_apply_update_f32); a model built
+    with ``fuse_bf16=True`` takes a bf16 batch on :func:`mlp_step_bf16_supported` as two launches again
+    (ltr_mlp_train_step_bf16); shapes no
     kernel takes raise the ValueError of :func:`mlp_loss_step`.  The tensors `step` returns (the loss, ``last_losses``,
     the gradient views) are buffers of the trainer, overwritten by the next step on the same shape."""
 
@@ -1911,7 +1954,7 @@ class MLPTrainer:
         Fp = F + extra
         listwise = isinstance(kind, _ListwiseKind)
         plan = not listwise or _mlp_listwise_plan(kind, B, L, Fp, H1, H2)
-        route = _mlp_route_of("step", xp, Fp, H1, H2, kind, plan)
+        route = _mlp_route_of("step", xp, Fp, H1, H2, kind, plan, model.fuse_bf16)
         if route is _TORCH and _mlp_route_of("loss", xp, Fp, H1, H2, kind, plan) is _WIDE:
             route = _WIDE                                   # (the module's wide rows: the functions have no such route)
         step_params = (w1p,) + tuple(params[1:])
@@ -1922,7 +1965,7 @@ class MLPTrainer:
         optim = self._fill_optim()
         buf = self._buffers_for(B, L, Fp, H1, H2, dev)
         lib = _C.lib()
-        if route is not _FUSED:
+        if route is not _FUSED and route is not _FUSED_BF16:
             lossv, _, lsum = _mlp_step_pieces(X, flat_params, H1, H2, relevance, n, kind, sigma,
                                               None if mean else buf["ones"], False, True, buf["grads"])
             with _C.device_ctx(X):
@@ -1935,7 +1978,8 @@ class MLPTrainer:
             lossv = buf["loss"]
             family, code, k, tie = _mlp_family_call(kind, sigma, L, dev)[:4]
             with _C.device_ctx(X):
-                rc = lib.ltr_mlp_train_step_f32(
+                entry = lib.ltr_mlp_train_step_bf16 if route is _FUSED_BF16 else lib.ltr_mlp_train_step_f32
+                rc = entry(
                     family, code, k, float(sigma), X.data_ptr(), *[p.data_ptr() for p in params], F,
                     flat_params[0].data_ptr() if extra else None, r.data_ptr(), _LABEL_CODE[r.dtype], nn.data_ptr(),
                     *tie, None if mean else buf["ones"].data_ptr(), B, L, Fp, H1, H2, lossv.data_ptr(), None,
