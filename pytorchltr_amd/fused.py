@@ -935,6 +935,10 @@ _MLP_WIDE = _MLPFamily("wide", torch.float32, 4, MLP_MAX_FEATURES, MLP_WIDE_MAX_
 _MLP_BF16 = _MLPFamily("bf16", torch.bfloat16, 8, 0, MLP_MAX_FEATURES,    # include/ltr_mlp_bf16.h: rows of whole 16-byte pieces
                        "ltr_mlp_bf16_scores", "ltr_mlp_bf16_grad", "ltr_mlp_bf16_grad_workspace_bytes",
                        "the bf16 MLP kernels take F <= %d (after zero-padding to a multiple of 8)" % MLP_MAX_FEATURES)
+_MLP_WIDE_BF16 = _MLPFamily("wide bf16", torch.bfloat16, 8, MLP_MAX_FEATURES, MLP_WIDE_MAX_FEATURES,     # include/ltr_mlp_widebf16.h
+                            "ltr_mlp_widebf16_scores", "ltr_mlp_widebf16_grad", "ltr_mlp_widebf16_grad_workspace_bytes",
+                            "the wide bf16 MLP kernels take %d < F <= %d (after zero-padding to a multiple of 8)"
+                            % (MLP_MAX_FEATURES, MLP_WIDE_MAX_FEATURES))
 _mlp_rows_network, _mlp_wide_network, _mlp_bf16_network = _MLP_ROWS.takes, _MLP_WIDE.takes, _MLP_BF16.takes
 
 
@@ -1025,10 +1029,11 @@ def _mlp_prepare(xs, params, family=None, pad=True):
     device, the fp32 parameters, the hidden sizes, the number of zero columns appended (`pad`; W1 is padded to match)
     and the family, chosen from the batch where None is given (`_mlp_family_of`).  ValueError for a network the family
     does not take.  The f32 families go through `_prepare_features` (any dtype is cast, `_padded_rows` views are
-    honoured, the device is checked first); the bf16 family takes bf16 batches only and checks the device last."""
+    honoured, the device is checked first); the two bf16 families take bf16 batches only and check the device last
+    (a bf16 batch without a family: the narrow one, `_MLP_BF16` -- the wide one is opt-in, so callers name it)."""
     if family is None and torch.is_tensor(xs) and xs.dtype is torch.bfloat16:
         family = _MLP_BF16
-    bf16 = family is _MLP_BF16
+    bf16 = family is not None and family.dtype is torch.bfloat16        # (the narrow family or the wide one)
     if bf16:
         if not torch.is_tensor(xs) or xs.dtype is not torch.bfloat16:
             raise ValueError("the bf16 MLP kernels take torch.bfloat16 features (fp32 features: mlp_scores / mlp_grad)")
@@ -1108,12 +1113,12 @@ def _mlp_grad_call(X, flat_params, H1, H2, grad_scores, n, out, wide=False, fami
 
 
 def _mlp_family_scores(xs, params, n, family):
-    X, flat_params, H1, H2, _, family = _mlp_prepare(xs, params, family, pad=family is _MLP_BF16)
+    X, flat_params, H1, H2, _, family = _mlp_prepare(xs, params, family, pad=family.dtype is torch.bfloat16)
     return _mlp_rows_scores(X, flat_params, H1, H2, None if n is None else prepare_n(n, X.shape[0]), family=family)
 
 
 def _mlp_family_grad(xs, params, grad_scores, n, out, family):
-    X, flat_params, H1, H2, extra, family = _mlp_prepare(xs, params, family, pad=family is _MLP_BF16)
+    X, flat_params, H1, H2, extra, family = _mlp_prepare(xs, params, family, pad=family.dtype is torch.bfloat16)
     return _crop_grads(_mlp_grad_call(X, flat_params, H1, H2, grad_scores, n, out, family=family), extra)
 
 
@@ -1167,16 +1172,34 @@ def mlp_grad_bf16(xs, params, grad_scores, n=None, out=None):
     return _mlp_family_grad(xs, params, grad_scores, n, out, _MLP_BF16)
 
 
+def mlp_wide_scores_bf16(xs, params, n=None):
+    """:func:`mlp_scores_bf16` for rows wider than 224 features, up to 704 (ltr_mlp_widebf16_scores: the wave's bf16 W1
+    fragments of the whole row stay in registers, X streams through the LDS in pieces of 32 rows x 256 features; any
+    list length; no autograd).  The same numerics: the scores of the network with ``W1.bfloat16()``, accumulated in
+    fp32, fp32 behind the first layer.  Feature counts that are not a multiple of 8 are zero-padded with one copy (Yahoo:
+    699 -> 704); 232 to 704 features after that, other networks raise ValueError."""
+    return _mlp_family_scores(xs, params, n, _MLP_WIDE_BF16)
+
+
+def mlp_wide_grad_bf16(xs, params, grad_scores, n=None, out=None):
+    """:func:`mlp_grad_bf16` for rows wider than 224 features, up to 704 (ltr_mlp_widebf16_grad): the fp32 gradients of
+    ``sum grad_scores * mlp_wide_scores_bf16(xs, params)``, ``dW1`` with respect to the rounded W1.  Same arguments and
+    the same ``(dW1, db1, dW2, db2, dW3, db3)`` views of one flat buffer; with a feature count that is not a multiple of
+    8, `out` holds the padded network's parameters and ``dW1`` is the view of its first F columns."""
+    return _mlp_family_grad(xs, params, grad_scores, n, out, _MLP_WIDE_BF16)
+
+
 class _MLPScoreFunction(torch.autograd.Function):
-    """``mlp(xs)`` with parameter gradients: forward is the score kernel of the batch's family (`_mlp_family_of`: the
-    row kernels, the wide-row pair past 224 features, the bf16 pair on a bf16 batch), backward its gradient kernel on
+    """``mlp(xs)`` with parameter gradients: forward is the score kernel of `family` (the route's; None: the batch's,
+    `_mlp_family_of`: the row kernels, the wide-row pair past 224 features, the bf16 pair on a bf16 batch), backward its
+    gradient kernel on
     ``grad_scores`` (the activations are recomputed; nothing but the prepared batch -- a copy only where the feature
     count had to be padded -- and the parameters is kept).  The features get no gradient (they are data; callers route
     an input that requires one to the torch layers)."""
 
     @staticmethod
-    def forward(ctx, xs, n, *params):
-        X, flat_params, H1, H2, extra, family = _mlp_prepare(xs, [t.detach() for t in params])
+    def forward(ctx, xs, n, family, *params):
+        X, flat_params, H1, H2, extra, family = _mlp_prepare(xs, [t.detach() for t in params], family)
         nn = None if n is None else prepare_n(n, X.shape[0])
         scores = _mlp_rows_scores(X, flat_params, H1, H2, nn, family=family)
         ctx.save_for_backward(X, nn if nn is not None else torch.empty(0, device=X.device), *flat_params)
@@ -1191,14 +1214,15 @@ class _MLPScoreFunction(torch.autograd.Function):
         X, nn, *flat_params = ctx.saved_tensors
         H1, H2 = flat_params[0].shape[0], flat_params[2].shape[0]
         parts = _mlp_grad_call(X, flat_params, H1, H2, grad_scores, nn if ctx.has_n else None, None, family=ctx.family)
-        return (None, None) + _crop_grads(parts, ctx.extra, ctx.shapes)
+        return (None, None, None) + _crop_grads(parts, ctx.extra, ctx.shapes)
 
 
 # ---- the route table: which kernels a batch reaches from each caller ----
 _FUSED, _PER_QUERY, _ROWS, _WIDE, _BF16, _TORCH = "fused step", "per-query scores", "rows", "wide", "bf16", "torch layers"
 _FUSED_BF16 = "fused bf16 step"
+_WIDE_BF16 = "wide bf16"
 _ROUTE_FAMILY = {_FUSED: _MLP_ROWS, _PER_QUERY: _MLP_ROWS, _ROWS: _MLP_ROWS, _WIDE: _MLP_WIDE, _BF16: _MLP_BF16,
-                 _FUSED_BF16: _MLP_BF16}
+                 _FUSED_BF16: _MLP_BF16, _WIDE_BF16: _MLP_WIDE_BF16}
 MLP_STEP_BF16_MAX_LIST_LEN = 128
 MLP_STEP_BF16_MAX_FEATURES = 160
 
@@ -1216,7 +1240,7 @@ def _f4(F):
 
 
 def _mlp_route(caller, dtype, dim, is_cuda, requires_grad, grad_enabled, autocast, L, F, H1, H2, kind=None, plan=True,
-               fuse_bf16=False):
+               fuse_bf16=False, wide_bf16=False):
     """Which kernels compute ``mlp(xs)`` (and, for a caller with a loss `kind`, the step): plain values in, one of
     _FUSED (the one-launch step, ltr_mlp_pairwise_f32 / ltr_mlp_listwise_f32 / ltr_mlp_lambdarank_f32), _PER_QUERY (ltr_mlp_scores_f32), _ROWS,
     _WIDE, _BF16 (the three families) or _TORCH out -- the three ``nn.Linear`` layers in a module, ValueError in a
@@ -1228,6 +1252,9 @@ def _mlp_route(caller, dtype, dim, is_cuda, requires_grad, grad_enabled, autocas
     The modules zero-pad the feature count to a multiple of 4 (bf16: 8), the functions take it as it is.
     `fuse_bf16`: the caller's opt-in to _FUSED_BF16 (ltr_mlp_step_bf16, the one-launch step on the bf16 batch), returned
     only where the answer is otherwise _BF16, the caller has a loss and :func:`mlp_step_bf16_supported` accepts.
+    `wide_bf16`: the caller's opt-in to _WIDE_BF16 (ltr_mlp_widebf16_*, the K-streamed bf16 kernels), returned only where
+    the answer is otherwise _BF16 -- whose kernels stop at 224 features and raise ValueError past them -- and the network
+    after padding to 8 has more than 224 and at most 704 features with hidden sizes up to (64, 16).
     """
     if dim != 3 or not is_cuda or L <= 0:
         return _TORCH
@@ -1237,6 +1264,8 @@ def _mlp_route(caller, dtype, dim, is_cuda, requires_grad, grad_enabled, autocas
         if (fuse_bf16 and kind is not None and caller in ("loss", "step")
                 and mlp_step_bf16_supported(L, (F + 7) & ~7, H1, H2)):
             return _FUSED_BF16                           # opt-in: one bf16-MFMA launch, lists up to 128 documents
+        if wide_bf16 and _MLP_WIDE_BF16.takes((F + 7) & ~7, H1, H2):
+            return _WIDE_BF16                            # opt-in: 232 .. 704 features, at every list length
         return _BF16                                     # at every list length: the default fused kernels are fp32-only
     if module:
         F = _f4(F)                                       # (everything below computes in fp32)
@@ -1255,22 +1284,23 @@ def _mlp_route(caller, dtype, dim, is_cuda, requires_grad, grad_enabled, autocas
     return _ROWS if rows and f32_data else _WIDE if wide and f32_data else _TORCH
 
 
-def _mlp_route_of(caller, xs, F, H1, H2, kind=None, plan=True, fuse_bf16=False):
+def _mlp_route_of(caller, xs, F, H1, H2, kind=None, plan=True, fuse_bf16=False, wide_bf16=False):
     """`_mlp_route` on a batch: its dtype, shape and flags, the grad mode and the autocast state (F None: the batch's)."""
     if not torch.is_tensor(xs) or xs.dim() != 3:
         return _TORCH
     _, L, Fx = xs.shape
     return _mlp_route(caller, xs.dtype, 3, xs.is_cuda, xs.requires_grad, torch.is_grad_enabled(),
-                      torch.is_autocast_enabled(), L, Fx if F is None else F, H1, H2, kind, plan, fuse_bf16)
+                      torch.is_autocast_enabled(), L, Fx if F is None else F, H1, H2, kind, plan, fuse_bf16, wide_bf16)
 
 
-def _mlp_step_pieces(X, flat_params, H1, H2, relevance, n, kind, sigma, grad_out, return_scores, return_loss_sum, out):
+def _mlp_step_pieces(X, flat_params, H1, H2, relevance, n, kind, sigma, grad_out, return_scores, return_loss_sum, out,
+                     family=None):
     """mlp_loss_step past the limits of the fused kernels, as `_step_pieces` is for the Linear scorer: the row score
-    kernel, the stand-alone loss kernel (its d loss / d score scaled by `grad_out`), the row gradient kernel."""
+    kernel, the stand-alone loss kernel (its d loss / d score scaled by `grad_out`), the row gradient kernel -- those of `family` (None: the batch's)."""
     B, L, F = X.shape
     dev = X.device
     r, nn = _labels_and_n(relevance, n, B, L, dev)
-    scores = _mlp_rows_scores(X, flat_params, H1, H2, nn)       # (a bf16 X: the bf16 kernels, here and below)
+    scores = _mlp_rows_scores(X, flat_params, H1, H2, nn, family=family)    # (a bf16 X: the bf16 kernels, here and below)
     with torch.enable_grad():
         s = scores.unsqueeze(-1).requires_grad_(True)
         lossv = (_listwise_pieces(s, r, nn, kind, sigma) if isinstance(kind, _ListwiseKind)
@@ -1279,7 +1309,7 @@ def _mlp_step_pieces(X, flat_params, H1, H2, relevance, n, kind, sigma, grad_out
               else grad_out.reshape(B).float())
         (ds,) = torch.autograd.grad((lossv * go).sum(), s)
     lossv = lossv.detach()
-    res = (lossv, _mlp_grad_call(X, flat_params, H1, H2, ds, nn, out))
+    res = (lossv, _mlp_grad_call(X, flat_params, H1, H2, ds, nn, out, family=family))
     if return_scores:
         res = res + (scores,)
     if return_loss_sum:
@@ -1288,7 +1318,7 @@ def _mlp_step_pieces(X, flat_params, H1, H2, relevance, n, kind, sigma, grad_out
 
 
 def mlp_loss_step(xs, params, relevance, n, loss="hinge", grad_out=None, return_scores=False,
-                  return_loss_sum=False, out=None, fuse_bf16=False):
+                  return_loss_sum=False, out=None, fuse_bf16=False, wide_bf16=False):
     """One fused forward+backward step of ``loss_fn(mlp(xs), relevance, n)`` without autograd.
 
     Args:
@@ -1297,6 +1327,9 @@ def mlp_loss_step(xs, params, relevance, n, loss="hinge", grad_out=None, return_
         fuse_bf16: True: a bf16 batch of lists up to 128 documents (:func:`mlp_step_bf16_supported`) runs as ONE
             bf16-MFMA launch plus the reduction (ltr_mlp_step_bf16; F <= 160) instead of those pieces -- the same function (W1
             rounded to bf16 for the first layer), the same returned tuple.  Nothing else changes.
+        wide_bf16: True: a bf16 batch of 232 to 704 features (F % 8 == 0), which raises ValueError otherwise, runs the
+            three pieces on the wide bf16 kernels (:func:`mlp_wide_scores_bf16`, :func:`mlp_wide_grad_bf16`) at every
+            list length.  Nothing else changes.
         loss: a pairwise kind name or module, or a listwise loss -- ``"listnet"`` / ``"softmax"``, ``"listmle"``,
             ``ListwiseSoftmaxLoss()``, ``ListMLELoss(k)`` (ltr_mlp_listwise_f32; ListMLE draws one tie seed per call,
             as ``ListMLELoss`` does, and ``utils.tie_breaking("index")`` turns it off).
@@ -1319,11 +1352,12 @@ def mlp_loss_step(xs, params, relevance, n, loss="hinge", grad_out=None, return_
     if isinstance(kind, _ListwiseKind) and kind.loss == _C.LISTWISE_LAMBDARANK:
         raise TypeError("mlp_loss_step has no LambdaRank slot: take mlp_lambdarank_step (the module: "
                         "FusedMLPLambdaRankLoss), or the Linear scorer: FusedLinearLoss, linear_loss_step, LinearScorer")
-    return _mlp_step(xs, params, relevance, n, kind, sigma, grad_out, return_scores, return_loss_sum, out, fuse_bf16)
+    return _mlp_step(xs, params, relevance, n, kind, sigma, grad_out, return_scores, return_loss_sum, out, fuse_bf16,
+                     wide_bf16)
 
 
 def mlp_lambdarank_step(xs, params, relevance, n, sigma=1.0, k=None, grad_out=None, return_scores=False,
-                        return_loss_sum=False, out=None, fuse_bf16=False):
+                        return_loss_sum=False, out=None, fuse_bf16=False, wide_bf16=False):
     """:func:`mlp_loss_step` for LambdaRank (:class:`pytorchltr_amd.loss.LambdaRankLoss` ``(sigma, k)``): one fused
     forward+backward step of ``LambdaRankLoss(sigma, k)(mlp(xs), relevance, n)`` without autograd, by
     ``ltr_mlp_lambdarank_f32`` (include/ltr_mlp_lambdarank.h) -- the NDCG@k swap weights and the top-k pair pass in the
@@ -1331,11 +1365,12 @@ def mlp_lambdarank_step(xs, params, relevance, n, sigma=1.0, k=None, grad_out=No
     shapes are those of :func:`mlp_loss_step`; off the plan (:func:`mlp_lambdarank_supported`: longer lists, a
     ``torch.bfloat16`` batch) the step runs as the three pieces -- the row score kernel, the stand-alone LambdaRank
     kernel (past ``max_list_len()`` documents its long path), the row gradient kernel.  ``fuse_bf16=True``: a bf16
-    batch on :func:`mlp_step_bf16_supported` runs as one launch (ltr_mlp_step_bf16), as in :func:`mlp_loss_step`."""
+    batch on :func:`mlp_step_bf16_supported` runs as one launch (ltr_mlp_step_bf16), as in :func:`mlp_loss_step`;
+    ``wide_bf16=True``: a bf16 batch of 232 to 704 features runs the pieces on the wide bf16 kernels, as there."""
     from .loss import pairwise_lambda as _pl
     k = _pl.LambdaRankLoss(sigma, k).k                      # (its check of k)
     return _mlp_step(xs, params, relevance, n, _ListwiseKind(_C.LISTWISE_LAMBDARANK, k), float(sigma), grad_out,
-                     return_scores, return_loss_sum, out, fuse_bf16)
+                     return_scores, return_loss_sum, out, fuse_bf16, wide_bf16)
 
 
 def _mlp_listwise_plan(kind, B, L, F, H1, H2):
@@ -1364,20 +1399,21 @@ def _mlp_family_call(kind, sigma, L, dev):
     return _C.MLP_TRAIN_LISTWISE, kind.loss, k, tie, "ltr_mlp_listwise_f32", (kind.loss, k), True
 
 
-def _mlp_step(xs, params, relevance, n, kind, sigma, grad_out, return_scores, return_loss_sum, out, fuse_bf16=False):
+def _mlp_step(xs, params, relevance, n, kind, sigma, grad_out, return_scores, return_loss_sum, out, fuse_bf16=False,
+              wide_bf16=False):
     """The step behind mlp_loss_step, mlp_lambdarank_step and the loss modules (`_MLPLossFunction`), on a resolved
     (kind, sigma): a pairwise kind, or a :class:`_ListwiseKind` of ListNet, ListMLE or LambdaRank."""
     listwise = isinstance(kind, _ListwiseKind)
     F, H1, H2 = params[0].shape[-1], params[0].shape[0], params[2].shape[0]    # (the network's: W1 is (H1, F))
     plan = not listwise or (xs.dim() == 3 and _mlp_listwise_plan(kind, xs.shape[0], xs.shape[1], F, H1, H2))
-    route = _mlp_route_of("step", xs, F, H1, H2, kind, plan, fuse_bf16)
+    route = _mlp_route_of("step", xs, F, H1, H2, kind, plan, fuse_bf16, wide_bf16)
     if route is _TORCH:
         _mlp_not_taken(xs, params, True)
-    X, flat_params, H1, H2, _, _ = _mlp_prepare(xs, params, _ROUTE_FAMILY[route], pad=False)
+    X, flat_params, H1, H2, _, family = _mlp_prepare(xs, params, _ROUTE_FAMILY[route], pad=False)
     if route is not _FUSED and route is not _FUSED_BF16:
         # past the fused kernels' list lengths or listwise plan, or a bf16 batch (they are fp32-only): three pieces
         return _mlp_step_pieces(X, flat_params, H1, H2, relevance, n, kind, sigma, grad_out, return_scores,
-                                return_loss_sum, out)
+                                return_loss_sum, out, family)
     B, L, F = X.shape
     dev = X.device
     r, nn = _labels_and_n(relevance, n, B, L, dev)
@@ -1391,7 +1427,7 @@ def _mlp_step(xs, params, relevance, n, kind, sigma, grad_out, return_scores, re
         lsum = (torch.empty if B > 0 else torch.zeros)(1, dtype=torch.float32, device=dev)
     scores = torch.zeros(B, L, dtype=torch.float32, device=dev) if return_scores else None
     go = None if grad_out is None else grad_out.reshape(B).float().contiguous()
-    family, code, k, tie, entry, lead, empty_is_noop = _mlp_family_call(kind, sigma, L, dev)
+    family, code, k, tie, entry, lead, empty_is_noop = _mlp_family_call(kind, sigma, L, dev)     # (the loss family now)
     takes_tie = family == _C.MLP_TRAIN_LISTWISE
     if route is _FUSED_BF16:
         # one entry point for the three families (include/ltr_mlp_step_bf16.h): it always takes the tie arguments, and
@@ -1496,6 +1532,8 @@ class _MLPLayers(torch.nn.Module):
     """What the MLP modules share: the three ``nn.Linear`` layers (``l1`` / ``l2`` / ``l3``, the state_dict of the
     guide's ``Model``) and ``mlp(xs)`` by the route `_mlp_route` names."""
 
+    wide_bf16 = False        # plain attribute, the opt-in: a bf16 batch of 232 .. 704 features takes ltr_mlp_widebf16_*
+
     def __init__(self, in_features, hidden=(50, 10)):
         super().__init__()
         self.in_features = in_features
@@ -1514,11 +1552,14 @@ class _MLPLayers(torch.nn.Module):
         if route is _TORCH:
             return self.l3(torch.nn.functional.relu(self.l2(torch.nn.functional.relu(self.l1(xs)))))
         if torch.is_grad_enabled():
-            return _MLPScoreFunction.apply(xs, n, *self._params())     # (backward: the family's gradient kernel)
+            # (backward: the family's gradient kernel)
+            return _MLPScoreFunction.apply(xs, n, _ROUTE_FAMILY[route], *self._params())
         # evaluation: one launch (the per-query kernel up to mlp_max_list_len documents)
-        X, flat_params, H1, H2, _, _ = _mlp_prepare(xs, self._params(), _ROUTE_FAMILY[route])
-        fn = _mlp_query_scores if route is _PER_QUERY else _mlp_rows_scores
-        return fn(X, flat_params, H1, H2, None if n is None else prepare_n(n, X.shape[0])).unsqueeze(-1)
+        X, flat_params, H1, H2, _, family = _mlp_prepare(xs, self._params(), _ROUTE_FAMILY[route])
+        nn = None if n is None else prepare_n(n, X.shape[0])
+        if route is _PER_QUERY:
+            return _mlp_query_scores(X, flat_params, H1, H2, nn).unsqueeze(-1)
+        return _mlp_rows_scores(X, flat_params, H1, H2, nn, family=family).unsqueeze(-1)
 
 
 class _FusedMLPBase(_MLPLayers):
@@ -1527,13 +1568,15 @@ class _FusedMLPBase(_MLPLayers):
 
     fuse_bf16 = False        # plain attribute, the opt-in: a bf16 batch on mlp_step_bf16_supported takes ltr_mlp_step_bf16
 
-    def __init__(self, in_features, loss, hidden, reduction, fuse_bf16=False):
+    def __init__(self, in_features, loss, hidden, reduction, fuse_bf16=False, wide_bf16=False):
         if reduction not in ("mean", "sum"):
             raise ValueError("reduction must be 'mean' or 'sum'")
         super().__init__(in_features, hidden)
         self.reduction = reduction
         if fuse_bf16:
             self.fuse_bf16 = True
+        if wide_bf16:
+            self.wide_bf16 = True
         self.kind, self.sigma = self._resolve(loss)
         self.last_losses = None
 
@@ -1547,8 +1590,9 @@ class _FusedMLPBase(_MLPLayers):
         other dtypes, autocast.  A ``torch.bfloat16`` batch (outside autocast, no gradient of its own) runs the bf16
         kernels (ltr_mlp_bf16_*: W1 rounded to bf16 for the first layer, fp32 behind it) at every list length, with
         and without gradients; more than 224 features (after padding to 8) or hidden sizes past (64, 16) raise
-        ValueError there."""
-        return self._score(xs, n, _mlp_route_of("score", xs, None, *self._hidden()))
+        ValueError there -- unless ``model.wide_bf16`` is set: then 232 to 704 features (after padding) run the wide
+        bf16 kernels (ltr_mlp_widebf16_*, :func:`mlp_wide_scores_bf16`), with and without gradients."""
+        return self._score(xs, n, _mlp_route_of("score", xs, None, *self._hidden(), wide_bf16=self.wide_bf16))
 
     def _plan(self, B, L, F4, H1, H2):
         """The `plan` of `_mlp_route`: the pairwise fused step has none beyond :func:`mlp_supported`."""
@@ -1562,7 +1606,7 @@ class _FusedMLPBase(_MLPLayers):
         B, L, F = xs.shape
         H1, H2 = self._hidden()
         route = _mlp_route_of("loss", xs, F, H1, H2, self.kind, self._plan(B, L, _f4(F), H1, H2),
-                              self.fuse_bf16)
+                              self.fuse_bf16, self.wide_bf16)
         if route is _FUSED or route is _FUSED_BF16:
             total, per_query = _MLPLossFunction.apply(
                 xs, relevance, n, (self.kind, self.sigma) + ((True,) if route is _FUSED_BF16 else ()),
@@ -1591,12 +1635,15 @@ class FusedMLPLoss(_FusedMLPBase):
     module is built with ``fuse_bf16=True``: then a bf16 batch of lists up to 128 documents runs as one bf16-MFMA launch
     plus the reduction (ltr_mlp_step_bf16; :func:`mlp_step_bf16_supported`).  The flag is the plain attribute
     ``model.fuse_bf16``, which :class:`FusedMLPListwiseLoss`, :class:`FusedMLPLambdaRankLoss` (set it after
-    construction) and :class:`MLPTrainer` read as well.  More than 704 features or hidden sizes past (64, 16): the torch layers + the HIP loss kernel.  ``score(xs)`` evaluates the
+    construction) and :class:`MLPTrainer` read as well.  A bf16 batch of more than 224 features raises ValueError unless
+    the module is built with ``wide_bf16=True`` (the plain attribute ``model.wide_bf16``, read by the same classes): then
+    232 to 704 features, after padding to a multiple of 8, run the three pieces on the wide bf16 kernels
+    (ltr_mlp_widebf16_*, :func:`mlp_wide_scores_bf16`) at every list length.  More than 704 features or hidden sizes past (64, 16): the torch layers + the HIP loss kernel.  ``score(xs)`` evaluates the
     network alone (for the metrics).  The seven pairwise losses; the listwise ones: :class:`FusedMLPListwiseLoss`.
     """
 
-    def __init__(self, in_features, loss="hinge", hidden=(50, 10), reduction="mean", fuse_bf16=False):
-        super().__init__(in_features, loss, hidden, reduction, fuse_bf16)
+    def __init__(self, in_features, loss="hinge", hidden=(50, 10), reduction="mean", fuse_bf16=False, wide_bf16=False):
+        super().__init__(in_features, loss, hidden, reduction, fuse_bf16, wide_bf16)
 
     _resolve = staticmethod(_resolve_pairwise_loss)
 
@@ -1677,11 +1724,18 @@ class MLPScorer(_MLPLayers):
     that require a gradient, inputs that are neither fp32 nor bf16, more than 704 features or hidden sizes past (64, 16)
     run the torch layers; a ``torch.bfloat16`` batch runs the bf16 kernels (ltr_mlp_bf16_*, :func:`mlp_scores_bf16`:
     half the bytes, W1 rounded to bf16 for the first layer; up to 224 features, ValueError past that); 228 to 704 features (Yahoo: 699, padded to 700) run the wide-row kernels (ltr_mlp_wide_*_f32), which
-    stream the feature dimension in chunks.  CPU tensors are refused: there is no CPU fallback."""
+    stream the feature dimension in chunks.  ``wide_bf16=True`` (the plain attribute ``scorer.wide_bf16``): a bf16 batch
+    of 232 to 704 features after padding to 8 runs the wide bf16 kernels (ltr_mlp_widebf16_*) instead of raising.  CPU
+    tensors are refused: there is no CPU fallback."""
+
+    def __init__(self, in_features, hidden=(50, 10), wide_bf16=False):
+        super().__init__(in_features, hidden)
+        if wide_bf16:
+            self.wide_bf16 = True
 
     def forward(self, xs, n=None):
         _C.require_device(xs, "xs")
-        return self._score(xs, n, _mlp_route_of("scorer", xs, None, *self._hidden()))
+        return self._score(xs, n, _mlp_route_of("scorer", xs, None, *self._hidden(), wide_bf16=self.wide_bf16))
 
 
 # ---- MLPTrainer: the fused MLP step with the optimizer update inside the reduction launch (include/ltr_mlp_train.h) ----
@@ -1783,7 +1837,8 @@ class MLPTrainer:
     ``trainer.lr`` is a plain attribute, read at every eager step (schedulers set it).  ``state_dict()`` /
     ``load_state_dict()`` speak the format of the matching torch optimizer built on ``model.parameters()``, in both
     directions.  Batches off the fused route (longer lists, wide rows, bf16, a listwise loss off its plan) run the
-    pieces of :func:`mlp_loss_step` into a flat gradient and one update launch (ltr_mlp_apply_update_f32); a model built
+    pieces of :func:`mlp_loss_step` into a flat gradient and one update launch (ltr_mlp_apply_update_f32) -- with
+    ``model.wide_bf16`` set that includes a bf16 batch of 232 to 704 features, on the wide bf16 kernels; a model built
     with ``fuse_bf16=True`` takes a bf16 batch on :func:`mlp_step_bf16_supported` as two launches again
     (ltr_mlp_train_step_bf16); shapes no
     kernel takes raise the ValueError of :func:`mlp_loss_step`.  The tensors `step` returns (the loss, ``last_losses``,
@@ -1954,20 +2009,20 @@ class MLPTrainer:
         Fp = F + extra
         listwise = isinstance(kind, _ListwiseKind)
         plan = not listwise or _mlp_listwise_plan(kind, B, L, Fp, H1, H2)
-        route = _mlp_route_of("step", xp, Fp, H1, H2, kind, plan, model.fuse_bf16)
+        route = _mlp_route_of("step", xp, Fp, H1, H2, kind, plan, model.fuse_bf16, model.wide_bf16)
         if route is _TORCH and _mlp_route_of("loss", xp, Fp, H1, H2, kind, plan) is _WIDE:
             route = _WIDE                                   # (the module's wide rows: the functions have no such route)
         step_params = (w1p,) + tuple(params[1:])
         if route is _TORCH:
             _mlp_not_taken(xp, step_params, True)
-        X, flat_params, H1, H2, _, _ = _mlp_prepare(xp, step_params, _ROUTE_FAMILY[route], pad=False)
+        X, flat_params, H1, H2, _, family = _mlp_prepare(xp, step_params, _ROUTE_FAMILY[route], pad=False)
         state = self._state_for(Fp, dev)
         optim = self._fill_optim()
         buf = self._buffers_for(B, L, Fp, H1, H2, dev)
         lib = _C.lib()
         if route is not _FUSED and route is not _FUSED_BF16:
             lossv, _, lsum = _mlp_step_pieces(X, flat_params, H1, H2, relevance, n, kind, sigma,
-                                              None if mean else buf["ones"], False, True, buf["grads"])
+                                              None if mean else buf["ones"], False, True, buf["grads"], family)
             with _C.device_ctx(X):
                 _C.check(lib.ltr_mlp_apply_update_f32(
                     buf["grads"].data_ptr(), *[p.data_ptr() for p in params], F, state.data_ptr(), ctypes.byref(optim),
