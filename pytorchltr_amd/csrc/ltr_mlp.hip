@@ -21,6 +21,7 @@
 #include "ltr_mlp_step.inc"       // host: the layout choice, the slot dispatch, the launch path, the step's entry points; needs both kernels' launchers and mlp_reduce_launch
 #include "ltr_mlp_train.inc"      // the optimizer update as the reduction's epilogue (include/ltr_mlp_train.h) and its entry points; needs the cores and the launch path
 #include "ltr_mlp_stream.inc"     // the stand-alone MLP scorer's streaming core and host glue; needs MlpParams' helpers and mlp_reduce_launch
+#include "ltr_mlp_big.inc"        // f32 rows under hidden layers up to (256, 64): its own eight-wave kernels; needs the streaming core's ring, dW1 chain and host glue
 #include "ltr_mlp_rows.inc"       // f32 rows of any length; needs the streaming core
 #include "ltr_mlp_bf16.inc"       // bf16 feature batches; needs the streaming core
 #include "ltr_mlp2_bf16.inc"      // the 4-wave tile kernel of the training step on a bf16 batch, mlp_tile_bf16_kernel; needs the tile kernel's geometry and the bf16 front

@@ -116,7 +116,7 @@ mlp_bf16_kernel(MlpStreamParams p)
 
 // ---- host side ----
 struct MlpBf16Host {
-    static constexpr int kAlign = 8, kMaxF = 32 * kMbMaxKS;
+    static constexpr int kAlign = 8, kMaxF = 32 * kMbMaxKS, kMaxH1 = kMlpH1, kMaxH2 = kMlpH2;
     static int grid(long long rows, int, bool) { return mlp_stream_grid(rows, kMsWgs); }
     template <int KS, bool GRAD>
     static int launch_ks(const MlpStreamParams &p, int grid, hipStream_t stream)

@@ -79,7 +79,7 @@ mlp_rows_kernel(MlpStreamParams p)
 
 // ---- host side ----
 struct MlpRowsHost {
-    static constexpr int kAlign = 4, kMaxF = 16 * 14;
+    static constexpr int kAlign = 4, kMaxF = 16 * 14, kMaxH1 = kMlpH1, kMaxH2 = kMlpH2;
     static int grid(long long rows, int F, bool grad) { return mlp_stream_grid(rows, mlp_rows_wgs(mlp_bucket(F), grad)); }
     template <int NT, bool GRAD>
     static int launch_nt(const MlpStreamParams &p, int grid, hipStream_t stream)

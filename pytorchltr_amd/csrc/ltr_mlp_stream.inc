@@ -465,11 +465,11 @@ __device__ __forceinline__ void mlp_stream_body(const MlpStreamParams &p)
 }
 
 // ---- host side ----
-// align: features per 16 bytes of a row of X; maxF: the widest row of the family
-inline bool mlp_stream_bad_shape(int B, int L, int F, int H1, int H2, int align, int maxF)
+// align: features per 16 bytes of a row of X; maxF: the widest row of the family; maxH1, maxH2: its widest hidden layers
+inline bool mlp_stream_bad_shape(int B, int L, int F, int H1, int H2, int align, int maxF, int maxH1, int maxH2)
 {
     if (B < 0 || L <= 0 || F <= 0 || H1 <= 0 || H2 <= 0) return true;
-    if ((F & (align - 1)) || F > maxF || H1 > kMlpH1 || H2 > kMlpH2) return true;
+    if ((F & (align - 1)) || F > maxF || H1 > maxH1 || H2 > maxH2) return true;
     return (long long)B * L > 0x7fffffffLL;
 }
 
@@ -494,14 +494,14 @@ inline int mlp_stream_grid(long long rows, int wgs_per_cu)
     return (int)(tiles < wgs ? tiles : wgs);
 }
 
-// The entry points of a row-streaming family.  Host: kAlign, kMaxF, grid(rows, F, grad), launch<GRAD>(p, grid, stream)
+// The entry points of a row-streaming family.  Host: kAlign, kMaxF, kMaxH1, kMaxH2, grid(rows, F, grad), launch<GRAD>(p, grid, stream)
 template <class Host>
 int mlp_stream_scores(const void *X, const float *W1, const float *b1, const float *W2, const float *b2,
                       const float *W3, const float *b3, const int64_t *n, int B, int L, int F, int H1, int H2,
                       float *scores_out, void *stream)
 {
     LTR_CLEAR_STALE_ERROR();
-    if (mlp_stream_bad_shape(B, L, F, H1, H2, Host::kAlign, Host::kMaxF)) return LTR_ERR_SHAPE;
+    if (mlp_stream_bad_shape(B, L, F, H1, H2, Host::kAlign, Host::kMaxF, Host::kMaxH1, Host::kMaxH2)) return LTR_ERR_SHAPE;
     if (!W1 || !b1 || !W2 || !b2 || !W3 || !b3) return LTR_ERR_NULL;
     if (B == 0) return LTR_OK;
     if (!X || !scores_out) return LTR_ERR_NULL;
@@ -513,7 +513,7 @@ int mlp_stream_scores(const void *X, const float *W1, const float *b1, const flo
 template <class Host>
 size_t mlp_stream_grad_workspace_bytes(int B, int L, int F, int H1, int H2)
 {
-    if (B <= 0 || mlp_stream_bad_shape(B, L, F, H1, H2, Host::kAlign, Host::kMaxF)) return 0;
+    if (B <= 0 || mlp_stream_bad_shape(B, L, F, H1, H2, Host::kAlign, Host::kMaxF, Host::kMaxH1, Host::kMaxH2)) return 0;
     return (size_t)Host::grid((long long)B * L, F, true) * (size_t)mlp_pitch(mlp_param_count(F, H1, H2)) * sizeof(float);
 }
 
@@ -523,7 +523,7 @@ int mlp_stream_grad(const void *X, const float *W1, const float *b1, const float
                     float *grads, void *workspace, size_t workspace_bytes, void *stream)
 {
     LTR_CLEAR_STALE_ERROR();
-    if (mlp_stream_bad_shape(B, L, F, H1, H2, Host::kAlign, Host::kMaxF)) return LTR_ERR_SHAPE;
+    if (mlp_stream_bad_shape(B, L, F, H1, H2, Host::kAlign, Host::kMaxF, Host::kMaxH1, Host::kMaxH2)) return LTR_ERR_SHAPE;
     if (!W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !grads) return LTR_ERR_NULL;
     const int P = mlp_param_count(F, H1, H2);
     hipStream_t s = (hipStream_t)stream;

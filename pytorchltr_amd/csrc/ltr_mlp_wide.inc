@@ -367,7 +367,7 @@ int ltr_mlp_wide_scores_f32(const float *X, const float *W1, const float *b1, co
                             float *scores_out, void *stream)
 {
     LTR_CLEAR_STALE_ERROR();
-    if (mlp_stream_bad_shape(B, L, F, H1, H2, 4, kMwMaxF)) return LTR_ERR_SHAPE;
+    if (mlp_stream_bad_shape(B, L, F, H1, H2, 4, kMwMaxF, kMlpH1, kMlpH2)) return LTR_ERR_SHAPE;
     if (!W1 || !b1 || !W2 || !b2 || !W3 || !b3) return LTR_ERR_NULL;
     if (B == 0) return LTR_OK;
     if (!X || !scores_out) return LTR_ERR_NULL;
@@ -379,7 +379,7 @@ int ltr_mlp_wide_scores_f32(const float *X, const float *W1, const float *b1, co
 
 size_t ltr_mlp_wide_grad_workspace_bytes(int B, int L, int F, int H1, int H2)
 {
-    if (B <= 0 || mlp_stream_bad_shape(B, L, F, H1, H2, 4, kMwMaxF)) return 0;
+    if (B <= 0 || mlp_stream_bad_shape(B, L, F, H1, H2, 4, kMwMaxF, kMlpH1, kMlpH2)) return 0;
     return mlp_wide_plan((long long)B * L, F, H1, H2).bytes;
 }
 
@@ -388,7 +388,7 @@ int ltr_mlp_wide_grad_f32(const float *X, const float *W1, const float *b1, cons
                           int H1, int H2, float *grads, void *workspace, size_t workspace_bytes, void *stream)
 {
     LTR_CLEAR_STALE_ERROR();
-    if (mlp_stream_bad_shape(B, L, F, H1, H2, 4, kMwMaxF)) return LTR_ERR_SHAPE;
+    if (mlp_stream_bad_shape(B, L, F, H1, H2, 4, kMwMaxF, kMlpH1, kMlpH2)) return LTR_ERR_SHAPE;
     if (!W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !grads) return LTR_ERR_NULL;
     const int P = mlp_param_count(F, H1, H2);
     hipStream_t st = (hipStream_t)stream;
