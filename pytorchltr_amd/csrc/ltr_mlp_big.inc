@@ -30,6 +30,9 @@
 // The feed is mlp_stream_body's, restated for 512 threads: 16-byte unconditional loads one tile ahead, a padded row's
 // lanes redirected to the head of W1 and zeroed on the way into the image, row masks and g two tiles ahead in the
 // three-slot ring (mlp_ring_write).  One partial vector per workgroup, mlp_reduce_launch adds them: no atomics.
+// The kernel body is mlp_big_body<Front, GRAD>: what depends on the element type of X (the image, the W1 fragments,
+// layer 1, the dW1 step) comes from a front -- MlpBigFrontF32<NT> below, under the kernel names mlp_big_kernel<NT, GRAD>;
+// MlpBigFrontBf16<KS> in ltr_mlp_bigbf16.inc -- and everything from the store of the H1 tile to the dH1 write exists once.
 // DESIGN.md section 32 has the design answers, the resource table and the measurements.
 #pragma once
 
@@ -56,34 +59,123 @@ constexpr int kBgSums = kBgH1 + 4 * kBgH2 + 4;   // LDS sums across the tiles: [
 // neither costs it anything.
 constexpr size_t kBgFixedFloats = (size_t)kMsRows * kBgHP + (size_t)kBgH2 * kBgHP + (size_t)kMsRows * kBgDP +
                                   4 * kMsRows + kBgH1 + 2 * kBgH2 + kMsRing * kMsRows + 4;
+__host__ __device__ constexpr size_t mlp_big_lds_bytes_of(size_t image_bytes, bool grad)
+{
+    return image_bytes + (kBgFixedFloats + (grad ? kBgSums : 0)) * sizeof(float);
+}
 __host__ __device__ constexpr size_t mlp_big_lds_bytes(int NT, bool grad)
 {
-    return ((size_t)kMsRows * (16 * NT + 4) + kBgFixedFloats + (grad ? kBgSums : 0)) * sizeof(float);
+    return mlp_big_lds_bytes_of((size_t)kMsRows * (16 * NT + 4) * sizeof(float), grad);
 }
 static_assert(mlp_big_lds_bytes(kBgMaxNT, true) <= kLdsBudget, "one workgroup per CU");
 
 // whether the W1 fragments stay in registers: not in the gradient kernel of the widest bucket
 constexpr bool mlp_big_w1_regs(int NT, bool grad) { return !(grad && NT > 5); }
 
-template <int NT, bool GRAD>
-__global__ void __launch_bounds__(kBgThreads, 1)
-mlp_big_kernel(MlpStreamParams p)
+// ---- the f32 FRONT of mlp_big_body: what depends on the element type of X -- the image, the W1 fragments, layer 1 and
+//      the dW1 step of one hidden-1 block (the bf16 one: MlpBigFrontBf16, ltr_mlp_bigbf16.inc) ----
+template <int NT>
+struct MlpBigFrontF32 {
+    typedef float elem;
+    typedef mlp_f4 w1frag;                          // W1[j1A][16c + 4g .. +3]
+    static constexpr int EU = 4;                    // elements per 16 bytes
+    static constexpr int IP = 16 * NT + 4;          // image pitch (elements)
+    static constexpr int FU = 4 * NT;               // 16-byte units of the widest row
+    static constexpr int NW1 = NT;                  // W1 fragments of a block
+    static constexpr int NC = NT;                   // dW1 chunks of 16 features
+    static constexpr bool w1_regs(bool grad) { return mlp_big_w1_regs(NT, grad); }
+    static constexpr size_t lds_bytes(bool grad) { return mlp_big_lds_bytes(NT, grad); }
+
+    // W1 fragments of the block whose A-operand row of this lane is j1A: zeros past H1 / F
+    static __device__ __forceinline__ void load_w1(w1frag (&wf)[NT], const MlpStreamParams &p, int j1A, int g)
+    {
+#pragma unroll
+        for (int c = 0; c < NT; ++c) {
+            const int f0 = 16 * c + 4 * g;
+            const bool ok = j1A < p.H1 && f0 < p.F;
+            const mlp_f4 v = *reinterpret_cast<const mlp_f4 *>(p.W1 + (ok ? (size_t)j1A * p.F + f0 : 0));
+#pragma unroll
+            for (int i = 0; i < 4; ++i) wf[c][i] = ok ? v[i] : 0.f;
+        }
+    }
+    // h[u] += W1 block . X^T over subtiles u0 .. u0 + NS - 1 of the image
+    template <int NS>
+    static __device__ __forceinline__ void layer1(mlp_f4 (&h)[NS], const w1frag (&wf)[NT], const float *img, int u0,
+                                                  int c16, int g)
+    {
+        const float *bsrc = img + (16 * u0 + c16) * IP + 4 * g;
+        // (one chunk of B fragments ahead, and a scheduling fence per chunk: left alone, the scheduler requests the
+        // fragments of all NT chunks in front of the first MFMA -- 8 NT registers the gradient kernel does not have)
+        mlp_f4 xb[NS], xn[NS];
+#pragma unroll
+        for (int u = 0; u < NS; ++u) xb[u] = *reinterpret_cast<const mlp_f4 *>(bsrc + 16 * u * IP);
+#pragma unroll
+        for (int c = 0; c < NT; ++c) {
+#pragma unroll
+            for (int u = 0; u < NS; ++u)
+                if (c + 1 < NT) xn[u] = *reinterpret_cast<const mlp_f4 *>(bsrc + 16 * u * IP + 16 * (c + 1));
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+#pragma unroll
+                for (int u = 0; u < NS; ++u) h[u] = mfma16(wf[c][i], xb[u][i], h[u]);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int u = 0; u < NS; ++u) xb[u] = xn[u];
+        }
+    }
+    // layer 1 where the fragments do not stay in registers: the block's are fetched again, then the chain above
+    template <int NS>
+    static __device__ __forceinline__ void layer1_refetch(mlp_f4 (&h)[NS], const MlpStreamParams &p, int j1A,
+                                                          const float *img, int u0, int c16, int g)
+    {
+        w1frag wt[NT];
+        load_w1(wt, p, j1A, g);
+        layer1<NS>(h, wt, img, u0, c16, g);
+    }
+    // dW1[block] += dH1^T . X over the documents of subtiles u0 .. u0 + NS - 1: A = the dH1 columns the wave has just
+    // written through `own` (document 4s + g), B = image columns
+    template <int NS>
+    static __device__ __forceinline__ void dw1(mlp_f4 (&acc)[NT], const float *img, const float *own, int u0, int c16,
+                                               int g)
+    {
+        const int d0 = 16 * u0;
+        float a1[4 * NS];
+#pragma unroll
+        for (int s = 0; s < 4 * NS; ++s) a1[s] = own[(d0 + 4 * s + g) * kBgHP + c16];
+        const float *xsrc = img + (d0 + g) * IP + c16;
+#pragma unroll
+        for (int c = 0; c < NT; ++c) {                 // (a fence per chunk, as in layer 1)
+#pragma unroll
+            for (int s = 0; s < 4 * NS; ++s) acc[c] = mfma16(a1[s], xsrc[4 * s * IP + 16 * c], acc[c]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+};
+
+// ---- the kernel body under both fronts.  Front: elem (type of X), EU (elements per 16 bytes), IP (image pitch,
+//      elements), FU (16-byte units of the widest row), NW1 / w1frag / load_w1 / w1_regs, layer1<NS>, NC / dw1<NS>,
+//      lds_bytes.  Everything between the store of the H1 tile and the dH1 write is here, once ----
+template <class Front, bool GRAD>
+__device__ __forceinline__ void mlp_big_body(const MlpStreamParams &p)
 {
-    constexpr bool W1R = mlp_big_w1_regs(NT, GRAD);
+    typedef typename Front::elem elem;
+    typedef typename Front::w1frag w1frag;
+    constexpr bool W1R = Front::w1_regs(GRAD);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int T = kBgThreads, IP = 16 * NT + 4, HP = kBgHP, DP = kBgDP;
-    constexpr int KP = (kMsRows * 4 * NT + T - 1) / T;              // 16-byte units of a fill per thread
+    constexpr int T = kBgThreads, EU = Front::EU, IP = Front::IP, NW1 = Front::NW1, NC = Front::NC, HP = kBgHP, DP = kBgDP;
+    constexpr int KP = (kMsRows * Front::FU + T - 1) / T;           // 16-byte units of a fill per thread
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     int c16 = lane & 15, g = lane >> 4;             // (not const: see the top of the tile loop)
     const int F = p.F, H1 = p.H1, H2 = p.H2;
-    const int C = F >> 2;                           // 16-byte units per feature row
+    const int C = F >> (EU == 8 ? 3 : 2);           // 16-byte units per feature row
     const int nb1 = (H1 + 15) >> 4, nb2 = (H2 + 15) >> 4;          // 16-row blocks of the two hidden layers
     const int nh = (w < nb1 ? 1 : 0) + (w + 8 < nb1 ? 1 : 0);      // hidden-1 blocks of this wave: w, w + 8
     const int jb = w & 3, ju = w >> 2;              // layers 2 / 3: hidden-2 block and row subtile of this wave
 
-    float *img = reinterpret_cast<float *>(smem);                  // [32][IP]   feature rows of the fill
-    float *h1s = img + (size_t)kMsRows * IP;                       // [32][HP]   H1 tile, document-major; later dH1
+    elem *img = reinterpret_cast<elem *>(smem);                    // [32][IP]   feature rows of the fill
+    float *h1s = reinterpret_cast<float *>(img + (size_t)kMsRows * IP);        // [32][HP]   H1 tile, document-major; later dH1
     float *w2s = h1s + (size_t)kMsRows * HP;                       // [64][HP]   W2, zeros past (H2, H1)
     float *dH2s = w2s + (size_t)kBgH2 * HP;                        // [32][DP]
     float *sp = dH2s + (size_t)kMsRows * DP;                       // [4][32]    layer-3 partial dots per hidden-2 block
@@ -99,51 +191,41 @@ mlp_big_kernel(MlpStreamParams p)
     const mlp_f4 zero4 = {0.f, 0.f, 0.f, 0.f};
     const mlp_i4 zero4i = {0, 0, 0, 0};
 
-    // ---- W1 fragments of block w + 8 hb: W1[16 (w + 8 hb) + c16][16c + 4g .. +3], zeros past H1 / F.  W1R: both blocks'
-    //      stay in registers; else (the widest gradient bucket: 72 registers it does not have next to dW1 and dW2) layer 1
-    //      fetches a block's fragments again for every tile -- 147 KB per tile at (256, 144), from the L2 ----
-    auto load_w1 = [&](mlp_f4 (&wf)[NT], int hb) {
-        const int j1A = 16 * (w + 8 * hb) + c16;
-#pragma unroll
-        for (int c = 0; c < NT; ++c) {
-            const int f0 = 16 * c + 4 * g;
-            const bool ok = j1A < H1 && f0 < F;
-            const mlp_f4 v = *reinterpret_cast<const mlp_f4 *>(p.W1 + (ok ? (size_t)j1A * F + f0 : 0));
-#pragma unroll
-            for (int i = 0; i < 4; ++i) wf[c][i] = ok ? v[i] : 0.f;
-        }
-    };
-    mlp_f4 w1r[W1R ? 2 : 1][NT];
+    // ---- W1 fragments of block w + 8 hb (Front::load_w1, A-operand row 16 (w + 8 hb) + c16), zeros past H1 / F.  W1R:
+    //      both blocks' stay in registers; else (the widest gradient buckets: registers they do not have next to dW1 and
+    //      dW2) layer 1 fetches a block's fragments again for every tile -- f32: 147 KB per tile at (256, 144) -- from
+    //      the L2 ----
+    w1frag w1r[W1R ? 2 : 1][NW1];
     if constexpr (W1R) {
-        load_w1(w1r[0], 0);
-        load_w1(w1r[1], 1);
+        Front::load_w1(w1r[0], p, 16 * w + c16, g);
+        Front::load_w1(w1r[1], p, 16 * (w + 8) + c16, g);
     }
     const float b3 = p.b3[0];
 
     // ---- accumulators that live across the tiles ----
-    mlp_f4 acc[2][GRAD ? NT : 1];    // dW1[16 (w + 8 hb) + 4g + i][16c + c16]
+    mlp_f4 acc[2][GRAD ? NC : 1];    // dW1[16 (w + 8 hb) + 4g + i][16c + c16]
     mlp_f4 accW2[4][2];              // dW2[16 jb + 4g + i][16 (w + 8 hb) + c16]
 #pragma unroll
     for (int hb = 0; hb < 2; ++hb) {
 #pragma unroll
-        for (int c = 0; c < (GRAD ? NT : 1); ++c) acc[hb][c] = zero4;
+        for (int c = 0; c < (GRAD ? NC : 1); ++c) acc[hb][c] = zero4;
 #pragma unroll
         for (int b = 0; b < 4; ++b) accW2[b][hb] = zero4;
     }
 
     // ---- the fill (mlp_stream_body's, 512 threads): unit k of this thread is 16-byte unit u = tid + 512 k of the tile's
-    //      rows in memory, row ur[k] = u / C of the tile (>= 32: past the tile), image float 4u + ur[k] (IP - 4C) ----
+    //      rows in memory, row ur[k] = u / C of the tile (>= 32: past the tile), image element EU u + ur[k] (IP - EU C) ----
     int ur[KP];
 #pragma unroll
     for (int k = 0; k < KP; ++k) ur[k] = (tid + k * T) / C;
     mlp_i4 P[KP];
     auto issue_fill = [&](int tile, unsigned m) {
-        const float *Xt = static_cast<const float *>(p.X) + (size_t)tile * kMsRows * (size_t)F;
+        const elem *Xt = static_cast<const elem *>(p.X) + (size_t)tile * kMsRows * (size_t)F;
 #pragma unroll
         for (int k = 0; k < KP; ++k) {
             const bool ok = ur[k] < kMsRows && ((m >> (ur[k] & 31)) & 1u);
             // (a padded row is never read: its lanes fetch the first 16 bytes of W1 and drop them)
-            const void *src = ok ? (const void *)(Xt + 4 * (size_t)(tid + k * T)) : (const void *)p.W1;
+            const void *src = ok ? (const void *)(Xt + EU * (size_t)(tid + k * T)) : (const void *)p.W1;
             P[k] = *reinterpret_cast<const mlp_i4 *>(src);
         }
     };
@@ -152,7 +234,7 @@ mlp_big_kernel(MlpStreamParams p)
         for (int k = 0; k < KP; ++k) {
             const bool ok = (m >> (ur[k] & 31)) & 1u;
             const mlp_i4 v = ok ? P[k] : zero4i;
-            if (ur[k] < kMsRows) *reinterpret_cast<mlp_i4 *>(img + 4 * (tid + k * T) + ur[k] * (IP - 4 * C)) = v;
+            if (ur[k] < kMsRows) *reinterpret_cast<mlp_i4 *>(img + EU * (tid + k * T) + ur[k] * (IP - EU * C)) = v;
         }
     };
 
@@ -163,32 +245,12 @@ mlp_big_kernel(MlpStreamParams p)
         for (int hb = 0; hb < 2; ++hb) {
             if (hb < nh) {
                 const int j0 = 16 * (w + 8 * hb);
-                mlp_f4 wt[W1R ? 1 : NT];
-                if constexpr (!W1R) load_w1(wt, hb);
                 const mlp_f4 b1v = *reinterpret_cast<const mlp_f4 *>(b1s + j0 + 4 * g);
                 mlp_f4 h[NS];
 #pragma unroll
                 for (int u = 0; u < NS; ++u) h[u] = b1v;
-                const float *bsrc = img + (16 * u0 + c16) * IP + 4 * g;
-                // (one chunk of B fragments ahead, and a scheduling fence per chunk: left alone, the scheduler requests the
-                // fragments of all NT chunks in front of the first MFMA -- 8 NT registers the gradient kernel does not have)
-                mlp_f4 xb[NS], xn[NS];
-#pragma unroll
-                for (int u = 0; u < NS; ++u) xb[u] = *reinterpret_cast<const mlp_f4 *>(bsrc + 16 * u * IP);
-#pragma unroll
-                for (int c = 0; c < NT; ++c) {
-#pragma unroll
-                    for (int u = 0; u < NS; ++u)
-                        if (c + 1 < NT) xn[u] = *reinterpret_cast<const mlp_f4 *>(bsrc + 16 * u * IP + 16 * (c + 1));
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-#pragma unroll
-                        for (int u = 0; u < NS; ++u) h[u] = mfma16(W1R ? w1r[W1R ? hb : 0][c][i] : wt[W1R ? 0 : c][i], xb[u][i], h[u]);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int u = 0; u < NS; ++u) xb[u] = xn[u];
-                }
+                if constexpr (W1R) Front::template layer1<NS>(h, w1r[hb], img, u0, c16, g);
+                else Front::template layer1_refetch<NS>(h, p, j0 + c16, img, u0, c16, g);
 #pragma unroll
                 for (int u = 0; u < NS; ++u) {
 #pragma unroll
@@ -293,20 +355,9 @@ mlp_big_kernel(MlpStreamParams p)
                     for (int i = 0; i < 4; ++i) s1[i] = row16_sum(NS == 2 ? d1[0][i] + d1[NS - 1][i] : d1[0][i]);
                     if (c16 == 0) *reinterpret_cast<mlp_f4 *>(db1s + j0 + 4 * g) += s1;
                 }
-                // dW1[block] += dH1^T . X: A = the dH1 columns just written (document 4s + g), B = image columns
+                // dW1[block] += dH1^T . X: A = the dH1 columns just written, B = image columns (Front::dw1)
                 // (cells written by OTHER lanes of this wave: in-order DS, and stores and loads through `own` alike)
-                if constexpr (GRAD) {
-                    float a1[4 * NS];
-#pragma unroll
-                    for (int s = 0; s < 4 * NS; ++s) a1[s] = own[(d0 + 4 * s + g) * HP + c16];
-                    const float *xsrc = img + (d0 + g) * IP + c16;
-#pragma unroll
-                    for (int c = 0; c < NT; ++c) {                 // (a fence per chunk, as in layer 1)
-#pragma unroll
-                        for (int s = 0; s < 4 * NS; ++s) acc[hb][c] = mfma16(a1[s], xsrc[4 * s * IP + 16 * c], acc[hb][c]);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                }
+                if constexpr (GRAD) Front::template dw1<NS>(acc[hb], img, own, u0, c16, g);
             }
         }
     };
@@ -317,9 +368,9 @@ mlp_big_kernel(MlpStreamParams p)
     mlp_ring_write<GRAD>(p, tid, tile, 0, vmask, gs);
     mlp_ring_write<GRAD>(p, tid, tile + G, 1, vmask, gs);
     // the feature columns F .. IP - 1 of the image are never written by a fill: zero them once
-    for (int i = tid; i < kMsRows * (IP - 4 * C); i += T) {
-        const int r = i / (IP - 4 * C), cc = i - r * (IP - 4 * C);
-        img[r * IP + 4 * C + cc] = 0.f;
+    for (int i = tid; i < kMsRows * (IP - EU * C); i += T) {
+        const int r = i / (IP - EU * C), cc = i - r * (IP - EU * C);
+        img[r * IP + EU * C + cc] = 0;
     }
     for (int i = tid; i < kBgH2 * kBgH1; i += T) {                 // W2 over the blocks in use, zeros past (H2, H1)
         const int j2 = i >> 8, j1 = i & (kBgH1 - 1);
@@ -401,7 +452,7 @@ mlp_big_kernel(MlpStreamParams p)
                 for (int i = 0; i < 4; ++i) {
                     const int j1 = j0 + 4 * g + i;
 #pragma unroll
-                    for (int c = 0; c < NT; ++c) {
+                    for (int c = 0; c < NC; ++c) {
                         const int f = 16 * c + c16;
                         if (j1 < H1 && f < F) dst[(size_t)j1 * F + f] = acc[hb][c][i];
                     }
@@ -421,6 +472,13 @@ mlp_big_kernel(MlpStreamParams p)
         }
         if (tid == 0) dst[oB3] = db3s[0] + db3s[1];
     }
+}
+
+template <int NT, bool GRAD>
+__global__ void __launch_bounds__(kBgThreads, 1)
+mlp_big_kernel(MlpStreamParams p)
+{
+    mlp_big_body<MlpBigFrontF32<NT>, GRAD>(p);
 }
 
 // ---- host side ----
