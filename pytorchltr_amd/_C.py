@@ -1,5 +1,5 @@
 """ctypes binding of the C ABI in ``include/ltr_hip.h``, ``include/ltr_eval.h``, ``include/ltr_listwise.h``,
-``include/ltr_lambdarank.h``, ``include/ltr_longpair.h``, ``include/ltr_lambdarank_long.h``, ``include/ltr_mlp_rows.h``, ``include/ltr_mlp_big.h``, ``include/ltr_mlp_bigbf16.h``, ``include/ltr_mlp_bigwide.h``, ``include/ltr_mlp_bf16.h``, ``include/ltr_mlp_step_bf16.h``, ``include/ltr_mlp_wide.h``, ``include/ltr_mlp_widebf16.h``,
+``include/ltr_lambdarank.h``, ``include/ltr_longpair.h``, ``include/ltr_lambdarank_long.h``, ``include/ltr_mlp_rows.h``, ``include/ltr_mlp_big.h``, ``include/ltr_mlp_bigbf16.h``, ``include/ltr_mlp_bigwide.h``, ``include/ltr_mlp_bigwidebf16.h``, ``include/ltr_mlp_bf16.h``, ``include/ltr_mlp_step_bf16.h``, ``include/ltr_mlp_wide.h``, ``include/ltr_mlp_widebf16.h``,
 ``include/ltr_linear_bf16.h``, ``include/ltr_mlp_train.h`` and ``include/ltr_sched.h`` (pytorchltr_amd/csrc/libltr_hip.so).
 
 PyTorch supplies device memory and the current HIP stream; every call here hands raw device
@@ -203,6 +203,13 @@ MLP_BIGWIDE_SIGNATURES = {
     "ltr_mlp_bigwide_grad_f32": (_i, [_vp] * 9 + [_i] * 5 + [_vp, _vp, _sz, _vp]),
 }
 
+# name -> (restype, argtypes); mirrors include/ltr_mlp_bigwidebf16.h (the same hidden layers on bf16 rows of up to 704 features)
+MLP_BIGWIDEBF16_SIGNATURES = {
+    "ltr_mlp_bigwidebf16_scores": (_i, [_vp] * 8 + [_i] * 5 + [_vp, _vp]),
+    "ltr_mlp_bigwidebf16_grad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "ltr_mlp_bigwidebf16_grad": (_i, [_vp] * 9 + [_i] * 5 + [_vp, _vp, _sz, _vp]),
+}
+
 # name -> (restype, argtypes); mirrors include/ltr_mlp_bf16.h (the same scorer on a bf16 feature batch, bf16 MFMA layer 1)
 MLP_BF16_SIGNATURES = {
     "ltr_mlp_bf16_scores": (_i, [_vp] * 8 + [_i] * 5 + [_vp, _vp]),
@@ -308,7 +315,7 @@ def lib():
                                           + list(MLP_LAMBDARANK_SIGNATURES.items()) + list(MLP_TRAIN_SIGNATURES.items())
                                           + list(MLP_ROWS_SIGNATURES.items()) + list(MLP_WIDE_SIGNATURES.items())
                                           + list(MLP_BIG_SIGNATURES.items()) + list(MLP_BIGBF16_SIGNATURES.items())
-                                          + list(MLP_BIGWIDE_SIGNATURES.items())
+                                          + list(MLP_BIGWIDE_SIGNATURES.items()) + list(MLP_BIGWIDEBF16_SIGNATURES.items())
                                           + list(MLP_BF16_SIGNATURES.items()) + list(LINEAR_BF16_SIGNATURES.items())
                                           + list(MLP_STEP_BF16_SIGNATURES.items()) + list(MLP_WIDEBF16_SIGNATURES.items())
                                           + list(SCHED_SIGNATURES.items())):

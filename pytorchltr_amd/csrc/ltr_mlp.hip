@@ -28,5 +28,6 @@
 #include "ltr_mlp2_bf16.inc"     // the 4-wave tile kernel of the training step on a bf16 batch, mlp_tile_bf16_kernel; needs the tile kernel's geometry and the bf16 front
 #include "ltr_mlp_wide.inc"     // wide rows (K-streamed); needs the streaming core's host glue and mlp_reduce_launch
 #include "ltr_mlp_bigwide.inc"  // f32 rows up to 704 features under hidden layers up to (256, 64): K-streamed eight-wave kernels; needs the wide-hidden kernels' geometry and the streaming core's host glue
+#include "ltr_mlp_bigwidebf16.inc" // bf16 rows up to 704 features under hidden layers up to (256, 64): the bf16 front of ltr_mlp_bigwide.inc's body and a bf16 dW1 kernel; needs that body, its plan and the bf16 vector types
 #include "ltr_mlp_widebf16.inc" // wide bf16 rows (W1 register-resident, X K-streamed); needs the bf16 front's chunk and the streaming core's host glue
 #include "ltr_scorer.inc"        // the stand-alone Linear scorer on f32 and bf16 rows; needs mlp_reduce_kernel

@@ -6,7 +6,8 @@
 // plan are this file's own: ltr_mlp_big.inc keeps a wave's W1 fragments and dW1 tile in registers (72 + 72 at F = 144,
 // 352 + 352 at 704), ltr_mlp_wide.inc keeps one hidden-1 block per wave and one hidden-2 fragment.
 //
-// Forward (mlp_bigwide_fwd_kernel): one workgroup of EIGHT waves per CU, wave w owns the hidden-1 blocks w and w + 8.
+// Forward (mlp_bigwide_body behind a front; mlp_bigwide_fwd_kernel is its f32 front, described here, and
+// ltr_mlp_bigwidebf16.inc holds the bf16 one): one workgroup of EIGHT waves per CU, wave w owns the hidden-1 blocks w and w + 8.
 // A workgroup takes its 32-row tiles in GROUPS (eight for the scores, four in front of the backward half) and keeps the
 // layer-1 accumulators of the whole group in registers, 16 per tile (two blocks x two subtiles).  Chunk loop outside,
 // tile loop inside:
@@ -51,10 +52,15 @@ constexpr int mlp_bigwide_group(bool grad) { return grad ? 4 : kBwTG; }
 
 // LDS of the forward kernel: [2][32][68] X images | [32][272] H1 tile | [64][272] W2 | [32][68] dH2 rows | [4][32] layer-3
 // shares | [256] b1 [64] b2 [64] W3 | [8][32] g | [8] masks | GRAD: [516] small sums -- 135 728 bytes
+// (images_bytes: both images of the front -- f32 here, bf16 in ltr_mlp_bigwidebf16.inc)
+constexpr size_t mlp_bigwide_lds_bytes_of(size_t images_bytes, bool grad)
+{
+    return images_bytes + ((size_t)kMsRows * kBgHP + (size_t)kBgH2 * kBgHP + (size_t)kMsRows * kBgDP +
+                           4 * kMsRows + kBgH1 + 2 * kBgH2 + kBwTG * kMsRows + 8 + (grad ? kBgSums : 0)) * sizeof(float);
+}
 constexpr size_t mlp_bigwide_fwd_lds_bytes(bool grad)
 {
-    return ((size_t)2 * kMsRows * kBwIP + (size_t)kMsRows * kBgHP + (size_t)kBgH2 * kBgHP + (size_t)kMsRows * kBgDP +
-            4 * kMsRows + kBgH1 + 2 * kBgH2 + kBwTG * kMsRows + 8 + (grad ? kBgSums : 0)) * sizeof(float);
+    return mlp_bigwide_lds_bytes_of((size_t)2 * kMsRows * kBwIP * sizeof(float), grad);
 }
 // LDS of the dW1 kernel: two images [32][16 NTS + 4] and the ring's masks
 constexpr size_t mlp_bigwide_dw1_lds_bytes(int NTS)
@@ -101,26 +107,63 @@ __device__ __forceinline__ void mlp_bigwide_l1(mlp_f4 (&h)[2][2], const mlp_f4 (
     else mlp_bigwide_l1_step<NB, 1, 1>(h, wf, im, nc, c16, g);
 }
 
-template <bool GRAD>
-__global__ void __launch_bounds__(kBgThreads, 1)
-mlp_bigwide_fwd_kernel(MlpStreamParams p)
+// The f32 front of mlp_bigwide_body.  A front supplies what differs between the element types of X in front of the
+// layer-1 accumulators: the image (element, 16-byte unit, pitch IP, chunk width KC), a chunk's W1 fragments of the wave's
+// two blocks (NW per block), how many of a chunk's MFMA steps exist, and the layer-1 step itself.  The bf16 front is
+// MlpBigWideFrontBf16 (ltr_mlp_bigwidebf16.inc).
+struct MlpBigWideFrontF32 {
+    typedef float elem;
+    typedef mlp_f4 unit;                 // 16 bytes of X on their way into the image
+    typedef mlp_f4 w1frag;               // W1[16 (w + 8 hb) + c16][64 ch + 16c + 4g .. +3], zeros past H1 / F
+    static constexpr int EU = 4, KC = kBwKC, IP = kBwIP, NW = kBwNTC;
+    static __device__ __forceinline__ int steps(int left)          // the chunk's 16-feature steps (uniform)
+    {
+        const int rem = (left + 15) >> 4;
+        return rem < NW ? rem : NW;
+    }
+    static __device__ __forceinline__ void load_w1_chunk(w1frag (&wf)[2][NW], const MlpStreamParams &p, int tid, int lane,
+                                                         int w, int c16, int g, int ch)
+    {
+#pragma unroll
+        for (int hb = 0; hb < 2; ++hb) {
+            MlpLane ln;
+            ln.tid = tid; ln.lane = lane; ln.w = w + 8 * hb; ln.c16 = c16; ln.g = g; ln.j1A = 16 * (w + 8 * hb) + c16;
+            mlp_load_w1_f32<NW>(wf[hb], p, ln, ch * KC);
+        }
+    }
+    template <int NB>
+    static __device__ __forceinline__ void layer1(mlp_f4 (&h)[2][2], const w1frag (&wf)[2][NW], const float *im, int nc,
+                                                  unsigned m, int c16, int g)
+    {
+        mlp_bigwide_l1<NB>(h, wf, im, nc, m, c16, g);
+    }
+};
+
+// the forward kernel (GRAD: and the backward down to dH1) behind a front: everything in the header comment
+template <class Front, bool GRAD>
+__device__ __forceinline__ void mlp_bigwide_body(const MlpStreamParams &p)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int IP = kBwIP, HP = kBgHP, DP = kBgDP, TG = mlp_bigwide_group(GRAD);
+    typedef typename Front::elem elem;
+    typedef typename Front::unit unit;
+    constexpr int IP = Front::IP, HP = kBgHP, DP = kBgDP, TG = mlp_bigwide_group(GRAD);
+    constexpr int RU = Front::KC / Front::EU;       // 16-byte units per image row
+    constexpr int NP = kMsRows * RU / kBgThreads;   // units of a step per thread: rows fr + (32 / NP) k
+    static_assert(NP >= 1 && NP * kBgThreads == kMsRows * RU, "whole units per thread");
     static_assert(TG % 2 == 0 && TG <= kBwTG && 32 * kBwTG <= kBgThreads, "image parity; one thread per row of a group");
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     int c16 = lane & 15, g = lane >> 4;             // (not const: see the top of the chunk loop)
     const int F = p.F, H1 = p.H1, H2 = p.H2;
-    const float *X = static_cast<const float *>(p.X);
-    const int NCH = (F + kBwKC - 1) / kBwKC;        // feature chunks
+    const elem *X = static_cast<const elem *>(p.X);
+    const int NCH = (F + Front::KC - 1) / Front::KC;               // feature chunks
     const int nb1 = (H1 + 15) >> 4, nb2 = (H2 + 15) >> 4;          // 16-row blocks of the two hidden layers
     const int nh = (w < nb1 ? 1 : 0) + (w + 8 < nb1 ? 1 : 0);      // hidden-1 blocks of this wave: w, w + 8
     const int jb = w & 3, ju = w >> 2;              // layers 2 / 3: hidden-2 block and row subtile of this wave
     const int DH = mlp_bigwide_dh(H1);
 
-    float *img = reinterpret_cast<float *>(smem);                  // [2][32][IP] the piece of X of a step
-    float *h1s = img + (size_t)2 * kMsRows * IP;                   // [32][HP]    H1 tile, document-major
+    elem *img = reinterpret_cast<elem *>(smem);                    // [2][32][IP] the piece of X of a step
+    float *h1s = reinterpret_cast<float *>(img + (size_t)2 * kMsRows * IP);    // [32][HP] H1 tile, document-major
     float *w2s = h1s + (size_t)kMsRows * HP;                       // [64][HP]    W2, zeros past (H2, H1)
     float *dH2s = w2s + (size_t)kBgH2 * HP;                        // [32][DP]
     float *sp = dH2s + (size_t)kMsRows * DP;                       // [4][32]     layer-3 partial dots per hidden-2 block
@@ -163,23 +206,32 @@ mlp_bigwide_fwd_kernel(MlpStreamParams p)
 #pragma unroll
     for (int b = 0; b < 4; ++b) { accW2[b][0] = zero4; accW2[b][1] = zero4; }
 
-    // ---- a step moves a 32 x 64 piece of X: 512 float4 units, one per thread -- row fr of the tile, float 4 fc of the
-    //      chunk ----
-    const int fr = tid >> 4, fc = tid & 15;
-    mlp_f4 P = zero4;                               // the piece in flight
-    auto issue_fill = [&](int tile, int ch, unsigned m) {
-        const int f = ch * kBwKC + 4 * fc;
-        const bool ok = ((m >> fr) & 1u) && f < F;
-        // (a padded row is never read: its lanes fetch the first 16 bytes of W1 and drop them)
-        const float *src = ok ? X + ((size_t)tile * kMsRows + fr) * (size_t)F + f : p.W1;
-        P = *reinterpret_cast<const mlp_f4 *>(src);
-    };
-    auto fill_image = [&](float *im, int ch, unsigned m) {
-        const bool ok = ((m >> fr) & 1u) && ch * kBwKC + 4 * fc < F;
-        mlp_f4 v;
+    // ---- a step moves a 32 x KC piece of X: 512 NP units of 16 bytes, NP per thread -- rows fr + (32 / NP) k of the
+    //      tile, unit fc of the chunk (f32: 32 x 64, one float4 per thread) ----
+    const int fr = tid / RU, fc = tid % RU;
+    const unit zerou = {};
+    unit P[NP];                                     // the piece in flight
 #pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = ok ? P[i] : 0.f;
-        *reinterpret_cast<mlp_f4 *>(im + fr * IP + 4 * fc) = v;
+    for (int k = 0; k < NP; ++k) P[k] = zerou;
+    auto issue_fill = [&](int tile, int ch, unsigned m) {
+        const int f = ch * Front::KC + Front::EU * fc;
+#pragma unroll
+        for (int k = 0; k < NP; ++k) {
+            const int r = fr + (kMsRows / NP) * k;
+            const bool ok = ((m >> r) & 1u) && f < F;
+            // (a padded row is never read: its lanes fetch the first 16 bytes of W1 and drop them)
+            const void *src = ok ? (const void *)(X + ((size_t)tile * kMsRows + r) * (size_t)F + f) : (const void *)p.W1;
+            P[k] = *reinterpret_cast<const unit *>(src);
+        }
+    };
+    // (every unit of the piece is written, zeros on padded rows and past F: no step multiplies stale LDS contents)
+    auto fill_image = [&](elem *im, int ch, unsigned m) {
+#pragma unroll
+        for (int k = 0; k < NP; ++k) {
+            const int r = fr + (kMsRows / NP) * k;
+            const bool ok = ((m >> r) & 1u) && ch * Front::KC + Front::EU * fc < F;
+            *reinterpret_cast<unit *>(im + r * IP + Front::EU * fc) = ok ? P[k] : zerou;
+        }
     };
 
     // ---- layers 2 and 3 of hidden-2 block jb on the 16 documents of subtile ju of tile j (ltr_mlp_big.inc's layer23:
@@ -312,18 +364,12 @@ mlp_bigwide_fwd_kernel(MlpStreamParams p)
         for (int ch = 0; ch < NCH; ++ch) {
             // (opaque lane indices keep the address arithmetic of the steps inside the loop: ltr_mlp_big.inc)
             asm volatile("" : "+v"(c16), "+v"(g));
-            mlp_f4 w1r[2][kBwNTC];                  // W1[16 (w + 8 hb) + c16][64 ch + 16c + 4g .. +3], zeros past H1 / F
-#pragma unroll
-            for (int hb = 0; hb < 2; ++hb) {
-                MlpLane ln;
-                ln.tid = tid; ln.lane = lane; ln.w = w + 8 * hb; ln.c16 = c16; ln.g = g; ln.j1A = 16 * (w + 8 * hb) + c16;
-                mlp_load_w1_f32<kBwNTC>(w1r[hb], p, ln, ch * kBwKC);
-            }
-            const int rem = (F - ch * kBwKC + 15) >> 4;
-            const int nc = rem < kBwNTC ? rem : kBwNTC;         // the chunk's 16-feature steps (uniform)
+            typename Front::w1frag w1r[2][Front::NW];           // the chunk's W1 fragments of the wave's two blocks
+            Front::load_w1_chunk(w1r, p, tid, lane, w, c16, g, ch);
+            const int nc = Front::steps(F - ch * Front::KC);    // the chunk's MFMA steps that exist (uniform)
 #pragma unroll
             for (int j = 0; j < TG; ++j) {
-                float *im = img + (size_t)(j & 1) * kMsRows * IP;
+                elem *im = img + (size_t)(j & 1) * kMsRows * IP;
                 if (mcur) fill_image(im, ch, mcur);             // (waits for the piece in P)
                 const int jn = j + 1 < TG ? j + 1 : 0;
                 const int chn = j + 1 < TG ? ch : ch + 1;
@@ -333,8 +379,8 @@ mlp_bigwide_fwd_kernel(MlpStreamParams p)
                 // through the barrier of the step between, which every wave reaches behind its reads of this step
                 lds_barrier();
                 if (mcur) {
-                    if (nh == 2) mlp_bigwide_l1<2>(h1a[j], w1r, im, nc, mcur, c16, g);
-                    else if (nh == 1) mlp_bigwide_l1<1>(h1a[j], w1r, im, nc, mcur, c16, g);
+                    if (nh == 2) Front::template layer1<2>(h1a[j], w1r, im, nc, mcur, c16, g);
+                    else if (nh == 1) Front::template layer1<1>(h1a[j], w1r, im, nc, mcur, c16, g);
                 }
                 mcur = mn;
             }
@@ -413,6 +459,13 @@ mlp_bigwide_fwd_kernel(MlpStreamParams p)
         }
         if (tid == 0) dst[oB3] = db3s[0] + db3s[1];
     }
+}
+
+template <bool GRAD>
+__global__ void __launch_bounds__(kBgThreads, 1)
+mlp_bigwide_fwd_kernel(MlpStreamParams p)
+{
+    mlp_bigwide_body<MlpBigWideFrontF32, GRAD>(p);
 }
 
 // dW1[block hb][slice] += dH1^T . X over the 32 documents of a tile, 16-feature steps c0 .. c0 + CN - 1: A = a[hb][s]
@@ -576,15 +629,15 @@ struct MlpBigWidePlan {
     size_t offB, offH, bytes;        // workspace: [gr partial dW1 | g1 small vectors | dH1 rows]
 };
 
-inline MlpBigWidePlan mlp_bigwide_plan(long long rows, int F, int H1, int H2)
+// nsl column slices of nts 16-feature steps each (the front's choice)
+inline MlpBigWidePlan mlp_bigwide_plan_of(long long rows, int F, int H1, int H2, int nsl, int nts)
 {
     MlpBigWidePlan s;
     s.tiles = (int)((rows + kMsRows - 1) / kMsRows);
     const long long wgs = device_cu_count();        // one workgroup per CU
     s.g1 = (int)(s.tiles < wgs ? s.tiles : wgs);
-    const int NT = (F + 15) >> 4;
-    s.nsl = (NT + 10) / 11;
-    s.nts = (NT + s.nsl - 1) / s.nsl <= 8 ? 8 : 11;
+    s.nsl = nsl;
+    s.nts = nts;
     const long long per = wgs / s.nsl > 0 ? wgs / s.nsl : 1;
     s.gr = (int)(s.tiles < per ? s.tiles : per);
     s.pitchA = H1 * F;               // (F % 4 == 0: rows of 16 bytes)
@@ -599,6 +652,12 @@ inline MlpBigWidePlan mlp_bigwide_plan(long long rows, int F, int H1, int H2)
 struct MlpBigWideHost {
     static constexpr int kAlign = 4, kMaxF = kBwMaxF, kMaxH1 = kBgH1, kMaxH2 = kBgH2;
     static int grid(long long rows, int, bool) { return mlp_stream_grid(rows, 1); }
+    static MlpBigWidePlan plan(long long rows, int F, int H1, int H2)
+    {
+        const int NT = (F + 15) >> 4;
+        const int nsl = (NT + 10) / 11;
+        return mlp_bigwide_plan_of(rows, F, H1, H2, nsl, (NT + nsl - 1) / nsl <= 8 ? 8 : 11);
+    }
     template <bool GRAD>
     static int launch(const MlpStreamParams &p, int grid, hipStream_t stream)
     {
@@ -608,7 +667,7 @@ struct MlpBigWideHost {
         return (int)hipGetLastError();
     }
     template <int NTS>
-    static int launch_dw1(const MlpStreamParams &p, const MlpBigWidePlan &s, hipStream_t stream)
+    static int launch_dw1_nts(const MlpStreamParams &p, const MlpBigWidePlan &s, hipStream_t stream)
     {
         const size_t lds = mlp_bigwide_dw1_lds_bytes(NTS);
         LTR_ENSURE_LDS((mlp_bigwide_dw1_kernel<NTS>), lds);
@@ -616,7 +675,51 @@ struct MlpBigWideHost {
                            s.nsl);
         return (int)hipGetLastError();
     }
+    static int launch_dw1(const MlpStreamParams &p, const MlpBigWidePlan &s, hipStream_t stream)
+    {
+        return s.nts == 8 ? launch_dw1_nts<8>(p, s, stream) : launch_dw1_nts<11>(p, s, stream);
+    }
 };
+
+// The gradient entry points of a front.  Host: kAlign, kMaxF, kMaxH1, kMaxH2, plan(rows, F, H1, H2), launch<true>(p, grid,
+// stream), launch_dw1(p, plan, stream)
+template <class Host>
+size_t mlp_bigwide_grad_workspace_bytes(int B, int L, int F, int H1, int H2)
+{
+    if (B <= 0 || mlp_stream_bad_shape(B, L, F, H1, H2, Host::kAlign, Host::kMaxF, Host::kMaxH1, Host::kMaxH2)) return 0;
+    return Host::plan((long long)B * L, F, H1, H2).bytes;
+}
+
+template <class Host>
+int mlp_bigwide_grad(const void *X, const float *W1, const float *b1, const float *W2, const float *b2, const float *W3,
+                     const float *b3, const float *g, const int64_t *n, int B, int L, int F, int H1, int H2,
+                     float *grads, void *workspace, size_t workspace_bytes, void *stream)
+{
+    LTR_CLEAR_STALE_ERROR();
+    if (mlp_stream_bad_shape(B, L, F, H1, H2, Host::kAlign, Host::kMaxF, Host::kMaxH1, Host::kMaxH2)) return LTR_ERR_SHAPE;
+    if (!W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !grads) return LTR_ERR_NULL;
+    const int P = mlp_param_count(F, H1, H2);
+    hipStream_t st = (hipStream_t)stream;
+    if (B == 0) return mlp_reduce_launch(nullptr, 0, P, grads, nullptr, 0, nullptr, st);     // zero gradients
+    if (!X || !g) return LTR_ERR_NULL;
+    const MlpBigWidePlan s = Host::plan((long long)B * L, F, H1, H2);
+    if (!workspace || workspace_bytes < s.bytes) return LTR_ERR_WORKSPACE;
+    unsigned char *ws = static_cast<unsigned char *>(workspace);
+    MlpStreamParams p = mlp_stream_params(X, W1, b1, W2, b2, W3, b3, g, n, B, L, F, H1, H2);
+    p.dH1 = reinterpret_cast<float *>(ws + s.offH);
+    // forward and back down to dH1; the small sums, one partial vector per workgroup
+    p.part = reinterpret_cast<float *>(ws + s.offB); p.pitch = s.pitchB;
+    int rc = Host::template launch<true>(p, s.g1, st);
+    if (rc != 0) return rc;
+    // dW1, one partial matrix per row range
+    p.part = reinterpret_cast<float *>(ws); p.pitch = s.pitchA;
+    rc = Host::launch_dw1(p, s, st);
+    if (rc != 0) return rc;
+    // grads = [dW1 | the small sums]: both sums in a fixed order (H1 * F floats are whole 16-byte units)
+    rc = mlp_reduce_launch(ws, s.gr, s.pitchA, grads, nullptr, 0, nullptr, st);
+    if (rc != 0) return rc;
+    return mlp_reduce_launch(ws + s.offB, s.g1, s.psmall, grads + s.pitchA, nullptr, 0, nullptr, st);
+}
 
 #ifdef __HIP_DEVICE_COMPILE__
 #pragma clang attribute pop
@@ -633,38 +736,15 @@ int ltr_mlp_bigwide_scores_f32(const float *X, const float *W1, const float *b1,
 
 size_t ltr_mlp_bigwide_grad_workspace_bytes(int B, int L, int F, int H1, int H2)
 {
-    if (B <= 0 || mlp_stream_bad_shape(B, L, F, H1, H2, 4, kBwMaxF, kBgH1, kBgH2)) return 0;
-    return mlp_bigwide_plan((long long)B * L, F, H1, H2).bytes;
+    return mlp_bigwide_grad_workspace_bytes<MlpBigWideHost>(B, L, F, H1, H2);
 }
 
 int ltr_mlp_bigwide_grad_f32(const float *X, const float *W1, const float *b1, const float *W2, const float *b2,
                              const float *W3, const float *b3, const float *g, const int64_t *n, int B, int L, int F,
                              int H1, int H2, float *grads, void *workspace, size_t workspace_bytes, void *stream)
 {
-    LTR_CLEAR_STALE_ERROR();
-    if (mlp_stream_bad_shape(B, L, F, H1, H2, 4, kBwMaxF, kBgH1, kBgH2)) return LTR_ERR_SHAPE;
-    if (!W1 || !b1 || !W2 || !b2 || !W3 || !b3 || !grads) return LTR_ERR_NULL;
-    const int P = mlp_param_count(F, H1, H2);
-    hipStream_t st = (hipStream_t)stream;
-    if (B == 0) return mlp_reduce_launch(nullptr, 0, P, grads, nullptr, 0, nullptr, st);     // zero gradients
-    if (!X || !g) return LTR_ERR_NULL;
-    const MlpBigWidePlan s = mlp_bigwide_plan((long long)B * L, F, H1, H2);
-    if (!workspace || workspace_bytes < s.bytes) return LTR_ERR_WORKSPACE;
-    unsigned char *ws = static_cast<unsigned char *>(workspace);
-    MlpStreamParams p = mlp_stream_params(X, W1, b1, W2, b2, W3, b3, g, n, B, L, F, H1, H2);
-    p.dH1 = reinterpret_cast<float *>(ws + s.offH);
-    // forward and back down to dH1; the small sums, one partial vector per workgroup
-    p.part = reinterpret_cast<float *>(ws + s.offB); p.pitch = s.pitchB;
-    int rc = MlpBigWideHost::launch<true>(p, s.g1, st);
-    if (rc != 0) return rc;
-    // dW1, one partial matrix per row range
-    p.part = reinterpret_cast<float *>(ws); p.pitch = s.pitchA;
-    rc = s.nts == 8 ? MlpBigWideHost::launch_dw1<8>(p, s, st) : MlpBigWideHost::launch_dw1<11>(p, s, st);
-    if (rc != 0) return rc;
-    // grads = [dW1 | the small sums]: both sums in a fixed order (H1 * F floats are whole 16-byte units)
-    rc = mlp_reduce_launch(ws, s.gr, s.pitchA, grads, nullptr, 0, nullptr, st);
-    if (rc != 0) return rc;
-    return mlp_reduce_launch(ws + s.offB, s.g1, s.psmall, grads + s.pitchA, nullptr, 0, nullptr, st);
+    return mlp_bigwide_grad<MlpBigWideHost>(X, W1, b1, W2, b2, W3, b3, g, n, B, L, F, H1, H2, grads, workspace,
+                                            workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -905,6 +905,7 @@ MLP_BIG_MAX_FEATURES = 144       # the wide-hidden kernels of include/ltr_mlp_bi
 MLP_BIG_MAX_HIDDEN = (256, 64)
 MLP_BIG_BF16_MAX_FEATURES = 160  # the wide-hidden kernels on a bf16 batch, include/ltr_mlp_bigbf16.h
 MLP_BIG_WIDE_MAX_FEATURES = 704  # the K-streamed wide-hidden kernels of include/ltr_mlp_bigwide.h (Istella: 220, Yahoo: 700)
+MLP_BIG_WIDE_BF16_MAX_FEATURES = 704  # the same on a bf16 batch, include/ltr_mlp_bigwidebf16.h (Istella: 224, Yahoo: 704)
 
 
 def mlp_max_list_len(F):
@@ -956,6 +957,11 @@ _MLP_BIG_WIDE = _MLPFamily("big hidden wide", torch.float32, 4, MLP_BIG_MAX_FEAT
                            "ltr_mlp_bigwide_scores_f32", "ltr_mlp_bigwide_grad_f32", "ltr_mlp_bigwide_grad_workspace_bytes",
                            "the wide-hidden wide-row MLP kernels take %d < F <= %d with F %% 4 == 0"
                            % (MLP_BIG_MAX_FEATURES, MLP_BIG_WIDE_MAX_FEATURES), MLP_BIG_MAX_HIDDEN)
+_MLP_BIG_WIDE_BF16 = _MLPFamily("big hidden wide bf16", torch.bfloat16, 8, MLP_BIG_BF16_MAX_FEATURES,              # include/ltr_mlp_bigwidebf16.h
+                                MLP_BIG_WIDE_BF16_MAX_FEATURES, "ltr_mlp_bigwidebf16_scores", "ltr_mlp_bigwidebf16_grad",
+                                "ltr_mlp_bigwidebf16_grad_workspace_bytes",
+                                "the wide-hidden wide-row bf16 MLP kernels take %d < F <= %d (after zero-padding to a multiple "
+                                "of 8)" % (MLP_BIG_BF16_MAX_FEATURES, MLP_BIG_WIDE_BF16_MAX_FEATURES), MLP_BIG_MAX_HIDDEN)
 _mlp_rows_network, _mlp_wide_network, _mlp_bf16_network = _MLP_ROWS.takes, _MLP_WIDE.takes, _MLP_BF16.takes
 
 
@@ -1201,6 +1207,25 @@ def mlp_bigwide_grad(xs, params, grad_scores, n=None, out=None):
     return _mlp_family_grad(xs, params, grad_scores, n, out, _MLP_BIG_WIDE)
 
 
+def mlp_bigwide_scores_bf16(xs, params, n=None):
+    """:func:`mlp_big_scores_bf16` for rows wider than 160 features, up to 704 (ltr_mlp_bigwidebf16_scores: the eight-wave
+    workgroup of :func:`mlp_bigwide_scores` with the feature dimension streamed in chunks of 128 through the bf16 MFMA;
+    any list length; no autograd).  The same numerics as :func:`mlp_scores_bf16`: the scores of the network with
+    ``W1.bfloat16()``, accumulated in fp32, fp32 behind the first layer.  Feature counts that are not a multiple of 8
+    are zero-padded with one copy (Istella: 220 -> 224, Yahoo: 699 -> 704); 168 to 704 features after that, hidden layers
+    up to (256, 64), small networks included.  Other networks raise ValueError."""
+    return _mlp_family_scores(xs, params, n, _MLP_BIG_WIDE_BF16)
+
+
+def mlp_bigwide_grad_bf16(xs, params, grad_scores, n=None, out=None):
+    """:func:`mlp_big_grad_bf16` for rows wider than 160 features, up to 704 (ltr_mlp_bigwidebf16_grad: the forward and
+    the backward down to d loss / d hidden-1, then dW1 by a second bf16-MFMA kernel over column slices): the fp32
+    gradients of ``sum grad_scores * mlp_bigwide_scores_bf16(xs, params)``, ``dW1`` with respect to the rounded W1.  Same
+    arguments and the same ``(dW1, db1, dW2, db2, dW3, db3)`` views of one flat buffer; with a feature count that is not
+    a multiple of 8, `out` holds the padded network's parameters and ``dW1`` is the view of its first F columns."""
+    return _mlp_family_grad(xs, params, grad_scores, n, out, _MLP_BIG_WIDE_BF16)
+
+
 def mlp_big_scores_bf16(xs, params, n=None):
     """:func:`mlp_scores_bf16` for hidden layers up to (256, 64) (ltr_mlp_bigbf16_scores: the eight-wave workgroup of
     :func:`mlp_big_scores` with the first layer on the bf16 MFMA; any list length; no autograd).  The same numerics as
@@ -1289,9 +1314,10 @@ _WIDE_BF16 = "wide bf16"
 _BIG = "big hidden"
 _BIG_BF16 = "big hidden bf16"
 _BIG_WIDE = "big hidden wide"
+_BIG_WIDE_BF16 = "big hidden wide bf16"
 _ROUTE_FAMILY = {_FUSED: _MLP_ROWS, _PER_QUERY: _MLP_ROWS, _ROWS: _MLP_ROWS, _WIDE: _MLP_WIDE, _BF16: _MLP_BF16,
                  _FUSED_BF16: _MLP_BF16, _WIDE_BF16: _MLP_WIDE_BF16, _BIG: _MLP_BIG, _BIG_BF16: _MLP_BIG_BF16,
-                 _BIG_WIDE: _MLP_BIG_WIDE}
+                 _BIG_WIDE: _MLP_BIG_WIDE, _BIG_WIDE_BF16: _MLP_BIG_WIDE_BF16}
 MLP_STEP_BF16_MAX_LIST_LEN = 128
 MLP_STEP_BF16_MAX_FEATURES = 160
 
@@ -1309,7 +1335,8 @@ def _f4(F):
 
 
 def _mlp_route(caller, dtype, dim, is_cuda, requires_grad, grad_enabled, autocast, L, F, H1, H2, kind=None, plan=True,
-               fuse_bf16=False, wide_bf16=False, big_hidden=False, big_hidden_bf16=False, big_hidden_wide=False):
+               fuse_bf16=False, wide_bf16=False, big_hidden=False, big_hidden_bf16=False, big_hidden_wide=False,
+               big_hidden_wide_bf16=False):
     """Which kernels compute ``mlp(xs)`` (and, for a caller with a loss `kind`, the step): plain values in, one of
     _FUSED (the one-launch step, ltr_mlp_pairwise_f32 / ltr_mlp_listwise_f32 / ltr_mlp_lambdarank_f32), _PER_QUERY (ltr_mlp_scores_f32), _ROWS,
     _WIDE, _BF16 (the three families) or _TORCH out -- the three ``nn.Linear`` layers in a module, ValueError in a
@@ -1337,6 +1364,10 @@ def _mlp_route(caller, dtype, dim, is_cuda, requires_grad, grad_enabled, autocas
     fp32 batch on the device that needs no gradient itself, outside autocast, with H1 > 64 or H2 > 16 inside (256, 64)
     -- and 144 < F <= 704 (the modules': after padding to 4), at every list length.  `big_hidden` alone keeps its answers
     past 144 features, and this flag alone keeps the answers at 144 and below.
+    `big_hidden_wide_bf16`: the caller's opt-in to _BIG_WIDE_BF16 (ltr_mlp_bigwidebf16_*, the same hidden layers on bf16
+    rows of 168 to 704 features), returned only where the answer is otherwise _BF16 -- whose ValueError it replaces --
+    with H1 > 64 or H2 > 16 inside (256, 64) and more than 160, at most 704 features after padding to 8.  No other flag
+    answers there, and this flag answers nowhere else.
     """
     if dim != 3 or not is_cuda or L <= 0:
         return _TORCH
@@ -1351,6 +1382,9 @@ def _mlp_route(caller, dtype, dim, is_cuda, requires_grad, grad_enabled, autocas
         if (big_hidden_bf16 and (H1 > MLP_MAX_HIDDEN[0] or H2 > MLP_MAX_HIDDEN[1])
                 and _MLP_BIG_BF16.takes((F + 7) & ~7, H1, H2)):
             return _BIG_BF16                             # opt-in: hidden layers up to (256, 64), the three pieces
+        if (big_hidden_wide_bf16 and (H1 > MLP_MAX_HIDDEN[0] or H2 > MLP_MAX_HIDDEN[1])
+                and _MLP_BIG_WIDE_BF16.takes((F + 7) & ~7, H1, H2)):
+            return _BIG_WIDE_BF16                        # opt-in: the same on 168 .. 704 features, K-streamed
         return _BF16                                     # at every list length: the default fused kernels are fp32-only
     if module:
         F = _f4(F)                                       # (everything below computes in fp32)
@@ -1376,14 +1410,14 @@ def _mlp_route(caller, dtype, dim, is_cuda, requires_grad, grad_enabled, autocas
 
 
 def _mlp_route_of(caller, xs, F, H1, H2, kind=None, plan=True, fuse_bf16=False, wide_bf16=False, big_hidden=False,
-                  big_hidden_bf16=False, big_hidden_wide=False):
+                  big_hidden_bf16=False, big_hidden_wide=False, big_hidden_wide_bf16=False):
     """`_mlp_route` on a batch: its dtype, shape and flags, the grad mode and the autocast state (F None: the batch's)."""
     if not torch.is_tensor(xs) or xs.dim() != 3:
         return _TORCH
     _, L, Fx = xs.shape
     return _mlp_route(caller, xs.dtype, 3, xs.is_cuda, xs.requires_grad, torch.is_grad_enabled(),
                       torch.is_autocast_enabled(), L, Fx if F is None else F, H1, H2, kind, plan, fuse_bf16, wide_bf16,
-                      big_hidden, big_hidden_bf16, big_hidden_wide)
+                      big_hidden, big_hidden_bf16, big_hidden_wide, big_hidden_wide_bf16)
 
 
 def _mlp_step_pieces(X, flat_params, H1, H2, relevance, n, kind, sigma, grad_out, return_scores, return_loss_sum, out,
@@ -1412,7 +1446,7 @@ def _mlp_step_pieces(X, flat_params, H1, H2, relevance, n, kind, sigma, grad_out
 
 def mlp_loss_step(xs, params, relevance, n, loss="hinge", grad_out=None, return_scores=False,
                   return_loss_sum=False, out=None, fuse_bf16=False, wide_bf16=False, big_hidden=False,
-                  big_hidden_bf16=False, big_hidden_wide=False):
+                  big_hidden_bf16=False, big_hidden_wide=False, big_hidden_wide_bf16=False):
     """One fused forward+backward step of ``loss_fn(mlp(xs), relevance, n)`` without autograd.
 
     Args:
@@ -1433,6 +1467,10 @@ def mlp_loss_step(xs, params, relevance, n, loss="hinge", grad_out=None, return_
         big_hidden_wide: True: an fp32 batch of 148 to 704 features (F % 4 == 0) under a network with H1 > 64 or H2 > 16,
             up to (256, 64), which raises ValueError otherwise, runs the three pieces on the K-streamed wide-hidden
             kernels (:func:`mlp_bigwide_scores`, :func:`mlp_bigwide_grad`) at every list length.  Nothing else changes.
+        big_hidden_wide_bf16: True: a bf16 batch of 168 to 704 features (F % 8 == 0) under a network with H1 > 64 or
+            H2 > 16, up to (256, 64), which raises ValueError otherwise, runs the three pieces on the K-streamed wide-hidden
+            bf16 kernels (:func:`mlp_bigwide_scores_bf16`, :func:`mlp_bigwide_grad_bf16`) at every list length.  Nothing
+            else changes.
         loss: a pairwise kind name or module, or a listwise loss -- ``"listnet"`` / ``"softmax"``, ``"listmle"``,
             ``ListwiseSoftmaxLoss()``, ``ListMLELoss(k)`` (ltr_mlp_listwise_f32; ListMLE draws one tie seed per call,
             as ``ListMLELoss`` does, and ``utils.tie_breaking("index")`` turns it off).
@@ -1456,12 +1494,12 @@ def mlp_loss_step(xs, params, relevance, n, loss="hinge", grad_out=None, return_
         raise TypeError("mlp_loss_step has no LambdaRank slot: take mlp_lambdarank_step (the module: "
                         "FusedMLPLambdaRankLoss), or the Linear scorer: FusedLinearLoss, linear_loss_step, LinearScorer")
     return _mlp_step(xs, params, relevance, n, kind, sigma, grad_out, return_scores, return_loss_sum, out, fuse_bf16,
-                     wide_bf16, big_hidden, big_hidden_bf16, big_hidden_wide)
+                     wide_bf16, big_hidden, big_hidden_bf16, big_hidden_wide, big_hidden_wide_bf16)
 
 
 def mlp_lambdarank_step(xs, params, relevance, n, sigma=1.0, k=None, grad_out=None, return_scores=False,
                         return_loss_sum=False, out=None, fuse_bf16=False, wide_bf16=False, big_hidden=False,
-                        big_hidden_bf16=False, big_hidden_wide=False):
+                        big_hidden_bf16=False, big_hidden_wide=False, big_hidden_wide_bf16=False):
     """:func:`mlp_loss_step` for LambdaRank (:class:`pytorchltr_amd.loss.LambdaRankLoss` ``(sigma, k)``): one fused
     forward+backward step of ``LambdaRankLoss(sigma, k)(mlp(xs), relevance, n)`` without autograd, by
     ``ltr_mlp_lambdarank_f32`` (include/ltr_mlp_lambdarank.h) -- the NDCG@k swap weights and the top-k pair pass in the
@@ -1473,12 +1511,13 @@ def mlp_lambdarank_step(xs, params, relevance, n, sigma=1.0, k=None, grad_out=No
     ``wide_bf16=True``: a bf16 batch of 232 to 704 features runs the pieces on the wide bf16 kernels, as there;
     ``big_hidden=True``: hidden layers past (64, 16), up to (256, 64), run the pieces on the wide-hidden kernels, as there;
     ``big_hidden_bf16=True``: the same hidden layers on a bf16 batch of at most 160 features, as there;
-    ``big_hidden_wide=True``: the same hidden layers on an fp32 batch of 148 to 704 features, as there."""
+    ``big_hidden_wide=True``: the same hidden layers on an fp32 batch of 148 to 704 features, as there;
+    ``big_hidden_wide_bf16=True``: the same hidden layers on a bf16 batch of 168 to 704 features, as there."""
     from .loss import pairwise_lambda as _pl
     k = _pl.LambdaRankLoss(sigma, k).k                      # (its check of k)
     return _mlp_step(xs, params, relevance, n, _ListwiseKind(_C.LISTWISE_LAMBDARANK, k), float(sigma), grad_out,
                      return_scores, return_loss_sum, out, fuse_bf16, wide_bf16, big_hidden, big_hidden_bf16,
-                     big_hidden_wide)
+                     big_hidden_wide, big_hidden_wide_bf16)
 
 
 def _mlp_listwise_plan(kind, B, L, F, H1, H2):
@@ -1508,14 +1547,15 @@ def _mlp_family_call(kind, sigma, L, dev):
 
 
 def _mlp_step(xs, params, relevance, n, kind, sigma, grad_out, return_scores, return_loss_sum, out, fuse_bf16=False,
-              wide_bf16=False, big_hidden=False, big_hidden_bf16=False, big_hidden_wide=False):
+              wide_bf16=False, big_hidden=False, big_hidden_bf16=False, big_hidden_wide=False,
+              big_hidden_wide_bf16=False):
     """The step behind mlp_loss_step, mlp_lambdarank_step and the loss modules (`_MLPLossFunction`), on a resolved
     (kind, sigma): a pairwise kind, or a :class:`_ListwiseKind` of ListNet, ListMLE or LambdaRank."""
     listwise = isinstance(kind, _ListwiseKind)
     F, H1, H2 = params[0].shape[-1], params[0].shape[0], params[2].shape[0]    # (the network's: W1 is (H1, F))
     plan = not listwise or (xs.dim() == 3 and _mlp_listwise_plan(kind, xs.shape[0], xs.shape[1], F, H1, H2))
     route = _mlp_route_of("step", xs, F, H1, H2, kind, plan, fuse_bf16, wide_bf16, big_hidden, big_hidden_bf16,
-                          big_hidden_wide)
+                          big_hidden_wide, big_hidden_wide_bf16)
     if route is _TORCH:
         _mlp_not_taken(xs, params, True)
     X, flat_params, H1, H2, _, family = _mlp_prepare(xs, params, _ROUTE_FAMILY[route], pad=False)
@@ -1645,6 +1685,7 @@ class _MLPLayers(torch.nn.Module):
     big_hidden = False       # plain attribute, the opt-in: hidden layers past (64, 16), up to (256, 64), take ltr_mlp_big_*
     big_hidden_bf16 = False  # plain attribute, the opt-in: the same hidden layers on a bf16 batch take ltr_mlp_bigbf16_*
     big_hidden_wide = False  # plain attribute, the opt-in: the same hidden layers on 148 .. 704 fp32 features take ltr_mlp_bigwide_*
+    big_hidden_wide_bf16 = False  # plain attribute, the opt-in: the same on 168 .. 704 bf16 features take ltr_mlp_bigwidebf16_*
 
     def __init__(self, in_features, hidden=(50, 10)):
         super().__init__()
@@ -1681,7 +1722,7 @@ class _FusedMLPBase(_MLPLayers):
     fuse_bf16 = False        # plain attribute, the opt-in: a bf16 batch on mlp_step_bf16_supported takes ltr_mlp_step_bf16
 
     def __init__(self, in_features, loss, hidden, reduction, fuse_bf16=False, wide_bf16=False, big_hidden=False,
-                 big_hidden_bf16=False, big_hidden_wide=False):
+                 big_hidden_bf16=False, big_hidden_wide=False, big_hidden_wide_bf16=False):
         if reduction not in ("mean", "sum"):
             raise ValueError("reduction must be 'mean' or 'sum'")
         super().__init__(in_features, hidden)
@@ -1696,6 +1737,8 @@ class _FusedMLPBase(_MLPLayers):
             self.big_hidden_bf16 = True
         if big_hidden_wide:
             self.big_hidden_wide = True
+        if big_hidden_wide_bf16:
+            self.big_hidden_wide_bf16 = True
         self.kind, self.sigma = self._resolve(loss)
         self.last_losses = None
 
@@ -1716,10 +1759,14 @@ class _FusedMLPBase(_MLPLayers):
         ``model.big_hidden_bf16`` set, a bf16 batch of at most 160 features (after padding) under such hidden layers runs
         the wide-hidden bf16 kernels (ltr_mlp_bigbf16_*, :func:`mlp_big_scores_bf16`) instead of raising; with
         ``model.big_hidden_wide`` set, an fp32 batch of 148 to 704 features under such hidden layers runs the K-streamed
-        wide-hidden kernels (ltr_mlp_bigwide_*, :func:`mlp_bigwide_scores`) instead of the torch layers."""
+        wide-hidden kernels (ltr_mlp_bigwide_*, :func:`mlp_bigwide_scores`) instead of the torch layers; with
+        ``model.big_hidden_wide_bf16`` set, a bf16 batch of 168 to 704 features (after padding) under such hidden layers
+        runs the K-streamed wide-hidden bf16 kernels (ltr_mlp_bigwidebf16_*, :func:`mlp_bigwide_scores_bf16`) instead of
+        raising."""
         return self._score(xs, n, _mlp_route_of("score", xs, None, *self._hidden(), wide_bf16=self.wide_bf16,
                                                 big_hidden=self.big_hidden, big_hidden_bf16=self.big_hidden_bf16,
-                                                big_hidden_wide=self.big_hidden_wide))
+                                                big_hidden_wide=self.big_hidden_wide,
+                                                big_hidden_wide_bf16=self.big_hidden_wide_bf16))
 
     def _plan(self, B, L, F4, H1, H2):
         """The `plan` of `_mlp_route`: the pairwise fused step has none beyond :func:`mlp_supported`."""
@@ -1734,7 +1781,7 @@ class _FusedMLPBase(_MLPLayers):
         H1, H2 = self._hidden()
         route = _mlp_route_of("loss", xs, F, H1, H2, self.kind, self._plan(B, L, _f4(F), H1, H2),
                               self.fuse_bf16, self.wide_bf16, self.big_hidden, self.big_hidden_bf16,
-                              self.big_hidden_wide)
+                              self.big_hidden_wide, self.big_hidden_wide_bf16)
         if route is _FUSED or route is _FUSED_BF16:
             total, per_query = _MLPLossFunction.apply(
                 xs, relevance, n, (self.kind, self.sigma) + ((True,) if route is _FUSED_BF16 else ()),
@@ -1774,14 +1821,17 @@ class FusedMLPLoss(_FusedMLPBase):
     them on the wide-hidden bf16 kernels (ltr_mlp_bigbf16_*, :func:`mlp_big_scores_bf16`) instead of raising
     ValueError; with ``big_hidden_wide=True`` (``model.big_hidden_wide``) an fp32 batch of 148 to 704 features (Istella:
     220, Yahoo: 699 -> 700) under such hidden layers runs them on the K-streamed wide-hidden kernels (ltr_mlp_bigwide_*,
-    :func:`mlp_bigwide_scores`) instead of the torch layers.  ``score(xs)`` evaluates the
+    :func:`mlp_bigwide_scores`) instead of the torch layers; with ``big_hidden_wide_bf16=True``
+    (``model.big_hidden_wide_bf16``) a bf16 batch of 168 to 704 features after padding to 8 (Istella: 224, Yahoo: 704)
+    under such hidden layers runs them on the K-streamed wide-hidden bf16 kernels (ltr_mlp_bigwidebf16_*,
+    :func:`mlp_bigwide_scores_bf16`) instead of raising ValueError.  ``score(xs)`` evaluates the
     network alone (for the metrics).  The seven pairwise losses; the listwise ones: :class:`FusedMLPListwiseLoss`.
     """
 
     def __init__(self, in_features, loss="hinge", hidden=(50, 10), reduction="mean", fuse_bf16=False, wide_bf16=False,
-                 big_hidden=False, big_hidden_bf16=False, big_hidden_wide=False):
+                 big_hidden=False, big_hidden_bf16=False, big_hidden_wide=False, big_hidden_wide_bf16=False):
         super().__init__(in_features, loss, hidden, reduction, fuse_bf16, wide_bf16, big_hidden, big_hidden_bf16,
-                         big_hidden_wide)
+                         big_hidden_wide, big_hidden_wide_bf16)
 
     _resolve = staticmethod(_resolve_pairwise_loss)
 
@@ -1867,11 +1917,13 @@ class MLPScorer(_MLPLayers):
     ``big_hidden_bf16=True`` (``scorer.big_hidden_bf16``): a bf16 batch of at most 160 features after padding to 8 under
     hidden layers past (64, 16), up to (256, 64), runs the wide-hidden bf16 kernels (ltr_mlp_bigbf16_*) instead of raising.
     ``big_hidden_wide=True`` (``scorer.big_hidden_wide``): an fp32 batch of 148 to 704 features after padding to 4 under
-    such hidden layers runs the K-streamed wide-hidden kernels (ltr_mlp_bigwide_*) instead of the torch layers.  CPU
+    such hidden layers runs the K-streamed wide-hidden kernels (ltr_mlp_bigwide_*) instead of the torch layers.
+    ``big_hidden_wide_bf16=True`` (``scorer.big_hidden_wide_bf16``): a bf16 batch of 168 to 704 features after padding to
+    8 under such hidden layers runs the K-streamed wide-hidden bf16 kernels (ltr_mlp_bigwidebf16_*) instead of raising.  CPU
     tensors are refused: there is no CPU fallback."""
 
     def __init__(self, in_features, hidden=(50, 10), wide_bf16=False, big_hidden=False, big_hidden_bf16=False,
-                 big_hidden_wide=False):
+                 big_hidden_wide=False, big_hidden_wide_bf16=False):
         super().__init__(in_features, hidden)
         if wide_bf16:
             self.wide_bf16 = True
@@ -1881,12 +1933,15 @@ class MLPScorer(_MLPLayers):
             self.big_hidden_bf16 = True
         if big_hidden_wide:
             self.big_hidden_wide = True
+        if big_hidden_wide_bf16:
+            self.big_hidden_wide_bf16 = True
 
     def forward(self, xs, n=None):
         _C.require_device(xs, "xs")
         return self._score(xs, n, _mlp_route_of("scorer", xs, None, *self._hidden(), wide_bf16=self.wide_bf16,
                                                 big_hidden=self.big_hidden, big_hidden_bf16=self.big_hidden_bf16,
-                                                big_hidden_wide=self.big_hidden_wide))
+                                                big_hidden_wide=self.big_hidden_wide,
+                                                big_hidden_wide_bf16=self.big_hidden_wide_bf16))
 
 
 # ---- MLPTrainer: the fused MLP step with the optimizer update inside the reduction launch (include/ltr_mlp_train.h) ----
@@ -2161,7 +2216,7 @@ class MLPTrainer:
         listwise = isinstance(kind, _ListwiseKind)
         plan = not listwise or _mlp_listwise_plan(kind, B, L, Fp, H1, H2)
         route = _mlp_route_of("step", xp, Fp, H1, H2, kind, plan, model.fuse_bf16, model.wide_bf16, model.big_hidden,
-                              model.big_hidden_bf16, model.big_hidden_wide)
+                              model.big_hidden_bf16, model.big_hidden_wide, model.big_hidden_wide_bf16)
         if route is _TORCH and _mlp_route_of("loss", xp, Fp, H1, H2, kind, plan) is _WIDE:
             route = _WIDE                                   # (the module's wide rows: the functions have no such route)
         step_params = (w1p,) + tuple(params[1:])
