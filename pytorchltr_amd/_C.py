@@ -1,6 +1,6 @@
 """ctypes binding of the C ABI in ``include/ltr_hip.h``, ``include/ltr_eval.h``, ``include/ltr_listwise.h``,
 ``include/ltr_lambdarank.h``, ``include/ltr_longpair.h``, ``include/ltr_lambdarank_long.h``, ``include/ltr_mlp_rows.h``, ``include/ltr_mlp_big.h``, ``include/ltr_mlp_bigbf16.h``, ``include/ltr_mlp_bigwide.h``, ``include/ltr_mlp_bigwidebf16.h``, ``include/ltr_mlp_bf16.h``, ``include/ltr_mlp_step_bf16.h``, ``include/ltr_mlp_wide.h``, ``include/ltr_mlp_widebf16.h``,
-``include/ltr_linear_bf16.h``, ``include/ltr_mlp_train.h`` and ``include/ltr_sched.h`` (pytorchltr_amd/csrc/libltr_hip.so).
+``include/ltr_linear_bf16.h``, ``include/ltr_bf16_general.h``, ``include/ltr_mlp_train.h`` and ``include/ltr_sched.h`` (pytorchltr_amd/csrc/libltr_hip.so).
 
 PyTorch supplies device memory and the current HIP stream; every call here hands raw device
 pointers to the library.  The library must exist -- there is deliberately no fallback.
@@ -240,6 +240,13 @@ LINEAR_BF16_SIGNATURES = {
     "ltr_collate_pad_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
 }
 
+# name -> (restype, argtypes); mirrors include/ltr_bf16_general.h (the general fused Linear step on a bf16 batch: any list of
+# up to max_list_len() documents, rows of up to 1024 features; the prototypes of ltr_linear_bf16_plan / _partials_bf16)
+BF16_GENERAL_SIGNATURES = {
+    "ltr_bf16_general_linear_plan": LINEAR_BF16_SIGNATURES["ltr_linear_bf16_plan"],
+    "ltr_bf16_general_linear_partials": LINEAR_BF16_SIGNATURES["ltr_linear_partials_bf16"],
+}
+
 # name -> (restype, argtypes); mirrors include/ltr_mlp_wide.h (the same scorer on rows of up to 704 features)
 MLP_WIDE_SIGNATURES = {
     "ltr_mlp_wide_scores_f32": (_i, [_vp] * 8 + [_i] * 5 + [_vp, _vp]),
@@ -318,7 +325,7 @@ def lib():
                                           + list(MLP_BIGWIDE_SIGNATURES.items()) + list(MLP_BIGWIDEBF16_SIGNATURES.items())
                                           + list(MLP_BF16_SIGNATURES.items()) + list(LINEAR_BF16_SIGNATURES.items())
                                           + list(MLP_STEP_BF16_SIGNATURES.items()) + list(MLP_WIDEBF16_SIGNATURES.items())
-                                          + list(SCHED_SIGNATURES.items())):
+                                          + list(SCHED_SIGNATURES.items()) + list(BF16_GENERAL_SIGNATURES.items())):
             if name.startswith("ltr_debug_") and not hasattr(handle, name):
                 continue                     # a production build (-DLTR_NO_DEBUG_HOOKS) leaves the test hooks out
             fn = getattr(handle, name)       # AttributeError if the symbol is missing

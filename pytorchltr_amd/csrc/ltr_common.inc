@@ -1500,4 +1500,68 @@ inline bool lb_shape_bad(int B, int L, int F)
     return B < 0 || L <= 0 || F <= 0 || F % 8 != 0 || F > kLbMaxF || (long long)B * L > 0x7fffffffLL;
 }
 
+
+// ---- the general fused Linear step (one workgroup per query: scores, pair pass, dW_b with the rows read twice): its LDS
+// layout and launch shape, shared by the fp32 kernel (ltr_linear.inc) and the bf16 one (ltr_linear_bf16_general.inc) ----
+constexpr int kLinearThreads = 512;
+// LDS layout of the general fused kernel (bytes), after the query block of loss_lds_bytes():
+//   wl    float[F4]           W
+//   gfin  float[L4]           d loss[b] / d s_l
+//   dred  float[R * F4]       phase-3 cross-row reduction
+// (Ls = LDS row stride: L rounded to 4, or to 64-wide tiles for the symmetric pass; slices =
+// gradient slices: msplit, or waves per workgroup for the symmetric pass)
+__host__ __device__ inline size_t linear_lds_bytes(int kind, int Ls, int F, int slices, int R)
+{
+    const size_t L4 = (size_t)Ls;
+    const size_t F4 = (size_t)((F + 3) & ~3);
+    size_t bytes = loss_lds_bytes(kind, Ls, slices);
+    bytes = (bytes + 15) & ~(size_t)15;
+    bytes += 4 * F4 + 4 * L4 + 4 * (size_t)R * F4;
+    return (bytes + 15) & ~(size_t)15;
+}
+
+struct LinearShape { int dpt, msplit, R, threads; size_t lds; };
+
+inline bool choose_linear_shape(int kind, int B, int L, int F, int vec, LinearShape &s)
+{
+    // 512-thread workgroups; 1024 when the batch cannot even give every CU two of those; 256 once every CU has eight queries -- what
+    // bounds the launch then is the number of queries a CU has in flight (ltr_kernels.hip: choose_loss_shape).  Round 6, 512 -> 256
+    // threads, us: hinge 2048 x 300 x 64 51.6 -> 47.2, 4096 x 300 x 64 100.6 -> 88.1, 16 384 x 300 x 32 392 -> 316, 2048 x 128 x 45
+    // 26.4 -> 20.2, 65 536 x 128 x 45 751 -> 496, LambdaNDCG2 16 384 x 128 x 45 259 -> 181; at 1024 queries 29.6 -> 41.9 and
+    // 15.3 -> 16.0: not below eight per CU.  (128 threads: 65 536 x 128 x 45 439, but 4096 x 600 x 32 204 -> 259.)
+    const int cus = device_cu_count();
+    const int T = (B <= 2 * cus) ? 1024 : (B >= 8 * cus ? 256 : kLinearThreads);
+    s.threads = T;
+    const int C = F / vec;
+    const int CT = C < T ? C : T;               // column vectors per phase-3 tile
+    s.R = T / CT;
+    if (s.R > 64) s.R = 64;
+    int Ls, slices;
+    if (L <= kSymMaxLen) {
+        // symmetric pair pass: rows padded to 64-wide tiles, one gradient slice per wave
+        s.dpt = 0;
+        Ls = (L + 63) & ~63;
+        slices = T / 64;
+        s.msplit = slices;
+    } else {
+        // both-ends pass: owners = smallest power-of-two multiple of 64 covering L (capped at T)
+        int owners = 64;
+        while (owners < L && owners < T) owners *= 2;
+        s.dpt = (L > owners) ? 4 : 1;
+        s.msplit = T / owners;
+        Ls = (L + 3) & ~3;
+        slices = s.msplit;
+    }
+    s.lds = linear_lds_bytes(kind, Ls, F, slices, s.R);
+    while (s.dpt != 0 && s.lds > kLdsBudget && s.msplit > 1) {
+        s.msplit /= 2;
+        s.lds = linear_lds_bytes(kind, Ls, F, s.msplit, s.R);
+    }
+    while (s.lds > kLdsBudget && s.R > 1) {         // very wide rows: shrink the phase-3 fan-out
+        s.R /= 2;
+        s.lds = linear_lds_bytes(kind, Ls, F, s.dpt == 0 ? slices : s.msplit, s.R);
+    }
+    return s.lds <= kLdsBudget;
+}
+
 }  // namespace

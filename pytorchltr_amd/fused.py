@@ -237,9 +237,10 @@ def _linear_prepare(xs, weight, relevance, n, kind, raw=None):
     return X, r, nn, (B, L, F), Fw
 
 
-def _linear_launch(kind, sigma, X, weight, bias, r, nn, dims, Fw, want_scores=False, empty=False):
+def _linear_launch(kind, sigma, X, weight, bias, r, nn, dims, Fw, want_scores=False, empty=False, route=None):
     """The fused launch on a prepared batch: ``(loss[B], rows, scores | None)`` -- the family's partials entry point
-    (ltr_linear_partials_f32 / _bf16) for a pairwise kind, ltr_linear_listwise_partials_f32 for a listwise one (ListMLE
+    (ltr_linear_partials_f32 / _bf16) for a pairwise kind, or the one `route` names (`_LIN_PARTIALS`: the general bf16
+    step, ltr_bf16_general_linear_partials), ltr_linear_listwise_partials_f32 for a listwise one (ListMLE
     draws its tie seed here, one per launch), ltr_linear_lambdarank_partials_f32 for LambdaRank.  `rows`: the workspace,
     the (B, PF) per-query gradient rows first, which `_reduce_rows` / ltr_linear_reduce_loss_f32 sum.  An empty batch
     launches nothing unless `empty` (linear_loss_step hands it to the entry point)."""
@@ -268,7 +269,7 @@ def _linear_launch(kind, sigma, X, weight, bias, r, nn, dims, Fw, want_scores=Fa
                     kind.loss, int(kind.k or 0), X.data_ptr(), W.data_ptr(), bp, r.data_ptr(), _LABEL_CODE[r.dtype],
                     nn.data_ptr(), *_ties.tie_args(sd), B, L, F, loss.data_ptr(), sp, ws.data_ptr(), _C.stream_of(X))
             else:
-                rc = getattr(lib, _linear_family_of(X).partials)(
+                rc = getattr(lib, _LIN_PARTIALS.get(route) or _linear_family_of(X).partials)(
                     kind, float(sigma), X.data_ptr(), W.data_ptr(), bp, r.data_ptr(), _LABEL_CODE[r.dtype],
                     nn.data_ptr(), B, L, F, loss.data_ptr(), sp, ws.data_ptr(), _C.stream_of(X))
             if rc != 0:
@@ -281,7 +282,7 @@ class _LinearLossFunction(torch.autograd.Function):
     Linear(F, 1)(xs) as ONE launch; backward is the cross-query reduction of its rows (`_reduce_rows`)."""
 
     @staticmethod
-    def forward(ctx, xs, weight, bias, relevance, n, kind, sigma, want_scores):
+    def forward(ctx, xs, weight, bias, relevance, n, kind, sigma, want_scores, route=None):
         X, r, nn, dims, Fw = _linear_prepare(xs, weight, relevance, n, kind)
         B, L, F = dims
         ctx.dims = (B, F)
@@ -303,7 +304,7 @@ class _LinearLossFunction(torch.autograd.Function):
                     ctx.lazy_args = (kind, sigma)
                     return loss
             st.settle()                                      # the ordinary path reads the weights: no update may be pending
-        loss, ws, scores = _linear_launch(kind, sigma, X, weight, bias, r, nn, dims, Fw, want_scores)
+        loss, ws, scores = _linear_launch(kind, sigma, X, weight, bias, r, nn, dims, Fw, want_scores, route=route)
         ctx.save_for_backward(ws)
         if want_scores:
             ctx.mark_non_differentiable(scores)
@@ -318,7 +319,7 @@ class _LinearLossFunction(torch.autograd.Function):
             st = lz[0]
             out = st.backward(ctx, grad_loss)
             if out is not None:
-                return (None, out[0], out[1], None, None, None, None, None)
+                return (None, out[0], out[1], None, None, None, None, None, None)
             # an upstream gradient that is not one broadcast scalar (per-query weights): the rows again, the ordinary way
             # (the weights have not moved since the forward pass: no step can have been taken on this gradient)
             if lz[1] != st.gen:
@@ -331,7 +332,7 @@ class _LinearLossFunction(torch.autograd.Function):
         else:
             (ws,) = ctx.saved_tensors
         dW, db = _reduce_rows(ctx, ws, grad_loss)
-        return (None, dW, db, None, None, None, None, None)
+        return (None, dW, db, None, None, None, None, None, None)
 
 
 def _reduce_rows(ctx, ws, grad_loss):
@@ -378,6 +379,9 @@ def _loss_pieces(scores, relevance, n, kind, sigma):
 _LIN_F32, _LIN_BF16_FUSED, _LIN_LISTWISE = "f32 fused", "bf16 fused", "listwise fused"
 _LIN_F32_PIECES, _LIN_BF16_PIECES, _LIN_SCORES = "f32 pieces", "bf16 pieces", "scores"
 _LIN_PIECES = (_LIN_F32_PIECES, _LIN_BF16_PIECES)
+# opt-in (bf16_general=True): the general fused step on a bf16 batch off the plan of its register tile
+_LIN_BF16_GENERAL = "bf16 general"
+_LIN_PARTIALS = {_LIN_BF16_GENERAL: "ltr_bf16_general_linear_partials"}     # routes with a partials entry point of their own
 _listwise_plan_cache = {}
 _pieces_cache = {}
 _bf16_plan_cache = {}
@@ -410,6 +414,12 @@ def _linear_bf16_plan(kind, B, L, F8):
     if v is None:
         v = _bf16_plan_cache[key] = _C.lib().ltr_linear_bf16_plan(int(kind), B, L, F8) == _C.PLAN_REGISTER_TILE
     return v
+
+
+def _bf16_general_plan(kind, B, L, F8):
+    """True where ltr_bf16_general_linear_partials takes the shape (ltr_bf16_general_linear_plan; F8: the row width in
+    memory).  Not cached: the answer follows the current device's CU count."""
+    return _C.lib().ltr_bf16_general_linear_plan(int(kind), B, L, F8) == 1
 
 
 def _prefer_pieces(kind, B, L, F, cus=None, plan=None, exempt=True):
@@ -447,7 +457,7 @@ def _prefer_pieces(kind, B, L, F, cus=None, plan=None, exempt=True):
 
 
 def _linear_route(caller, dtype, dim, is_cuda, requires_grad, autocast, kind, B, L, F, cus=None, Fq=None,
-                  computed=False, fused_plan=None, listwise_plan=False):
+                  computed=False, fused_plan=None, listwise_plan=False, bf16_general=False):
     """Which kernels run ``loss_fn(Linear(F, 1)(xs), ...)`` for a batch of these plain values: _LIN_F32 / _LIN_BF16_FUSED
     (ltr_linear_partials_f32 / _bf16 and the reduction), _LIN_LISTWISE (ltr_linear_listwise_partials_f32 and the
     reduction), _LIN_F32_PIECES / _LIN_BF16_PIECES (the scorer, the stand-alone loss on the fp32 scores, the
@@ -462,7 +472,12 @@ def _linear_route(caller, dtype, dim, is_cuda, requires_grad, autocast, kind, B,
     that is not contiguous).  What only the library on a device answers comes in as plain values: `cus` and
     `fused_plan` (`_prefer_pieces` asks where None) and `listwise_plan` (the caller's `_listwise_fused`: the listwise
     plan takes the rows as they lie in memory, 16-byte aligned).  A batch that is no (B, L, F) device tensor takes the
-    fused fp32 route, whose prepare step raises."""
+    fused fp32 route, whose prepare step raises.
+
+    `bf16_general` (opt-in): where the answer would be _LIN_BF16_PIECES because the register tile's plan refuses a
+    pairwise kind's shape -- a list past 256 documents or past 16 sweeps -- the answer is _LIN_BF16_GENERAL
+    (ltr_bf16_general_linear_partials and the reduction) where ltr_bf16_general_linear_plan takes it; the module callers
+    still take the pieces where `_prefer_pieces` prefers them.  Nothing else changes with the flag."""
     if computed:
         return _LIN_SCORES
     bf16 = dtype is torch.bfloat16 and dim == 3 and is_cuda and not requires_grad and not autocast   # (`_bf16_batch`)
@@ -477,6 +492,9 @@ def _linear_route(caller, dtype, dim, is_cuda, requires_grad, autocast, kind, B,
         return pieces                                    # past max_list_len() (long_lists=True) they are the only path
     if bf16:
         if not _linear_bf16_plan(kind, max(B, 1), L, (F + 7) & ~7):
+            if (bf16_general and _bf16_general_plan(kind, max(B, 1), L, (F + 7) & ~7)
+                    and (caller == "step" or not _prefer_pieces(kind, B, L, F, cus, exempt=False))):
+                return _LIN_BF16_GENERAL
             return pieces
         if caller != "step" and _prefer_pieces(kind, B, L, F, cus, exempt=False):
             return pieces
@@ -486,7 +504,7 @@ def _linear_route(caller, dtype, dim, is_cuda, requires_grad, autocast, kind, B,
     return _LIN_F32
 
 
-def _linear_routed(caller, xs, kind, Fq=None, computed=False):
+def _linear_routed(caller, xs, kind, Fq=None, computed=False, bf16_general=False):
     """``(route, batch)``: `_linear_route` on a batch -- its dtype, shape and flags, the autocast state, the library's
     answers -- and the batch to hand on: `xs`, or for a listwise kind the prepared fp32 batch the plan was asked about."""
     if computed:
@@ -501,7 +519,7 @@ def _linear_routed(caller, xs, kind, Fq=None, computed=False):
     if caller == "lazy" and not xs.is_contiguous():
         Fq = (F + 3) & ~3
     return _linear_route(caller, xs.dtype, 3, xs.is_cuda, xs.requires_grad, torch.is_autocast_enabled(), kind, B, L, F,
-                         None, Fq, False, None, plan), X
+                         None, Fq, False, None, plan, bf16_general), X
 
 
 def _linear_route_of(caller, xs, kind):
@@ -521,11 +539,18 @@ class FusedLinearLoss(torch.nn.Module):
     """``loss_fn(Linear(in_features, 1)(xs), relevance, n)`` as one fused op.
 
     Gradients flow to ``weight`` and ``bias`` (not to ``xs``: features are data).
+
+    ``bf16_general=True`` (opt-in, also settable afterwards as ``model.bf16_general``): a ``torch.bfloat16`` batch of a
+    pairwise loss that the register tile cannot hold -- a list past 256 documents, or 80 at 704 features -- takes the
+    general fused kernel (one launch, include/ltr_bf16_general.h) instead of the scorer, the loss and the
+    weight-gradient kernel.  Not covered: LazyScores / use_linear_scorer, optim.SGD's lazy launch, the listwise losses
+    and LambdaRank.
     """
 
-    def __init__(self, in_features, loss="hinge", bias=True):
+    def __init__(self, in_features, loss="hinge", bias=True, bf16_general=False):
         super().__init__()
         self.in_features = in_features
+        self.bf16_general = bool(bf16_general)
         self.kind, self.sigma = _resolve_loss(loss)
         self.weight = torch.nn.Parameter(torch.empty(1, in_features))
         self.bias = torch.nn.Parameter(torch.empty(1)) if bias else None
@@ -537,33 +562,36 @@ class FusedLinearLoss(torch.nn.Module):
     def forward(self, xs, relevance, n, return_scores=False):
         if isinstance(self.kind, _ListwiseKind) and self.weight.numel() != xs.shape[-1]:
             raise ValueError("weight has %d elements, features have %d" % (self.weight.numel(), xs.shape[-1]))
-        route, X = _linear_routed("module", xs, self.kind, self.in_features)
+        route, X = _linear_routed("module", xs, self.kind, self.in_features, bf16_general=getattr(self, "bf16_general", False))
         if route in _LIN_PIECES:
             # a few long lists (the balanced pieces are faster), a shape no fused kernel takes (there they are the only path)
             scores = _LinearScoreFunction.apply(xs, self.weight, self.bias, n)
             loss = _loss_pieces(scores, relevance, n, self.kind, self.sigma)
             return (loss, scores.detach().squeeze(-1)) if return_scores else loss
         return _LinearLossFunction.apply(X, self.weight, self.bias, relevance, n, self.kind, self.sigma,
-                                         bool(return_scores))
+                                         bool(return_scores), route)
 
     def _prefer_pieces(self, B, L):
         return _prefer_pieces(self.kind, B, L, self.in_features)
 
 
 def linear_loss_step(xs, weight, bias, relevance, n, loss="hinge", grad_out=None,
-                     return_scores=False, return_loss_sum=False):
+                     return_scores=False, return_loss_sum=False, bf16_general=False):
     """One fused fwd+bwd step without autograd: returns (loss[B], dW[F], db[1][, scores][, loss_sum]).
 
     dW/db are the gradients of ``sum_b grad_out[b] * loss[b]``; grad_out=None means the
     ``.mean()`` of the reference's training loop (1/B each).  Two launches: the fused
-    scorer+loss kernel and the cross-query reduction (which also totals the loss)."""
+    scorer+loss kernel and the cross-query reduction (which also totals the loss).
+
+    ``bf16_general=True`` (opt-in): a ``torch.bfloat16`` batch of a pairwise loss off the plan of the register tile
+    takes the general fused kernel (ltr_bf16_general_linear_partials) instead of the three-kernel pieces."""
     kind, sigma = _resolve_loss(loss)
-    route, X = _linear_routed("step", xs, kind)
+    route, X = _linear_routed("step", xs, kind, bf16_general=bf16_general)
     if route in _LIN_PIECES:
         return _step_pieces(xs, weight, bias, relevance, n, kind, sigma, grad_out, return_scores, return_loss_sum)
     X, r, nn, dims, Fw = _linear_prepare(X, weight, relevance, n, kind, raw=xs)
     B, L, F = dims                                  # (F: the row width in memory -- a padded view's F4)
-    lossv, ws, scores = _linear_launch(kind, sigma, X, weight, bias, r, nn, dims, Fw, return_scores, empty=True)
+    lossv, ws, scores = _linear_launch(kind, sigma, X, weight, bias, r, nn, dims, Fw, return_scores, empty=True, route=route)
     dW = torch.empty(F, dtype=torch.float32, device=X.device)
     db = torch.empty(1, dtype=torch.float32, device=X.device)
     lsum = torch.zeros(1, dtype=torch.float32, device=X.device) if return_loss_sum else None
